@@ -19,7 +19,14 @@ says so in config.vocab.
 
 The piece memo (the reference's LRUCache on the device) persists from call to call like the reference's: the W warm-up steps encode
 OTHER documents of the same generator, then one untimed pass with the memo switched off sizes the workspace for the bench batch;
---no-memo measures without it (config.piece_memo says which).  Companion figures of the same line, never `value`: `value_no_memo`
+--no-memo measures without it (config.piece_memo says which).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).  Everything below --
+the companion figures, the roofline with its per-kernel times, the oracle's parity check and the CPU baseline -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (ids, per-document token offsets, token count; sampled at fixed seeded
+positions when larger than 48 MB) as DIR/<name>.npy, so that two builds can be compared output for output.
+
+Companion figures of the --full line, never `value`: `value_no_memo`
 (the timed steps again with the memo off) and `value_two_in_flight` (the same batch two at a time through
 tkz_encode_batch_device_begin / _end on two streams: what keeping batches in flight buys over one synchronous call after the other).
 
@@ -208,6 +215,28 @@ def check_ranges(O, ov, pattern, d_bytes, d_offs, d_ids, d_ooffs, n_tokens, rang
     return res
 
 
+def dump_outputs(path, d_ids, ntok, d_ooffs, n_docs, total, suffix=""):
+    """What a caller of tkz_encode_batch_device receives from one step, as float .npy files under `path`: `n_tokens` (the return value),
+    `token_offsets` (the n_docs + 1 per-document token offsets, float64) and `ids` (float32: every id is < 2^24, so exact).  An array larger than
+    its budget (2^21 offsets, 2^23 ids: 48 MB in all) is sampled at that many sorted positions drawn from a fixed seed and the array's INPUT size
+    (ids: positions in [0, bytes), -1 where a position is at or past the token count), so the dumps of two builds compare element for element."""
+    import numpy as np
+    import torch
+
+    def positions(n, cap, seed):
+        if n <= cap:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    q = positions(n_docs + 1, 1 << 21, 0x5EED00FF)
+    p = positions(total, 1 << 23, 0x5EED01D5)
+    offs = d_ooffs[torch.from_numpy(q).to(d_ooffs.device)].cpu().numpy().astype(np.float64)
+    ids = d_ids[torch.from_numpy(p).to(d_ids.device)].cpu().numpy().astype(np.float32)
+    ids[p >= ntok] = -1
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("n_tokens", np.array([ntok], np.float64)), ("token_offsets", offs), ("ids", ids)):
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -242,6 +271,11 @@ def main():
                                                                   "warm-up and the sizing pass run under the profiler)")
     ap.add_argument("--no-memo", action="store_true", help="switch the piece memo (the device form of the reference's LRUCache) off")
     ap.add_argument("--write-shards", default=None, metavar="DIR", help="after the timed loop every rank writes its token shard file (SURVEY 8f-2)")
+    ap.add_argument("--full", action="store_true", help="also the companion figures, the roofline (per-kernel times by HIP events), the parity check "
+                                                        "against the oracle and the CPU baseline; without it the run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the outputs of the last one as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--real-text-root", action="append", default=None, metavar="DIR", help="kind 6 and the real_text leg: read the text under DIR "
+                                                                                            "(repeatable) instead of REAL_TEXT_ROOTS")
     args = ap.parse_args()
 
     if args.docs is None:
@@ -324,7 +358,7 @@ def main():
     if args.kind == 6:
         # REAL text, every file once: rank r takes the r-th of `world` contiguous shares of the documents
         lim = 0 if args.real_text_mb is None else args.real_text_mb
-        r_bytes, r_offs, real_meta = real_text_corpus(lim << 20, args.min_len, args.max_len)
+        r_bytes, r_offs, real_meta = real_text_corpus(lim << 20, args.min_len, args.max_len, roots=args.real_text_root)
         nd_all = len(r_offs) - 1
         lo, hi = N.shard_range(nd_all, rank, world)
         b0, b1 = int(r_offs[lo]), int(r_offs[hi])
@@ -466,8 +500,9 @@ def main():
             return {"error": "%s: %s" % (type(ex).__name__, ex)}
 
     ntok = prepare(enc)
-    enc.set_profiling(True)
-    enc.kernel_ms(reset=True)
+    if args.full:                                            # (per-kernel HIP events for the roofline)
+        enc.set_profiling(True)
+        enc.kernel_ms(reset=True)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -475,14 +510,17 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     dt_own = dt
-    enc.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_ids, ntok, d_ooffs, n_docs, total, "_rank%d" % rank if world > 1 else "")
+    if args.full:
+        enc.set_profiling(False)
     rank_ms = [dt / args.steps * 1e3]
     if world > 1:
         allt = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
         dist.all_gather(allt, torch.tensor([dt], dtype=torch.float64, device=dev))
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in allt]
         dt = max(float(x.item()) for x in allt)              # the slowest rank's time is the job's
-    kms = enc.kernel_ms()
+    kms = enc.kernel_ms() if args.full else None
     try:
         npromo = enc.piece_stats().get("promoted_pieces_in_tables", 0)
         promoted_note = ("%d memo entries promoted into the key tables during the warm-up steps (TKZ_OPT_PROMOTE, automatic: learnt from the warm-up documents, "
@@ -490,7 +528,7 @@ def main():
     except Exception as ex:
         promoted_note = "unknown (%s)" % ex
     kms_rank = rank
-    if world > 1:
+    if args.full and world > 1:
         # the roofline prices the SLOWEST rank's kernels (its time is the job's): every rank's per-kernel milliseconds travel with its step time
         names = sorted(kms)
         mine = torch.tensor([dt_own] + [kms[k][0] for k in names] + [float(kms[k][1]) for k in names], dtype=torch.float64, device=dev)
@@ -499,13 +537,13 @@ def main():
         rows = [r.cpu().tolist() for r in rows]
         kms_rank = max(range(world), key=lambda r: rows[r][0])
         kms = {k: (rows[kms_rank][1 + i], int(rows[kms_rank][1 + len(names) + i])) for i, k in enumerate(names)}
-    piece_stats = stats_of(enc) if (rank == 0 and not args.no_piece_stats) else None
+    piece_stats = stats_of(enc) if (args.full and rank == 0 and not args.no_piece_stats) else None
     if world > 1:
         fence()
     # kind 6 only: the same steps WITHOUT emptying the memo in between (it holds what the passes before put there from this very text: an upper
     # bound, every piece has been seen) -- `value_warm_memo`
     dt_warm = None
-    if empty_memo_each_step and args.steps > 0:
+    if args.full and empty_memo_each_step and args.steps > 0:
         memo_on[id(enc)] = False                                    # (step() leaves the memo alone)
         enc.set_option(N.OPT_PROMOTE, 1)
         for _ in range(min(6, 2 + int((1 << 30) // max(1, total)))):         # (untimed: the two learning batches an encoder gets -- the second one a gigabyte after the first -- and their promotions)
@@ -517,7 +555,7 @@ def main():
     # the same steps with the piece memo switched off (it neither reads nor fills it): the companion figure `value_no_memo`
     dt_nomemo = None
     nm_steps = args.steps if args.no_memo_steps is None else args.no_memo_steps
-    if not args.no_memo and nm_steps > 0:
+    if args.full and not args.no_memo and nm_steps > 0:
         # (no memo means no promoted pieces either -- they are memo answers moved into the key tables: dropped for this leg, learnt again after it by two
         #  untimed steps, the two automatic rounds an encoder gets)
         promoted_before = enc.piece_stats().get("promoted_pieces_in_tables", 0)
@@ -544,7 +582,7 @@ def main():
     ho_steps = args.heldout_steps
     if ho_steps is None:
         ho_steps = args.steps if (world == 1 and args.pattern == 2 and args.vocab is None and not args.no_memo and "VOCAB-SUBSTITUTED" in vocab_name) else 0
-    if ho_steps > 0:
+    if args.full and ho_steps > 0:
         try:
             raw_h, name_h = load_vocab_bytes(args.pattern, "synth100k_heldout")
             enc_h = N.Encoder(N.Vocab(raw_h), args.pattern, device=local_rank)
@@ -574,9 +612,9 @@ def main():
     # TikTokenizer meets the text), full-batch parity against the oracle, piece statistics.  Companion figures, never `value`.
     real_leg = None
     rt_mb = 256 if args.real_text_mb is None else args.real_text_mb
-    if world == 1 and args.kind == 1 and not args.parity_only and rt_mb > 0 and not args.no_memo:
+    if args.full and world == 1 and args.kind == 1 and not args.parity_only and rt_mb > 0 and not args.no_memo:
         try:
-            r_bytes, r_offs, r_meta = real_text_corpus(rt_mb << 20, 256, 768)
+            r_bytes, r_offs, r_meta = real_text_corpus(rt_mb << 20, 256, 768, roots=args.real_text_root)
             r_nd, r_total = len(r_offs) - 1, int(r_offs[-1])
             rd_bytes = torch.zeros(r_total + 64, dtype=torch.uint8, device=dev)
             rd_bytes[:r_total] = torch.from_numpy(r_bytes).to(dev)
@@ -722,7 +760,7 @@ def main():
     # reference pays construction costs in CreateTokenizer, TokenizerBuilder.cs:210-213), then the bench batch ONCE, timed, with nothing untimed before
     # it: empty memo, nothing promoted, cold tables, the sizing attempt and the learning window's counting inside the call.  `value` never includes it.
     first_call = None
-    if world == 1 and not args.parity_only and not args.no_memo and not args.no_first_call:
+    if args.full and world == 1 and not args.parity_only and not args.no_memo and not args.no_first_call:
         try:
             e_fc = N.Encoder(vocab, args.pattern, device=local_rank)
             device_sync(); t0 = time.perf_counter()
@@ -753,7 +791,7 @@ def main():
     # encoder): what keeping batches in flight buys over one synchronous call after the other -- a companion figure, never `value`
     dt_pipe = None
     pipe_note = None
-    if args.pipelined_steps > 0 and args.kind != 5 and not emu:
+    if args.full and args.pipelined_steps > 0 and args.kind != 5 and not emu:
         # every batch in flight has its own {docs, bytes, tokens} block (tkz_encode_batch_device_begin_counts) and its own gathered table: the
         # count all-gather of a batch is enqueued on that batch's stream behind its _end, at any N.  The untimed pass (the second workspace
         # takes its size) runs WITHOUT the collective, and the ranks agree that every one of them got through it before any enters a
@@ -820,7 +858,7 @@ def main():
     # (tkzo_check_batch on its share of the host's CPUs, all ranks at the same time), the verdicts are reduced, and rank 0's line says
     # "bit-exact on N x ... sampled docs" or names the first bad (rank, document).  Nothing of this is inside a timed region.
     multi = None
-    if world > 1 and not args.no_cpu_baseline:
+    if args.full and world > 1 and not args.no_cpu_baseline:
         verdict = [0, 0, 0, 0, 1 << 62, 0.0]                     # bad docs, docs checked, tokens, ranks that could not check, first bad (rank << 40 | doc), seconds
         note_err = None
         try:
@@ -872,57 +910,59 @@ def main():
         job_bytes, job_tokens, job_docs = g["bytes"], g["tokens"], g["docs"]
         ms_per_step = dt / args.steps * 1e3
         value = job_bytes * args.steps / dt / 1e6
-        # ---- roofline of the dominant kernel (HBM-bound integer/indexing work; no MFMA) ----
-        dom = max(kms, key=lambda k: kms[k][0])
-        dom_ms = kms[dom][0] / max(1, kms[dom][1])
-        # read text + write int32 ids + 8 B offset in + 8 B offset out -- of the rank whose kernels are priced (the slowest one at N > 1)
-        alg_bytes = int(g["table"][kms_rank][1]) + 4 * int(g["table"][kms_rank][2]) + 16 * int(g["table"][kms_rank][0])
-        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
-        traffic, traffic_pipeline, traffic_by_kernel, traffic_note = None, None, None, "no PMC summary for this build"
-        issue = None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("src_sha") != kernel_sources_sha():
-                    traffic_note = "profiles/traffic_latest.json was collected on other kernel sources (src_sha differs): not reported"
-                elif tj.get("docs_per_gpu") != n_docs or tj.get("kind") != args.kind or dom not in tj.get("by_kernel", {}):
-                    traffic_note = "profiles/traffic_latest.json is for another workload / kernel: not reported"
-                else:
-                    traffic, traffic_note = tj["by_kernel"][dom]["hbm_bytes_per_launch"], "rocprofv3 PMC passes of this build (profiles/traffic_latest.json)"
-                    traffic_by_kernel = {k: v["hbm_bytes_per_launch"] for k, v in tj["by_kernel"].items()}
-                    traffic_pipeline = int(sum(traffic_by_kernel.values()))
-                    # the binding limit in the record, not only in prose: the dominant kernel's VALU wave-instructions of the same PMC passes against the chip's
-                    # issue rate (256 CUs x 4 SIMDs, one wave64 VALU instruction per 4 cycles at 2.4 GHz = 0.614 T/s), and the lanes they had switched on
-                    iss = tj["by_kernel"][dom].get("issue")
-                    if iss and iss.get("valu_insts"):
-                        rate = iss["valu_insts"] / (dom_ms * 1e-3) / 1e12
-                        issue = {"kernel": dom, "valu_per_kib": round(iss["valu_insts"] / (int(g["table"][kms_rank][1]) / 1024.0), 1), "valu_rate_tps": round(rate, 3),
-                                 "frac_of_valu_peak": round(rate / VALU_PEAK_TPS, 3), "lanes_active": iss.get("lanes_active"), "peak_tps": VALU_PEAK_TPS,
-                                 "salu_per_kib": round(iss["salu_insts"] / (int(g["table"][kms_rank][1]) / 1024.0), 1) if iss.get("salu_insts") else None,
-                                 "by_kernel": {k: v.get("issue") for k, v in tj["by_kernel"].items() if v.get("issue")},
-                                 "note": "SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_THREAD_CYCLES_VALU of the rocprofv3 PMC passes of this build (profiles/traffic_latest.json), "
-                                         "per launch; rate = instructions / this run's launch duration"}
-            except Exception:
-                traffic = None
-        leftovers = enc.pretok_leftovers() if hasattr(enc, "pretok_leftovers") else (0, 0)
-        pipe_achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9      # (ms_per_step: the slowest rank's; alg_bytes: that rank's)
-        # `achieved` / `frac` price the WHOLE step (every kernel of the launch sequence has to move its share of the algorithmic bytes: crediting
-        # the dominant kernel alone with all of them flatters); the dominant kernel's own figure is beside it (`*_dominant`).  `traffic` is the
-        # dominant kernel's counted HBM bytes per launch, `traffic_pipeline` all kernels' together, `wasted` = traffic_pipeline / algorithmic.
-        roofline = {"kernel": dom, "bound": "hbm", "achieved": round(pipe_achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(pipe_achieved / HBM_PEAK_GBPS, 5),
-                    "achieved_dominant": round(achieved, 2), "frac_dominant": round(achieved / HBM_PEAK_GBPS, 5),
-                    "traffic": traffic, "traffic_pipeline": traffic_pipeline,
-                    "wasted": round(traffic_pipeline / alg_bytes, 3) if traffic_pipeline else None, "traffic_by_kernel": traffic_by_kernel, "traffic_note": traffic_note,
-                    "issue": issue,
-                    "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(dom_ms, 4), "rank": kms_rank,
-                    "kernels_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kms.items()},
-                    "side_by_side_batches": int(enc.side_by_side_batches) if hasattr(enc, "side_by_side_batches") else None,
-                    "note": "achieved = algorithmic bytes (SURVEY.md 8d: text + 4 B per id + 16 B per document) / the step's time; *_dominant = the same bytes / "
-                            "the dominant kernel's average launch duration (HIP events on the launch stream)"}
-        if args.pattern in (3, 4):     # of the 4 KiB blocks: handed on by the ASCII block scanner / by the multi-byte one as well (to the sequential matcher)
-            roofline["o200k_blocks"] = {"total": (total + 3967) // 3968, "after_ascii_scanner": leftovers[0], "after_multibyte_scanner": leftovers[1]}
+        roofline = None
+        if args.full:
+            # ---- roofline of the dominant kernel (HBM-bound integer/indexing work; no MFMA) ----
+            dom = max(kms, key=lambda k: kms[k][0])
+            dom_ms = kms[dom][0] / max(1, kms[dom][1])
+            # read text + write int32 ids + 8 B offset in + 8 B offset out -- of the rank whose kernels are priced (the slowest one at N > 1)
+            alg_bytes = int(g["table"][kms_rank][1]) + 4 * int(g["table"][kms_rank][2]) + 16 * int(g["table"][kms_rank][0])
+            achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
+            traffic, traffic_pipeline, traffic_by_kernel, traffic_note = None, None, None, "no PMC summary for this build"
+            issue = None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get("src_sha") != kernel_sources_sha():
+                        traffic_note = "profiles/traffic_latest.json was collected on other kernel sources (src_sha differs): not reported"
+                    elif tj.get("docs_per_gpu") != n_docs or tj.get("kind") != args.kind or dom not in tj.get("by_kernel", {}):
+                        traffic_note = "profiles/traffic_latest.json is for another workload / kernel: not reported"
+                    else:
+                        traffic, traffic_note = tj["by_kernel"][dom]["hbm_bytes_per_launch"], "rocprofv3 PMC passes of this build (profiles/traffic_latest.json)"
+                        traffic_by_kernel = {k: v["hbm_bytes_per_launch"] for k, v in tj["by_kernel"].items()}
+                        traffic_pipeline = int(sum(traffic_by_kernel.values()))
+                        # the binding limit in the record, not only in prose: the dominant kernel's VALU wave-instructions of the same PMC passes against the chip's
+                        # issue rate (256 CUs x 4 SIMDs, one wave64 VALU instruction per 4 cycles at 2.4 GHz = 0.614 T/s), and the lanes they had switched on
+                        iss = tj["by_kernel"][dom].get("issue")
+                        if iss and iss.get("valu_insts"):
+                            rate = iss["valu_insts"] / (dom_ms * 1e-3) / 1e12
+                            issue = {"kernel": dom, "valu_per_kib": round(iss["valu_insts"] / (int(g["table"][kms_rank][1]) / 1024.0), 1), "valu_rate_tps": round(rate, 3),
+                                     "frac_of_valu_peak": round(rate / VALU_PEAK_TPS, 3), "lanes_active": iss.get("lanes_active"), "peak_tps": VALU_PEAK_TPS,
+                                     "salu_per_kib": round(iss["salu_insts"] / (int(g["table"][kms_rank][1]) / 1024.0), 1) if iss.get("salu_insts") else None,
+                                     "by_kernel": {k: v.get("issue") for k, v in tj["by_kernel"].items() if v.get("issue")},
+                                     "note": "SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_THREAD_CYCLES_VALU of the rocprofv3 PMC passes of this build (profiles/traffic_latest.json), "
+                                             "per launch; rate = instructions / this run's launch duration"}
+                except Exception:
+                    traffic = None
+            leftovers = enc.pretok_leftovers() if hasattr(enc, "pretok_leftovers") else (0, 0)
+            pipe_achieved = alg_bytes / (ms_per_step * 1e-3) / 1e9      # (ms_per_step: the slowest rank's; alg_bytes: that rank's)
+            # `achieved` / `frac` price the WHOLE step (every kernel of the launch sequence has to move its share of the algorithmic bytes: crediting
+            # the dominant kernel alone with all of them flatters); the dominant kernel's own figure is beside it (`*_dominant`).  `traffic` is the
+            # dominant kernel's counted HBM bytes per launch, `traffic_pipeline` all kernels' together, `wasted` = traffic_pipeline / algorithmic.
+            roofline = {"kernel": dom, "bound": "hbm", "achieved": round(pipe_achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": round(pipe_achieved / HBM_PEAK_GBPS, 5),
+                        "achieved_dominant": round(achieved, 2), "frac_dominant": round(achieved / HBM_PEAK_GBPS, 5),
+                        "traffic": traffic, "traffic_pipeline": traffic_pipeline,
+                        "wasted": round(traffic_pipeline / alg_bytes, 3) if traffic_pipeline else None, "traffic_by_kernel": traffic_by_kernel, "traffic_note": traffic_note,
+                        "issue": issue,
+                        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(dom_ms, 4), "rank": kms_rank,
+                        "kernels_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kms.items()},
+                        "side_by_side_batches": int(enc.side_by_side_batches) if hasattr(enc, "side_by_side_batches") else None,
+                        "note": "achieved = algorithmic bytes (SURVEY.md 8d: text + 4 B per id + 16 B per document) / the step's time; *_dominant = the same bytes / "
+                                "the dominant kernel's average launch duration (HIP events on the launch stream)"}
+            if args.pattern in (3, 4):     # of the 4 KiB blocks: handed on by the ASCII block scanner / by the multi-byte one as well (to the sequential matcher)
+                roofline["o200k_blocks"] = {"total": (total + 3967) // 3968, "after_ascii_scanner": leftovers[0], "after_multibyte_scanner": leftovers[1]}
         # ---- CPU baseline (the oracle = reference-algorithm restatement, "port") + parity on the sample ----
         cpu = None
         host_path = None
@@ -932,7 +972,7 @@ def main():
             # N > 1: every rank has checked the first and the last --parity-sample-docs documents of ITS OWN shard (above, all ranks at once); the CPU
             # baseline is rank 0's alone, on a bounded sample of its shard, while the other ranks sleep on the store
             parity_note = multi["note"]
-        if not args.no_cpu_baseline and (world == 1 or multi is not None):
+        if args.full and not args.no_cpu_baseline and (world == 1 or multi is not None):
             try:
                 from oracle import oracle as O
                 ov = O.Vocab(raw)
@@ -1125,30 +1165,33 @@ def main():
                        "partitioning": "contiguous document ranges, one process per GPU; one all-gather of 3 int64 counts per rank per step"},
             "comm": comm_info,
             "tokens_per_s": round(job_tokens * args.steps / dt, 1),
-            "piece_stats": piece_stats,
-            "value_no_memo": round(job_bytes * nm_steps / dt_nomemo / 1e6, 1) if dt_nomemo else None,
-            "value_warm_memo": round(job_bytes / dt_warm * args.steps / 1e6, 1) if dt_warm else None,
-            "value_real_text": (real_leg.get("by_vocab", {}).get("gpt2/pattern1", {}).get("value") if real_leg else None),
-            "first_call_ms": first_call.get("first_call_ms") if first_call else None,
-            "first_call": first_call,
-            "value_after_drift": ((real_leg.get("drift") or {}).get("synthetic_then_real", {}).get("value_after_drift") if real_leg else None),
-            "real_text_roofline": (real_leg.get("by_vocab", {}).get("gpt2/pattern1", {}).get("roofline") if real_leg else None),
-            "real_text": real_leg,
-            "value_heldout_vocab": heldout["value"] if heldout and "value" in heldout else None,
-            "heldout_vocab": heldout,
-            "value_two_in_flight": round(job_bytes / dt_pipe / 1e6, 1) if dt_pipe else None,
-            "two_in_flight_note": pipe_note,
             "rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
-            "parity": parity_note,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "pcie_inclusive": host_path,
-            "value_host_api": host_api["value"] if host_api and "value" in host_api else None,
-            "value_host_api_utf16": (host_api.get("utf16") or {}).get("value") if host_api else None,
-            "value_host_api_utf16_as_csharp": (host_api.get("utf16") or {}).get("value_as_csharp") if host_api else None,
-            "value_host_api_utf16_as_csharp_managed_array": (host_api.get("utf16") or {}).get("value_as_csharp_managed_array") if host_api else None,
-            "host_api": host_api,
         }
+        if args.full:
+            line.update({
+                "piece_stats": piece_stats,
+                "value_no_memo": round(job_bytes * nm_steps / dt_nomemo / 1e6, 1) if dt_nomemo else None,
+                "value_warm_memo": round(job_bytes / dt_warm * args.steps / 1e6, 1) if dt_warm else None,
+                "value_real_text": (real_leg.get("by_vocab", {}).get("gpt2/pattern1", {}).get("value") if real_leg else None),
+                "first_call_ms": first_call.get("first_call_ms") if first_call else None,
+                "first_call": first_call,
+                "value_after_drift": ((real_leg.get("drift") or {}).get("synthetic_then_real", {}).get("value_after_drift") if real_leg else None),
+                "real_text_roofline": (real_leg.get("by_vocab", {}).get("gpt2/pattern1", {}).get("roofline") if real_leg else None),
+                "real_text": real_leg,
+                "value_heldout_vocab": heldout["value"] if heldout and "value" in heldout else None,
+                "heldout_vocab": heldout,
+                "value_two_in_flight": round(job_bytes / dt_pipe / 1e6, 1) if dt_pipe else None,
+                "two_in_flight_note": pipe_note,
+                "parity": parity_note,
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "pcie_inclusive": host_path,
+                "value_host_api": host_api["value"] if host_api and "value" in host_api else None,
+                "value_host_api_utf16": (host_api.get("utf16") or {}).get("value") if host_api else None,
+                "value_host_api_utf16_as_csharp": (host_api.get("utf16") or {}).get("value_as_csharp") if host_api else None,
+                "value_host_api_utf16_as_csharp_managed_array": (host_api.get("utf16") or {}).get("value_as_csharp_managed_array") if host_api else None,
+                "host_api": host_api,
+            })
         if real_meta:
             line["config"]["real_text"] = real_meta
         if emu:

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -21,8 +22,10 @@ def _free_port():
     return p
 
 
-def _run(world, extra, timeout=900):
+def _run(world, extra, timeout=900, full=True):
     args = ["--emulated", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--pipelined-steps", "0", "--min-len", "20", "--max-len", "300"] + extra
+    if full:
+        args.append("--full")
     env = dict(os.environ, OMP_NUM_THREADS="1")
     if world == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
@@ -65,10 +68,52 @@ def test_world_1_line_and_real_text_kind(tmp_path):
     # the default shape at N = 1 (full-batch parity) ...
     line = _run(1, ["--docs", "150", "--cpu-sample-docs", "100", "--real-text-mb", "0", "--heldout-steps", "0"])
     assert line["parity"].startswith("bit-exact vs oracle on all 150 docs") and line["cpu_baseline"] and line["roofline"] and line["n_gpus"] == 1
-    # ... and kind 6: real files of the box, every file once, cut at character boundaries; the memo emptied before every step
-    line = _run(1, ["--kind", "6", "--real-text-mb", "1", "--vocab", "gpt2", "--pattern", "1", "--cpu-sample-docs", "500"])
+    # ... and kind 6: real files (this repository's sources), every file once, cut at character boundaries; the memo emptied before every step
+    line = _run(1, ["--kind", "6", "--real-text-mb", "1", "--real-text-root", ROOT, "--vocab", "gpt2", "--pattern", "1", "--cpu-sample-docs", "500"])
     rt = line["config"]["real_text"]
     assert rt["bytes"] >= 1 << 20 and rt["files"] > 10 and len(rt["sha256"]) == 64 and rt["docs"] == line["config"]["docs_per_gpu"]
     assert line["parity"].startswith("bit-exact vs oracle on all %d docs" % rt["docs"]), line["parity"]
     assert "EMPTIED before every step" in line["config"]["piece_memo"] and line["value_warm_memo"] and line["value_no_memo"]
     assert line["config"]["vocab"] == "gpt2" and line["config"]["pattern"].startswith("pattern 1")
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    # a plain run times the headline steps and nothing else; --dump-outputs writes what its last step computed -- the same arrays as a --full
+    # run's, whose parity check holds every document against the oracle
+    common = ["--docs", "150", "--cpu-sample-docs", "100", "--real-text-mb", "0", "--heldout-steps", "0"]
+    plain = _run(1, common + ["--dump-outputs", str(tmp_path / "plain")], full=False)
+    assert plain["steps"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["unit"] == "MB/s" and plain["higher_is_better"] is True
+    assert not {"parity", "roofline", "cpu_baseline", "piece_stats", "value_no_memo", "first_call"} & set(plain)
+    full = _run(1, common + ["--dump-outputs", str(tmp_path / "full")])
+    assert full["parity"].startswith("bit-exact vs oracle on all 150 docs"), full["parity"]
+    for name in ("n_tokens", "token_offsets", "ids"):
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    n = plain["config"]["tokens_per_gpu"]
+    offs, ids = np.load(tmp_path / "plain" / "token_offsets.npy"), np.load(tmp_path / "plain" / "ids.npy")
+    assert np.load(tmp_path / "plain" / "n_tokens.npy").tolist() == [n]
+    assert len(offs) == 151 and offs[0] == 0 and offs[-1] == n and (np.diff(offs) > 0).all()
+    assert len(ids) == plain["config"]["bytes_per_gpu"] and (ids[:n] >= 0).all() and (ids[n:] == -1).all()
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    # past its budget an array is sampled at sorted positions of a fixed seed: ids[i] = i shows which, and -1 stands where a position is past the tokens
+    import torch
+    import bench
+    total, ntok, n_docs = 12 << 20, 10 << 20, 3 << 20
+    d_ids = torch.arange(total, dtype=torch.int32)
+    d_ooffs = torch.arange(n_docs + 1, dtype=torch.int64) * 3
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), d_ids, ntok, d_ooffs, n_docs, total)
+    size = 0
+    for name in ("n_tokens", "token_offsets", "ids"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.array_equal(a, b), name
+        size += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert size <= 64 << 20
+    ids, offs = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "token_offsets.npy")
+    assert ids.dtype == np.float32 and offs.dtype == np.float64
+    assert len(ids) == 1 << 23 and len(offs) == 1 << 21
+    kept = ids[ids >= 0]
+    assert (np.diff(kept) > 0).all() and kept[-1] < ntok and (ids[len(kept):] == -1).all() and len(kept) < len(ids)
+    assert (offs % 3 == 0).all() and (np.diff(offs) > 0).all() and offs[-1] <= 3 * n_docs

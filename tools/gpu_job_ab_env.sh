@@ -8,7 +8,7 @@ for envset in "$@"; do
   for shape in ${SHAPES_AB:-mixed real head heldout}; do
     case $shape in mixed) args="--kind 2 --docs 2000000";; real) args="--kind 6 --vocab gpt2 --pattern 1 --real-text-mb 256";; head) args="";; heldout) args="--vocab synth100k_heldout";; esac
     name=${shape}_$(echo "$envset" | tr -c 'A-Za-z0-9_\n' '_')
-    ( [ "$envset" != "-" ] && export $envset; timeout 900 python bench.py $COMMON $args > $O/$name.json 2>> $O/err.txt )
+    ( [ "$envset" != "-" ] && export $envset; timeout 900 python bench.py --full $COMMON $args > $O/$name.json 2>> $O/err.txt )
     python - $O/$name.json "$envset" $shape <<'P'
 import json,sys
 try:

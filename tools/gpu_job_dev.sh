@@ -4,11 +4,11 @@ set -u
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; TAG=${1:-dev}; O=gpurun_out/$TAG; mkdir -p $O
 KEXPR=${2:-"pieces or giant or arena or batch_vs_oracle or dense or memo or corpus_properties or adversarial or vocab_key or golden or errors or host_path or eight_shards"}
 ( time timeout 1200 python -m pytest tests -m gpu -x -q -k "$KEXPR" ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|Error" $O/pytest_gpu.log | tail -3
-timeout 900 python bench.py --no-cpu-baseline > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
-timeout 900 python bench.py --no-cpu-baseline --no-memo > $O/bench_nomemo.json 2>> $O/bench_n1.err; echo "bench no-memo rc=$?"
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --no-cpu-baseline --no-memo > $O/bench_nomemo.json 2>> $O/bench_n1.err; echo "bench no-memo rc=$?"
 rm -f $O/bench_shapes.jsonl
 for spec in "--kind 2 --docs 2000000" "--kind 4 --docs 4000000" "--kind 1 --vocab gpt2 --docs 4000000"; do
-  timeout 600 python bench.py $spec --no-cpu-baseline --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape [$spec] rc=$?"
+  timeout 600 python bench.py --full $spec --no-cpu-baseline --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape [$spec] rc=$?"
 done
 python - $TAG <<'P'
 import json,sys

@@ -9,7 +9,7 @@ for v in $VARS; do
   for shape in "mixed:--kind 2 --docs 2000000" "real:--kind 6 --vocab gpt2 --pattern 1" "${XS[@]}"; do
     [ -n "$shape" ] || continue
     name=${shape%%:*}; args=${shape#*:}
-    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py $COMMON $args > $O/${name}_$v.json 2>> $O/err.txt
+    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --full $COMMON $args > $O/${name}_$v.json 2>> $O/err.txt
     python - $O/${name}_$v.json $v $name <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); k=d["roofline"]["kernels_ms"]
@@ -19,6 +19,6 @@ P
 done
 if [ "${3:-}" = prof ]; then
   for shape in "--kind 2 --docs 2000000" "--kind 6 --vocab gpt2 --pattern 1"; do
-    TKZ_DEV_ABLATE=16 TKZ_LIBTKZ=$REPO/tokenizer_amd/lib_prof/libtkz.so timeout 600 python bench.py $COMMON --steps 2 $shape 2>&1 >/dev/null | grep 'k_merge_long' | tail -1 | tee -a $O/prof.txt
+    TKZ_DEV_ABLATE=16 TKZ_LIBTKZ=$REPO/tokenizer_amd/lib_prof/libtkz.so timeout 600 python bench.py --full $COMMON --steps 2 $shape 2>&1 >/dev/null | grep 'k_merge_long' | tail -1 | tee -a $O/prof.txt
   done
 fi

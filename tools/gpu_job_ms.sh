@@ -6,10 +6,10 @@ REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; O=gpurun_out/${1:-ms}; mkdir 
 for v in ${VARIANTS:-lib_r06base lib}; do
   [ -f tokenizer_amd/$v/libtkz.so ] || continue
   export TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so
-  timeout 600 python bench.py --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 3 --no-first-call > $O/head_$v.json 2>> $O/err.txt
-  timeout 600 python bench.py --kind 6 --real-text-mb 0 --vocab gpt2 --pattern 1 --steps 5 --warmup 1 --pipelined-steps 0 --no-cpu-baseline > $O/real_$v.json 2>> $O/err.txt
-  timeout 600 python bench.py --kind 6 --real-text-mb 0 --vocab gpt2 --pattern 2 --steps 5 --warmup 1 --pipelined-steps 0 --no-cpu-baseline > $O/real2_$v.json 2>> $O/err.txt
-  timeout 600 python bench.py --kind 2 --docs 2000000 --parity-only --steps 3 --warmup 1 > $O/mixed_$v.json 2>> $O/err.txt
+  timeout 600 python bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 3 --no-first-call > $O/head_$v.json 2>> $O/err.txt
+  timeout 600 python bench.py --full --kind 6 --real-text-mb 0 --vocab gpt2 --pattern 1 --steps 5 --warmup 1 --pipelined-steps 0 --no-cpu-baseline > $O/real_$v.json 2>> $O/err.txt
+  timeout 600 python bench.py --full --kind 6 --real-text-mb 0 --vocab gpt2 --pattern 2 --steps 5 --warmup 1 --pipelined-steps 0 --no-cpu-baseline > $O/real2_$v.json 2>> $O/err.txt
+  timeout 600 python bench.py --full --kind 2 --docs 2000000 --parity-only --steps 3 --warmup 1 > $O/mixed_$v.json 2>> $O/err.txt
   python - $O $v >> $O/table.txt <<'P'
 import json,sys
 O,v=sys.argv[1:3]

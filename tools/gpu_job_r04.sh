@@ -9,12 +9,12 @@ if has subset; then ( time timeout 1200 python -m pytest tests -m gpu -x -q -k "
 if has smoke; then timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log; fi
 if has profile; then bash tools/gpu_profile.sh $TAG 10000000 "--no-memo-steps 0" > $O/profile.log 2>&1; echo "profile rc=$?"; cp gpurun_out/prof_$TAG/traffic.json profiles/traffic_latest.json 2>/dev/null; fi
 if has profile_mixed; then bash tools/gpu_profile.sh ${TAG}_mixed 2000000 "--kind 2 --no-memo-steps 0" > $O/profile_mixed.log 2>&1; echo "profile mixed rc=$?"; fi
-if has bench; then timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; cut -c1-400 $O/bench_n1.json; fi
+if has bench; then timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; cut -c1-400 $O/bench_n1.json; fi
 if has variants; then
   rm -f $O/variants.txt
   for v in ${VARIANTS:-lib lib_w1 lib_noxcd}; do
     [ -f tokenizer_amd/$v/libtkz.so ] || continue
-    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --no-cpu-baseline --steps 4 --warmup 1 ${VARGS:-} > $O/b_$v.json 2>> $O/variants.err
+    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --full --no-cpu-baseline --steps 4 --warmup 1 ${VARGS:-} > $O/b_$v.json 2>> $O/variants.err
     python - $O/b_$v.json $v >> $O/variants.txt <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); print(sys.argv[2], d["value"], d.get("value_no_memo"), d["ms_per_step"], d["roofline"]["kernels_ms"])
@@ -27,7 +27,7 @@ if has shapes; then
   IFS='|' read -ra SPECS <<< "${SHAPES:---kind 2 --docs 2000000|--kind 4 --docs 4000000|--kind 5|--kind 3 --pattern 2 --docs 32768 --min-len 30000 --max-len 34000|--kind 3 --pattern 4 --docs 32768 --min-len 30000 --max-len 34000|--kind 2 --pattern 4 --docs 2000000|--kind 2 --pattern 3 --docs 2000000|--pattern 4|--vocab gpt2|--vocab gpt2 --pattern 1}"
   for spec in "${SPECS[@]}"; do
     # (--parity-only: the oracle compares EVERY document of the shape's batch; no thread sweep, no PCIe / host-API legs)
-    timeout 900 python bench.py $spec --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape [$spec] rc=$?"
+    timeout 900 python bench.py --full $spec --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape [$spec] rc=$?"
   done
   python - $O/bench_shapes.jsonl <<'P'
 import json,sys

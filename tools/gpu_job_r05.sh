@@ -9,7 +9,7 @@ rocm-smi --showproductname 2>/dev/null | head -8 > $O/gpu.txt; nproc >> $O/gpu.t
 if has tests; then ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.log 2>&1; lap "pytest rc=$?"; grep -E "passed|failed|Error|error" $O/pytest_gpu.log | tail -4; fi
 if has subset; then ( time timeout 1200 python -m pytest tests -m gpu -x -q -k "${KEXPR:-promoted or memo or miss or two_halves or small_batches or batch_vs_oracle or golden or by_name or long_pieces or host_path or utf16}" ) > $O/pytest_subset.log 2>&1; lap "pytest subset rc=$?"; grep -E "passed|failed|Error|error" $O/pytest_subset.log | tail -6; fi
 if has smoke; then timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; lap "smoke rc=$?"; tail -1 $O/smoke.log; fi
-if has bench; then timeout 1200 python bench.py ${BARGS:-} > $O/bench_n1.json 2> $O/bench_n1.err; lap "bench rc=$?"; cut -c1-300 $O/bench_n1.json; tail -3 $O/bench_n1.err
+if has bench; then timeout 1200 python bench.py --full ${BARGS:-} > $O/bench_n1.json 2> $O/bench_n1.err; lap "bench rc=$?"; cut -c1-300 $O/bench_n1.json; tail -3 $O/bench_n1.err
   python - $O/bench_n1.json <<'P'
 import json,sys
 try:
@@ -26,7 +26,7 @@ P
 fi
 if has kind6; then
   for spec in "--vocab gpt2 --pattern 1" "--vocab gpt2 --pattern 2" "" "--vocab synth100k_heldout"; do
-    timeout 900 python bench.py --kind 6 --real-text-mb 0 $spec --steps 5 --warmup 1 --pipelined-steps 0 ${K6ARGS:-} >> $O/bench_kind6.jsonl 2>> $O/bench_kind6.err; lap "kind6 [$spec] rc=$?"
+    timeout 900 python bench.py --full --kind 6 --real-text-mb 0 $spec --steps 5 --warmup 1 --pipelined-steps 0 ${K6ARGS:-} >> $O/bench_kind6.jsonl 2>> $O/bench_kind6.err; lap "kind6 [$spec] rc=$?"
   done
   python - $O/bench_kind6.jsonl <<'P'
 import json,sys
@@ -39,7 +39,7 @@ if has variants; then
   rm -f $O/variants.txt
   for v in ${VARIANTS:-lib lib_a2048 lib_a3584 lib_lane32}; do
     [ -f tokenizer_amd/$v/libtkz.so ] || continue
-    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 0 ${VARGS:-} > $O/b_$v.json 2>> $O/variants.err
+    TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 0 ${VARGS:-} > $O/b_$v.json 2>> $O/variants.err
     python - $O/b_$v.json $v >> $O/variants.txt <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); print(sys.argv[2], d["value"], d["ms_per_step"], d["roofline"]["kernels_ms"])
@@ -50,7 +50,7 @@ P
     rm -f $O/variants2.txt
     for v in ${VARIANTS:-lib}; do
       [ -f tokenizer_amd/$v/libtkz.so ] || continue
-      TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 0 ${VARGS2} > $O/b2_$v.json 2>> $O/variants.err
+      TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 600 python bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --real-text-mb 0 --heldout-steps 0 ${VARGS2} > $O/b2_$v.json 2>> $O/variants.err
       python - $O/b2_$v.json $v >> $O/variants2.txt <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); print(sys.argv[2], d["value"], d["ms_per_step"], d["roofline"]["kernels_ms"])
@@ -63,7 +63,7 @@ if has shapes; then
   rm -f $O/bench_shapes.jsonl
   IFS='|' read -ra SPECS <<< "${SHAPES:---kind 2 --docs 2000000|--kind 4 --docs 4000000|--kind 5|--kind 3 --pattern 2 --docs 32768 --min-len 30000 --max-len 34000|--kind 3 --pattern 4 --docs 32768 --min-len 30000 --max-len 34000|--kind 2 --pattern 4 --docs 2000000|--kind 2 --pattern 3 --docs 2000000|--pattern 4|--vocab gpt2|--vocab gpt2 --pattern 1|--vocab synth100k_heldout}"
   for spec in "${SPECS[@]}"; do
-    timeout 900 python bench.py $spec --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; lap "shape [$spec] rc=$?"
+    timeout 900 python bench.py --full $spec --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; lap "shape [$spec] rc=$?"
   done
   python - $O/bench_shapes.jsonl <<'P'
 import json,sys

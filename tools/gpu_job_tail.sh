@@ -10,7 +10,7 @@ rm -f $O/variants.txt
 for pat in 2 4; do
 for v in lib lib_rf; do
   [ -f tokenizer_amd/$v/libtkz.so ] || continue
-  TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 300 python bench.py $LONGRUN --pattern $pat --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --no-piece-stats > $O/b_${v}_$pat.json 2>> $O/variants.err
+  TKZ_LIBTKZ=$REPO/tokenizer_amd/$v/libtkz.so timeout 300 python bench.py --full $LONGRUN --pattern $pat --no-cpu-baseline --steps 4 --warmup 1 --pipelined-steps 0 --no-memo-steps 0 --no-piece-stats > $O/b_${v}_$pat.json 2>> $O/variants.err
   python - $O/b_${v}_$pat.json $v $pat >> $O/variants.txt <<'P'
 import json,sys
 d=json.load(open(sys.argv[1])); print(sys.argv[2], "pattern", sys.argv[3], d["value"], d["ms_per_step"], d["roofline"]["kernels_ms"])
@@ -20,13 +20,13 @@ done
 cat $O/variants.txt
 if [ -f tokenizer_amd/lib_prof/libtkz.so ]; then
   for pat in 2 4; do
-    TKZ_DEV_ABLATE=16 TKZ_LIBTKZ=$REPO/tokenizer_amd/lib_prof/libtkz.so timeout 300 python bench.py $LONGRUN --pattern $pat --no-cpu-baseline --steps 1 --warmup 0 --pipelined-steps 0 --no-memo-steps 0 --no-piece-stats > $O/b_prof_$pat.json 2> $O/devprof_$pat.txt
+    TKZ_DEV_ABLATE=16 TKZ_LIBTKZ=$REPO/tokenizer_amd/lib_prof/libtkz.so timeout 300 python bench.py --full $LONGRUN --pattern $pat --no-cpu-baseline --steps 1 --warmup 0 --pipelined-steps 0 --no-memo-steps 0 --no-piece-stats > $O/b_prof_$pat.json 2> $O/devprof_$pat.txt
     echo "pattern $pat:"; grep "devprof" $O/devprof_$pat.txt | tail -3 | cut -c1-420
   done
 fi
 rm -f $O/bench_shapes.jsonl
 for pat in 2 4; do
-  timeout 600 python bench.py $LONGRUN --pattern $pat --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape pattern $pat rc=$?"
+  timeout 600 python bench.py --full $LONGRUN --pattern $pat --parity-only --steps 3 --warmup 1 >> $O/bench_shapes.jsonl 2>> $O/bench_shapes.err; echo "shape pattern $pat rc=$?"
 done
 python - $O/bench_shapes.jsonl <<'P'
 import json,sys
