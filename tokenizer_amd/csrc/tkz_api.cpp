@@ -25,9 +25,6 @@
 namespace {
 
 thread_local std::string g_err;
-#ifdef TKZ_DEVPROF
-unsigned long long* g_devprof = nullptr;   // development builds only (make DEVPROF=1, env TKZ_DEV_ABLATE bit 4)
-#endif
 
 tkz_status fail(tkz_status s, const std::string& msg) { g_err = msg; return s; }
 
@@ -49,6 +46,11 @@ struct DeviceScope {
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(TKZ_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+#define TKZ_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        const tkz_status s_ = (expr);                                                                   \
+        if (s_ != TKZ_OK) return s_;                                                                    \
     } while (0)
 
 // a grow-only device buffer
@@ -635,7 +637,6 @@ tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, bool 
 // where the piece-granular entry point wants its arrays (all on the device)
 struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
 
-// the batch on the device; when pretok == false every "document" is taken as one piece
 struct SlowCallLog {
     int64_t total; int attempts = 0; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     SlowCallLog(int64_t n) : total(n) { g_alloc_ns = 0; g_alloc_calls = 0; }
@@ -651,22 +652,420 @@ struct SlowCallLog {
 enum { kCallWhole = 0, kCallBegin = 1, kCallEnd = 2 };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
+// ---- the stages of one attempt of encode_device ---------------------------------------------------------------------------------------
+
+// a large batch: two more streams, for the two kernels of the long pieces that last as long as their slowest wavefront (launch_encode runs them beside k_merge_short;
+// without the streams -- the runtime refused one, or an event -- they follow it as they always did).
+// WHEN: the workspace's previous batch left a class queue short enough for its kernel to be a matter of latency -- at most kForkMaxLong entries, ~4 batches of 64 for
+// each of the 4,096 wavefronts the chip holds --; with a long queue (mixed text: 17 M entries in 1 GB) the queue kernel is the step's largest and needs the whole chip
+// (measured with the tail grids: 17.0 -> 19.8 ms), and on the bench text (1.3 M) the two forms are equal (20.6 / 20.8 ms).
+constexpr int64_t kForkMaxLong = int64_t(1) << 20;
+// (round 6, last session) ... or up to twice that many when one in 2,048 of them is a piece of more than 128 bytes: such a queue ends in a tail of slow wavefronts
+// whatever its length.  436 MB of source text (1.18 M long misses, 1,467 of them of 129+ bytes): 94.5 -> 104.3 GB/s side by side; the bench text (1.31-1.43 M, none
+// above 128 bytes) loses 0.1-0.3 ms that way and stays serial.  profiles/r06/variants_side_by_side2.txt
+constexpr int64_t kForkMaxLongTail = int64_t(1) << 21, kForkTailShare = 2048;
+void side_streams(tkz_encoder* e, Workspace* ws, int64_t total, tkz::Launch* L) {
+    const bool short_queue = ws->last_lq_total >= 0 && (ws->last_lq_total <= kForkMaxLong || (ws->last_lq_total <= kForkMaxLongTail && ws->last_coop * kForkTailShare >= ws->last_lq_total));
+    if (total <= e->latency_bytes || !short_queue) return;
+    if (!ws->fork_token) { int none = 0; ws->fork_token = g_fork_in_flight.compare_exchange_strong(none, 1); }      // (given back when the call ends: ~Lease)
+    bool ok = ws->fork_token;
+    for (hipStream_t* st : {&ws->st_side, &ws->st_side2}) if (!*st && hipStreamCreateWithFlags(st, hipStreamNonBlocking) != hipSuccess) { *st = nullptr; ok = false; }
+    for (hipEvent_t* ev : {&ws->ev_fork, &ws->ev_join, &ws->ev_join2}) if (!*ev && hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { *ev = nullptr; ok = false; }
+    if (ok) { L->side = ws->st_side; L->side2 = ws->st_side2; L->ev_fork = ws->ev_fork; L->ev_join = ws->ev_join; L->ev_join2 = ws->ev_join2; }
+    else (void)hipGetLastError();
+}
+
+// THE SIZING ATTEMPT: a fresh workspace's first large batch probes a sixteenth of its sub-tiles first.  How long the miss lists must be (and, from the
+// scan, how many records there are) is known after ~1 ms instead of after a whole attempt up to k_probe that is thrown away: a fresh encoder's first
+// batch of text its vocabulary has not seen (5.1 GB, held-out vocabulary) went from 100 ms to ~50.  The full attempt follows on the same bitmaps; a
+// sample that under-estimates leaves the ordinary retry.  Returns the sub-tiles of the sample, or -1: the batch is too small for a sizing attempt.
+int64_t sizing_sample(int64_t ntiles) {
+    int64_t min_sub = (int64_t(64) << 20) / tkz::kSub;                      // (64 MB of text; TKZ_SIZING_MIN_SUB: the tests' handle on it)
+    { const char* v = getenv("TKZ_SIZING_MIN_SUB"); if (v && atoll(v) > 0) min_sub = atoll(v); }
+    return ntiles >= min_sub ? std::min<int64_t>(ntiles, std::max<int64_t>(ntiles / 16, min_sub / 16)) : -1;
+}
+
+// The tables as they are NOW, one consistent copy for the whole attempt (a promotion at the end of another call's batch replaces the SHORT / MID images and
+// the promo array together: k_probe and k_place of one attempt must see the same generation) -- and whether this batch counts the memo's hits.
+tkz_status arm_learning(tkz_encoder* e, Workspace* ws, int64_t total, bool first, bool may_learn, hipStream_t stream, TkzTables* T) {
+    using namespace tkz;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        // LEARNING: the first batches of documents on the batch path (and once more, kPromoSecondBytes later; and again whenever the text has drifted:
+        // adapt_after_batch) count the memo's hits per slot.  A learning WINDOW is promo_min_bytes of text: one large batch, or -- TKZ_OPT_ADAPT --
+        // as many smaller ones as it takes (a caller whose batches are 1 MB learns too).
+        // (TKZ_OPT_ADAPT: the rounds go on -- a gigabyte after the first window began, then two, four, eight ... gigabytes after the one before: text that
+        //  changed without moving the miss share, or right behind a promotion, is still learnt, a round costs one batch that counts hits and ~50 ms of a
+        //  host thread; pieces are only ever ADDED by a round -- what empties the list is a drift, or the list reaching its cap: adapt_after_batch)
+        const int64_t round_gap = e->adapt_round_bytes << std::min(std::max(e->promo_rounds - 1, 0), 20);
+        if (first && !ws->learning && may_learn && e->promo_mode == 1 && !e->learning && (e->adapt || e->promo_rounds < kPromoAutoRounds) &&
+            e->T.memo_n != 0 && e->T.max_rank < (int32_t)kPromoFlag && (e->adapt || total >= e->promo_min_bytes) && e->promo_items.size() < e->promo_cap &&
+            (e->promo_rounds == 0 || e->bytes_seen - e->bytes_at_promo >= round_gap)) {
+            // (the gigabyte to the second round counts from the START of the first learning window: a job of 5 GB batches learns in its first two)
+            // The memo is emptied for a window that follows a drift -- it is full of the old text's pieces and takes no new ones --, and that only while
+            // no OTHER call is in flight: an entry never changes once it is valid (tkz_tables.h), which is what makes a hit exact, so the table is
+            // cleared under nobody's feet, synchronously, with the encoder's lock held (16 MB: microseconds, once per drift)
+            bool quiet = true;
+            if (e->memo_clear_pending) for (Workspace* w : e->pool) if (w != ws && w->busy) quiet = false;
+            if (quiet && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
+                e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
+                bool ok = true;
+                if (e->memo_clear_pending) {
+                    ok = hipMemsetAsync(e->t_memo.p, 0, size_t(e->memo_slots) * sizeof(TkzMemoSlot), stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+                    if (ok) e->memo_clear_pending = false;
+                }
+                if (ok) {
+                    ws->learn_window_start = e->learn_bytes == 0;
+                    if (ws->learn_window_start) e->bytes_at_promo = e->bytes_seen;
+                    e->learning = true; ws->learning = true;
+                }
+            }
+        }
+        *T = e->T;
+    }
+    if (ws->learning) {
+        T->memo_hits = e->t_memo_hits.as<uint32_t>();
+        T->memo_hits_sparse = total >= (int64_t(64) << 20) ? 1u : 0u;       // (below 64 MB every hit is counted: a few million atomics at most)
+        if (ws->learn_window_start && first) {                              // (a window's later batches add to its counters and its log)
+            HIP_TRY(hipMemsetAsync(T->memo_hits, 0, (size_t)e->memo_slots * 4, stream));
+            HIP_TRY(hipMemsetAsync(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4, 0, 64, stream));
+        }
+    }
+    return TKZ_OK;
+}
+
+// the workspace's buffers as the kernels see them (the batch path and the single-launch kernel alike)
+tkz::EncodeParams bind_params(Workspace* ws, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs, int64_t total) {
+    using namespace tkz;
+    char* cb = ws->w_counters.as<char>();
+    EncodeParams P{};
+    P.bytes = d_bytes; P.total = total; P.startbits = ws->w_startbits.as<uint64_t>(); P.docbits = ws->w_docbits.as<uint64_t>(); P.nwords = total / 64 + 1;
+    P.offs = d_offs; P.n_docs = n_docs;
+    P.tmp = ws->w_tmp.as<int32_t>(); P.dense = ws->w_dense.as<int32_t>(); P.tile_count = ws->w_tcount.as<int32_t>();
+    P.prank = ws->w_prank.as<int32_t>(); P.prank_cap = (int64_t)(ws->w_prank.cap / 4); P.pcount = ws->w_pcount.as<int32_t>(); P.pbase = ws->w_pbase.as<int64_t>();
+    P.mlist = ws->w_mlist.as<uint32_t>(); P.mquad = ws->w_mquad.as<uint4>(); P.mcap = ws->mcap; P.mcount = ws->w_mcount.as<uint32_t>();
+    P.docord_base = ws->w_dbase.as<int64_t>(); P.doc_tok = ws->w_doctok.as<int32_t>(); P.counters = ws->w_counters.as<int32_t>();
+    P.giant_q = ws->w_gq.as<int64_t>(); P.giant_cap = total / kArenaPiece + 1; P.giant_cnt = ws->w_gcnt.as<int32_t>();
+    P.giant_count = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, heavy_count));
+    P.giant_ticket = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, giant_ticket));
+    P.heavy_flag = ws->w_heavyq.as<uint8_t>(); P.nsub = (total + kSub - 1) / kSub;
+    P.pool = ws->w_pool.as<int32_t>(); P.pool_head = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, pool_head)); P.pool_cap = (int64_t)(ws->w_pool.cap / 4);
+    return P;
+}
+
+#ifdef TKZ_DEVPROF
+unsigned long long* g_devprof = nullptr;   // development builds only (make DEVPROF=1, env TKZ_DEV_ABLATE bit 4)
+tkz_status devprof_arm(tkz::EncodeParams* P, hipStream_t stream) {
+    { const char* ab = getenv("TKZ_DEV_ABLATE"); P->ablate = ab ? atoi(ab) : 0; }
+    if (P->ablate & 16) {
+        if (!g_devprof) { HIP_TRY(hipMalloc((void**)&g_devprof, 64 * 8)); }
+        HIP_TRY(hipMemsetAsync(g_devprof, 0, 64 * 8, stream));
+    }
+    P->devprof = g_devprof;
+    return TKZ_OK;
+}
+tkz_status devprof_report() {
+    if (!g_devprof || !getenv("TKZ_DEV_ABLATE") || !(atoi(getenv("TKZ_DEV_ABLATE")) & 16)) return TKZ_OK;
+    unsigned long long h[64];
+    HIP_TRY(hipMemcpy(h, g_devprof, sizeof h, hipMemcpyDeviceToHost));
+    const double w = h[0] ? (double)h[0] : 1.0;
+    fprintf(stderr, "[tkz devprof] k_probe waves %llu  clock ticks/wave: total %.0f  load+compact %.0f  short batches %.0f  mid batches %.0f | mid pieces/wave %.1f pieces/wave %.1f\n",
+            h[0], h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w);
+    if (h[51]) fprintf(stderr, "[tkz devprof] k_probe lane-cycle table, per sub-tile: load+compact %.0f ticks (64 lanes) | 13+-byte pre-pass %.0f ticks, %.1f pieces in %.2f passes of 64 (lane use %.3f) | main loop: first bucket %.0f ticks at lane use %.3f (%.2f batches of 64, %.1f pieces), second bucket %.0f ticks for %.1f lanes (%.3f of the lanes of the iterations that run it: %.2f of %.2f iterations), records and lists %.0f ticks at lane use %.3f\n",
+                       h[2] / w, h[4] / w, h[5] / w, (double)((h[5] + 63 * h[0]) / 64) / w, h[5] ? (double)h[5] / (64.0 * (double)((h[5] + 63 * h[0]) / 64)) : 0.0,
+                       h[48] / w, (double)h[52] / (64.0 * (double)h[51]), h[51] / w, h[52] / w, h[49] / w, h[53] / w, h[54] ? (double)h[53] / (128.0 * (double)h[54]) : 0.0, h[54] / w, (double)((h[51] + 1) / 2) / w,
+                       h[50] / w, (double)h[52] / (64.0 * (double)h[51]));
+    if (h[8]) fprintf(stderr, "[tkz devprof] k_giant_merge pieces %llu  clock ticks/piece: rounds in global memory %.0f  the tail %.0f | bytes/piece %.0f tokens/piece %.0f | slowest piece %llu ticks | global rounds/piece %.2f | parts/piece when the tail took over %.0f\n",
+                      h[8], (double)h[9] / h[8], (double)h[10] / h[8], (double)h[11] / h[8], (double)h[12] / h[8], h[13], (double)h[14] / h[8], (double)h[7] / h[8]);
+    if (h[8]) fprintf(stderr, "[tkz devprof] slowest giant piece: %llu bytes -> %llu tokens, global rounds %llu (%llu ticks), bytes first/middle/last %02llx %02llx %02llx\n",
+                      h[24], h[27], h[25], h[28], h[29] & 255, (h[29] >> 8) & 255, (h[29] >> 16) & 255);
+    if (h[32]) fprintf(stderr, "[tkz devprof] k_merge_long waves %llu units %llu  ticks/wave %.0f | of all ticks: sort %.3f batch formation %.3f bytes %.3f first level %.3f merges %.3f emission %.3f | fast batches %llu lanes/batch %.1f steps/batch %.1f merges/lane %.2f lane use in the merge loop %.3f ticks/step %.0f\n",
+                       h[32], h[44], (double)h[33] / h[32], (double)h[34] / h[33], (double)h[35] / h[33], (double)h[36] / h[33], (double)h[37] / h[33], (double)h[38] / h[33], (double)h[39] / h[33],
+                       h[40], (double)h[41] / (h[40] ? h[40] : 1), (double)h[42] / (h[40] ? h[40] : 1), (double)h[43] / (h[41] ? h[41] : 1), (double)h[43] / (64.0 * (h[42] ? h[42] : 1)), (double)h[38] / (h[42] ? h[42] : 1));
+    if (h[16]) fprintf(stderr, "[tkz devprof] tail: batches %llu merges %llu (%.2f a batch) proposals/batch %.1f | rounds for chains of equal pairs %llu | ticks/batch %.0f | longest tail: %llu batches, %llu ticks\n",
+                       h[16], h[17], (double)h[17] / h[16], (double)h[18] / h[16], h[19], (double)h[22] / h[16], h[20], h[23]);
+    return TKZ_OK;
+}
+#else
+tkz_status devprof_arm(tkz::EncodeParams*, hipStream_t) { return TKZ_OK; }
+tkz_status devprof_report() { return TKZ_OK; }
+#endif
+
+// One attempt on the stream: the zero region and the text (k_ingest), the document marks and the pre-tokenizer (or, on a re-run, the counters and the
+// sub-tile flags only: it starts behind the pre-tokenizer), the counts of the marks and pieces and their scan, the piece index, then the sizing probe
+// (nsample >= 0) or the whole launch sequence, and the counter block back to the host.
+tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, const TkzTables& T, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs,
+                           int64_t total, int32_t* d_out, int64_t out_cap, int64_t* d_out_offs, bool pretok, uint64_t* d_bitmap_only, PiecesOut* po,
+                           int64_t* d_counts3, const IngestSrc* ingest, bool marks_reused, int64_t nsample, bool* pieces_over) {
+    using namespace tkz;
+    const hipStream_t stream = L.stream;
+    const int64_t nwords = total / 64 + 1, ntiles = (total + kSub - 1) / kSub;
+    int32_t* counters = ws->w_counters.as<int32_t>();
+    char* cb = ws->w_counters.as<char>();
+    uint64_t* docbits = ws->w_docbits.as<uint64_t>();
+    uint64_t* startbits = ws->w_startbits.as<uint64_t>();
+    if (marks_reused) {      // (the counters and the sub-tile flags only)
+        HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, 256, stream));
+        if (!d_bitmap_only) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
+    } else {
+        if (ingest) launch_ingest(L, ingest->h_bytes, total, const_cast<uint8_t*>(d_bytes), ingest->h_offs, n_docs + 1, const_cast<int64_t*>(d_offs), ws->w_zero.p, (int64_t)ws->zero_bytes);
+        // counters, document-start bits, sub-tile flags.  (A chunk of a host batch clears them with a kernel of its own, not a fill command: the runtime's fill is
+        //  a blit kernel that queued behind its D2H blit of the chunk before -- the 16 MB call's second chunk started when the first one's download ended.)
+        else if (ws->zero_bytes <= (size_t(8) << 20)) launch_ingest(L, nullptr, 0, nullptr, nullptr, 0, nullptr, ws->w_zero.p, (int64_t)ws->zero_bytes);
+        else HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, ws->zero_bytes, stream));
+        launch_docmark(L, d_offs, n_docs, total, docbits, counters);
+        if (!pretok) {
+            HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
+        } else if (e->pretok_seq) {
+            HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
+            launch_pretok_seq(L, e->pattern, d_bytes, d_offs, n_docs, total, startbits, T.bmp_class, counters);
+        } else {
+            HIP_TRY(ws->w_xq.ensure((size_t)(nwords / kRowsPerWave + 4) * 16, &ws->bytes_allocated));     // two queues (launch_pretok_rows)
+            launch_pretok_rows(L, e->pattern, d_bytes, d_offs, n_docs, total, docbits, startbits, nwords, T.bmp_class, counters,
+                               ws->w_xq.as<int64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, xcount)));
+        }
+        if (pretok && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, docbits, startbits);
+    }
+    if (d_bitmap_only) {
+        HIP_TRY(hipMemcpyAsync(d_bitmap_only, startbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
+    } else {
+        EncodeParams P = bind_params(ws, d_bytes, d_offs, n_docs, total);
+        // (a batch of at most 16 MB waits for the slowest wavefront of every kernel, not for throughput: TKZ_OPT_LATENCY_BYTES, launch_encode.  Handing its
+        //  pieces of 33..128 bytes to k_merge_coop as well was tried: 115 us in that kernel for what the lanes do in 6 -- a wavefront takes ~30 us a piece)
+        P.lane_piece = kLanePiece;
+        P.latency = total <= e->latency_bytes ? 1 : 0;
+        // (... and in a small batch, whose three merge stages run as ONE launch -- k_merge_latency --, or beside one another: the token counts are summed with atomics)
+        P.tc_atomic = (L.side || P.latency) ? 1 : 0;
+        if (L.side && nsample < 0) ++ws->forked_batches;
+        P.coop_cap = total / P.lane_piece + 64;
+        P.coop_q = ws->w_coopq.as<uint64_t>();
+        P.coop_count = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, coop_count));
+        P.coop_ticket = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, coop_ticket));
+        P.lq_cnt = ws->w_lqcnt.as<int32_t>(); P.lq_base = ws->w_lqbase.as<int64_t>(); P.lq = ws->w_lq.as<uint64_t>(); P.lq_cap = total / (kShortMax + 1) + 64;
+        P.lq_total = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, lq_total)); P.lq_bsum = ws->w_bsum.as<int64_t>();
+        P.miss_sums = reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, miss_short));
+        P.stats = e->piece_stats ? e->t_stats.as<unsigned long long>() : nullptr;
+        // (statistics: an attempt that has to be run again -- lists or records to grow -- must not be counted twice: the block as it was before
+        //  this attempt waits behind it and is put back on a retry)
+        if (P.stats) HIP_TRY(hipMemcpyAsync(e->t_stats.as<char>() + 64, P.stats, 64, hipMemcpyDeviceToDevice, stream));
+        P.place128 = ws->place128 ? 1 : 0;
+        P.promo = T.promo; P.pextra = T.promo ? ws->w_pextra.as<int32_t>() : nullptr;
+        if (ws->learning) {
+            P.long_log = e->t_long_log.as<uint32_t>(); P.long_log_cap = (int32_t)kLongLogCap; P.long_log_sparse = T.memo_hits_sparse ? 1 : 0;
+            P.long_log_count = reinterpret_cast<unsigned long long*>(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4);   // (the encoder's: it runs on through the batches of a window)
+        }
+        TKZ_TRY(devprof_arm(&P, stream));
+        int64_t* ndocstarts = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, ndocstarts));
+        int64_t* npieces = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, npieces));
+        int64_t* grand = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, grand));
+        // piece granularity: the piece-start bitmap takes the place of the document bitmap from here on, so that the encode
+        // kernels record the token position of every PIECE start and k_docoffs yields the token range of every piece
+        const uint64_t* markbits = po ? startbits : docbits;
+        P.docbits = markbits;
+        // the marks (document starts; at piece granularity the piece starts) and the piece starts of every sub-tile, counted in ONE pass over
+        // the two bitmaps and scanned by ONE launch (the piece counts rounded up to whole record lines: where a sub-tile's records live in `prank`)
+        launch_doccount2(L, markbits, startbits, nwords, total, ntiles, ws->w_dcount.as<int32_t>(), ws->w_pcount.as<int32_t>());
+        launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), ws->w_dcount.as<int32_t>(), ws->w_dbase.as<int64_t>(), ndocstarts, 1,
+                     ws->w_pcount.as<int32_t>(), ws->w_pbase.as<int64_t>(), npieces, kRecordLine, -1);
+        if (po) {
+            HIP_TRY(hipMemcpyAsync(&ws->h_counters->ndocstarts, ndocstarts, 8, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            po->n_pieces = ws->h_counters->ndocstarts;                  // piece starts below `total` (a document start is one)
+            // piece arrays too small: the launch sequence still runs to its end (without the piece arrays), so that the caller
+            // learns BOTH required sizes from this one call (tkz.h: *n_pieces and *needed_ids on TKZ_E_CAPACITY)
+            *pieces_over = po->n_pieces > po->piece_cap;
+            if (!*pieces_over) launch_piece_index(L, startbits, nwords, total, ntiles, ws->w_dbase.as<int64_t>(), po->n_pieces, po->piece_boffs, d_offs, n_docs, po->doc_piece);
+        }
+        if (nsample >= 0) {
+            launch_probe_sample(L, T, P, nsample);
+        } else {
+            launch_encode(L, T, P, ntiles);
+            if (P.stats) launch_miss_stats(L, P, ntiles);
+            launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), P.tile_count, ws->w_tbase.as<int64_t>(), grand, 1, nullptr, nullptr, nullptr, 1, K_SCAN);
+            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, d_out, out_cap);
+            if (po) {
+                if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
+                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
+            } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
+                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, d_out_offs,
+                               n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, sizeof(CounterBlock), hipMemcpyDeviceToHost, stream));
+    return TKZ_OK;
+}
+
+// The counter block of an attempt that has run: a failure status for input that is wrong or a buffer that cannot grow; TKZ_OK with *retry when a buffer
+// was grown (or, after the sizing attempt, sized) and the batch runs again; TKZ_OK alone when the batch is done.
+tkz_status check_counters(tkz_encoder* e, Workspace* ws, hipStream_t stream, int64_t total, int attempt, int64_t nsample, bool bitmap_only, bool* retry) {
+    using namespace tkz;
+    const CounterBlock& c = *ws->h_counters;
+    const int64_t ntiles = (total + kSub - 1) / kSub;
+    int64_t* acc = &ws->bytes_allocated;
+    const int32_t err = c.err;
+    *retry = false;
+    if (err & kErrOffsets) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count");
+    if (err & kErrUtf8) return fail(TKZ_E_INVALID_UTF8, "input is not well-formed UTF-8 (or a document boundary falls inside a character)");
+    if (err & kErrTooLong) return fail(TKZ_E_UNSUPPORTED, "a single piece longer than 2^30 bytes");
+    // (what is wrong from here on is the size of a buffer)
+    if (!bitmap_only) ws->sized = true;
+    if (!bitmap_only && nsample < 0 && total > e->latency_bytes) {      // (the next batch's form of the long pieces' kernels: side_streams)
+        ws->last_coop = (int64_t)c.coop_count;
+        ws->last_lq_total = c.lq_total;
+    }
+    // k_place's form for THIS batch from the sample (it is otherwise chosen from the batch before: a fresh encoder's first miss-heavy batch ran
+    // k_place<64> with most sub-tiles on its general path, 11.7 ms against 7)
+    if (nsample >= 0 && (int64_t)c.over64 * 5 > nsample) { ws->place128 = true; ws->low_place = 0; }
+    const bool last = attempt >= 4;
+    if (err & kErrPool) {
+        if (last) return fail(TKZ_E_OUT_OF_MEMORY, "long-piece scratch exhausted");
+        // scratch for the giant pieces was too small.  pool_head keeps counting past the capacity, so it holds the exact need
+        // (6 int32 per byte of every giant piece of the batch): size the pool for that -- not for the whole batch -- and rerun
+        const size_t need = (size_t)c.pool_head * 4 + 4096;
+        if (ws->w_pool.ensure(need, acc) != hipSuccess)
+            return fail(TKZ_E_OUT_OF_MEMORY, "scratch for the pieces longer than 1024 bytes: " + std::to_string(need) + " bytes could not be allocated");
+    } else if (err & kErrMissCap) {
+        if (last) return fail(TKZ_E_DEVICE, "miss list overflow");
+        // a sub-tile missed more pieces than its list holds (text where nearly every piece misses the vocabulary): the longest list
+        // any sub-tile needed is known now -- longer lists for this workspace from here on, and the batch again
+        int32_t want = kMissCapMin;
+        while (want < c.mneed && want < kMissCapMax) want *= 2;
+        if (want <= ws->mcap) return fail(TKZ_E_DEVICE, "miss list overflow");
+        if (ws->w_mlist.ensure((size_t)ntiles * (size_t)want * 4, acc) != hipSuccess || ws->w_mquad.ensure((size_t)ntiles * (size_t)want * 16, acc) != hipSuccess)
+            return fail(TKZ_E_OUT_OF_MEMORY, "miss lists: " + std::to_string((size_t)ntiles * (size_t)want * 20) + " bytes could not be allocated");
+        ws->mcap = want;
+    } else if (err & kErrCapacity) {          // more pieces than the record buffer was sized for: the exact count is known now
+        if (last) return fail(TKZ_E_DEVICE, "piece record buffer overflow");
+        const size_t need = ((size_t)c.npieces + 4096) * 4;
+        if (ws->w_prank.ensure(need, acc) != hipSuccess)
+            return fail(TKZ_E_OUT_OF_MEMORY, "piece records: " + std::to_string(need) + " bytes could not be allocated");
+    } else if (nsample >= 0) {                // (the sample fitted the lists as they are; the records are counted exactly by the scan)
+        const size_t need = ((size_t)c.npieces + 4096) * 4;
+        if (need > ws->w_prank.cap && ws->w_prank.ensure(need, acc) != hipSuccess)
+            return fail(TKZ_E_OUT_OF_MEMORY, "piece records: " + std::to_string(need) + " bytes could not be allocated");
+    } else {
+        if (err & kErrKeyNotFound) return fail(TKZ_E_KEY_NOT_FOUND, "a byte of the input is not in the vocabulary (KeyNotFoundException in the reference)");
+        if (!bitmap_only && e->piece_stats) {
+            std::lock_guard<std::mutex> lock(e->mu);
+            ++e->stat_batches; e->stat_giants += (int64_t)c.heavy_count;
+        }
+        return TKZ_OK;
+    }
+    // the statistics block as it was before this attempt (enqueue_attempt): the batch is counted once
+    if (e->piece_stats && e->t_stats.p && !bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
+    *retry = true;
+    return TKZ_OK;
+}
+
+// Growing is immediate, shrinking waits for kLowBatches consecutive batches that would have done with less (the round-4 advisor: a
+// workspace that alternates miss-heavy and ordinary batches -- or the 48 MB chunks of one host call that does -- must not overflow,
+// re-run, free and re-allocate on every other batch).
+void settle_workspace(Workspace* ws, int64_t ntiles) {
+    using namespace tkz;
+    constexpr int kLowBatches = 3;
+    const bool heavy = (int64_t)ws->h_counters->over64 * 5 > ntiles;      // (more than a fifth of the sub-tiles: the next batches' k_place)
+    if (heavy) { ws->place128 = true; ws->low_place = 0; }
+    else if (ws->place128 && ++ws->low_place >= kLowBatches) { ws->place128 = false; ws->low_place = 0; }
+    if (ws->mcap <= kMissCapMin) return;
+    // lists that were grown for an earlier batch (text where nearly every piece misses) and that the last kLowBatches batches filled to
+    // less than half: half as long from here on (one step at a time), and the buffers given back when they are far larger than such
+    // batches need (the lists are ntiles * mcap * 20 bytes: 1.25 B per input byte at 64 entries, 20 B at 1024)
+    int32_t want = kMissCapMin;
+    while (want < ws->h_counters->mhigh) want *= 2;
+    if (want >= ws->mcap) ws->low_lists = 0;
+    else if (++ws->low_lists >= kLowBatches) {
+        ws->low_lists = 0;
+        ws->mcap = std::max(want, ws->mcap / 2);
+        if (ws->w_mquad.cap > (size_t)ntiles * (size_t)ws->mcap * 16 * 4) {
+            ws->bytes_allocated -= (int64_t)(ws->w_mquad.cap + ws->w_mlist.cap);
+            ws->w_mquad.release(); ws->w_mlist.release();
+        }
+    }
+}
+
+// a learning window's promotion, or the drop of the promotions for a re-learn: on a thread of its own behind the batch (after_batch)
+void promote_or_drop(tkz_encoder* e, bool promote) {
+    DeviceScope scope;
+    const bool dev = scope.enter(e->device) == hipSuccess;
+    if (promote) {
+        int64_t added = 0;
+        size_t held;
+        { std::lock_guard<std::mutex> lock(e->mu); held = e->promo_items.size(); }
+        if (dev) (void)promote_from_memo(e, true, true, &added);   // (a failure leaves the tables as they were)
+        std::lock_guard<std::mutex> lock(e->mu);
+        e->learning = false; ++e->promo_rounds; ++e->n_promotions;
+        // A round that found much it did not know -- more than a tenth of what the list held -- is a young encoder, or text that CHANGED without the miss
+        // share having had a settled level to leave (the change fell between two installs): the next round then follows a gigabyte later, not
+        // 2^rounds gigabytes.  (bench.py's drift leg, synthetic -> real text: the steps beyond 2 GB ran at 0.81 of an encoder that only ever saw
+        // the real text, whose second round comes after 1 GB while this one's was 4 GB away.)
+        if (e->adapt && e->promo_rounds > 1 && (size_t)added * 10 > held) e->promo_rounds = 1;
+        e->bytes_at_install = e->bytes_seen; e->ew_valid = e->base_valid = false;
+    } else {
+        if (dev) (void)drop_promotions(e, true);
+        std::lock_guard<std::mutex> lock(e->mu);
+        e->learning = false; e->promo_rounds = 0; e->learn_bytes = 0; e->memo_clear_pending = true; ++e->n_relearns;
+        e->bytes_at_install = e->bytes_at_promo = e->bytes_seen; e->ew_valid = e->base_valid = e->window_valid = e->last_window_valid = false; e->win_miss = e->win_pieces = 0;
+    }
+}
+
+// The batch is done: if it completes a learning window, the hottest entries are promoted now (the copy of the memo back to the host and the
+// rebuilt key tables cost tens of milliseconds: on a thread, behind the batch); else the share of pieces that missed the key tables is
+// compared with what it was after the last promotion (adapt_after_batch)
+void after_batch(tkz_encoder* e, Workspace* ws, int64_t total) {
+    const CounterBlock& c = *ws->h_counters;
+    bool promote = false, relearn = false;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        e->bytes_seen += total;
+        if (ws->learning) {
+            e->learn_bytes += total;
+            e->win_miss += (double)(c.miss_short + c.miss_long); e->win_pieces += (double)c.npieces;
+            promote = !e->adapt || e->learn_bytes >= e->promo_min_bytes;
+            if (!promote) { ws->learning = false; e->learning = false; }      // (the window goes on with the next batch)
+            else if (e->adapt && e->last_window_valid && e->win_pieces >= 1 && e->win_miss / e->win_pieces > e->last_window_miss * 1.25 + 0.01) {
+                // A window whose miss share is a quarter (and a point) ABOVE the window's before it -- although that one's promotions have been installed since,
+                // and promotions only lower the share on unchanged text -- was counted on ANOTHER text, with a memo full of the old one's pieces (it takes no
+                // new entry into a full bucket): what it found is a fraction of what a fresh encoder finds (2 k against 9 k pieces on the source text behind 3 GB
+                // of synthetic text).  A drift: start over -- this window's counts are dropped with the promotions, the memo is emptied, the next batch begins a window.
+                promote = false; relearn = true; ws->learning = false;
+                e->learn_bytes = 0; e->win_miss = e->win_pieces = 0;
+            }
+        } else relearn = adapt_after_batch(e, total, (double)(c.miss_short + c.miss_long), (double)c.npieces);
+        if (relearn) e->learning = true;                                     // (nothing learns while the promotions are being dropped)
+    }
+    if (!promote && !relearn) return;
+    if (promote) {
+        std::lock_guard<std::mutex> lock(e->mu);
+        ws->learning = false; e->learn_bytes = 0;
+        e->window_valid = e->win_pieces >= 1; e->window_miss = e->window_valid ? e->win_miss / e->win_pieces : 0; e->win_miss = e->win_pieces = 0;
+        e->last_window_valid = e->window_valid; e->last_window_miss = e->window_miss;
+    }
+    // (the workspace is this call's no longer once it returns; the counters, the log and the memo are the encoder's, and no other batch writes the
+    //  first two while e->learning is set)
+    join_promotion(e);                 // (the previous one ended before this batch could be armed: this only reaps the thread)
+    bool started = false;
+    {
+        std::lock_guard<std::mutex> jl(e->promo_join_mu);
+        try { e->promo_thread = std::thread(promote_or_drop, e, promote); started = true; } catch (...) {}      // (no thread to be had: built here, as before round 5)
+    }
+    if (!started) { const std::string keep_msg = g_err; promote_or_drop(e, promote); g_err = keep_msg; }
+}
+
+// The batch on the device; when pretok == false every "document" is taken as one piece.
+// phase: kCallWhole -- enqueue, wait, evaluate (and again if a buffer had to grow); kCallBegin -- enqueue the first attempt and
+// return; kCallEnd -- wait for that attempt, evaluate, and carry on as kCallWhole does (tkz_encode_batch_device_begin / _end)
 tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs, int64_t total,
                          int32_t* d_out, int64_t out_cap, int64_t* d_out_offs, hipStream_t stream, bool pretok,
                          uint64_t* d_bitmap_only, int64_t* total_tokens, PiecesOut* po = nullptr, int phase = kCallWhole, int64_t* d_counts3 = nullptr,
                          const IngestSrc* ingest = nullptr) {
-    // phase: kCallWhole -- enqueue, wait, evaluate (and again if a buffer had to grow); kCallBegin -- enqueue the first attempt and
-    // return; kCallEnd -- wait for that attempt, evaluate, and carry on as kCallWhole does (tkz_encode_batch_device_begin / _end)
     using namespace tkz;
     if (n_docs < 0 || total < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
     if (total_tokens) *total_tokens = 0;
     if (n_docs == 0 && total != 0) return fail(TKZ_E_ARG, "bytes without documents");
-    const int64_t nwords = total / 64 + 1;
     if (total == 0) {
         if (phase != kCallEnd) {                                  // (kCallEnd: enqueued when it began)
-            int64_t* acc0 = &ws->bytes_allocated;
-            HIP_TRY(ws->w_counts3.ensure(32, acc0));
-            { tkz::Launch L0{stream, nullptr, ws}; tkz::launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3); }
+            HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
+            { Launch L0{stream, nullptr, ws}; launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3); }
             if (d_out_offs) HIP_TRY(hipMemsetAsync(d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
             if (d_bitmap_only) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(d_bitmap_only, &one, 8, hipMemcpyHostToDevice, stream)); }
             if (phase == kCallBegin) return TKZ_OK;               // (_begin returns without waiting)
@@ -676,8 +1075,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
     }
     const int64_t ntiles = (total + kSub - 1) / kSub;       // sub-tiles: one wavefront each
     SlowCallLog slow_log(total);
-    { const tkz_status ps = prepare_workspace(ws, total, n_docs, d_bitmap_only != nullptr, po != nullptr); if (ps != TKZ_OK) return ps; }
-    int64_t* acc = &ws->bytes_allocated;
+    TKZ_TRY(prepare_workspace(ws, total, n_docs, d_bitmap_only != nullptr, po != nullptr));
     if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
 
     // a learning batch that ends any other way than with its promotion gives the encoder's one learning slot back
@@ -691,381 +1089,32 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
     for (int attempt = 0; attempt < 5; ++attempt) {
         slow_log.attempts = attempt + 1;
         bool pieces_over = false;
-        // THE SIZING ATTEMPT: a fresh workspace's first large batch probes a sixteenth of its sub-tiles first.  How long the miss lists must be (and, from the
-        // scan, how many records there are) is known after ~1 ms instead of after a whole attempt up to k_probe that is thrown away: a fresh encoder's first
-        // batch of text its vocabulary has not seen (5.1 GB, held-out vocabulary) went from 100 ms to ~50.  The full attempt follows on the same bitmaps; a
-        // sample that under-estimates leaves the ordinary retry.
-        int64_t kSizingMinSub = (int64_t(64) << 20) / kSub;                     // (64 MB of text; TKZ_SIZING_MIN_SUB: the tests' handle on it)
-        if (attempt == 0 && !ws->sized) { const char* v = getenv("TKZ_SIZING_MIN_SUB"); if (v && atoll(v) > 0) kSizingMinSub = atoll(v); }
-        const bool sizing = attempt == 0 && phase == kCallWhole && !ws->sized && pretok && !d_bitmap_only && !po && (total + kSub - 1) / kSub >= kSizingMinSub;
+        const int64_t nsample = attempt == 0 && phase == kCallWhole && !ws->sized && pretok && !d_bitmap_only && !po ? sizing_sample(ntiles) : -1;
         const bool marks_reused = marks_ready;
         Launch L{stream, e->profiling ? prof_hook : nullptr, ws};
-        // a large batch: two more streams, for the two kernels of the long pieces that last as long as their slowest wavefront (launch_encode runs them beside k_merge_short;
-        // without the streams -- the runtime refused one, or an event -- they follow it as they always did)
-        static const bool kNoFork = getenv("TKZ_NO_FORK") != nullptr;          // (development: A/B of the forked form)
-        static const int kSideLong = [] { const char* v = getenv("TKZ_SIDE_LONG_GRID"); return v ? atoi(v) : 2048; }();
-        static const int kSideCoop = [] { const char* v = getenv("TKZ_SIDE_COOP_GRID"); return v ? atoi(v) : 1024; }();
-        // WHEN: the workspace's previous batch left a class queue short enough for its kernel to be a matter of latency -- at most kForkMaxLong entries, ~4 batches of 64 for
-        // each of the 4,096 wavefronts the chip holds --; with a long queue (mixed text: 17 M entries in 1 GB) the queue kernel is the step's largest and needs the whole chip
-        // (measured with the tail grids: 17.0 -> 19.8 ms), and on the bench text (1.3 M) the two forms are equal (20.6 / 20.8 ms).
-        static const int64_t kForkMaxLong = [] { const char* v = getenv("TKZ_FORK_MAX_LONG"); return v ? (int64_t)atoll(v) : int64_t(1) << 20; }();
-        // (round 6, last session) ... or up to twice that many when one in 2,048 of them is a piece of more than 128 bytes: such a queue ends in a tail of slow wavefronts
-        // whatever its length.  436 MB of source text (1.18 M long misses, 1,467 of them of 129+ bytes): 94.5 -> 104.3 GB/s side by side; the bench text (1.31-1.43 M, none
-        // above 128 bytes) loses 0.1-0.3 ms that way and stays serial.  profiles/r06/variants_side_by_side2.txt
-        static const int64_t kForkMaxLongTail = [] { const char* v = getenv("TKZ_FORK_MAX_LONG_TAIL"); return v ? (int64_t)atoll(v) : int64_t(1) << 21; }();
-        static const int64_t kForkTailShare = [] { const char* v = getenv("TKZ_FORK_TAIL_SHARE"); return v && atoll(v) > 0 ? (int64_t)atoll(v) : int64_t(2048); }();
-        static const bool kTraceFork = getenv("TKZ_TRACE_FORK") != nullptr;
-        if (kTraceFork && attempt == 0 && total > e->latency_bytes) fprintf(stderr, "[tkz fork] bytes %lld: the batch before left %lld long misses, %lld of more than 128 bytes\n", (long long)total, (long long)ws->last_lq_total, (long long)ws->last_coop);
-        const bool short_queue = ws->last_lq_total >= 0 && (ws->last_lq_total <= kForkMaxLong || (ws->last_lq_total <= kForkMaxLongTail && ws->last_coop * kForkTailShare >= ws->last_lq_total));
-        if (total > e->latency_bytes && !kNoFork && short_queue) {
-            if (!ws->fork_token) { int none = 0; ws->fork_token = g_fork_in_flight.compare_exchange_strong(none, 1); }      // (given back when the call ends: ~Lease)
-            bool ok = ws->fork_token;
-            for (hipStream_t* st : {&ws->st_side, &ws->st_side2}) if (!*st && hipStreamCreateWithFlags(st, hipStreamNonBlocking) != hipSuccess) { *st = nullptr; ok = false; }
-            for (hipEvent_t* ev : {&ws->ev_fork, &ws->ev_join, &ws->ev_join2}) if (!*ev && hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { *ev = nullptr; ok = false; }
-            if (ok) { L.side = ws->st_side; L.side2 = ws->st_side2; L.ev_fork = ws->ev_fork; L.ev_join = ws->ev_join; L.ev_join2 = ws->ev_join2; L.side_long_grid = kSideLong; L.side_coop_grid = kSideCoop; }
-            else (void)hipGetLastError();
-        }
-        int32_t* counters = ws->w_counters.as<int32_t>();
+        side_streams(e, ws, total, &L);
         if (!(phase == kCallEnd && attempt == 0)) {              // (kCallEnd: the first attempt is in flight already)
-        // the tables as they are NOW, one consistent copy for the whole attempt (a promotion at the end of another call's batch replaces the
-        // SHORT / MID images and the promo array together: k_probe and k_place of one attempt must see the same generation)
-        TkzTables T;
-        {
-            std::lock_guard<std::mutex> lock(e->mu);
-            // LEARNING: the first batches of documents on the batch path (and once more, kPromoSecondBytes later; and again whenever the text has drifted:
-            // adapt_after_batch below) count the memo's hits per slot.  A learning WINDOW is promo_min_bytes of text: one large batch, or -- TKZ_OPT_ADAPT --
-            // as many smaller ones as it takes (a caller whose batches are 1 MB learns too).
-            // (TKZ_OPT_ADAPT: the rounds go on -- a gigabyte after the first window began, then two, four, eight ... gigabytes after the one before: text that
-            //  changed without moving the miss share, or right behind a promotion, is still learnt, a round costs one batch that counts hits and ~50 ms of a
-            //  host thread; pieces are only ever ADDED by a round -- what empties the list is a drift, or the list reaching its cap: adapt_after_batch)
-            const int64_t round_gap = e->adapt_round_bytes << std::min(std::max(e->promo_rounds - 1, 0), 20);
-            if (attempt == 0 && !ws->learning && pretok && !d_bitmap_only && e->promo_mode == 1 && !e->learning && (e->adapt || e->promo_rounds < kPromoAutoRounds) &&
-                e->T.memo_n != 0 && e->T.max_rank < (int32_t)kPromoFlag && (e->adapt || total >= e->promo_min_bytes) && e->promo_items.size() < e->promo_cap &&
-                (e->promo_rounds == 0 || e->bytes_seen - e->bytes_at_promo >= round_gap)) {
-                // (the gigabyte to the second round counts from the START of the first learning window: a job of 5 GB batches learns in its first two)
-                // The memo is emptied for a window that follows a drift -- it is full of the old text's pieces and takes no new ones --, and that only while
-                // no OTHER call is in flight: an entry never changes once it is valid (tkz_tables.h), which is what makes a hit exact, so the table is
-                // cleared under nobody's feet, synchronously, with the encoder's lock held (16 MB: microseconds, once per drift)
-                bool quiet = true;
-                if (e->memo_clear_pending) for (Workspace* w : e->pool) if (w != ws && w->busy) quiet = false;
-                if (quiet && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
-                    e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
-                    bool ok = true;
-                    if (e->memo_clear_pending) {
-                        ok = hipMemsetAsync(e->t_memo.p, 0, size_t(e->memo_slots) * sizeof(TkzMemoSlot), stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-                        if (ok) e->memo_clear_pending = false;
-                    }
-                    if (ok) {
-                        ws->learn_window_start = e->learn_bytes == 0;
-                        if (ws->learn_window_start) e->bytes_at_promo = e->bytes_seen;
-                        e->learning = true; ws->learning = true;
-                    }
-                }
-            }
-            T = e->T;
-        }
-        if (ws->learning) {
-            T.memo_hits = e->t_memo_hits.as<uint32_t>();
-            T.memo_hits_sparse = total >= (int64_t(64) << 20) ? 1u : 0u;       // (below 64 MB every hit is counted: a few million atomics at most)
-            if (ws->learn_window_start && attempt == 0) {                       // (a window's later batches add to its counters and its log)
-                HIP_TRY(hipMemsetAsync(T.memo_hits, 0, (size_t)e->memo_slots * 4, stream));
-                HIP_TRY(hipMemsetAsync(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4, 0, 64, stream));
-            }
-        }
-        int64_t* grand = reinterpret_cast<int64_t*>(ws->w_counters.as<char>() + offsetof(CounterBlock, grand));
-        unsigned long long* pool_head = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, pool_head));
-        uint64_t* docbits = ws->w_docbits.as<uint64_t>();
-        uint64_t* startbits = ws->w_startbits.as<uint64_t>();
-        if (marks_reused) {      // (the counters and the sub-tile flags only)
-            HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, 256, stream));
-            if (!d_bitmap_only) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
-        } else {
-        if (ingest) launch_ingest(L, ingest->h_bytes, total, const_cast<uint8_t*>(d_bytes), ingest->h_offs, n_docs + 1, const_cast<int64_t*>(d_offs), ws->w_zero.p, (int64_t)ws->zero_bytes);
-        // counters, document-start bits, sub-tile flags.  (A chunk of a host batch clears them with a kernel of its own, not a fill command: the runtime's fill is
-        //  a blit kernel that queued behind its D2H blit of the chunk before -- the 16 MB call's second chunk started when the first one's download ended.)
-        else if (ws->zero_bytes <= (size_t(8) << 20)) launch_ingest(L, nullptr, 0, nullptr, nullptr, 0, nullptr, ws->w_zero.p, (int64_t)ws->zero_bytes);
-        else HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, ws->zero_bytes, stream));
-        launch_docmark(L, d_offs, n_docs, total, docbits, counters);
-        if (!pretok) {
-            HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
-        } else if (e->pretok_seq) {
-            HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
-            launch_pretok_seq(L, e->pattern, d_bytes, d_offs, n_docs, total, startbits, T.bmp_class, counters);
-        } else {
-            HIP_TRY(ws->w_xq.ensure((size_t)(nwords / kRowsPerWave + 4) * 16, acc));     // two queues (launch_pretok_rows)
-            launch_pretok_rows(L, e->pattern, d_bytes, d_offs, n_docs, total, docbits, startbits, nwords, T.bmp_class, counters,
-                               ws->w_xq.as<int64_t>(), reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, xcount)));
-        }
-        if (pretok && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, docbits, startbits);
-        }
-        if (d_bitmap_only) {
-            HIP_TRY(hipMemcpyAsync(d_bitmap_only, startbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
-        } else {
-            EncodeParams P{};
-            P.bytes = d_bytes; P.total = total; P.startbits = startbits; P.docbits = docbits; P.nwords = nwords;
-            P.offs = d_offs; P.n_docs = n_docs;
-            P.tmp = ws->w_tmp.as<int32_t>(); P.dense = ws->w_dense.as<int32_t>(); P.tile_count = ws->w_tcount.as<int32_t>();
-            P.prank = ws->w_prank.as<int32_t>(); P.prank_cap = (int64_t)(ws->w_prank.cap / 4); P.pcount = ws->w_pcount.as<int32_t>(); P.pbase = ws->w_pbase.as<int64_t>();
-            P.mlist = ws->w_mlist.as<uint32_t>(); P.mquad = ws->w_mquad.as<uint4>(); P.mcap = ws->mcap; P.mcount = ws->w_mcount.as<uint32_t>();
-            P.docord_base = ws->w_dbase.as<int64_t>(); P.doc_tok = ws->w_doctok.as<int32_t>(); P.counters = counters;
-            P.giant_q = ws->w_gq.as<int64_t>(); P.giant_cap = total / kArenaPiece + 1; P.giant_cnt = ws->w_gcnt.as<int32_t>();
-            P.giant_count = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, heavy_count));
-            P.giant_ticket = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, giant_ticket));
-            P.heavy_flag = ws->w_heavyq.as<uint8_t>(); P.nsub = ntiles;
-            // (a batch of at most 16 MB waits for the slowest wavefront of every kernel, not for throughput: TKZ_OPT_LATENCY_BYTES, launch_encode.  Handing its
-            //  pieces of 33..128 bytes to k_merge_coop as well was tried: 115 us in that kernel for what the lanes do in 6 -- a wavefront takes ~30 us a piece)
-            P.lane_piece = kLanePiece;
-            P.latency = total <= e->latency_bytes ? 1 : 0;
-            // (... and in a small batch, whose three merge stages run as ONE launch: k_merge_latency.  $TKZ_NO_LATENCY_FUSE: the three launches, development A/B)
-            static const bool kNoLatencyFuse = getenv("TKZ_NO_LATENCY_FUSE") != nullptr;
-            P.tc_atomic = (L.side || (P.latency && !kNoLatencyFuse)) ? 1 : 0;
-            if (L.side && !sizing) ++ws->forked_batches;
-            P.coop_cap = total / P.lane_piece + 64;
-            HIP_TRY(ws->w_coopq.ensure((size_t)P.coop_cap * 8, acc));
-            P.coop_q = ws->w_coopq.as<uint64_t>();
-            P.coop_count = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, coop_count));
-            P.coop_ticket = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, coop_ticket));
-            P.pool = ws->w_pool.as<int32_t>(); P.pool_head = pool_head; P.pool_cap = (int64_t)(ws->w_pool.cap / 4);
-            P.lq_cnt = ws->w_lqcnt.as<int32_t>(); P.lq_base = ws->w_lqbase.as<int64_t>(); P.lq = ws->w_lq.as<uint64_t>(); P.lq_cap = total / (kShortMax + 1) + 64;
-            P.lq_total = reinterpret_cast<int64_t*>(ws->w_counters.as<char>() + offsetof(CounterBlock, lq_total)); P.lq_bsum = ws->w_bsum.as<int64_t>();
-            P.miss_sums = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, miss_short));
-            P.ablate = 0; P.devprof = nullptr;
-            P.stats = e->piece_stats ? e->t_stats.as<unsigned long long>() : nullptr;
-            // (statistics: an attempt that has to be run again -- lists or records to grow -- must not be counted twice: the block as it was before
-            //  this attempt waits behind it and is put back on a retry)
-            if (P.stats) HIP_TRY(hipMemcpyAsync(e->t_stats.as<char>() + 64, P.stats, 64, hipMemcpyDeviceToDevice, stream));
-            P.place128 = ws->place128 ? 1 : 0;
-            P.promo = T.promo; P.pextra = T.promo ? ws->w_pextra.as<int32_t>() : nullptr;
-            if (ws->learning) {
-                P.long_log = e->t_long_log.as<uint32_t>(); P.long_log_cap = (int32_t)kLongLogCap; P.long_log_sparse = T.memo_hits_sparse ? 1 : 0;
-                P.long_log_count = reinterpret_cast<unsigned long long*>(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4);   // (the encoder's: it runs on through the batches of a window)
-            }
-#ifdef TKZ_DEVPROF
-            { const char* ab = getenv("TKZ_DEV_ABLATE"); P.ablate = ab ? atoi(ab) : 0; }
-            if (P.ablate & 16) {
-                if (!g_devprof) { HIP_TRY(hipMalloc((void**)&g_devprof, 64 * 8)); }
-                HIP_TRY(hipMemsetAsync(g_devprof, 0, 64 * 8, stream));
-            }
-            P.devprof = g_devprof;
-#endif
-            int64_t* ndocstarts = reinterpret_cast<int64_t*>(ws->w_counters.as<char>() + offsetof(CounterBlock, ndocstarts));
-            // piece granularity: the piece-start bitmap takes the place of the document bitmap from here on, so that the encode
-            // kernels record the token position of every PIECE start and k_docoffs yields the token range of every piece
-            const uint64_t* markbits = po ? startbits : docbits;
-            P.docbits = markbits;
-            int64_t* npieces = reinterpret_cast<int64_t*>(ws->w_counters.as<char>() + offsetof(CounterBlock, npieces));
-            // the marks (document starts; at piece granularity the piece starts) and the piece starts of every sub-tile, counted in ONE pass over
-            // the two bitmaps and scanned by ONE launch (the piece counts rounded up to whole record lines: where a sub-tile's records live in `prank`)
-            launch_doccount2(L, markbits, startbits, nwords, total, ntiles, ws->w_dcount.as<int32_t>(), ws->w_pcount.as<int32_t>());
-            launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), ws->w_dcount.as<int32_t>(), ws->w_dbase.as<int64_t>(), ndocstarts, 1,
-                         ws->w_pcount.as<int32_t>(), ws->w_pbase.as<int64_t>(), npieces, kRecordLine, -1);
-            if (po) {
-                int64_t np = 0;
-                HIP_TRY(hipMemcpyAsync(&ws->h_counters->ndocstarts, ndocstarts, 8, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                np = ws->h_counters->ndocstarts;                  // piece starts below `total` (a document start is one)
-                po->n_pieces = np;
-                // piece arrays too small: the launch sequence still runs to its end (without the piece arrays), so that the caller
-                // learns BOTH required sizes from this one call (tkz.h: *n_pieces and *needed_ids on TKZ_E_CAPACITY)
-                pieces_over = np > po->piece_cap;
-                if (!pieces_over) launch_piece_index(L, startbits, nwords, total, ntiles, ws->w_dbase.as<int64_t>(), np, po->piece_boffs, d_offs, n_docs, po->doc_piece);
-            }
-            if (sizing) {
-                launch_probe_sample(L, T, P, std::min<int64_t>(ntiles, std::max<int64_t>(ntiles / 16, kSizingMinSub / 16)));
-            } else {
-            launch_encode(L, T, P, ntiles);
-            if (P.stats) launch_miss_stats(L, P, ntiles);
-            launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), P.tile_count, ws->w_tbase.as<int64_t>(), grand, 1, nullptr, nullptr, nullptr, 1, K_SCAN);
-            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, d_out, out_cap);
-            if (po) {
-                if (!pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
-                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
-            } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
-                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, d_out_offs,
-                               n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, sizeof(CounterBlock), hipMemcpyDeviceToHost, stream));
+            TkzTables T;
+            TKZ_TRY(arm_learning(e, ws, total, attempt == 0, pretok && !d_bitmap_only, stream, &T));
+            TKZ_TRY(enqueue_attempt(e, ws, L, T, d_bytes, d_offs, n_docs, total, d_out, out_cap, d_out_offs, pretok, d_bitmap_only, po, d_counts3, ingest,
+                                    marks_reused, nsample, &pieces_over));
         }
         if (phase == kCallBegin) { learn_guard.keep = true; return TKZ_OK; }
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipGetLastError());
         if (e->profiling) prof_collect(ws);
-#ifdef TKZ_DEVPROF
-        if (g_devprof && getenv("TKZ_DEV_ABLATE") && (atoi(getenv("TKZ_DEV_ABLATE")) & 16) && !d_bitmap_only) {
-            unsigned long long h[64];
-            HIP_TRY(hipMemcpy(h, g_devprof, sizeof h, hipMemcpyDeviceToHost));
-            const double w = h[0] ? (double)h[0] : 1.0;
-            fprintf(stderr, "[tkz devprof] k_probe waves %llu  clock ticks/wave: total %.0f  load+compact %.0f  short batches %.0f  mid batches %.0f | mid pieces/wave %.1f pieces/wave %.1f\n",
-                    h[0], h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w);
-            if (h[51]) fprintf(stderr, "[tkz devprof] k_probe lane-cycle table, per sub-tile: load+compact %.0f ticks (64 lanes) | 13+-byte pre-pass %.0f ticks, %.1f pieces in %.2f passes of 64 (lane use %.3f) | main loop: first bucket %.0f ticks at lane use %.3f (%.2f batches of 64, %.1f pieces), second bucket %.0f ticks for %.1f lanes (%.3f of the lanes of the iterations that run it: %.2f of %.2f iterations), records and lists %.0f ticks at lane use %.3f\n",
-                               h[2] / w, h[4] / w, h[5] / w, (double)((h[5] + 63 * h[0]) / 64) / w, h[5] ? (double)h[5] / (64.0 * (double)((h[5] + 63 * h[0]) / 64)) : 0.0,
-                               h[48] / w, (double)h[52] / (64.0 * (double)h[51]), h[51] / w, h[52] / w, h[49] / w, h[53] / w, h[54] ? (double)h[53] / (128.0 * (double)h[54]) : 0.0, h[54] / w, (double)((h[51] + 1) / 2) / w,
-                               h[50] / w, (double)h[52] / (64.0 * (double)h[51]));
-            if (h[8]) fprintf(stderr, "[tkz devprof] k_giant_merge pieces %llu  clock ticks/piece: rounds in global memory %.0f  the tail %.0f | bytes/piece %.0f tokens/piece %.0f | slowest piece %llu ticks | global rounds/piece %.2f | parts/piece when the tail took over %.0f\n",
-                              h[8], (double)h[9] / h[8], (double)h[10] / h[8], (double)h[11] / h[8], (double)h[12] / h[8], h[13], (double)h[14] / h[8], (double)h[7] / h[8]);
-            if (h[8]) fprintf(stderr, "[tkz devprof] slowest giant piece: %llu bytes -> %llu tokens, global rounds %llu (%llu ticks), bytes first/middle/last %02llx %02llx %02llx\n",
-                              h[24], h[27], h[25], h[28], h[29] & 255, (h[29] >> 8) & 255, (h[29] >> 16) & 255);
-            if (h[32]) fprintf(stderr, "[tkz devprof] k_merge_long waves %llu units %llu  ticks/wave %.0f | of all ticks: sort %.3f batch formation %.3f bytes %.3f first level %.3f merges %.3f emission %.3f | fast batches %llu lanes/batch %.1f steps/batch %.1f merges/lane %.2f lane use in the merge loop %.3f ticks/step %.0f\n",
-                               h[32], h[44], (double)h[33] / h[32], (double)h[34] / h[33], (double)h[35] / h[33], (double)h[36] / h[33], (double)h[37] / h[33], (double)h[38] / h[33], (double)h[39] / h[33],
-                               h[40], (double)h[41] / (h[40] ? h[40] : 1), (double)h[42] / (h[40] ? h[40] : 1), (double)h[43] / (h[41] ? h[41] : 1), (double)h[43] / (64.0 * (h[42] ? h[42] : 1)), (double)h[38] / (h[42] ? h[42] : 1));
-            if (h[16]) fprintf(stderr, "[tkz devprof] tail: batches %llu merges %llu (%.2f a batch) proposals/batch %.1f | rounds for chains of equal pairs %llu | ticks/batch %.0f | longest tail: %llu batches, %llu ticks\n",
-                               h[16], h[17], (double)h[17] / h[16], (double)h[18] / h[16], h[19], (double)h[22] / h[16], h[20], h[23]);
-        }
-#endif
+        if (!d_bitmap_only) TKZ_TRY(devprof_report());
         if (!marks_reused) { e->last_xcount = (int64_t)ws->h_counters->xcount; e->last_xcount2 = (int64_t)ws->h_counters->xcount2; }
-        const int32_t err = ws->h_counters->err;
-        if (err & kErrOffsets) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count");
-        if (err & kErrUtf8) return fail(TKZ_E_INVALID_UTF8, "input is not well-formed UTF-8 (or a document boundary falls inside a character)");
-        if (err & kErrTooLong) return fail(TKZ_E_UNSUPPORTED, "a single piece longer than 2^30 bytes");
-        marks_ready = true;                // (what is wrong from here on is the size of a buffer)
-        if (!d_bitmap_only) ws->sized = true;
-        if (!d_bitmap_only && !sizing && total > e->latency_bytes) ws->last_coop = (int64_t)ws->h_counters->coop_count;
-        if (!d_bitmap_only && !sizing && total > e->latency_bytes) ws->last_lq_total = ws->h_counters->lq_total;      // (the next batch's form of the long pieces' kernels: above)
-        if (sizing) {
-            // k_place's form for THIS batch from the sample (it is otherwise chosen from the batch before: a fresh encoder's first miss-heavy batch ran
-            // k_place<64> with most sub-tiles on its general path, 11.7 ms against 7)
-            const int64_t nsample = std::min<int64_t>(ntiles, std::max<int64_t>(ntiles / 16, kSizingMinSub / 16));
-            if ((int64_t)ws->h_counters->over64 * 5 > nsample) { ws->place128 = true; ws->low_place = 0; }
-        }
-        if ((err & kErrPool) && attempt < 4) {
-            // scratch for the giant pieces was too small.  pool_head keeps counting past the capacity, so it holds the exact need
-            // (6 int32 per byte of every giant piece of the batch): size the pool for that -- not for the whole batch -- and rerun
-            const size_t need = (size_t)ws->h_counters->pool_head * 4 + 4096;
-            if (ws->w_pool.ensure(need, acc) != hipSuccess)
-                return fail(TKZ_E_OUT_OF_MEMORY, "scratch for the pieces longer than 1024 bytes: " + std::to_string(need) + " bytes could not be allocated");
-            if (e->piece_stats && e->t_stats.p && !d_bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
-            continue;
-        }
-        if (err & kErrPool) return fail(TKZ_E_OUT_OF_MEMORY, "long-piece scratch exhausted");
-        if ((err & kErrMissCap) && attempt < 4) {
-            // a sub-tile missed more pieces than its list holds (text where nearly every piece misses the vocabulary): the longest list
-            // any sub-tile needed is known now -- longer lists for this workspace from here on, and the batch again
-            int32_t want = kMissCapMin;
-            while (want < ws->h_counters->mneed && want < kMissCapMax) want *= 2;
-            if (want <= ws->mcap) return fail(TKZ_E_DEVICE, "miss list overflow");
-            if (ws->w_mlist.ensure((size_t)ntiles * (size_t)want * 4, acc) != hipSuccess || ws->w_mquad.ensure((size_t)ntiles * (size_t)want * 16, acc) != hipSuccess)
-                return fail(TKZ_E_OUT_OF_MEMORY, "miss lists: " + std::to_string((size_t)ntiles * (size_t)want * 20) + " bytes could not be allocated");
-            ws->mcap = want;
-            if (e->piece_stats && e->t_stats.p && !d_bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
-            continue;
-        }
-        if (err & kErrMissCap) return fail(TKZ_E_DEVICE, "miss list overflow");
-        if ((err & kErrCapacity) && attempt < 4) {          // more pieces than the record buffer was sized for: the exact count is known now
-            const size_t need = ((size_t)ws->h_counters->npieces + 4096) * 4;
-            if (ws->w_prank.ensure(need, acc) != hipSuccess)
-                return fail(TKZ_E_OUT_OF_MEMORY, "piece records: " + std::to_string(need) + " bytes could not be allocated");
-            if (e->piece_stats && e->t_stats.p && !d_bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
-            continue;
-        }
-        if (err & kErrCapacity) return fail(TKZ_E_DEVICE, "piece record buffer overflow");
-        if (sizing) {       // (the sample fitted the lists as they are; the records are counted exactly by the scan)
-            const size_t need = ((size_t)ws->h_counters->npieces + 4096) * 4;
-            if (need > ws->w_prank.cap && ws->w_prank.ensure(need, acc) != hipSuccess)
-                return fail(TKZ_E_OUT_OF_MEMORY, "piece records: " + std::to_string(need) + " bytes could not be allocated");
-            if (e->piece_stats && e->t_stats.p) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
-            continue;
-        }
-        if (err & kErrKeyNotFound) return fail(TKZ_E_KEY_NOT_FOUND, "a byte of the input is not in the vocabulary (KeyNotFoundException in the reference)");
-        if (!d_bitmap_only && e->piece_stats) {
-            std::lock_guard<std::mutex> lock(e->mu);
-            ++e->stat_batches; e->stat_giants += (int64_t)ws->h_counters->heavy_count;
-        }
-        // Growing is immediate, shrinking waits for kLowBatches consecutive batches that would have done with less (the round-4 advisor: a
-        // workspace that alternates miss-heavy and ordinary batches -- or the 48 MB chunks of one host call that does -- must not overflow,
-        // re-run, free and re-allocate on every other batch).
-        constexpr int kLowBatches = 3;
-        if (!d_bitmap_only) {
-            const bool heavy = (int64_t)ws->h_counters->over64 * 5 > ntiles;      // (more than a fifth of the sub-tiles: the next batches' k_place)
-            if (heavy) { ws->place128 = true; ws->low_place = 0; }
-            else if (ws->place128 && ++ws->low_place >= kLowBatches) { ws->place128 = false; ws->low_place = 0; }
-        }
-        if (!d_bitmap_only && ws->mcap > kMissCapMin) {
-            // lists that were grown for an earlier batch (text where nearly every piece misses) and that the last kLowBatches batches filled to
-            // less than half: half as long from here on (one step at a time), and the buffers given back when they are far larger than such
-            // batches need (the lists are ntiles * mcap * 20 bytes: 1.25 B per input byte at 64 entries, 20 B at 1024)
-            int32_t want = kMissCapMin;
-            while (want < ws->h_counters->mhigh) want *= 2;
-            if (want >= ws->mcap) ws->low_lists = 0;
-            else if (++ws->low_lists >= kLowBatches) {
-                ws->low_lists = 0;
-                ws->mcap = std::max(want, ws->mcap / 2);
-                if (ws->w_mquad.cap > (size_t)ntiles * (size_t)ws->mcap * 16 * 4) {
-                    *acc -= (int64_t)(ws->w_mquad.cap + ws->w_mlist.cap);
-                    ws->w_mquad.release(); ws->w_mlist.release();
-                }
-            }
-        }
-        if (!d_bitmap_only && pretok) {
-            // the batch is done: if it completes a learning window, the hottest entries are promoted now (the copy of the memo back to the host and the
-            // rebuilt key tables cost tens of milliseconds: on a thread, behind the batch); else the share of pieces that missed the key tables is
-            // compared with what it was after the last promotion (adapt_after_batch)
-            bool promote = false, relearn = false;
-            {
-                std::lock_guard<std::mutex> lock(e->mu);
-                e->bytes_seen += total;
-                if (ws->learning) {
-                    e->learn_bytes += total;
-                    e->win_miss += (double)(ws->h_counters->miss_short + ws->h_counters->miss_long); e->win_pieces += (double)ws->h_counters->npieces;
-                    promote = !e->adapt || e->learn_bytes >= e->promo_min_bytes;
-                    if (!promote) { ws->learning = false; e->learning = false; }      // (the window goes on with the next batch)
-                    else if (e->adapt && e->last_window_valid && e->win_pieces >= 1 && e->win_miss / e->win_pieces > e->last_window_miss * 1.25 + 0.01) {
-                        // A window whose miss share is a quarter (and a point) ABOVE the window's before it -- although that one's promotions have been installed since,
-                        // and promotions only lower the share on unchanged text -- was counted on ANOTHER text, with a memo full of the old one's pieces (it takes no
-                        // new entry into a full bucket): what it found is a fraction of what a fresh encoder finds (2 k against 9 k pieces on the source text behind 3 GB
-                        // of synthetic text).  A drift: start over -- this window's counts are dropped with the promotions, the memo is emptied, the next batch begins a window.
-                        promote = false; relearn = true; ws->learning = false;
-                        e->learn_bytes = 0; e->win_miss = e->win_pieces = 0;
-                    }
-                } else relearn = adapt_after_batch(e, total, (double)(ws->h_counters->miss_short + ws->h_counters->miss_long), (double)ws->h_counters->npieces);
-                if (relearn) e->learning = true;                                     // (nothing learns while the promotions are being dropped)
-            }
-            if (promote || relearn) {
-                if (promote) {
-                    std::lock_guard<std::mutex> lock(e->mu);
-                    ws->learning = false; e->learn_bytes = 0;
-                    e->window_valid = e->win_pieces >= 1; e->window_miss = e->window_valid ? e->win_miss / e->win_pieces : 0; e->win_miss = e->win_pieces = 0;
-                    e->last_window_valid = e->window_valid; e->last_window_miss = e->window_miss;
-                }
-                // (the workspace is this call's no longer once it returns; the counters, the log and the memo are the encoder's, and no other batch writes the
-                //  first two while e->learning is set)
-                join_promotion(e);                 // (the previous one ended before this batch could be armed: this only reaps the thread)
-                auto work = [e, promote] {
-                    DeviceScope scope;
-                    const bool dev = scope.enter(e->device) == hipSuccess;
-                    if (promote) {
-                        int64_t added = 0;
-                        size_t held;
-                        { std::lock_guard<std::mutex> lock(e->mu); held = e->promo_items.size(); }
-                        if (dev) (void)promote_from_memo(e, true, true, &added);   // (a failure leaves the tables as they were)
-                        std::lock_guard<std::mutex> lock(e->mu);
-                        e->learning = false; ++e->promo_rounds; ++e->n_promotions;
-                        // A round that found much it did not know -- more than a tenth of what the list held -- is a young encoder, or text that CHANGED without the miss
-                        // share having had a settled level to leave (the change fell between two installs): the next round then follows a gigabyte later, not
-                        // 2^rounds gigabytes.  (bench.py's drift leg, synthetic -> real text: the steps beyond 2 GB ran at 0.81 of an encoder that only ever saw
-                        // the real text, whose second round comes after 1 GB while this one's was 4 GB away.)
-                        if (e->adapt && e->promo_rounds > 1 && (size_t)added * 10 > held) e->promo_rounds = 1;
-                        e->bytes_at_install = e->bytes_seen; e->ew_valid = e->base_valid = false;
-                    } else {
-                        if (dev) (void)drop_promotions(e, true);
-                        std::lock_guard<std::mutex> lock(e->mu);
-                        e->learning = false; e->promo_rounds = 0; e->learn_bytes = 0; e->memo_clear_pending = true; ++e->n_relearns;
-                        e->bytes_at_install = e->bytes_at_promo = e->bytes_seen; e->ew_valid = e->base_valid = e->window_valid = e->last_window_valid = false; e->win_miss = e->win_pieces = 0;
-                    }
-                };
-                bool started = false;
-                {
-                    std::lock_guard<std::mutex> jl(e->promo_join_mu);
-                    try { e->promo_thread = std::thread(work); started = true; } catch (...) {}      // (no thread to be had: built here, as before round 5)
-                }
-                if (!started) { const std::string keep_msg = g_err; work(); g_err = keep_msg; }
-            }
-        }
-        if (!d_bitmap_only) {
-            if (total_tokens) *total_tokens = ws->h_counters->grand;
-            if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
-            if (ws->h_counters->grand > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
-        }
+        bool retry = false;
+        TKZ_TRY(check_counters(e, ws, stream, total, attempt, nsample, d_bitmap_only != nullptr, &retry));
+        marks_ready = true;
+        if (retry) continue;
+        if (d_bitmap_only) return TKZ_OK;
+        settle_workspace(ws, ntiles);
+        if (pretok) after_batch(e, ws, total);
+        if (total_tokens) *total_tokens = ws->h_counters->grand;
+        if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
+        if (ws->h_counters->grand > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
         return TKZ_OK;
     }
     return fail(TKZ_E_DEVICE, "unreachable");
@@ -1103,20 +1152,8 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const uint8_t* bytes, con
     memcpy(H + kSmallOffOffs, offs, (size_t)(n_docs + 1) * 8);
     int64_t* h_res = reinterpret_cast<int64_t*>(H + kSmallOffRes);
     h_res[0] = -1; h_res[1] = 0; h_res[2] = 0;
-    const int64_t ntiles = (total + kSub - 1) / kSub;
-    EncodeParams P{};
-    P.bytes = ws->s_bytes[0].as<uint8_t>(); P.total = total; P.startbits = ws->w_startbits.as<uint64_t>(); P.docbits = ws->w_docbits.as<uint64_t>(); P.nwords = total / 64 + 1;
-    P.offs = ws->s_offs[0].as<int64_t>(); P.n_docs = n_docs;
-    P.tmp = ws->w_tmp.as<int32_t>(); P.dense = ws->w_dense.as<int32_t>(); P.tile_count = ws->w_tcount.as<int32_t>();
-    P.prank = ws->w_prank.as<int32_t>(); P.prank_cap = (int64_t)(ws->w_prank.cap / 4); P.pcount = ws->w_pcount.as<int32_t>(); P.pbase = ws->w_pbase.as<int64_t>();
-    P.mlist = ws->w_mlist.as<uint32_t>(); P.mquad = ws->w_mquad.as<uint4>(); P.mcap = ws->mcap; P.mcount = ws->w_mcount.as<uint32_t>();
-    P.docord_base = ws->w_dbase.as<int64_t>(); P.doc_tok = ws->w_doctok.as<int32_t>(); P.counters = ws->w_counters.as<int32_t>();
-    P.giant_q = ws->w_gq.as<int64_t>(); P.giant_cap = total / kArenaPiece + 1; P.giant_cnt = ws->w_gcnt.as<int32_t>();
-    P.giant_count = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, heavy_count));
-    P.giant_ticket = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, giant_ticket));
-    P.heavy_flag = ws->w_heavyq.as<uint8_t>(); P.nsub = ntiles;
-    P.pool = ws->w_pool.as<int32_t>(); P.pool_head = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, pool_head)); P.pool_cap = (int64_t)(ws->w_pool.cap / 4);
-    P.ablate = 0; P.devprof = nullptr; P.stats = nullptr; P.place128 = 0; P.promo = nullptr; P.pextra = nullptr; P.lane_piece = kSmallLanePiece; P.latency = 0;
+    EncodeParams P = bind_params(ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total);
+    P.lane_piece = kSmallLanePiece;
     SmallArgs A{};
     A.h_bytes = H + kSmallOffBytes; A.h_offs = reinterpret_cast<const int64_t*>(H + kSmallOffOffs);
     A.out = reinterpret_cast<int32_t*>(H + kSmallOffIds); A.out_cap = std::min<int64_t>(out_cap, kSmallMaxBytes); A.out_offs = reinterpret_cast<int64_t*>(H + kSmallOffOut);

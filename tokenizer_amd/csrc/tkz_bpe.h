@@ -852,11 +852,7 @@ TKZ_DEV void tkz_bpe_long_tail(const TkzTables& T, int cnt, int32_t* ids, int32_
     for (int w = tid; w < nw; w += G) alive[w] = tkz_lowmask32(cnt - 32 * w);
     if (tid == 0) { reinterpret_cast<int*>(s_red + 2 * (G >> 6))[0] = 0; reinterpret_cast<int*>(s_red + 2 * (G >> 6))[1] = 0; }
     simt::sync();
-#ifdef TKZ_TAIL_GLOBAL_TAU       // (development builds: the global tau whatever the vocabulary)
-    const bool local = false;
-#else
     const bool local = T.max_key_len <= kTailLocalKeyMax;
-#endif
     const bool windowed = open_lo || open_hi;                    // (only with the local bound: the caller checks)
     const int reach = T.max_key_len;
     const int blk = tid;

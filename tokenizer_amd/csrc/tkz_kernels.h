@@ -72,7 +72,7 @@ struct EncodeParams {
     // long misses of more than kLanePiece bytes (k_merge_coop: a wavefront each): queued by k_list_stats as sub-tile << 10 | index in the sub-tile's long list
     uint64_t* coop_q; unsigned long long* coop_count; unsigned long long* coop_ticket; int64_t coop_cap;
     // the long misses of up to lane_piece bytes, binned by length class across the batch (large batches: k_long_count -> scan -> k_long_scatter -> k_merge_long_q).
-    // lq null: the chunk form (k_merge_long).  lq_cnt / lq_base: [16 classes x chunks of 64 sub-tiles]; lq: sub-tile << 30 | list index << 20 | (len - 1) << 10 | byte in the sub-tile
+    // (a small batch takes them in the chunk form instead: k_merge_latency).  lq_cnt / lq_base: [16 classes x chunks of 64 sub-tiles]; lq: sub-tile << 30 | list index << 20 | (len - 1) << 10 | byte in the sub-tile
     int32_t* lq_cnt; int64_t* lq_base; int64_t* lq_total; int64_t* lq_bsum; uint64_t* lq; int64_t lq_cap;
     unsigned long long* miss_sums;   // null, or [2]: k_list_stats adds the batch's short and long misses (the sums of mcount) -- TKZ_OPT_ADAPT follows their share of the pieces
     // development builds only (make DEVPROF=1; env TKZ_DEV_ABLATE bit 4): per-phase clock counters of k_probe.  Compiled out of libtkz.so otherwise.
@@ -107,11 +107,9 @@ struct SmallArgs {
 };
 
 typedef void (*KernelHook)(void* ctx, int kernel_id, int phase /*0 before, 1 after*/, hipStream_t s);
-// side / side2 / ev_fork / ev_join / ev_join2: null, or two more streams and three events of the workspace -- launch_encode runs k_merge_long_q and k_merge_coop there, beside
-// k_merge_short on `stream`, with grids of at most side_long_grid / side_coop_grid wavefronts (a large batch only: EncodeParams::tc_atomic says that the token counts of the
-// sub-tiles are summed with atomics from zero)
-struct Launch { hipStream_t stream; KernelHook hook; void* hook_ctx; hipStream_t side = nullptr, side2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
-                int side_long_grid = 2048, side_coop_grid = 1024; };
+// side / side2 / ev_fork / ev_join / ev_join2: all null, or two more streams and three events of the workspace -- launch_encode runs k_merge_long_q and k_merge_coop there,
+// beside k_merge_short on `stream` (a large batch only: EncodeParams::tc_atomic says that the token counts of the sub-tiles are summed with atomics from zero)
+struct Launch { hipStream_t stream; KernelHook hook; void* hook_ctx; hipStream_t side = nullptr, side2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr; };
 
 void launch_docmark(const Launch& L, const int64_t* d_offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters);
 // position-parallel Regex.Matches; xq / xcount: queue of row blocks left to the sequential matcher (o200k only)
@@ -124,7 +122,6 @@ void launch_ingest(const Launch& L, const uint8_t* h_bytes, int64_t total, uint8
 void launch_probe_sample(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsample);
 void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsub);
 void launch_small(const Launch& L, const TkzTables& T, const EncodeParams& P, const SmallArgs& A);
-void launch_doccount(const Launch& L, const uint64_t* docbits, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt);
 // exclusive scan int32 -> int64 (+ grand total); kid = profiling id of the bracket, or -1
 // round_to (a power of two): every count is rounded up to a multiple of it before it is summed
 void launch_scan(const Launch& L, const int32_t* tile_count, int64_t ntiles, int64_t* bsum, int64_t* tile_base, int64_t* grand, int kid, int round_to = 1);

@@ -8,7 +8,7 @@
 //   k_pretok_rows    Regex.Matches for pattern 1 / cl100k, position-parallel (tkz_pretok.h (2))
 //   k_pretok_seq     Regex.Matches for any pattern, one lane per document (tkz_pretok.h (1))
 //                    -> 1 bit per byte "a piece starts here"
-//   k_doccount/scan  documents and pieces that start in each 1 KiB sub-tile -> ordinal bases
+//   k_doccount2/scan documents and pieces that start in each 1 KiB sub-tile -> ordinal bases
 //   k_probe          per sub-tile, one wavefront: enumerate pieces from the bitmap, whole-piece lookup
 //                    (TikTokenizer.cs:262) -> one 32-bit record per piece
 //   k_merge_short    BytePairEncode (BytePairEncoder.cs:13-76) of the missed pieces of <= 16 bytes, 64 per wavefront
@@ -576,11 +576,7 @@ constexpr int kMidMax = kSub / (TKZ_SHORT_KEY_MAX + 1) + 2;   // pieces of 13+ b
 
 // The workgroup a block stands for: blocks b, b + 8, b + 16 ... of a grid run on one XCD (observed dispatch: XCD = b % 8; for speed only,
 // nothing depends on it), so XCD x takes the x-th eighth of the work, in order.  nblocks is a multiple of 8.
-#ifdef TKZ_NO_XCD_REMAP      // (development: A/B of the mapping)
-TKZ_DEV int64_t tkz_xcd_block(int64_t b, int64_t nblocks) { return b; }
-#else
 TKZ_DEV int64_t tkz_xcd_block(int64_t b, int64_t nblocks) { return (b & 7) * (nblocks >> 3) + (b >> 3); }
-#endif
 
 // exclusive prefix over the wave of a small non-negative value (< 2^BITS), and the wave total;
 // bit-sliced: one ballot + mbcnt per bit, no LDS traffic
@@ -1631,19 +1627,9 @@ TKZ_DEV void tkz_merge_long_chunks(const TkzTables& T, const EncodeParams& P, in
     if (err) simt::atomic_or((unsigned*)&P.counters[0], (unsigned)err);
     tkz_long_prof_end(P, PF);
 }
-// (a kernel of its own per form so that the general forms' registers stay out of the compact one)
-// (LATENCY: a small batch -- TKZ_OPT_LATENCY_BYTES --, where the call waits for the slowest wavefront: a unit of work is 4 sub-tiles whatever their lists hold
-//  -- ~20 entries of ordinary text, one batch of lanes -- instead of up to 64 sub-tiles and five batches one after the other: 93 us of a 1 MB call)
+// (a small batch -- TKZ_OPT_LATENCY_BYTES --, where the call waits for the slowest wavefront: k_merge_latency's unit of work is 4 sub-tiles whatever their lists
+//  hold -- ~20 entries of ordinary text, one batch of lanes -- instead of up to 64 sub-tiles and five batches one after the other: 93 us of a 1 MB call)
 constexpr int kLongPartsLatency = 16;
-template <bool COMPACT, bool LATENCY>
-TKZ_KERNEL_OCC(64, 4) void k_merge_long(TkzTables T, EncodeParams P) {
-    if (tkz_attempt_failed(P)) return;
-    TKZ_SHARED uint4 s_lds[kLongLdsQuads];
-    const LongLds LD = tkz_long_lds(s_lds);
-    tkz_long_brank_init(T, LD.brank);
-    if (LATENCY) tkz_merge_long_chunks<COMPACT, kLongPartsLatency, -1>(T, P, simt::bid(), simt::nblocks(), LD, P.lane_piece);
-    else tkz_merge_long_chunks<COMPACT>(T, P, simt::bid(), simt::nblocks(), LD, P.lane_piece);
-}
 
 // ---- The long misses of a LARGE batch, binned by length class ACROSS the batch (round 6) ----------------------------------------------------------
 // The chunk form above forms its batches inside one unit of work (a chunk of 64 sub-tiles or a quarter of it): on mixed text that is ~290 entries cut
@@ -2313,24 +2299,7 @@ TKZ_KERNEL(1024) void k_giant_merge(TkzTables T, EncodeParams P) {
     if (err) simt::atomic_or((unsigned*)&P.counters[0], (unsigned)err);
 }
 
-// documents that start in each sub-tile (for the document ordinals)
-TKZ_KERNEL(256) void k_doccount(const uint64_t* docbits, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt) {
-    // one lane per bitmap word (coalesced), the kSub/64 = 16 words of a sub-tile summed across 16 lanes
-    static_assert(kSub / 64 == 16, "k_doccount sums 16 lanes per sub-tile");
-    const int lane = simt::lane();
-    const int64_t stride = simt::nblocks() * simt::nthreads(), nw = nsub * (kSub / 64);
-    for (int64_t w0 = simt::bid() * simt::nthreads() + (simt::tid() & ~63); w0 < nw; w0 += stride) {
-        const int64_t w = w0 + lane;
-        uint64_t m = (w < nw && w < nwords) ? docbits[w] : 0ull;
-        const int64_t lim = total - (w << 6);              // (the sentinel bit at `total` is not a start)
-        if (lim <= 0) m = 0; else if (lim < 64) m &= tkz_lowmask((int)lim);
-        int c = tkz_popc64(m);
-        c += simt::shfl_xor(c, 1); c += simt::shfl_xor(c, 2); c += simt::shfl_xor(c, 4); c += simt::shfl_xor(c, 8);
-        if ((lane & 15) == 0 && w < nw) cnt[w >> 4] = c;
-    }
-}
-
-// the same for TWO bitmaps in one pass (document starts and piece starts: one launch instead of two, the words of both read by the same lane)
+// documents and pieces that start in each sub-tile (for their ordinals), the two bitmaps in one pass (the words of both read by the same lane)
 TKZ_KERNEL(256) void k_doccount2(const uint64_t* bits_a, const uint64_t* bits_b, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt_a, int32_t* cnt_b) {
     static_assert(kSub / 64 == 16, "k_doccount2 sums 16 lanes per sub-tile");
     const int lane = simt::lane();
@@ -2721,7 +2690,7 @@ TKZ_KERNEL(256) void k_u16_docoffs(const uint16_t* units, int64_t total, const u
 // -------------------------------------------------------------------------------------------------
 // piece granularity (EncodeTrimSuffix / EncodeTrimPrefix walk the regex matches, TikTokenizer.cs:288-341, :483-519): the byte
 // offset of every piece and the first piece of every document, straight from the piece-start bitmap -- no host round trip
-//   (k_doccount + scan over STARTBITS give every sub-tile its first piece ordinal)
+//   (k_doccount2 + scan over STARTBITS give every sub-tile its first piece ordinal)
 //   k_piece_index   one wavefront per sub-tile: positions of the set bits below `total`, in order
 //   k_doc_piece     first piece of document d = number of piece starts before its first byte
 // The encode kernels then run with the piece-start bitmap AS the document bitmap: they record the token position of every
@@ -2964,7 +2933,7 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     }
     simt::sync();
     stamp();
-    // ---- 3. documents and pieces that start in each sub-tile, their scans (k_doccount + k_scan_*): one lane per sub-tile ----
+    // ---- 3. documents and pieces that start in each sub-tile, their scans (k_doccount2 + k_scan_*): one lane per sub-tile ----
     if (wave == 0) {
         int dcarry = 0, pcarry = 0;
         for (int q0 = 0; q0 < nsub; q0 += 64) {                   // 64 sub-tiles per round, one per lane
@@ -3112,6 +3081,35 @@ void launch_pretok_seq(const Launch& L, int pattern, const uint8_t* d_bytes, con
     TKZ_LAUNCH(k_pretok_seq, grid_for(n_docs), kThreads, L.stream, d_bytes, d_offs, n_docs, total, startbits, pattern, bmp, counters);
     hook(L, K_PRETOK, 1);
 }
+// giant pieces (queued by k_list_stats): ordered, merged (k_giant_merge takes pieces off the ordered queue and exits at once when it is empty)
+static void launch_giants(const Launch& L, const TkzTables& T, const EncodeParams& P) {
+#ifdef TKZ_HOSTEMU
+    constexpr int kGiantGrid = 2;       // (the CPU emulator pays for every thread of an idle workgroup)
+#else
+    constexpr int kGiantGrid = 256;
+#endif
+    TKZ_LAUNCH(k_giant_order, 1, 1024, L.stream, P);
+    TKZ_LAUNCH(k_giant_merge, kGiantGrid, 1024, L.stream, T, P);
+}
+// a large batch's long misses of 17..lane_piece bytes binned by length class: the class queue k_merge_long_q takes them off
+static void launch_long_queue(const Launch& L, const EncodeParams& P, int64_t nsub) {
+    const int64_t nchunks = cdiv(nsub, 64), g4 = cdiv(nchunks, 4);
+    TKZ_LAUNCH(k_long_count, g4 < 4096 ? g4 : 4096, kThreads, L.stream, P);
+    launch_scan2(L, nchunks * kLenClasses, P.lq_bsum, P.lq_cnt, P.lq_base, P.lq_total, 1, nullptr, nullptr, nullptr, 1, -1);
+    TKZ_LAUNCH(k_long_scatter, g4 < 4096 ? g4 : 4096, kThreads, L.stream, P);
+}
+// ... merged off the queue 256 at a time by at most `cap` wavefronts
+static void launch_long_q(hipStream_t st, const TkzTables& T, const EncodeParams& P, int64_t cap) {
+    const int64_t ranges = cdiv(P.lq_cap, kLqRangeLong), grid = ranges < cap ? (ranges < 1 ? 1 : ranges) : cap;
+    if (T.max_rank <= kVarCompactMaxRank) TKZ_LAUNCH((k_merge_long_q<true>), grid, 64, st, T, P);
+    else TKZ_LAUNCH((k_merge_long_q<false>), grid, 64, st, T, P);
+}
+// the pieces the lane mergers leave to a whole wavefront, off the queue k_list_stats filled (every wavefront exits at once when it is empty)
+static void launch_coop(hipStream_t st, const TkzTables& T, const EncodeParams& P, int64_t grid, int64_t cap) {
+    TKZ_LAUNCH(k_merge_coop, grid < cap ? grid : cap, 64, st, T, P);
+}
+// grids of the two tail kernels beside k_merge_short: they fit the chip beside each other and leave k_merge_short the rest
+constexpr int64_t kSideLongGrid = 2048, kSideCoopGrid = 1024;
 void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsub) {
     hook(L, K_ENCODE, 0);
     TKZ_LAUNCH(k_probe, xcd_grid(cdiv(nsub, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
@@ -3120,85 +3118,54 @@ void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, i
     { const int64_t g = grid_for(nsub); TKZ_LAUNCH(k_list_stats, g < 1024 ? g : 1024, kThreads, L.stream, (const uint32_t*)P.mcount, nsub, P.mcap, P.counters,
                                                      (const uint8_t*)P.heavy_flag, P.startbits, P.nwords, P.total, P.giant_q, P.giant_count, P.giant_cap,
                                                      (const uint32_t*)P.mlist, P.coop_q, P.coop_count, P.coop_cap, (int)P.lane_piece, P.miss_sums); }
-    // The short misses and the long ones touch different list entries and the sub-tiles' token counts are summed with atomics from zero (P.tc_atomic), so the
-    // kernels of the two kinds may run side by side.  What makes that worth having: k_merge_long_q and k_merge_coop last as long as their slowest wavefronts, not as
-    // long as their work (0.43 + 0.31 of the 3.7 ms of a 268 MB batch of real text, for 0.6 M pieces), while k_merge_short keeps the whole chip busy.
-    // How: this chip starts no workgroup of a second kernel while a first one still has workgroups waiting (tools/stream_overlap_probe.hip: 8,192 + 64 workgroups on two
-    // streams take 20 + 5 ms whatever the streams' priorities; 1,024 + 64 take 5) -- so the two tail kernels go FIRST, each on a stream of its own with a grid that fits
-    // the chip beside the other, and k_merge_short behind them on L.stream takes what is left and, as their wavefronts retire, everything.
-    // The counting, the scan and the scatter of the class queue stay in front on L.stream (they are short and the queue kernel needs them).
-    // (k_merge_coop ALONE beside k_merge_short, for workspaces whose class queue is long, was measured too: mixed text 15.97 -> 15.87 ms, headline 20.59 -> 20.84 -- not kept.)
-    const bool fork = L.side && L.side2 && L.ev_fork && L.ev_join && L.ev_join2 && P.tc_atomic && P.latency == 0 && P.lq != nullptr;
-        // giant pieces (queued by k_list_stats): ordered, merged; then the pieces of 17..1024 bytes and the giants' token counts
-#ifdef TKZ_HOSTEMU
-    constexpr int kGiantGrid = 2;       // (the CPU emulator pays for every thread of an idle workgroup)
-#else
-    constexpr int kGiantGrid = 256;
-#endif
-    const bool latency = P.latency != 0 || !P.lq;
-    auto coop = [&](hipStream_t st, int64_t cap) {
-        // the pieces k_merge_long leaves to a whole wavefront, off the queue k_list_stats filled (every wavefront exits at once when it is empty).  A small batch
-        // gets as many wavefronts as a large one: 16 of them took 107 us over the queue of a 1 MB call
-        const int64_t cgrid = latency ? 512 : cdiv(nsub, 64);
-        TKZ_LAUNCH(k_merge_coop, cgrid < cap ? cgrid : cap, 64, st, T, P);
-    };
-    // (a small batch whose token counts are summed with atomics: the three merge stages as one launch, behind the giant pieces -- k_merge_latency)
-    const bool fused = !fork && P.latency != 0 && P.tc_atomic != 0 && P.lq != nullptr;
-    if (fused) {
+    const int64_t nb_short = xcd_grid(cdiv(nsub, (kMsThreads / 64) * kGroup));     // (workgroups of k_merge_short)
+    if (P.latency) {
+        // A SMALL batch (its token counts are summed with atomics: P.tc_atomic): the giant pieces, then the three merge stages as one launch -- k_merge_latency.
+        // A small batch gets as many k_merge_coop wavefronts as a large one: 16 of them took 107 us over the queue of a 1 MB call.
         hook(L, K_HEAVY, 0);
-        TKZ_LAUNCH(k_giant_order, 1, 1024, L.stream, P);
-        TKZ_LAUNCH(k_giant_merge, kGiantGrid, 1024, L.stream, T, P);
+        launch_giants(L, T, P);
         hook(L, K_HEAVY, 1);
-        const int64_t nb_short = xcd_grid(cdiv(nsub, (kMsThreads / 64) * kGroup)), chunks = cdiv(nsub, 64) * kLongPartsLatency, nb_long = cdiv(chunks < 65536 ? chunks : 65536, kMsThreads / 64);
+        const int64_t chunks = cdiv(nsub, 64) * kLongPartsLatency, nb_long = cdiv(chunks < 65536 ? chunks : 65536, kMsThreads / 64);
         hook(L, K_MERGE_SHORT, 0);
         if (T.max_rank <= kVarCompactMaxRank) TKZ_LAUNCH((k_merge_latency<true>), nb_short + nb_long, kMsThreads, L.stream, T, P, (int)nb_short, (int)nb_long);
         else TKZ_LAUNCH((k_merge_latency<false>), nb_short + nb_long, kMsThreads, L.stream, T, P, (int)nb_short, (int)nb_long);
         // (the queue of the 129+-byte pieces stays a launch of its own BEHIND the chunk form of the long lists, as it always was: inside the same launch its pieces came
         //  out wrong on the GPU -- test_pieces_vs_oracle_bpe, test_mid_pieces_share_the_arena -- while the emulator, whose workgroups take turns, saw nothing)
-        coop(L.stream, kCoopGrid);
+        launch_coop(L.stream, T, P, 512, kCoopGrid);
         hook(L, K_MERGE_SHORT, 1);
-        return;
-    }
-    if (!fork) {                   // (the serial form keeps k_merge_short in front, as it always was)
+    } else if (!L.side) {
+        // a large batch, serial: k_merge_short in front, as it always was, then the giant pieces, the class queue and the long misses
         hook(L, K_MERGE_SHORT, 0);
-        TKZ_LAUNCH(k_merge_short, xcd_grid(cdiv(nsub, (kMsThreads / 64) * kGroup)), kMsThreads, L.stream, T, P);
+        TKZ_LAUNCH(k_merge_short, nb_short, kMsThreads, L.stream, T, P);
         hook(L, K_MERGE_SHORT, 1);
-    }
-    hook(L, K_HEAVY, 0);
-    TKZ_LAUNCH(k_giant_order, 1, 1024, L.stream, P);
-    TKZ_LAUNCH(k_giant_merge, kGiantGrid, 1024, L.stream, T, P);   // takes pieces off the ordered queue; exits at once when it is empty
-    if (!latency) {         // the queue form: the batch's long misses binned by length class ...
-        const int64_t nchunks = cdiv(nsub, 64), g4 = cdiv(nchunks, 4);
-        TKZ_LAUNCH(k_long_count, g4 < 4096 ? g4 : 4096, kThreads, L.stream, P);
-        launch_scan2(L, nchunks * kLenClasses, P.lq_bsum, P.lq_cnt, P.lq_base, P.lq_total, 1, nullptr, nullptr, nullptr, 1, -1);
-        TKZ_LAUNCH(k_long_scatter, g4 < 4096 ? g4 : 4096, kThreads, L.stream, P);
-    }
-    hipStream_t sq = L.stream;                           // the stream of the queue kernel
-    int64_t qcap = kLongQGrid;
-    if (fork) {
+        hook(L, K_HEAVY, 0);
+        launch_giants(L, T, P);
+        launch_long_queue(L, P, nsub);
+        launch_long_q(L.stream, T, P, kLongQGrid);
+        launch_coop(L.stream, T, P, cdiv(nsub, 64), kCoopGrid);
+        hook(L, K_HEAVY, 1);
+    } else {
+        // a large batch, side by side (L.side: P.tc_atomic).  The short misses and the long ones touch different list entries and the sub-tiles' token counts are
+        // summed with atomics from zero, so the kernels of the two kinds may run side by side.  What makes that worth having: k_merge_long_q and k_merge_coop last as
+        // long as their slowest wavefronts, not as long as their work (0.43 + 0.31 of the 3.7 ms of a 268 MB batch of real text, for 0.6 M pieces), while
+        // k_merge_short keeps the whole chip busy.
+        // How: this chip starts no workgroup of a second kernel while a first one still has workgroups waiting (tools/stream_overlap_probe.hip: 8,192 + 64 workgroups
+        // on two streams take 20 + 5 ms whatever the streams' priorities; 1,024 + 64 take 5) -- so the two tail kernels go FIRST, each on a stream of its own with a
+        // grid that fits the chip beside the other, and k_merge_short behind them on L.stream takes what is left and, as their wavefronts retire, everything.
+        // The giant pieces and the counting, the scan and the scatter of the class queue stay in front on L.stream (they are short and the queue kernel needs them).
+        // (k_merge_coop ALONE beside k_merge_short, for workspaces whose class queue is long, was measured too: mixed text 15.97 -> 15.87 ms, headline 20.59 -> 20.84 -- not kept.)
+        hook(L, K_HEAVY, 0);
+        launch_giants(L, T, P);
+        launch_long_queue(L, P, nsub);
         hook(L, K_HEAVY, 1);            // (the bracket of this form: what runs in front of the three; K_MERGE_SHORT's is the three side by side)
         hook(L, K_MERGE_SHORT, 0);
         (void)hipEventRecord(L.ev_fork, L.stream); (void)hipStreamWaitEvent(L.side, L.ev_fork, 0); (void)hipStreamWaitEvent(L.side2, L.ev_fork, 0);
-        sq = L.side; qcap = L.side_long_grid;
-    }
-    if (latency) {          // the chunk form: strides over units of 4 sub-tiles
-        const int64_t chunks = cdiv(nsub, 64) * kLongPartsLatency, grid = chunks < 65536 ? chunks : 65536;
-        if (T.max_rank <= kVarCompactMaxRank) TKZ_LAUNCH((k_merge_long<true, true>), grid, 64, sq, T, P);
-        else TKZ_LAUNCH((k_merge_long<false, true>), grid, 64, sq, T, P);
-    } else {                // ... and merged off the queue 256 at a time
-        const int64_t ranges = cdiv(P.lq_cap, kLqRangeLong), grid = ranges < qcap ? (ranges < 1 ? 1 : ranges) : qcap;
-        if (T.max_rank <= kVarCompactMaxRank) TKZ_LAUNCH((k_merge_long_q<true>), grid, 64, sq, T, P);
-        else TKZ_LAUNCH((k_merge_long_q<false>), grid, 64, sq, T, P);
-    }
-    if (fork) {
-        coop(L.side2, L.side_coop_grid);
+        launch_long_q(L.side, T, P, kSideLongGrid);
+        launch_coop(L.side2, T, P, cdiv(nsub, 64), kSideCoopGrid);
         (void)hipEventRecord(L.ev_join, L.side); (void)hipEventRecord(L.ev_join2, L.side2);
-        TKZ_LAUNCH(k_merge_short, xcd_grid(cdiv(nsub, (kMsThreads / 64) * kGroup)), kMsThreads, L.stream, T, P);
+        TKZ_LAUNCH(k_merge_short, nb_short, kMsThreads, L.stream, T, P);
         (void)hipStreamWaitEvent(L.stream, L.ev_join, 0); (void)hipStreamWaitEvent(L.stream, L.ev_join2, 0);
         hook(L, K_MERGE_SHORT, 1);
-    } else {
-        coop(L.stream, kCoopGrid);
-        hook(L, K_HEAVY, 1);
     }
 }
 // k_probe and the list statistics over the first `nsample` sub-tiles only (tkz_api.cpp: the sizing attempt of a fresh workspace)
@@ -3230,9 +3197,6 @@ void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_ba
         else TKZ_LAUNCH((k_place<64, false>), grid, kThreads, L.stream, P, tile_base, out, out_cap);
     }
     hook(L, K_GATHER, 1);
-}
-void launch_doccount(const Launch& L, const uint64_t* docbits, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt) {
-    TKZ_LAUNCH(k_doccount, grid_for(nsub * (kSub / 64)), kThreads, L.stream, docbits, nwords, total, nsub, cnt);
 }
 void launch_doccount2(const Launch& L, const uint64_t* bits_a, const uint64_t* bits_b, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt_a, int32_t* cnt_b) {
     TKZ_LAUNCH(k_doccount2, grid_for(nsub * (kSub / 64)), kThreads, L.stream, bits_a, bits_b, nwords, total, nsub, cnt_a, cnt_b);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# development A/B of ONE build under two environments (e.g. TKZ_NO_FORK=1 against the default), every shape with --parity-only (the oracle compares every document)
+# development A/B of ONE build under two environments (e.g. TKZ_LATENCY_BYTES=0 against the default), every shape with --parity-only (the oracle compares every document)
 #   usage: tools/gpu_job_ab_env.sh <tag> "<ENV=1 or ->" ...      shapes: mixed real head heldout (SHAPES_AB to choose)
 set -u
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; TAG=${1:-ab}; shift; O=gpurun_out/$TAG; mkdir -p $O
