@@ -107,7 +107,7 @@ struct CounterBlock {          // mirrors the device block
 
 }  // namespace
 
-namespace tkz { tkz_status set_error(tkz_status s, const std::string& msg) { return fail(s, msg); } }   // (tkz_comm.cpp, tkz_decode.cpp)
+namespace tkz { tkz_status set_error(tkz_status s, const std::string& msg) { return fail(s, msg); } }   // (tkz_comm.cpp)
 
 struct tkz_vocab { tkz::Vocab v; };
 
@@ -135,7 +135,22 @@ struct Workspace {
     DevBuf s_bytes[2], s_offs[2], s_out[3], s_outoffs[3];      // staging of the host-buffer entry points: two input sets, three output sets (encode_host)
     // the UTF-16 batch entry point: code units, their document marks, per-tile / per-group lengths (two sets: the units of chunk k+1 are uploaded and
     // measured while chunk k is encoded), the UTF-8 batch they become
-    struct U16Stage { DevBuf units, offs, docbits, grp, tsum, tbase, bsum, counters, boffs; struct Host { int32_t err; int32_t pad; int64_t grand; }* h = nullptr; } u16[2];
+    struct U16Stage {
+        DevBuf units, offs, docbits, grp, tsum, tbase, bsum, counters, boffs; struct Host { int32_t err; int32_t pad; int64_t grand; }* h = nullptr;
+        hipError_t ensure(int64_t max_units, int64_t max_docs, int64_t* acc) {      // room for a chunk of max_units code units in max_docs documents
+            const int64_t nw = max_units / 64 + 1, nt = tkz::u16_tiles(max_units), nblk = (nt + tkz::kScanBlock - 1) / tkz::kScanBlock;
+            const std::pair<DevBuf*, size_t> want[] = {{&units, (size_t)(max_units + 64) * 2}, {&offs, (size_t)(max_docs + 1) * 8}, {&docbits, (size_t)(nw + 8) * 8},
+                                                       {&grp, (size_t)nt * 64 * 4}, {&tsum, (size_t)nt * 4}, {&tbase, (size_t)nt * 8}, {&bsum, (size_t)(nblk + 1) * 8},
+                                                       {&counters, 64}, {&boffs, (size_t)(max_docs + 1) * 8}};
+            for (const auto& w : want) { const hipError_t r = w.first->ensure(w.second, acc); if (r != hipSuccess) return r; }
+            return h ? hipSuccess : hipHostMalloc((void**)&h, 64, 0);
+        }
+        void release() {
+            for (DevBuf* b : {&units, &offs, &docbits, &grp, &tsum, &tbase, &bsum, &counters, &boffs}) b->release();
+            if (h) (void)hipHostFree(h);
+            h = nullptr;
+        }
+    } u16[2];
     DevBuf u_bytes[2];
     // Decode
     DevBuf d_grp, d_tsum, d_tbase, d_bsum, d_counters, d_ids, d_idoffs, d_out, d_outoffs;
@@ -153,7 +168,7 @@ struct Workspace {
     std::atomic<int64_t> small_calls{0}, small_fallbacks{0};   // (read by tkz_encoder_small_path_calls from other threads)
     int64_t small_clocks[16] = {};         // the phase stamps of the last single-launch call, copied out after its synchronisation
     hipStream_t st_compute = nullptr, st_in = nullptr, st_out = nullptr;   // the host-buffer entry points: kernels / uploads / downloads
-    hipEvent_t ev_in[2] = {}, ev_done[2] = {}, ev_out[3] = {};
+    hipEvent_t ev_in[2] = {}, ev_out[3] = {};
     tkz::SdmaSignal sig_out[3], sig_outoffs[3];   // downloads on a copy engine of their own (tkz_sdma.h): the completion signal of each staging set
     int sdma_state = 0;                    // 0 not looked at, 1 in use, -1 not available: the runtime's hipMemcpyAsync
     std::atomic<int64_t> engine_downloads{0};      // copies of results that went by copy engine (tkz_encoder_engine_downloads)
@@ -168,18 +183,16 @@ struct Workspace {
         DevBuf* bufs[] = {&w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
                           &w_doctok, &w_dcount, &w_dbase, &w_pool, &s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2],
                           &s_outoffs[0], &s_outoffs[1], &s_outoffs[2], &u_bytes[0], &u_bytes[1],
-                          &u16[0].units, &u16[0].offs, &u16[0].docbits, &u16[0].grp, &u16[0].tsum, &u16[0].tbase, &u16[0].bsum, &u16[0].counters, &u16[0].boffs,
-                          &u16[1].units, &u16[1].offs, &u16[1].docbits, &u16[1].grp, &u16[1].tsum, &u16[1].tbase, &u16[1].bsum, &u16[1].counters, &u16[1].boffs,
                           &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &p_boffs, &p_toffs, &p_docp};
         for (DevBuf* b : bufs) b->release();
+        for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
-        for (int q = 0; q < 2; ++q) if (u16[q].h) (void)hipHostFree(u16[q].h);
         if (h_small) (void)hipHostFree(h_small);
         if (st_small) (void)hipStreamDestroy(st_small);
         for (hipStream_t st : {st_side, st_side2}) if (st) (void)hipStreamDestroy(st);
         for (hipEvent_t ev : {ev_fork, ev_join, ev_join2}) if (ev) (void)hipEventDestroy(ev);
         for (int k = 0; k < tkz::K_COUNT; ++k) for (int q = 0; q < 2; ++q) if (ev[k][q]) (void)hipEventDestroy(ev[k][q]);
-        for (int q = 0; q < 2; ++q) { if (ev_in[q]) (void)hipEventDestroy(ev_in[q]); if (ev_done[q]) (void)hipEventDestroy(ev_done[q]); }
+        for (int q = 0; q < 2; ++q) if (ev_in[q]) (void)hipEventDestroy(ev_in[q]);
         for (int q = 0; q < 3; ++q) if (ev_out[q]) (void)hipEventDestroy(ev_out[q]);
         if (st_compute) (void)hipStreamDestroy(st_compute);
         if (st_in) (void)hipStreamDestroy(st_in);
@@ -647,6 +660,21 @@ struct SlowCallLog {
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (ms > (double)limit_ms)
             { fprintf(stderr, "tkz: batch call of %lld bytes: %.1f ms on the host, %.1f ms of it in %d hipMalloc/hipFree calls, %d attempt(s)\n", (long long)total, ms, (double)g_alloc_ns * 1e-6, g_alloc_calls, attempts); fflush(stderr); }
+    }
+};
+// ($TKZ_TRACE_HOST: the host's side of the chunk pipeline on stderr -- microseconds since the pipeline started at which each step RETURNED; development)
+struct HostTrace {
+    static bool on() { static const bool v = getenv("TKZ_TRACE_HOST") != nullptr; return v; }
+    std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    std::vector<std::pair<std::string, double>> stamps;
+    void stamp(const char* what, int64_t k) {
+        if (on()) stamps.emplace_back(std::string(what) + " " + std::to_string(k), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count());
+    }
+    void print(int64_t nchunks) const {
+        if (!on()) return;
+        std::string line = "[tkz host trace] " + std::to_string(nchunks) + " chunks:";
+        for (const auto& sp : stamps) { char b[96]; snprintf(b, sizeof b, " %s @%.0f", sp.first.c_str(), sp.second); line += b; }
+        fprintf(stderr, "%s\n", line.c_str());
     }
 };
 enum { kCallWhole = 0, kCallBegin = 1, kCallEnd = 2 };
@@ -1213,138 +1241,167 @@ bool pinned_host(const void* p, void** dev) {
 // host buffers -> staging -> device path -> back, for documents given as UTF-8 bytes (`bytes`) or as UTF-16 code units (`units`: uploaded as they are,
 // Encoding.UTF8.GetBytes -- TikTokenizer.cs:261 -- runs on the device; offsets in units then).
 //  * at most 128 KiB of UTF-8: the single-launch kernel (encode_small);
-//  * a batch whose upload is below 1.5 chunks (a chunk: 16 MB from page-locked buffers, 32 MB from pageable ones; at least 8 MB): one launch sequence.  From
-//    page-locked caller buffers the inputs are copied asynchronously and -- up to 8 MB of text -- the ids and offsets are written by the kernels STRAIGHT into
-//    the caller's memory (k_place / k_docoffs store whole lines over PCIe): no download commands, one synchronisation;
-//  * larger: document ranges of a chunk each, pipelined -- the upload of chunk k+2 (and, for UTF-16, its length pass), the launch sequences of chunks k+1 and
-//    k+2 (enqueued ahead, on two workspaces) and the download of chunk k (page-locked results: on a copy engine of its own, tkz_sdma.h) run at the same time.
-//    512 MB of page-locked text: 22 -> 37 GB/s, 64 MB: 22 -> 29.5 (profiles/r06/host_batches_ab.txt); what bounds it now is the download of the ids at the
-//    link's duplex rate.
-tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* units, const int64_t* offs, int64_t n_docs, int32_t* out_ids,
-                       int64_t out_cap, int64_t* out_offsets, int64_t* needed, bool pretok, uint64_t* bitmap) {
-    using namespace tkz;
-    DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    const bool u16 = units != nullptr;
-    if (n_docs < 0 || !offs || (n_docs > 0 && !bytes && !units && offs[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    if (offs[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = offs[n_docs];                      // bytes, or code units
-    if (total < 0) return fail(TKZ_E_ARG, u16 ? "negative unit count" : "negative byte count");
-    if (needed) *needed = 0;
-    if (u16 && total == 0) {
-        for (int64_t d = 0; d <= n_docs; ++d) { if (offs[d] != 0) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the unit count"); out_offsets[d] = 0; }
-        return TKZ_OK;
-    }
-    Lease lease(e);
-    Workspace* ws = lease.ws;
-    int64_t* acc = &ws->bytes_allocated;
-    const int64_t unit = u16 ? 2 : 1;
-    // ($TKZ_HOST_CHUNK_BYTES: test knob, so that the CPU-emulated tests can exercise the pipeline on kilobytes)
-    // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the questions below are asked of a 64-byte prompt)
-    if (!u16 && pretok && !bitmap && small_eligible(e, offs, n_docs, total)) {
-        bool handled = false;
-        st = encode_small(e, ws, bytes, offs, n_docs, total, out_ids, out_cap, out_offsets, needed, &handled);
-        if (st != TKZ_OK || handled) return st;
-    }
-    // page-locked caller buffers?  (a single chunk then needs no staging for its results; the copies of every path are asynchronous)
-    void *dv_in = nullptr, *dv_offs = nullptr, *dv_ids = nullptr, *dv_ooffs = nullptr;
-    const bool pin_in = pinned_host(u16 ? (const void*)units : (const void*)bytes, &dv_in) && pinned_host(offs, &dv_offs);
-    const bool pin_out = !bitmap && pinned_host(out_offsets, &dv_ooffs) && (out_cap == 0 || pinned_host(out_ids, &dv_ids));
+//  * one chunk (plan_host_batch: an upload below 1.5 chunks) from ordinary buffers: encode_host_blocking.  From page-locked caller buffers the inputs are copied
+//    asynchronously and -- up to 8 MB of text -- the ids and offsets are written by the kernels STRAIGHT into the caller's memory (k_place / k_docoffs store whole
+//    lines over PCIe): no download commands, one synchronisation (HostPipeline, its one iteration);
+//  * larger: document ranges of a chunk each, pipelined (HostPipeline::run) -- the upload of chunk k+2 (and, for UTF-16, its length pass), the launch sequences of
+//    chunks k+1 and k+2 (enqueued ahead, on two workspaces) and the download of chunk k (page-locked results: on a copy engine of its own, tkz_sdma.h) run at the
+//    same time.  512 MB of page-locked text: 22 -> 37 GB/s, 64 MB: 22 -> 29.5 (profiles/r06/host_batches_ab.txt); what bounds it now is the download of the ids at
+//    the link's duplex rate.
+const char* const kMsgUnitOffsets = "document offsets must start at 0, be non-decreasing and end at the unit count";
+const char* const kMsgEngineDownload = "a copy engine reported an error for a download";
+constexpr int64_t kHostChunkMin = int64_t(8) << 20;      // a chunk is at least this large (smaller ones were measured through an environment knob: profiles/r06/host_batches_ab.txt)
+
+// How a host batch travels: which of the caller's buffers are page-locked, the chunks it is cut into, where its results are written.  Host arithmetic only.
+struct HostPlan {
+    bool pin_in = false, pin_out = false;              // page-locked caller buffers (a single chunk then needs no staging for its results; the copies of every path are asynchronous)
+    void *dv_in = nullptr, *dv_offs = nullptr, *dv_ids = nullptr, *dv_ooffs = nullptr;      // ... as the device addresses them
+    int64_t unit = 1, up_bytes = 0, chunk_bytes = 0, nchunks = 1;
+    std::vector<int64_t> cut;                          // chunk k = documents [cut[k], cut[k+1])
+    bool blocking = false;                             // one chunk, ordinary (pageable) buffers: encode_host_blocking
+    bool direct_out = false, ingest_in = false;        // one small chunk on page-locked buffers: the kernels write the caller's results / fetch the caller's text themselves
+    int nout = 1;                                      // output staging sets in use
+    int64_t max_units = 0, max_docs = 0;               // the largest chunk
+};
+HostPlan plan_host_batch(const void* in, bool u16, const int64_t* offs, int64_t n_docs, const int32_t* out_ids, int64_t out_cap, const int64_t* out_offsets,
+                         bool pretok, const uint64_t* bitmap) {
+    HostPlan p;
+    const int64_t total = offs[n_docs];
+    p.pin_in = pinned_host(in, &p.dv_in) && pinned_host(offs, &p.dv_offs);
+    p.pin_out = !bitmap && pinned_host(out_offsets, &p.dv_ooffs) && (out_cap == 0 || pinned_host(out_ids, &p.dv_ids));
     // (16 MB of upload a chunk.  Until round 6 a chunk's kernels were launched when the chunk before had drained, every chunk paid its launch sequence's
     //  floor of ~0.4 ms and 32 MB chunks were the optimum; with two launch sequences enqueued ahead and the downloads on a copy engine of their own the
     //  floor is hidden: profiles/r06/host_batches_ab.txt.  Pageable buffers keep 32 MB: the runtime stages their copies itself, synchronously, a cost per copy)
+    // ($TKZ_HOST_CHUNK_BYTES: test knob, so that the CPU-emulated tests can exercise the pipeline on kilobytes)
     static const int64_t kChunkEnv = [] { const char* v = getenv("TKZ_HOST_CHUNK_BYTES"); const long long n = v ? atoll(v) : 0; return n > 0 ? (int64_t)n : (int64_t)0; }();
-    const int64_t kChunkBytes = kChunkEnv ? kChunkEnv : (pin_in && pin_out ? int64_t(16) << 20 : int64_t(32) << 20);
-    static const int64_t kChunkMin = [] { const char* v = getenv("TKZ_HOST_CHUNK_MIN"); const long long n = v ? atoll(v) : 0; return n > 0 ? (int64_t)n : (int64_t(8) << 20); }();
-    const int64_t up_bytes = total * unit;
+    const int64_t kChunkBytes = kChunkEnv ? kChunkEnv : (p.pin_in && p.pin_out ? int64_t(16) << 20 : int64_t(32) << 20);
+    p.unit = u16 ? 2 : 1;
+    p.up_bytes = total * p.unit;
     // (from 12 MB up a batch is two chunks at least, of 8 MB or more: the second chunk's upload runs beside the first one's kernels)
-    const int64_t chunk_bytes = std::min(kChunkBytes, std::max(std::min(kChunkBytes, kChunkMin), up_bytes / 2));
-    int64_t nchunks = (bitmap || !pretok || 2 * up_bytes < 3 * chunk_bytes) ? 1 : std::min<int64_t>(1024, std::max<int64_t>(2, (up_bytes + chunk_bytes / 2) / chunk_bytes));
-    // chunk boundaries on documents: chunk k = documents [cut[k], cut[k+1]).  Offsets that are not monotone cannot be cut: the
-    // whole batch then goes as one chunk and the device reports them (k_docmark)
-    std::vector<int64_t> cut((size_t)nchunks + 1, 0);
-    cut[(size_t)nchunks] = n_docs;
-    for (int64_t k = 1; k < nchunks; ++k) {
-        const int64_t want = total / nchunks * k;
+    p.chunk_bytes = std::min(kChunkBytes, std::max(std::min(kChunkBytes, kHostChunkMin), p.up_bytes / 2));
+    p.nchunks = (bitmap || !pretok || 2 * p.up_bytes < 3 * p.chunk_bytes) ? 1 : std::min<int64_t>(1024, std::max<int64_t>(2, (p.up_bytes + p.chunk_bytes / 2) / p.chunk_bytes));
+    // chunk boundaries on documents.  Offsets that are not monotone cannot be cut: the whole batch then goes as one chunk and the device reports them (k_docmark)
+    std::vector<int64_t>& cut = p.cut;
+    cut.assign((size_t)p.nchunks + 1, 0);
+    cut[(size_t)p.nchunks] = n_docs;
+    for (int64_t k = 1; k < p.nchunks; ++k) {
+        const int64_t want = total / p.nchunks * k;
         cut[(size_t)k] = std::lower_bound(offs, offs + n_docs, want) - offs;
-        if (cut[(size_t)k] < cut[(size_t)k - 1] || offs[cut[(size_t)k]] < offs[cut[(size_t)k - 1]]) { nchunks = 1; break; }
+        if (cut[(size_t)k] < cut[(size_t)k - 1] || offs[cut[(size_t)k]] < offs[cut[(size_t)k - 1]]) { p.nchunks = 1; break; }
     }
-    if (nchunks == 1) { cut.assign(2, 0); cut[1] = n_docs; }
-    if (!u16 && nchunks == 1 && !(pin_in && pin_out && pretok && !bitmap && total > 0)) {
-        // ---- one chunk, ordinary (pageable) buffers: blocking copies either side of the launch sequence ----
-        HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
-        HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-        const int64_t cap = bitmap ? 0 : std::min<int64_t>(out_cap, total);   // tokens <= bytes: more capacity is never used
-        if (!bitmap) {
-            HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
-            HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-        } else {
-            HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, acc));
-        }
-        if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ws->s_offs[0].p, offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-        int64_t tokens = 0;
-        st = encode_device(e, ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap,
-                           ws->s_outoffs[0].as<int64_t>(), nullptr, pretok, bitmap ? ws->s_out[0].as<uint64_t>() : nullptr, &tokens);
-        if (needed) *needed = tokens;
-        if (st != TKZ_OK) return st;
-        if (bitmap) {
-            HIP_TRY(hipMemcpy(bitmap, ws->s_out[0].p, (size_t)(total / 64 + 1) * 8, hipMemcpyDeviceToHost));
-            return TKZ_OK;
-        }
-        if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
-        return TKZ_OK;
-    }
-    // ---- chunks on three streams (a single chunk is the loop's one iteration) ----
-    HIP_TRY(ensure_streams(ws));
+    if (p.nchunks == 1) { cut.assign(2, 0); cut[1] = n_docs; }
+    p.blocking = !u16 && p.nchunks == 1 && !(p.pin_in && p.pin_out && pretok && !bitmap && total > 0);
     // the kernels write the caller's page-locked ids and offsets themselves -- up to 8 MB of text: beyond that a DMA download beats k_place's stores over PCIe
     // (measured, round 5: 16 MB 1.08 ms direct, 1.00 ms staged)
-    const bool direct_out = nchunks == 1 && pin_out && up_bytes <= (int64_t(8) << 20) * unit;
-    // TWO chunks' launch sequences are enqueued ahead (round 6).  Until then a chunk's kernels were launched when the chunk before had drained -- the host
-    // needs its token count to place the download --, so the device idled for the ~25 launches of every chunk (tools/gpu_job_sdma.sh: 64 MB as 8 chunks took
-    // 1.5 ms longer than as 2, ~250 us a chunk, whatever the download did).  Now chunk k + 2 is begun (encode_device, kCallBegin: enqueue and return) the
-    // moment chunk k has ended (kCallEnd: wait, evaluate, retry if a list has to grow), on the workspace and the stream chunk k has just left: odd and even chunks
-    // alternate between two leased workspaces, two input staging sets and -- since the download of chunk k is only ISSUED when k has ended -- three output sets.
+    p.direct_out = p.nchunks == 1 && p.pin_out && p.up_bytes <= (int64_t(8) << 20) * p.unit;
+    // (... and no upload stream at all: the launch sequence starts with k_ingest, which fetches the text itself)
+    p.ingest_in = p.direct_out && !u16 && p.pin_in && total > 0 && (reinterpret_cast<uintptr_t>(p.dv_in) & 15) == 0;
+    p.nout = p.nchunks > 2 ? 3 : (int)p.nchunks;
+    for (int64_t k = 0; k < p.nchunks; ++k) {
+        p.max_units = std::max(p.max_units, offs[cut[(size_t)k + 1]] - offs[cut[(size_t)k]]);
+        p.max_docs = std::max(p.max_docs, cut[(size_t)k + 1] - cut[(size_t)k]);
+    }
+    return p;
+}
+
+// one chunk, ordinary (pageable) buffers: blocking copies either side of the launch sequence
+tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const uint8_t* bytes, const int64_t* offs, int64_t n_docs, int32_t* out_ids, int64_t out_cap,
+                                int64_t* out_offsets, int64_t* needed, bool pretok, uint64_t* bitmap) {
+    int64_t* acc = &ws->bytes_allocated;
+    const int64_t total = offs[n_docs];
+    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
+    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
+    const int64_t cap = bitmap ? 0 : std::min<int64_t>(out_cap, total);   // tokens <= bytes: more capacity is never used
+    if (!bitmap) {
+        HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
+        HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
+    } else {
+        HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, acc));
+    }
+    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ws->s_offs[0].p, offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    int64_t tokens = 0;
+    const tkz_status st = encode_device(e, ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap,
+                                        ws->s_outoffs[0].as<int64_t>(), nullptr, pretok, bitmap ? ws->s_out[0].as<uint64_t>() : nullptr, &tokens);
+    if (needed) *needed = tokens;
+    if (st != TKZ_OK) return st;
+    if (bitmap) {
+        HIP_TRY(hipMemcpy(bitmap, ws->s_out[0].p, (size_t)(total / 64 + 1) * 8, hipMemcpyDeviceToHost));
+        return TKZ_OK;
+    }
+    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+
+// Inside the pipeline a failed runtime call is RECORDED (HostPipeline::note), never returned from encode_host: the upload of a later chunk may still be reading the
+// caller's text and the download of an earlier one writing the caller's ids, and the caller is free to release both the moment it sees the error; HostPipeline::drain
+// always runs first.  The `return` leaves the member function the macro stands in, no more.
+#define PIPELINE_TRY(expr) { const hipError_t e_ = (expr); if (e_ != hipSuccess) return this->note(fail(TKZ_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_))); }
+
+// Chunks on three streams (a single chunk is the loop's one iteration).
+// TWO chunks' launch sequences are enqueued ahead (round 6).  Until then a chunk's kernels were launched when the chunk before had drained -- the host
+// needs its token count to place the download --, so the device idled for the ~25 launches of every chunk (tools/gpu_job_sdma.sh: 64 MB as 8 chunks took
+// 1.5 ms longer than as 2, ~250 us a chunk, whatever the download did).  Now chunk k + 2 is begun (encode_device, kCallBegin: enqueue and return) the
+// moment chunk k has ended (kCallEnd: wait, evaluate, retry if a list has to grow), on the workspace and the stream chunk k has just left: odd and even chunks
+// alternate between two leased workspaces, two input staging sets and -- since the download of chunk k is only ISSUED when k has ended -- three output sets.
+struct HostPipeline {
+    // the call
+    tkz_encoder* e; Workspace* ws; const HostPlan& p;
+    const uint8_t* bytes; const uint16_t* units; const int64_t* offs; int64_t n_docs; int32_t* out_ids; int64_t out_cap; int64_t* out_offsets; int64_t* needed;
+    const bool u16 = units != nullptr;
+    int64_t* const acc = &ws->bytes_allocated;
+    // its state
     std::unique_ptr<Lease> lease_b;
     Workspace* W[2] = {ws, ws};
-    if (nchunks > 1) {
-        lease_b.reset(new Lease(e));
-        W[1] = lease_b->ws;
-        if (!W[1]->st_compute) HIP_TRY(hipStreamCreate(&W[1]->st_compute));
-    }
-    const int nout = nchunks > 2 ? 3 : (int)nchunks;
-    int64_t max_units = 0, max_docs = 0;
-    for (int64_t k = 0; k < nchunks; ++k) {
-        max_units = std::max(max_units, offs[cut[(size_t)k + 1]] - offs[cut[(size_t)k]]);
-        max_docs = std::max(max_docs, cut[(size_t)k + 1] - cut[(size_t)k]);
-    }
-    for (int q = 0; q < (nchunks > 1 ? 2 : 1); ++q) {
-        if (u16) {
-            Workspace::U16Stage& U = ws->u16[q];
-            const int64_t nw = max_units / 64 + 1, nt = u16_tiles(max_units), nblk = (nt + kScanBlock - 1) / kScanBlock;
-            HIP_TRY(U.units.ensure((size_t)(max_units + 64) * 2, acc));
-            HIP_TRY(U.offs.ensure((size_t)(max_docs + 1) * 8, acc));
-            HIP_TRY(U.docbits.ensure((size_t)(nw + 8) * 8, acc));
-            HIP_TRY(U.grp.ensure((size_t)nt * 64 * 4, acc));
-            HIP_TRY(U.tsum.ensure((size_t)nt * 4, acc));
-            HIP_TRY(U.tbase.ensure((size_t)nt * 8, acc));
-            HIP_TRY(U.bsum.ensure((size_t)(nblk + 1) * 8, acc));
-            HIP_TRY(U.counters.ensure(64, acc));
-            HIP_TRY(U.boffs.ensure((size_t)(max_docs + 1) * 8, acc));
-            if (!U.h) HIP_TRY(hipHostMalloc((void**)&U.h, 64, 0));
-        } else {
-            HIP_TRY(ws->s_bytes[q].ensure((size_t)max_units + 64, acc));
-            HIP_TRY(ws->s_offs[q].ensure((size_t)(max_docs + 1) * 8, acc));
+    // what encode_device was given for the chunk in flight on W[q] (kCallEnd is handed the same)
+    struct InFlight { const uint8_t* cb; const int64_t* co; int64_t cbytes, nd, cap; int32_t* dst_ids; int64_t* dst_offs; } fl[2] = {};
+    const IngestSrc ingest_src{static_cast<const uint8_t*>(p.dv_in), static_cast<const int64_t*>(p.dv_offs)};
+    std::vector<int64_t> tok_base = std::vector<int64_t>((size_t)p.nchunks + 1, 0);
+    bool over = false;                                       // out_cap exceeded: the remaining chunks are only counted
+    bool sdma_out = false;                                   // downloads by copy engine (reserve_staging)
+    bool sig_pending[3] = {false, false, false}, sigo_pending[3] = {false, false, false}, ev_pending[3] = {false, false, false};
+    tkz_status first_err = TKZ_OK;
+    std::string first_msg;
+
+    tkz_status note(tkz_status s) { if (first_err == TKZ_OK) { first_err = s; first_msg = g_err; } return s; }
+
+    // streams, the second workspace, staging for the largest chunk, the copy engine's signals.  Nothing is in flight yet: a failure here is returned as it is
+    tkz_status reserve_staging() {
+        using namespace tkz;
+        const int64_t nchunks = p.nchunks, max_units = p.max_units, max_docs = p.max_docs;
+        HIP_TRY(ensure_streams(ws));
+        if (nchunks > 1) {
+            lease_b.reset(new Lease(e));
+            W[1] = lease_b->ws;
+            if (!W[1]->st_compute) HIP_TRY(hipStreamCreate(&W[1]->st_compute));
         }
-    }
-    if (!direct_out) for (int o = 0; o < nout; ++o) {
-        HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
-        HIP_TRY(ws->s_outoffs[o].ensure((size_t)(max_docs + 1) * 8, acc));
+        for (int q = 0; q < (nchunks > 1 ? 2 : 1); ++q) {
+            if (u16) {
+                HIP_TRY(ws->u16[q].ensure(max_units, max_docs, acc));
+            } else {
+                HIP_TRY(ws->s_bytes[q].ensure((size_t)max_units + 64, acc));
+                HIP_TRY(ws->s_offs[q].ensure((size_t)(max_docs + 1) * 8, acc));
+            }
+        }
+        if (!p.direct_out) for (int o = 0; o < p.nout; ++o) {
+            HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
+            HIP_TRY(ws->s_outoffs[o].ensure((size_t)(max_docs + 1) * 8, acc));
+        }
+        // downloads by copy engine: page-locked results whose device-side address is their host address (hipHostMalloc, tkz_host_alloc, torch's pinned tensors --
+        // not memory registered after the fact, which the HSA runtime knows under another address)
+        if (ws->sdma_state == 0) {
+            bool ok = sdma_available(e->device);
+            for (int o = 0; o < 3 && ok; ++o) ok = sdma_signal_create(&ws->sig_out[o]) && sdma_signal_create(&ws->sig_outoffs[o]);
+            ws->sdma_state = ok ? 1 : -1;
+        }
+        sdma_out = ws->sdma_state == 1 && !p.direct_out && p.pin_out && p.dv_ooffs == (void*)out_offsets && (out_cap == 0 || p.dv_ids == (void*)out_ids);
+        return TKZ_OK;
     }
     // the input of chunk k, on its way to the device (stream st_in); for UTF-16 also its document marks, the UTF-8 length of every unit and their scan
-    auto stage_in = [&](int64_t k) -> tkz_status {
+    tkz_status stage_in(int64_t k) {
+        using namespace tkz;
+        const std::vector<int64_t>& cut = p.cut;
         const int q = (int)(k & 1);
         const int64_t d0 = cut[(size_t)k], d1 = cut[(size_t)k + 1], u0 = offs[d0], nu = offs[d1] - u0, nd = d1 - d0;
         Launch L{ws->st_in, nullptr, ws};
@@ -1367,38 +1424,18 @@ tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* uni
         }
         HIP_TRY(hipEventRecord(ws->ev_in[q], ws->st_in));
         return TKZ_OK;
-    };
-    std::vector<int64_t> tok_base((size_t)nchunks + 1, 0);
-    bool over = false;                                       // out_cap exceeded: the remaining chunks are only counted
-    // downloads by copy engine: page-locked results whose device-side address is their host address (hipHostMalloc, tkz_host_alloc, torch's pinned tensors --
-    // not memory registered after the fact, which the HSA runtime knows under another address)
-    if (ws->sdma_state == 0) {
-        bool ok = sdma_available(e->device);
-        for (int o = 0; o < 3 && ok; ++o) ok = sdma_signal_create(&ws->sig_out[o]) && sdma_signal_create(&ws->sig_outoffs[o]);
-        ws->sdma_state = ok ? 1 : -1;
     }
-    bool sdma_out = ws->sdma_state == 1 && !direct_out && pin_out && dv_ooffs == (void*)out_offsets && (out_cap == 0 || dv_ids == (void*)out_ids);
-    bool sig_pending[3] = {false, false, false}, sigo_pending[3] = {false, false, false}, ev_pending[3] = {false, false, false};
-    auto wait_engine = [&](int o) {          // the copies of output set o that went by engine have arrived
+    bool wait_engine(int o) {                // the copies of output set o that went by engine have arrived
         bool ok = true;
-        if (sig_pending[o]) { sig_pending[o] = false; ok = sdma_signal_wait(ws->sig_out[o]) && ok; }
-        if (sigo_pending[o]) { sigo_pending[o] = false; ok = sdma_signal_wait(ws->sig_outoffs[o]) && ok; }
+        if (sig_pending[o]) { sig_pending[o] = false; ok = tkz::sdma_signal_wait(ws->sig_out[o]) && ok; }
+        if (sigo_pending[o]) { sigo_pending[o] = false; ok = tkz::sdma_signal_wait(ws->sig_outoffs[o]) && ok; }
         return ok;
-    };
-    tkz_status first_err = TKZ_OK;
-    std::string first_msg;
-    auto note = [&](tkz_status s) { if (first_err == TKZ_OK) { first_err = s; first_msg = g_err; } return s; };
-    // (one small chunk on page-locked buffers: no upload stream at all -- the launch sequence starts with k_ingest, which fetches the text itself)
-    const bool ingest_in = direct_out && !u16 && pin_in && total > 0 && (reinterpret_cast<uintptr_t>(dv_in) & 15) == 0;
-    const IngestSrc ingest_src{static_cast<const uint8_t*>(dv_in), static_cast<const int64_t*>(dv_offs)};
-    // what encode_device was given for the chunk in flight on W[q] (kCallEnd is handed the same)
-    struct InFlight { const uint8_t* cb; const int64_t* co; int64_t cbytes, nd, cap; int32_t* dst_ids; int64_t* dst_offs; } fl[2] = {};
-    // (inside the lambdas a failed runtime call is RECORDED, never returned from the function: the upload of a later chunk may still be reading the caller's text and the
-    //  download of an earlier one writing the caller's ids, and the caller is free to release both the moment it sees the error; the drain behind the loop always runs first)
-#define CHUNK_TRY(expr) { const hipError_t e_ = (expr); if (e_ != hipSuccess) return note(fail(TKZ_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_))); }
+    }
     // enqueue chunk k's launch sequence behind its upload (one chunk: run it whole -- phase kCallWhole)
-    auto begin_chunk = [&](int64_t k, int phase, int64_t* tokens) -> tkz_status {
-        const int q = (int)(k & 1), o = (int)(k % nout);
+    tkz_status begin_chunk(int64_t k, int phase, int64_t* tokens) {
+        using namespace tkz;
+        const std::vector<int64_t>& cut = p.cut;
+        const int q = (int)(k & 1), o = (int)(k % p.nout);
         Workspace* w = W[q];
         const int64_t d0 = cut[(size_t)k], d1 = cut[(size_t)k + 1], nu = offs[d1] - offs[d0], nd = d1 - d0;
         InFlight& F = fl[q];
@@ -1406,131 +1443,158 @@ tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* uni
         if (u16) {
             // the UTF-8 size of the chunk is known once its length pass is through (the host needs it: the launch shapes of the encode path)
             Workspace::U16Stage& U = ws->u16[q];
-            CHUNK_TRY(hipEventSynchronize(ws->ev_in[q]));
-            if (U.h->err & kErrOffsets) return note(fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the unit count"));
+            PIPELINE_TRY(hipEventSynchronize(ws->ev_in[q]));
+            if (U.h->err & kErrOffsets) return note(fail(TKZ_E_ARG, kMsgUnitOffsets));
             F.cbytes = U.h->grand;
-            CHUNK_TRY(ws->u_bytes[q].ensure((size_t)F.cbytes + 64, acc));
+            PIPELINE_TRY(ws->u_bytes[q].ensure((size_t)F.cbytes + 64, acc));
             Launch L{w->st_compute, nullptr, w};
             launch_u16_write(L, U.units.as<uint16_t>(), nu, U.docbits.as<uint64_t>(), u16_tiles(nu), U.tbase.as<int64_t>(), ws->u_bytes[q].as<uint8_t>(),
                              U.offs.as<int64_t>(), nd, U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>());
             F.cb = ws->u_bytes[q].as<uint8_t>(); F.co = U.boffs.as<int64_t>();
         } else {
-            if (!ingest_in) CHUNK_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_in[q], 0));
+            if (!p.ingest_in) PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_in[q], 0));
             F.cb = ws->s_bytes[q].as<uint8_t>(); F.co = ws->s_offs[q].as<int64_t>(); F.cbytes = nu;
         }
         // the download of chunk k - nout has left this chunk's output set
-        if (!wait_engine(o)) return note(fail(TKZ_E_DEVICE, "a copy engine reported an error for a download"));
-        if (ev_pending[o]) { ev_pending[o] = false; CHUNK_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_out[o], 0)); }
-        F.dst_ids = direct_out ? static_cast<int32_t*>(dv_ids) : ws->s_out[o].as<int32_t>();
-        F.dst_offs = direct_out ? static_cast<int64_t*>(dv_ooffs) : ws->s_outoffs[o].as<int64_t>();
+        if (!wait_engine(o)) return note(fail(TKZ_E_DEVICE, kMsgEngineDownload));
+        if (ev_pending[o]) { ev_pending[o] = false; PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_out[o], 0)); }
+        F.dst_ids = p.direct_out ? static_cast<int32_t*>(p.dv_ids) : ws->s_out[o].as<int32_t>();
+        F.dst_offs = p.direct_out ? static_cast<int64_t*>(p.dv_ooffs) : ws->s_outoffs[o].as<int64_t>();
         // (how much of out_cap the chunks before leave is not known yet when a chunk is begun: the staging set holds a chunk's ids whatever their number, and the
         //  sum is checked when the chunk ends)
         F.cap = over ? 0 : std::min<int64_t>(out_cap, F.cbytes);
         return encode_device(e, w, F.cb, F.co, F.nd, F.cbytes, F.dst_ids, F.cap, F.dst_offs, w->st_compute, true, nullptr, tokens, nullptr, phase, nullptr,
-                             ingest_in ? &ingest_src : nullptr);
-    };
-    auto end_chunk = [&](int64_t k, int64_t* tokens) -> tkz_status {          // (returns when the chunk's stream has drained)
+                             p.ingest_in ? &ingest_src : nullptr);
+    }
+    tkz_status end_chunk(int64_t k, int64_t* tokens) {          // (returns when the chunk's stream has drained)
         const InFlight& F = fl[k & 1];
         Workspace* w = W[k & 1];
         return encode_device(e, w, F.cb, F.co, F.nd, F.cbytes, F.dst_ids, F.cap, F.dst_offs, w->st_compute, true, nullptr, tokens, nullptr, kCallEnd, nullptr, nullptr);
-    };
+    }
+    // (an engine that refuses a copy is not asked again: that copy and the rest of the call go through the runtime)
+    bool by_engine(void* dst, const void* src, size_t nb, tkz::SdmaSignal sg, bool* pending) {
+        using namespace tkz;
+        if (!sdma_out) return false;
+        sdma_signal_arm(sg, 1);
+        if (sdma_copy_d2h(e->device, dst, src, nb, sg)) { *pending = true; ws->engine_downloads.fetch_add(1, std::memory_order_relaxed); return true; }
+        sdma_signal_arm(sg, 0); sdma_out = false; ws->sdma_state = -1;
+        return false;
+    }
     // The download of chunk k.  The runtime's D2H copy of page-locked memory is a blit KERNEL and other kernels make no progress beside it (traced, round 5; a
     // small-grid download kernel of our own stalled their first stores until its PCIe writes had drained).  Page-locked results therefore leave on a COPY ENGINE
     // of their own, named through the HSA runtime (tkz_sdma.h; tools/sdma_probe.hip: 56 GB/s beside a store-heavy kernel, and beside the runtime's upload
     // when the engines differ).  The kernels of the chunk have completed (end_chunk returned), which is all such a copy waits for.
-    auto download = [&](int64_t k, int64_t tokens) -> tkz_status {
-        const int o = (int)(k % nout);
-        const int64_t d0 = cut[(size_t)k], nd = cut[(size_t)k + 1] - d0;
+    tkz_status download(int64_t k, int64_t tokens) {
+        const int o = (int)(k % p.nout);
+        const int64_t d0 = p.cut[(size_t)k], nd = p.cut[(size_t)k + 1] - d0;
         bool ids_sent = tokens == 0, offs_sent = false;
         const size_t nb_ids = (size_t)tokens * 4, nb_offs = (size_t)(nd + 1) * 8;
-        // (an engine that refuses a copy is not asked again: that copy and the rest of the call go through the runtime)
-        auto by_engine = [&](void* dst, const void* src, size_t nb, SdmaSignal sg, bool* pending) {
-            if (!sdma_out) return false;
-            sdma_signal_arm(sg, 1);
-            if (sdma_copy_d2h(e->device, dst, src, nb, sg)) { *pending = true; ws->engine_downloads.fetch_add(1, std::memory_order_relaxed); return true; }
-            sdma_signal_arm(sg, 0); sdma_out = false; ws->sdma_state = -1;
-            return false;
-        };
         if (tokens) ids_sent = by_engine(out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
         offs_sent = by_engine(out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
         if (!ids_sent || !offs_sent) {
-            if (!ids_sent) CHUNK_TRY(hipMemcpyAsync(out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
-            if (!offs_sent) CHUNK_TRY(hipMemcpyAsync(out_offsets + d0, ws->s_outoffs[o].p, nb_offs, hipMemcpyDeviceToHost, ws->st_out));
-            CHUNK_TRY(hipEventRecord(ws->ev_out[o], ws->st_out));
+            if (!ids_sent) PIPELINE_TRY(hipMemcpyAsync(out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
+            if (!offs_sent) PIPELINE_TRY(hipMemcpyAsync(out_offsets + d0, ws->s_outoffs[o].p, nb_offs, hipMemcpyDeviceToHost, ws->st_out));
+            PIPELINE_TRY(hipEventRecord(ws->ev_out[o], ws->st_out));
             ev_pending[o] = true;
         }
         return TKZ_OK;
-    };
-    int64_t begun = 0, ended = 0;            // chunks [ended, begun) are in flight
-    // ($TKZ_TRACE_HOST: the host's side of the pipeline on stderr -- microseconds since the call began at which each step RETURNED; development)
-    static const bool kTraceHost = getenv("TKZ_TRACE_HOST") != nullptr;
-    const auto t_call = std::chrono::steady_clock::now();
-    std::vector<std::pair<std::string, double>> stamps;
-    auto stamp = [&](const char* what, int64_t k) {
-        if (kTraceHost) stamps.emplace_back(std::string(what) + " " + std::to_string(k), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count());
-    };
-    auto finish = [&](int64_t k, tkz_status cs, int64_t tokens) -> bool {      // chunk k has ended with status cs: its place in the output, its download; false: stop
+    }
+    bool finish(int64_t k, tkz_status cs, int64_t tokens) {      // chunk k has ended with status cs: its place in the output, its download; false: stop
         tok_base[(size_t)k + 1] = tok_base[(size_t)k] + tokens;
         if (cs == TKZ_E_CAPACITY || (cs == TKZ_OK && tok_base[(size_t)k + 1] > out_cap)) { over = true; return true; }
         if (cs != TKZ_OK) { note(cs); return false; }
-        if (!over && !direct_out && download(k, tokens) != TKZ_OK) return false;
+        if (!over && !p.direct_out && download(k, tokens) != TKZ_OK) return false;
         return true;
-    };
-    if (nchunks == 1) {
-        int64_t tokens = 0;
-        const tkz_status ss = ingest_in ? TKZ_OK : stage_in(0);
-        if (ss == TKZ_OK) { const tkz_status cs = begin_chunk(0, kCallWhole, &tokens); if (first_err == TKZ_OK) (void)finish(0, cs, tokens); }
-        else note(ss);
-    } else {
-        // (upload 1 is issued BEHIND launch sequence 0, although that starts it ~130 us late: an upload stream's k_rebase kernel waits in a hardware queue for its copy, and
-        //  the launch sequence of chunk 0 enqueued behind it -- the runtime maps its streams onto a few hardware queues -- waited with it: 16 MB 884 -> 1,040 us)
-        for (int64_t k = 0; k < 2 && first_err == TKZ_OK; ++k) {
-            { const tkz_status ss = stage_in(k); if (ss != TKZ_OK) { note(ss); break; } }
-            const tkz_status bs = begin_chunk(k, kCallBegin, nullptr);
-            if (bs != TKZ_OK) { note(bs); break; }
-            ++begun;
-            stamp("begun", k);
-        }
-        for (int64_t k = 0; k < nchunks && first_err == TKZ_OK; ++k) {
+    }
+    void drain() {                           // every copy of the call has left the caller's buffers
+        (void)hipStreamSynchronize(ws->st_in);      // (an error of the runtime here is an error of the copies above: reported by them or by the next call)
+        (void)hipStreamSynchronize(ws->st_out);
+        for (int o = 0; o < 3; ++o)
+            if (!wait_engine(o)) note(fail(TKZ_E_DEVICE, kMsgEngineDownload));
+    }
+    tkz_status run() {
+        const int64_t nchunks = p.nchunks;
+        int64_t begun = 0, ended = 0;            // chunks [ended, begun) are in flight
+        HostTrace trace;
+        if (nchunks == 1) {
             int64_t tokens = 0;
-            const tkz_status cs = end_chunk(k, &tokens);
-            ++ended;
-            stamp("ended", k);
-            if (!finish(k, cs, tokens)) break;
-            stamp("download issued", k);
-            if (k + 2 < nchunks) {         // (its input set and its workspace are chunk k's: free now)
-                tkz_status bs = stage_in(k + 2);
-                if (bs == TKZ_OK) bs = begin_chunk(k + 2, kCallBegin, nullptr);
+            const tkz_status ss = p.ingest_in ? TKZ_OK : stage_in(0);
+            if (ss == TKZ_OK) { const tkz_status cs = begin_chunk(0, kCallWhole, &tokens); if (first_err == TKZ_OK) (void)finish(0, cs, tokens); }
+            else note(ss);
+        } else {
+            // (upload 1 is issued BEHIND launch sequence 0, although that starts it ~130 us late: an upload stream's k_rebase kernel waits in a hardware queue for its copy, and
+            //  the launch sequence of chunk 0 enqueued behind it -- the runtime maps its streams onto a few hardware queues -- waited with it: 16 MB 884 -> 1,040 us)
+            for (int64_t k = 0; k < 2 && first_err == TKZ_OK; ++k) {
+                { const tkz_status ss = stage_in(k); if (ss != TKZ_OK) { note(ss); break; } }
+                const tkz_status bs = begin_chunk(k, kCallBegin, nullptr);
                 if (bs != TKZ_OK) { note(bs); break; }
                 ++begun;
-                stamp("begun", k + 2);
+                trace.stamp("begun", k);
             }
+            for (int64_t k = 0; k < nchunks && first_err == TKZ_OK; ++k) {
+                int64_t tokens = 0;
+                const tkz_status cs = end_chunk(k, &tokens);
+                ++ended;
+                trace.stamp("ended", k);
+                if (!finish(k, cs, tokens)) break;
+                trace.stamp("download issued", k);
+                if (k + 2 < nchunks) {         // (its input set and its workspace are chunk k's: free now)
+                    tkz_status bs = stage_in(k + 2);
+                    if (bs == TKZ_OK) bs = begin_chunk(k + 2, kCallBegin, nullptr);
+                    if (bs != TKZ_OK) { note(bs); break; }
+                    ++begun;
+                    trace.stamp("begun", k + 2);
+                }
+            }
+            // (a chunk that was begun is always ended: its workspace may hold the encoder's learning slot, and its kernels write the staging sets)
+            for (; ended < begun; ++ended) { const std::string keep = g_err; int64_t t = 0; (void)end_chunk(ended, &t); g_err = keep; }
         }
-        // (a chunk that was begun is always ended: its workspace may hold the encoder's learning slot, and its kernels write the staging sets)
-        for (; ended < begun; ++ended) { const std::string keep = g_err; int64_t t = 0; (void)end_chunk(ended, &t); g_err = keep; }
+        drain();
+        if (nchunks > 1) { trace.stamp("downloads arrived", nchunks); trace.print(nchunks); }
+        if (first_err != TKZ_OK) return fail(first_err, first_msg);
+        if (needed) *needed = tok_base[(size_t)nchunks];
+        if (over) return fail(TKZ_E_CAPACITY, "output capacity too small");
+        // the offsets came back relative to their chunk: add the chunk's token base (chunk 0 needs nothing; the shared boundary entry
+        // of two chunks was written by the later one as 0 and gets that chunk's base, which is what the earlier chunk's last entry was)
+        for (int64_t k = 1; k < nchunks; ++k) {
+            const int64_t tb = tok_base[(size_t)k];
+            for (int64_t d = p.cut[(size_t)k]; d < p.cut[(size_t)k + 1]; ++d) out_offsets[d] += tb;
+        }
+        out_offsets[n_docs] = tok_base[(size_t)nchunks];
+        return TKZ_OK;
     }
-#undef CHUNK_TRY
-    (void)hipStreamSynchronize(ws->st_in);      // (an error of the runtime here is an error of the copies above: reported by them or by the next call)
-    (void)hipStreamSynchronize(ws->st_out);
-    for (int o = 0; o < 3; ++o)
-        if (!wait_engine(o)) note(fail(TKZ_E_DEVICE, "a copy engine reported an error for a download"));
-    if (kTraceHost && nchunks > 1) {
-        stamp("downloads arrived", nchunks);
-        std::string line = "[tkz host trace] " + std::to_string(nchunks) + " chunks:";
-        for (const auto& sp : stamps) { char b[96]; snprintf(b, sizeof b, " %s @%.0f", sp.first.c_str(), sp.second); line += b; }
-        fprintf(stderr, "%s\n", line.c_str());
+};
+#undef PIPELINE_TRY
+
+// validate -> the single-launch path -> plan -> one blocking chunk, or the pipeline
+tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* units, const int64_t* offs, int64_t n_docs, int32_t* out_ids,
+                       int64_t out_cap, int64_t* out_offsets, int64_t* needed, bool pretok, uint64_t* bitmap) {
+    DeviceScope scope;
+    tkz_status st = check_encoder(e, scope);
+    if (st != TKZ_OK) return st;
+    const bool u16 = units != nullptr;
+    if (n_docs < 0 || !offs || (n_docs > 0 && !bytes && !units && offs[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
+    if (offs[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
+    const int64_t total = offs[n_docs];                      // bytes, or code units
+    if (total < 0) return fail(TKZ_E_ARG, u16 ? "negative unit count" : "negative byte count");
+    if (needed) *needed = 0;
+    if (u16 && total == 0) {
+        for (int64_t d = 0; d <= n_docs; ++d) { if (offs[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); out_offsets[d] = 0; }
+        return TKZ_OK;
     }
-    if (first_err != TKZ_OK) return fail(first_err, first_msg);
-    if (needed) *needed = tok_base[(size_t)nchunks];
-    if (over) return fail(TKZ_E_CAPACITY, "output capacity too small");
-    // the offsets came back relative to their chunk: add the chunk's token base (chunk 0 needs nothing; the shared boundary entry
-    // of two chunks was written by the later one as 0 and gets that chunk's base, which is what the earlier chunk's last entry was)
-    for (int64_t k = 1; k < nchunks; ++k) {
-        const int64_t tb = tok_base[(size_t)k];
-        for (int64_t d = cut[(size_t)k]; d < cut[(size_t)k + 1]; ++d) out_offsets[d] += tb;
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
+    if (!u16 && pretok && !bitmap && small_eligible(e, offs, n_docs, total)) {
+        bool handled = false;
+        st = encode_small(e, ws, bytes, offs, n_docs, total, out_ids, out_cap, out_offsets, needed, &handled);
+        if (st != TKZ_OK || handled) return st;
     }
-    out_offsets[n_docs] = tok_base[(size_t)nchunks];
-    return TKZ_OK;
+    const HostPlan plan = plan_host_batch(u16 ? (const void*)units : (const void*)bytes, u16, offs, n_docs, out_ids, out_cap, out_offsets, pretok, bitmap);
+    if (plan.blocking) return encode_host_blocking(e, ws, bytes, offs, n_docs, out_ids, out_cap, out_offsets, needed, pretok, bitmap);
+    HostPipeline pipe{e, ws, plan, bytes, units, offs, n_docs, out_ids, out_cap, out_offsets, needed};
+    TKZ_TRY(pipe.reserve_staging());
+    return pipe.run();
 }
 
 const char* const kRegexP1 = "'s|'t|'re|'ve|'m|'ll|'d| ?\\p{L}+| ?\\p{N}+| ?[^\\s\\p{L}\\p{N}]+|\\s+(?!\\S)|\\s+";

@@ -12,6 +12,8 @@ export TKZ_SIZING_MIN_SUB=4000000000
 # (--heldout-steps 0 --pipelined-steps 0 --no-piece-stats: nothing but the headline steps, their warm-up and the sizing pass run under the profiler -- per-launch averages of a kernel are over THOSE launches)
 BENCH="python $REPO/bench.py --docs $DOCS --steps 3 --warmup 1 --no-cpu-baseline --heldout-steps 0 --pipelined-steps 0 --no-piece-stats --no-first-call $EXTRA"
 cd /tmp
+# a pass that does not exit 0 ends the script with that status: nothing more is started on a GPU that has just failed a program
+trap 'rc=$?; echo "a profiler pass exited $rc: stopping"; exit $rc' ERR
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/gpurun_out/prof_$TAG/trace -o trace -- $BENCH > $REPO/gpurun_out/prof_$TAG/trace.log 2>&1; echo "trace rc=$?"
 i=0
 for C in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
@@ -20,6 +22,7 @@ for C in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_
   i=$((i+1))
   timeout 600 rocprofv3 --pmc $C --output-format csv -d $REPO/gpurun_out/prof_$TAG/pmc$i -o pmc -- $BENCH > $REPO/gpurun_out/prof_$TAG/pmc$i.log 2>&1; echo "pmc$i rc=$?"
 done
+trap - ERR
 cd $REPO
 python tools/summarize_prof.py gpurun_out/prof_$TAG > gpurun_out/prof_$TAG/summary.txt 2>&1
 KIND=1; case "$EXTRA" in *"--kind 2"*) KIND=2;; *"--kind 3"*) KIND=3;; *"--kind 4"*) KIND=4;; *"--kind 6"*) KIND=6;; esac
