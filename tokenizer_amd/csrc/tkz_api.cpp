@@ -15,10 +15,12 @@
 #include <vector>
 
 #include "../../include/tkz.h"
+#include "tkz_adapt.h"
 #include "tkz_bpe.h"
 #include "tkz_corpus.h"
 #include "tkz_kernels.h"
 #include "tkz_pretok.h"
+#include "tkz_promo_select.h"
 #include "tkz_sdma.h"
 #include "tkz_vocab.h"
 
@@ -201,8 +203,6 @@ struct Workspace {
     }
 };
 
-constexpr int64_t kPromoSecondBytes = int64_t(1) << 30;      // the second learning round follows the first window by this much text (then 2, 4, 8 ... times: encode_device)
-
 struct tkz_encoder {
     int device = 0;
     int pattern = 0;
@@ -231,43 +231,17 @@ struct tkz_encoder {
     int pending = 0;                       // tkz_pending handles outstanding (under mu)
     bool destroyed = false;                // tkz_encoder_destroy was called while handles were outstanding: the last _end frees the encoder
     // ---- promoted pieces (tkz_tables.h): hot memo entries moved into the SHORT / MID tables themselves.  All under mu. ----
-    int promo_mode = 1;                    // TKZ_OPT_PROMOTE: 0 never on its own, 1 automatic (default)
-    int promo_rounds = 0;                  // automatic promotions so far
-    int64_t promo_min_bytes = int64_t(8) << 20;   // a batch of at least this many bytes may be a learning batch (TKZ_OPT_PROMOTE_MIN_BYTES)
-    size_t promo_cap = 65536;              // promoted pieces the key tables hold at most (TKZ_OPT_PROMOTE_CAP)
-    bool learning = false;                 // a batch that counts memo hits is in flight (one at a time)
-    int64_t bytes_seen = 0, bytes_at_promo = 0;   // bytes the batch path has encoded; ... when the last promotion happened
+    tkz::AdaptPolicy policy;               // WHEN a window opens, is promoted, is thrown away (tkz_adapt.h); every call to it is made with mu held
     DevBuf t_memo_hits, t_promo;           // the hit counters of a learning batch; the token quads of the promoted pieces
     DevBuf t_long_log;                     // ... and its log of merged pieces of 17..28 bytes (EncodeParams::long_log)
     int64_t long_log_n = 0;                // records the last learning batch left there (set when it ended)
     std::vector<DevBuf> retired;           // table images replaced while other calls may still have been probing them: freed when no call of the encoder is in flight (Lease)
-    // ---- the cache ADAPTS (round 6; TKZ_OPT_ADAPT, all under mu).  The reference's LRUCache evicts and refills for ever (LRUCache.cs:79-121); here the share
-    // of pieces that miss the key tables as a whole is followed from batch to batch (k_list_stats sums the miss lists: no extra kernel), and when it leaves
-    // the level it had after the last promotion the encoder LEARNS AGAIN: promotions dropped, memo emptied, the next batches count hits, the hottest pieces of
-    // the text as it is NOW are promoted (pieces that stopped hitting are simply not chosen again).
-    int adapt = 1;                         // TKZ_OPT_ADAPT
-    // (how much text the miss share is averaged over / has to settle for after a promotion, and how soon after one the encoder may learn again; the
-    //  environment variables are the tests' handle on them: their batches are kilobytes)
-    int64_t adapt_settle_bytes = [] { const char* v = getenv("TKZ_ADAPT_SETTLE_BYTES"); return v && atoll(v) > 0 ? (int64_t)atoll(v) : int64_t(64) << 20; }();
-    int64_t adapt_round_bytes = [] { const char* v = getenv("TKZ_ADAPT_ROUND_BYTES"); return v && atoll(v) > 0 ? (int64_t)atoll(v) : kPromoSecondBytes; }();     // (the tests' handle on the rounds' spacing)
-    int64_t adapt_min_bytes = [] { const char* v = getenv("TKZ_ADAPT_MIN_BYTES"); return v && atoll(v) > 0 ? (int64_t)atoll(v) : int64_t(256) << 20; }();
-    double ew_miss = 0, base_miss = 0;     // miss share of the recent batches (weighted by their bytes, 64 MB time constant); ... as it settled after the last promotion
-    bool ew_valid = false, base_valid = false;
-    double win_miss = 0, win_pieces = 0;   // misses and pieces of the learning window so far ...
-    double window_miss = 0;                // ... and the miss share of the window the LAST install was learnt in (promotions only lower it on unchanged text)
-    bool window_valid = false;
-    double last_window_miss = 0;           // the same, kept for the NEXT window to be compared with
-    bool last_window_valid = false;
-    int64_t bytes_at_install = 0;          // bytes_seen when the key tables were last replaced
-    int64_t learn_bytes = 0;               // bytes of the learning window so far (batches smaller than promo_min_bytes add up to one)
-    bool memo_clear_pending = false;       // the memo is emptied before the next learning window starts (only while no other call is in flight)
-    int64_t n_promotions = 0, n_relearns = 0;
     std::vector<tkz::KeyItem> promo_items; // promoted piece -> promo code, in order of promotion
     std::unordered_set<std::string> promo_keys;
     std::vector<uint32_t> promo_quads;     // 4 tokens per promoted piece (host copy of t_promo)
     uint32_t short_slots_n = 0, mid_slots_n = 0;
     // an automatic promotion runs behind the batch that gathered its statistics (the copy of the memo back to the host, the choice and the rebuilt key
-    // tables are ~50 ms of host work: not something the call that happened to be the learning batch should wait for).  `learning` stays set until it
+    // tables are ~50 ms of host work: not something the call that happened to be the learning batch should wait for).  The policy's learning slot stays taken until it
     // is done, so there is one at a time; joined by join_promotion()
     std::thread promo_thread;
     std::mutex promo_join_mu;
@@ -385,7 +359,6 @@ tkz_status build_decode_table(tkz_encoder* e) {
 // key, the merge kernels never see it, k_place gathers its <= 4 tokens.  Results are the same ids by construction (the memo's answers are exact and a
 // slot is read back under the same validity rule the kernels use); the tests compare a promoted encoder with the oracle.
 constexpr int64_t kLongLogCap = 65536;             // records of merged 17..28-byte pieces a learning batch may log (EncodeParams::long_log)
-constexpr int kPromoAutoRounds = 2;                // automatic promotions: the first batch of >= kPromoMinBytes, and one more after kPromoSecondBytes more
 
 // (re)builds the SHORT / MID images from the vocabulary's keys + the promoted pieces and publishes them; `retire`: other calls may be probing the
 // current images (they are kept until the encoder is destroyed), else they are freed
@@ -453,8 +426,7 @@ tkz_status promote_from_memo(tkz_encoder* e, bool use_hits, bool retire, int64_t
     HIP_TRY(hipMemcpyAsync(memo.data(), e->t_memo.p, memo.size() * sizeof(TkzMemoSlot), hipMemcpyDeviceToHost, cs));
     if (use_hits) { hits.resize(e->memo_slots); HIP_TRY(hipMemcpyAsync(hits.data(), e->t_memo_hits.p, hits.size() * 4, hipMemcpyDeviceToHost, cs)); }
     HIP_TRY(hipStreamSynchronize(cs));
-    // ... and the pieces of 17..28 bytes k_merge_long logged during the learning batch (each with its <= 4 tokens): those that were logged at least
-    // twice -- real source text is full of them: "\n" + 19 spaces, by the hundred thousand -- go into the MID key table the same way
+    // ... and the pieces of 17..28 bytes k_merge_long logged during the learning batch (each with its <= 4 tokens): select_promotions
     std::vector<uint32_t> llog;
     if (use_hits && e->t_long_log.p) {      // (the log's record count lives behind the records: it runs on through the batches of a learning window)
         unsigned long long n = 0;
@@ -469,76 +441,13 @@ tkz_status promote_from_memo(tkz_encoder* e, bool use_hits, bool retire, int64_t
     }
     std::vector<tkz::KeyItem> items_copy;
     std::vector<uint32_t> quads_copy;
-    int64_t n_new = 0;
     {
-    std::lock_guard<std::mutex> lock(e->mu);
-    const size_t cap = e->promo_cap;
-    if (e->promo_items.size() >= cap) return TKZ_OK;
-    if (!llog.empty()) {
-        struct LongCand { uint32_t count; uint32_t rec; };
-        std::unordered_map<std::string, LongCand> seen;
-        for (int64_t r = 0; r < e->long_log_n; ++r) {
-            const uint32_t* rec = &llog[(size_t)r * kLongLogDwords];
-            const uint32_t len = rec[7] & 0xFFu, cnt = (rec[7] >> 8) & 0xFFu;
-            if (len <= 16 || len > (uint32_t)kLongLogMaxLen || cnt < 1 || cnt > 4) continue;
-            std::string key(len, '\0');
-            for (uint32_t b = 0; b < len; ++b) key[b] = (char)((rec[b >> 2] >> (8 * (b & 3))) & 0xFFu);
-            auto it = seen.find(key);
-            if (it == seen.end()) seen.emplace(key, LongCand{1u, (uint32_t)r}); else ++it->second.count;
-        }
-        std::vector<std::pair<uint32_t, const std::string*>> order;
-        for (const auto& kv : seen) if (kv.second.count >= 2 && !e->promo_keys.count(kv.first)) order.emplace_back(kv.second.count, &kv.first);
-        std::sort(order.begin(), order.end(), [](const std::pair<uint32_t, const std::string*>& a, const std::pair<uint32_t, const std::string*>& b) { return a.first != b.first ? a.first > b.first : *a.second < *b.second; });
-        const size_t long_room = std::min(cap - e->promo_items.size(), std::max<size_t>(cap / 4, 1));
-        for (size_t i = 0; i < order.size() && (size_t)n_new < long_room; ++i) {
-            const std::string& key = *order[i].second;
-            const uint32_t* rec = &llog[(size_t)seen[key].rec * kLongLogDwords];
-            const uint32_t cnt = (rec[7] >> 8) & 0xFFu;
-            e->promo_keys.insert(key);
-            const uint32_t index = (uint32_t)e->promo_items.size();
-            e->promo_items.push_back(tkz::KeyItem{key, kPromoFlag | ((cnt - 1u) << kPromoCntShift) | index});
-            for (uint32_t t = 0; t < 4; ++t) e->promo_quads.push_back(t < cnt ? (rec[8 + t] & 0x07FFFFFFu) : 0u);
-            ++n_new;
-        }
-    }
-    struct Cand { uint32_t hits, slot; };
-    std::vector<Cand> cand;
-    uint32_t n_valid = 0;
-    for (uint32_t i = 0; i < e->memo_slots; ++i) {
-        const uint32_t* v = memo[i].v;
-        // the kernels' validity rule: the valid tag in every value word, not the BUSY mark; and a complete key: no zero byte inside its length, nothing
-        // but zero bytes beyond it (other calls may be inserting while this copy was taken)
-        if (!((v[0] & v[1] & v[2] & v[3]) & kMemoValid) || v[0] == kMemoBusy) continue;
-        ++n_valid;
-        if (use_hits && hits[i] == 0) continue;
-        const uint32_t len = ((v[1] >> 27) & 15u) + 1u;
-        bool ok = true;
-        for (uint32_t b = 0; b < 16 && ok; ++b) { const uint32_t byte = (memo[i].k[b >> 2] >> (8 * (b & 3))) & 0xFFu; ok = b < len ? byte != 0 : byte == 0; }
-        if (!ok) continue;
-        cand.push_back(Cand{use_hits ? hits[i] : 1u, i});
-    }
-    // A memo three quarters full takes hardly any new piece (an entry is never replaced; a bucket has two ways): text with many one-off pieces fills it within a
-    // gigabyte, and whatever the text turns into afterwards finds it closed -- the reference's LRUCache would have evicted (LRUCache.cs:79-88).  The next learning
-    // window therefore starts on an EMPTY memo (memo_clear_pending: cleared under the lock while no other call is in flight, as after a drift): the hot pieces are
-    // back within the first megabytes of that batch, the one-off ones are gone.  (tools/adapt_probe.py ... 1: source text behind 3 GB of synthetic text, the change
-    // inside the first promotion's build: 95 GB/s and 2 k new pieces a round with the full memo, against a fresh encoder's 118 and 9 k.)
-    if (use_hits && e->adapt && (uint64_t)n_valid * 4 >= (uint64_t)e->memo_slots * 3) e->memo_clear_pending = true;
-    std::stable_sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.hits > b.hits; });
-    for (const Cand& c : cand) {
-        if (e->promo_items.size() >= cap) break;
-        const TkzMemoSlot& m = memo[c.slot];
-        const uint32_t len = ((m.v[1] >> 27) & 15u) + 1u, cnt = ((m.v[0] >> 29) & 3u) + 1u;
-        std::string key(len, '\0');
-        for (uint32_t b = 0; b < len; ++b) key[b] = (char)((m.k[b >> 2] >> (8 * (b & 3))) & 0xFFu);
-        if (!e->promo_keys.insert(key).second) continue;                        // (promoted before: a stale memo entry)
-        const uint32_t index = (uint32_t)e->promo_items.size();
-        e->promo_items.push_back(tkz::KeyItem{key, kPromoFlag | ((cnt - 1u) << kPromoCntShift) | index});
-        for (int t = 0; t < 4; ++t) e->promo_quads.push_back((uint32_t)t < cnt ? (m.v[t] & 0x07FFFFFFu) : 0u);
-        ++n_new;
-    }
-    if (added) *added = n_new;
-    if (!n_new) return TKZ_OK;
-    items_copy = e->promo_items; quads_copy = e->promo_quads;
+        std::lock_guard<std::mutex> lock(e->mu);
+        const tkz::PromoSelection sel = tkz::select_promotions(memo, use_hits ? &hits : nullptr, llog, e->policy.cap(), &e->promo_items, &e->promo_keys, &e->promo_quads);
+        if (use_hits) e->policy.memo_read_back(sel.valid_slots, e->memo_slots);
+        if (added) *added = sel.added;
+        if (!sel.added) return TKZ_OK;
+        items_copy = e->promo_items; quads_copy = e->promo_quads;
     }
     // the key tables with the promoted pieces in them: built and uploaded WITHOUT the lock (tens of milliseconds), then put in place under it (only one
     // promotion runs at a time -- the encoder's one learning slot, or an idle encoder --, so the list has not changed in between)
@@ -563,38 +472,6 @@ tkz_status drop_promotions(tkz_encoder* e, bool retire) {
     e->promo_items.clear(); e->promo_keys.clear(); e->promo_quads.clear();
     install_key_tables(e, img, retire);
     return TKZ_OK;
-}
-
-// TKZ_OPT_ADAPT (e->mu held): a batch that was not a learning batch has ended; `misses` of its `pieces` regex matches were not found in the key tables
-// as a whole (vocabulary + promoted pieces).  Returns true when the encoder should learn again: the share of such pieces, averaged over the recent
-// batches by their bytes, has left the level at which it settled after the last promotion by more than a quarter (and a percentage point) either way
-// -- text whose pieces the promotions no longer answer, or text that a fresh encoder would answer better.  Not within adapt_min_bytes (256 MB) of the last
-// change of the tables: a re-learn costs one window at the speed of an encoder without promotions and two table builds on the host.
-bool adapt_after_batch(tkz_encoder* e, int64_t total, double misses, double pieces) {
-    if (!e->adapt || e->promo_mode != 1 || pieces < 1) return false;
-    const int64_t kAdaptSettleBytes = e->adapt_settle_bytes, kAdaptMinBytes = e->adapt_min_bytes;
-    const double rate = misses / pieces, w = std::min(1.0, (double)total / (double)kAdaptSettleBytes);
-    e->ew_miss = e->ew_valid ? e->ew_miss + (rate - e->ew_miss) * w : rate;
-    e->ew_valid = true;
-    if (e->learning || e->promo_rounds < 1) return false;
-    const int64_t since = e->bytes_seen - e->bytes_at_install;
-    if (!e->base_valid) {
-        if (since >= kAdaptSettleBytes) {
-            e->base_miss = e->ew_miss; e->base_valid = true;
-            // A change of text that falls between a learning window and the install of what it learnt -- a promotion is built on a host thread, tens of
-            // milliseconds, gigabytes of text at this rate -- has no settled level to leave: the level settles on the new text.  But an install only ever ADDS
-            // pieces, so on the text it was learnt from the level it leaves is at or below the WINDOW's own miss share; one that is a quarter (and a percentage
-            // point) ABOVE it means those promotions answer another text: a drift.  (bench.py's drift leg, 3 GB of synthetic text in 15 ms and real text
-            //  behind it: the first install landed ten real batches later, no drift was ever seen, and the encoder ran at 0.77 of a fresh one.)
-            const bool drifted = e->window_valid && e->base_miss > e->window_miss * 1.25 + 0.01;
-            e->window_valid = false;
-            if (drifted) return true;
-        }
-        return false;
-    }
-    if (since < kAdaptMinBytes) return false;
-    if (e->promo_items.size() * 10 >= e->promo_cap * 9) return true;     // the list is (nearly) full of what the rounds have added: start over from the text as it is now
-    return e->ew_miss > e->base_miss * 1.25 + 0.01 || e->ew_miss < e->base_miss * 0.75 - 0.01;
 }
 
 // workspace of one batch of `total` bytes / n_docs documents (grow-only buffers: nothing happens once they are large enough)
@@ -719,34 +596,16 @@ tkz_status arm_learning(tkz_encoder* e, Workspace* ws, int64_t total, bool first
     using namespace tkz;
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        // LEARNING: the first batches of documents on the batch path (and once more, kPromoSecondBytes later; and again whenever the text has drifted:
-        // adapt_after_batch) count the memo's hits per slot.  A learning WINDOW is promo_min_bytes of text: one large batch, or -- TKZ_OPT_ADAPT --
-        // as many smaller ones as it takes (a caller whose batches are 1 MB learns too).
-        // (TKZ_OPT_ADAPT: the rounds go on -- a gigabyte after the first window began, then two, four, eight ... gigabytes after the one before: text that
-        //  changed without moving the miss share, or right behind a promotion, is still learnt, a round costs one batch that counts hits and ~50 ms of a
-        //  host thread; pieces are only ever ADDED by a round -- what empties the list is a drift, or the list reaching its cap: adapt_after_batch)
-        const int64_t round_gap = e->adapt_round_bytes << std::min(std::max(e->promo_rounds - 1, 0), 20);
-        if (first && !ws->learning && may_learn && e->promo_mode == 1 && !e->learning && (e->adapt || e->promo_rounds < kPromoAutoRounds) &&
-            e->T.memo_n != 0 && e->T.max_rank < (int32_t)kPromoFlag && (e->adapt || total >= e->promo_min_bytes) && e->promo_items.size() < e->promo_cap &&
-            (e->promo_rounds == 0 || e->bytes_seen - e->bytes_at_promo >= round_gap)) {
-            // (the gigabyte to the second round counts from the START of the first learning window: a job of 5 GB batches learns in its first two)
-            // The memo is emptied for a window that follows a drift -- it is full of the old text's pieces and takes no new ones --, and that only while
-            // no OTHER call is in flight: an entry never changes once it is valid (tkz_tables.h), which is what makes a hit exact, so the table is
-            // cleared under nobody's feet, synchronously, with the encoder's lock held (16 MB: microseconds, once per drift)
-            bool quiet = true;
-            if (e->memo_clear_pending) for (Workspace* w : e->pool) if (w != ws && w->busy) quiet = false;
-            if (quiet && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
-                e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
-                bool ok = true;
-                if (e->memo_clear_pending) {
-                    ok = hipMemsetAsync(e->t_memo.p, 0, size_t(e->memo_slots) * sizeof(TkzMemoSlot), stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-                    if (ok) e->memo_clear_pending = false;
-                }
-                if (ok) {
-                    ws->learn_window_start = e->learn_bytes == 0;
-                    if (ws->learn_window_start) e->bytes_at_promo = e->bytes_seen;
-                    e->learning = true; ws->learning = true;
-                }
+        bool others = false;
+        for (Workspace* w : e->pool) if (w != ws && w->busy) others = true;
+        const AdaptPolicy::Arm arm = e->policy.may_learn(total, first && !ws->learning, may_learn, e->T.memo_n != 0, e->T.max_rank < (int32_t)kPromoFlag, e->promo_items.size(), others);
+        if (arm != AdaptPolicy::Arm::No && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
+            e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
+            // (the memo is cleared under nobody's feet, synchronously, with the encoder's lock held: 16 MB, microseconds, once per drift)
+            const bool clear = arm == AdaptPolicy::Arm::YesClearMemo;
+            if (!clear || (hipMemsetAsync(e->t_memo.p, 0, size_t(e->memo_slots) * sizeof(TkzMemoSlot), stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess)) {
+                ws->learn_window_start = e->policy.window_armed(clear);
+                ws->learning = true;
             }
         }
         *T = e->T;
@@ -1021,55 +880,29 @@ void promote_or_drop(tkz_encoder* e, bool promote) {
         { std::lock_guard<std::mutex> lock(e->mu); held = e->promo_items.size(); }
         if (dev) (void)promote_from_memo(e, true, true, &added);   // (a failure leaves the tables as they were)
         std::lock_guard<std::mutex> lock(e->mu);
-        e->learning = false; ++e->promo_rounds; ++e->n_promotions;
-        // A round that found much it did not know -- more than a tenth of what the list held -- is a young encoder, or text that CHANGED without the miss
-        // share having had a settled level to leave (the change fell between two installs): the next round then follows a gigabyte later, not
-        // 2^rounds gigabytes.  (bench.py's drift leg, synthetic -> real text: the steps beyond 2 GB ran at 0.81 of an encoder that only ever saw
-        // the real text, whose second round comes after 1 GB while this one's was 4 GB away.)
-        if (e->adapt && e->promo_rounds > 1 && (size_t)added * 10 > held) e->promo_rounds = 1;
-        e->bytes_at_install = e->bytes_seen; e->ew_valid = e->base_valid = false;
+        e->policy.promotion_installed(added, held);
     } else {
         if (dev) (void)drop_promotions(e, true);
         std::lock_guard<std::mutex> lock(e->mu);
-        e->learning = false; e->promo_rounds = 0; e->learn_bytes = 0; e->memo_clear_pending = true; ++e->n_relearns;
-        e->bytes_at_install = e->bytes_at_promo = e->bytes_seen; e->ew_valid = e->base_valid = e->window_valid = e->last_window_valid = false; e->win_miss = e->win_pieces = 0;
+        e->policy.promotions_dropped();
     }
 }
 
 // The batch is done: if it completes a learning window, the hottest entries are promoted now (the copy of the memo back to the host and the
 // rebuilt key tables cost tens of milliseconds: on a thread, behind the batch); else the share of pieces that missed the key tables is
-// compared with what it was after the last promotion (adapt_after_batch)
+// compared with what it was after the last promotion (AdaptPolicy::batch_ended decides, under the lock; the thread starts outside it)
 void after_batch(tkz_encoder* e, Workspace* ws, int64_t total) {
     const CounterBlock& c = *ws->h_counters;
-    bool promote = false, relearn = false;
+    tkz::AdaptPolicy::After what;
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        e->bytes_seen += total;
-        if (ws->learning) {
-            e->learn_bytes += total;
-            e->win_miss += (double)(c.miss_short + c.miss_long); e->win_pieces += (double)c.npieces;
-            promote = !e->adapt || e->learn_bytes >= e->promo_min_bytes;
-            if (!promote) { ws->learning = false; e->learning = false; }      // (the window goes on with the next batch)
-            else if (e->adapt && e->last_window_valid && e->win_pieces >= 1 && e->win_miss / e->win_pieces > e->last_window_miss * 1.25 + 0.01) {
-                // A window whose miss share is a quarter (and a point) ABOVE the window's before it -- although that one's promotions have been installed since,
-                // and promotions only lower the share on unchanged text -- was counted on ANOTHER text, with a memo full of the old one's pieces (it takes no
-                // new entry into a full bucket): what it found is a fraction of what a fresh encoder finds (2 k against 9 k pieces on the source text behind 3 GB
-                // of synthetic text).  A drift: start over -- this window's counts are dropped with the promotions, the memo is emptied, the next batch begins a window.
-                promote = false; relearn = true; ws->learning = false;
-                e->learn_bytes = 0; e->win_miss = e->win_pieces = 0;
-            }
-        } else relearn = adapt_after_batch(e, total, (double)(c.miss_short + c.miss_long), (double)c.npieces);
-        if (relearn) e->learning = true;                                     // (nothing learns while the promotions are being dropped)
+        what = e->policy.batch_ended(total, (double)(c.miss_short + c.miss_long), (double)c.npieces, ws->learning, e->promo_items.size());
+        ws->learning = false;
     }
-    if (!promote && !relearn) return;
-    if (promote) {
-        std::lock_guard<std::mutex> lock(e->mu);
-        ws->learning = false; e->learn_bytes = 0;
-        e->window_valid = e->win_pieces >= 1; e->window_miss = e->window_valid ? e->win_miss / e->win_pieces : 0; e->win_miss = e->win_pieces = 0;
-        e->last_window_valid = e->window_valid; e->last_window_miss = e->window_miss;
-    }
+    const bool promote = what == tkz::AdaptPolicy::After::Promote;
+    if (!promote && what != tkz::AdaptPolicy::After::Relearn) return;
     // (the workspace is this call's no longer once it returns; the counters, the log and the memo are the encoder's, and no other batch writes the
-    //  first two while e->learning is set)
+    //  first two while the policy's learning slot is taken)
     join_promotion(e);                 // (the previous one ended before this batch could be armed: this only reaps the thread)
     bool started = false;
     {
@@ -1109,7 +942,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
     // a learning batch that ends any other way than with its promotion gives the encoder's one learning slot back
     struct LearnGuard {
         tkz_encoder* e; Workspace* ws; bool keep = false;
-        ~LearnGuard() { if (!keep && ws->learning) { ws->learning = false; std::lock_guard<std::mutex> lock(e->mu); e->learning = false; } }
+        ~LearnGuard() { if (!keep && ws->learning) { ws->learning = false; std::lock_guard<std::mutex> lock(e->mu); e->policy.learning_abandoned(); } }
     } learn_guard{e, ws};
     // An attempt that has to be run again (lists, records or scratch to grow) leaves the document marks and the piece-start bitmap as they are: the
     // next one starts behind the pre-tokenizer.
@@ -2139,8 +1972,8 @@ tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value)
     if (option == TKZ_OPT_PROMOTE_MIN_BYTES || option == TKZ_OPT_PROMOTE_CAP) {
         if (value < 0) return fail(TKZ_E_ARG, "negative value");
         std::lock_guard<std::mutex> lock(e->mu);
-        if (option == TKZ_OPT_PROMOTE_MIN_BYTES) e->promo_min_bytes = value;
-        else e->promo_cap = (size_t)std::min<int64_t>(value, (int64_t)kPromoMaxEntries);
+        if (option == TKZ_OPT_PROMOTE_MIN_BYTES) e->policy.set_min_bytes(value);
+        else e->policy.set_cap((size_t)std::min<int64_t>(value, (int64_t)kPromoMaxEntries));
         return TKZ_OK;
     }
     if (option == TKZ_OPT_PROMOTE) {
@@ -2150,7 +1983,7 @@ tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value)
         tkz_status st = check_encoder(e, scope);
         if (st != TKZ_OK) return st;
         if (value == 0 || value == 1) {
-            { std::lock_guard<std::mutex> lock(e->mu); e->promo_mode = (int)value; }
+            { std::lock_guard<std::mutex> lock(e->mu); e->policy.set_mode((int)value); }
             if (value == 0) join_promotion(e);     // off: the tables do not change once this has returned
             return TKZ_OK;
         }
@@ -2164,16 +1997,8 @@ tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value)
         // (the images these two replace are RETIRED, not freed here: the check above is not held until the new ones are in place, and a call that started in
         //  between has taken its copy of the table descriptor -- the round-5 advisor; they go when no call is in flight, ~Lease)
         if (value == 2) return promote_from_memo(e, false, true, nullptr);
-        {
-            std::lock_guard<std::mutex> lock(e->mu);
-            e->promo_rounds = 0; e->learn_bytes = 0; e->bytes_at_promo = e->bytes_at_install = e->bytes_seen; e->ew_valid = e->base_valid = e->window_valid = e->last_window_valid = false; e->win_miss = e->win_pieces = 0;
-        }
-        {
-            bool none;
-            { std::lock_guard<std::mutex> lock(e->mu); none = e->promo_items.empty(); }
-            if (none) return TKZ_OK;
-        }
-        return drop_promotions(e, true);
+        { std::lock_guard<std::mutex> lock(e->mu); e->policy.reset_by_hand(); }
+        return drop_promotions(e, true);      // (nothing to do when nothing is promoted)
     }
     if (option == TKZ_OPT_PIECE_MEMO) {
         // 0: off, 1: on, 2: on and emptied.  Options are set while the encoder is idle: a call in flight on another thread reads
@@ -2195,7 +2020,7 @@ tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value)
     if (option == TKZ_OPT_ADAPT) {
         if (value != 0 && value != 1) return fail(TKZ_E_ARG, "TKZ_OPT_ADAPT takes 0 or 1");
         std::lock_guard<std::mutex> lock(e->mu);
-        e->adapt = (int)value;
+        e->policy.set_adapt((int)value);
         return TKZ_OK;
     }
     return fail(TKZ_E_ARG, "unknown option");
@@ -2205,9 +2030,8 @@ tkz_status tkz_encoder_adapt_stats(tkz_encoder* e, int64_t* out8) {
     if (!e || !out8) return fail(TKZ_E_ARG, "null argument");
     join_promotion(e);                     // (the figures after whatever is being built in the background)
     std::lock_guard<std::mutex> lock(e->mu);
-    out8[0] = e->n_promotions; out8[1] = e->n_relearns; out8[2] = (int64_t)e->promo_items.size(); out8[3] = (int64_t)e->retired.size();
-    out8[4] = e->base_valid ? (int64_t)(e->base_miss * 1e6) : -1; out8[5] = e->ew_valid ? (int64_t)(e->ew_miss * 1e6) : -1;
-    out8[6] = e->bytes_seen - e->bytes_at_install; out8[7] = e->learn_bytes;
+    e->policy.stats(out8);
+    out8[2] = (int64_t)e->promo_items.size(); out8[3] = (int64_t)e->retired.size();
     return TKZ_OK;
 }
 
@@ -2302,7 +2126,7 @@ tkz_status tkz_encoder_reserve(tkz_encoder* e, int64_t max_bytes, int64_t max_do
     }
     {   // the counters and the log of a learning window (TKZ_OPT_PROMOTE)
         std::lock_guard<std::mutex> lock(e->mu);
-        if (e->memo_slots && e->promo_mode == 1) {
+        if (e->memo_slots && e->policy.mode() == 1) {
             if (e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) != hipSuccess ||
                 e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) != hipSuccess)
                 return fail(TKZ_E_OUT_OF_MEMORY, "learning buffers could not be allocated");
