@@ -126,7 +126,7 @@ void tkz_host_free(void* p);
 
 /* EncodeBatch over HOST buffers: n_docs documents, document d = bytes[doc_offsets[d] .. doc_offsets[d+1]).
  * Each document is encoded exactly as ITokenizer.Encode(text, applySpecialTokens:false) would encode
- * the string it is the UTF-8 form of.  out_ids receives all ids, document after document;
+ * the string it is the UTF-8 form of (with special tokens: tkz_encode_batch_special_utf8 / _device).  out_ids receives all ids, document after document;
  * out_offsets (n_docs+1 entries) the id range of each document.  Caller-allocated; out_cap >= total
  * bytes is always sufficient (a token is at least one byte).  On TKZ_E_CAPACITY nothing useful is
  * in out_ids and *needed (if non-NULL) holds the required capacity. */
@@ -142,6 +142,23 @@ tkz_status tkz_encode_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const
                                    int64_t n_docs, int64_t total_bytes, int32_t* d_out_ids,
                                    int64_t out_cap, int64_t* d_out_offsets, void* hip_stream,
                                    int64_t* total_tokens);
+
+/* EncodeBatch with special tokens: every document is encoded exactly as ITokenizer.Encode(text, allowedSpecial) would encode it (TikTokenizer.cs:178-207,
+ * EncodeInternal / FindNextSpecialToken :141-170,230-241) -- the allowed literals are cut out of the text ON THE DEVICE, each becomes its id, and every plain
+ * stretch between them is split as a text of its own.  allowed[k]: index into the literals registered by tkz_encoder_set_special_tokens (registration order =
+ * the reference's alternation order: at one position the first registered literal that matches is the match, allowed or not; a literal never matches across a
+ * document boundary).  n_allowed == 0, or no literal registered: the plain entry, launched exactly as it is.  An index out of range or given twice: TKZ_E_ARG.
+ * The device path holds at most 256 registered literals of 1..128 bytes of well-formed UTF-8 with ids in [0, 2^26); with any other set registered these two
+ * entries return TKZ_E_UNSUPPORTED (the callers' host segmentation is the fallback).  Buffers, capacity (out_cap >= total bytes is always sufficient), errors and
+ * options as tkz_encode_batch_device / tkz_encode_batch_utf8; the host entry always takes the batch path (chunks are document ranges: no literal is cut).
+ * Under o200k and under TKZ_OPT_PRETOK_SEQUENTIAL the launch sequence waits once for the number of segments.  Register special tokens while no call is in flight. */
+tkz_status tkz_encode_batch_special_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                           const int32_t* allowed, int32_t n_allowed, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                           void* hip_stream, int64_t* total_tokens);
+tkz_status tkz_encode_batch_special_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
+                                         int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed);
+/* informational: calls that took the device special path, special-token literals they turned into ids */
+void tkz_encoder_special_stats(const tkz_encoder* e, int64_t* batches, int64_t* literals);
 
 /* The same in two halves, for callers that keep several batches in flight (or do their own work while one runs):
  * _begin enqueues the batch on `hip_stream` and returns without waiting; _end waits for it, reports errors and

@@ -84,7 +84,7 @@ public:
 private:
     friend class TikTokenizer;
     PinnedBuffer in_bytes_, in_offs_, sub_offs_, out_ids_, out_offs_;
-    std::vector<int32_t> spliced_ids_; std::vector<int64_t> spliced_offs_;     // (only when special tokens were spliced in)
+    std::vector<int32_t> spliced_ids_; std::vector<int64_t> spliced_offs_;     // (only when special tokens were spliced in on the host: the fallback)
     const int32_t* ids_ = nullptr; const int64_t* offsets_ = nullptr; int64_t n_texts_ = 0;
     double tokens_per_byte_ = 0;                                               // the densest batch seen: sizes the id buffer of the next one
 };
@@ -100,6 +100,12 @@ public:
         const tkz_status s = tkz_encoder_create(v, pat, device, &enc_);
         tkz_vocab_destroy(v);
         check(s);
+        if (!specials_.empty()) {                              // the literals the device cuts out of the text (EncodeBatchFlat), in registration order
+            std::vector<int32_t> ids; std::string blob; std::vector<int64_t> offs{0};
+            for (const auto& sp : specials_) { ids.push_back(sp.second); blob += sp.first; offs.push_back(static_cast<int64_t>(blob.size())); }
+            const tkz_status r = tkz_encoder_set_special_tokens(enc_, ids.data(), reinterpret_cast<const uint8_t*>(blob.data()), offs.data(), static_cast<int32_t>(ids.size()));
+            if (r != TKZ_OK) { tkz_encoder_destroy(enc_); enc_ = nullptr; check(r); }
+        }
     }
     ~TikTokenizer() { tkz_encoder_destroy(enc_); }
     TikTokenizer(const TikTokenizer&) = delete;
@@ -159,6 +165,18 @@ public:
             encode_segments(static_cast<int64_t>(texts.size()), [&](int64_t i) { return std::pair<const char*, size_t>(texts[static_cast<size_t>(i)].data(), texts[static_cast<size_t>(i)].size()); }, out, threads);
             out.ids_ = out.out_ids_.as<int32_t>(); out.offsets_ = out.out_offs_.as<int64_t>();
             return;
+        }
+        // The device cuts the allowed literals out itself (tkz_encode_batch_special_utf8): the whole texts through the same gather as the plain path, the
+        // result left in the page-locked buffers.  Only a registered set the device path does not hold (TKZ_E_UNSUPPORTED) is segmented here and spliced.
+        if (!special_on_host_) {
+            std::vector<int32_t> index;
+            for (size_t i = 0; i < specials_.size(); ++i)
+                for (const auto& a : allowedSpecial) if (a == specials_[i].first) { index.push_back(static_cast<int32_t>(i)); break; }
+            if (encode_segments(static_cast<int64_t>(texts.size()), [&](int64_t i) { return std::pair<const char*, size_t>(texts[static_cast<size_t>(i)].data(), texts[static_cast<size_t>(i)].size()); }, out, threads, &index)) {
+                out.ids_ = out.out_ids_.as<int32_t>(); out.offsets_ = out.out_offs_.as<int64_t>();
+                return;
+            }
+            special_on_host_ = true;
         }
         // what goes to the device: (source pointer, length) of every plain segment, and where the special ids go
         struct Item { size_t text; int32_t special; int64_t segment; };
@@ -375,8 +393,10 @@ private:
     // A token is at least one byte, English-like text has one per ~4: room for a token per two bytes first; when that was not enough, room
     // for a token per byte (always enough) and the calls again.
     struct Joiner { std::vector<std::thread> pool; ~Joiner() { for (std::thread& t : pool) if (t.joinable()) t.join(); } };
+    // allowed: null, or the indices of the allowed special tokens -- the segments are then whole texts and go to tkz_encode_batch_special_utf8; returns false
+    // (nothing encoded) when that entry refuses the registered set with TKZ_E_UNSUPPORTED, true otherwise.
     template <class SegAt>
-    void encode_segments(int64_t nseg, SegAt seg_at, FlatBatch& out, int threads) const {
+    bool encode_segments(int64_t nseg, SegAt seg_at, FlatBatch& out, int threads, const std::vector<int32_t>* allowed = nullptr) const {
         int nth = threads > 0 ? threads : static_cast<int>(std::min<int64_t>(16, nseg >> 14));
         const unsigned hw = std::thread::hardware_concurrency();
         if (hw && nth > static_cast<int>(hw)) nth = static_cast<int>(hw);
@@ -439,8 +459,11 @@ private:
                 const auto t_e = std::chrono::steady_clock::now();
                 const int64_t d0 = cut[static_cast<size_t>(k)], nd = cut[static_cast<size_t>(k) + 1] - d0;
                 int64_t needed = 0;
-                const tkz_status st = tkz_encode_batch_utf8(enc_, bytes + offs[d0], nsb > 1 ? sub + d0 + k : offs, nd, ids + tok_base, cap - tok_base, ooff + d0, &needed);
+                const tkz_status st = allowed ? tkz_encode_batch_special_utf8(enc_, bytes + offs[d0], nsb > 1 ? sub + d0 + k : offs, nd, allowed->data(), static_cast<int32_t>(allowed->size()),
+                                                                              ids + tok_base, cap - tok_base, ooff + d0, &needed)
+                                              : tkz_encode_batch_utf8(enc_, bytes + offs[d0], nsb > 1 ? sub + d0 + k : offs, nd, ids + tok_base, cap - tok_base, ooff + d0, &needed);
                 out.last_encode_ms += ms_since(t_e);
+                if (allowed && st == TKZ_E_UNSUPPORTED) return false;        // (the first sub-batch says so: the literal set is the encoder's)
                 if (st == TKZ_E_CAPACITY) { over = true; break; }
                 check(st);
                 if (tok_base) for (int64_t i = d0; i <= d0 + nd; ++i) ooff[i] += tok_base;
@@ -451,6 +474,7 @@ private:
             full = true;
         }
         if (total > 0) out.tokens_per_byte_ = std::max(out.tokens_per_byte_, static_cast<double>(ooff[nseg]) / static_cast<double>(total));
+        return true;
     }
     int match_at(const std::string& text, size_t p) const {       // first registered literal that matches at p
         for (size_t i = 0; i < specials_.size(); ++i) {
@@ -460,6 +484,7 @@ private:
         return -1;
     }
     SpecialTokens specials_;
+    mutable bool special_on_host_ = false;     // the device's special entries refused the registered set: EncodeBatchFlat segments on the host
     tkz_encoder* enc_ = nullptr;
 };
 

@@ -1,0 +1,142 @@
+"""Special tokens on the device (tkz_encode_batch_special_utf8 / _device): the case builders and the comparison the emulated (CPU) and
+the GPU test modules share.  Every comparison is bit-exact -- ids and offsets -- against oracle.Encoder(vocab, pattern,
+specials=...).encode(text, allowed) per document."""
+import random
+
+import numpy as np
+
+import parity
+import regex_crosscheck as RC
+from tokenizer_amd import _native as N
+from tokenizer_amd.tokenizer import ENCODERS
+
+EOT = "<|endoftext|>"
+# vocabulary (tests/conftest.py: vocab_bytes) -> its special tokens, ids from tokenizer.py: ENCODERS
+SPECIAL_SETS = {"gpt2": ENCODERS["gpt2"][2], "synth100k": ENCODERS["cl100k_base"][2], "synth200k": ENCODERS["o200k_base"][2]}
+PATTERNS = (1, 2, 3, 4)
+
+
+def indices(specials, allowed):
+    names = list(specials)
+    return [names.index(a) for a in allowed if a in names]
+
+
+def make_encoders(lib, O, vocab, ovocab, pattern, specials):
+    enc = N.Encoder(vocab, pattern)
+    enc.set_special_tokens(specials)
+    return enc, O.Encoder(ovocab, pattern, specials=specials)
+
+
+def oracle_docs(oenc, docs, allowed):
+    ids, offs = [], [0]
+    for d in docs:
+        ids += oenc.encode(d, list(allowed))
+        offs.append(len(ids))
+    return ids, offs
+
+
+def first_diff(got, exp):
+    n = min(len(got), len(exp))
+    for i in range(n):
+        if got[i] != exp[i]:
+            return i
+    return n
+
+
+def compare(enc, oenc, specials, allowed, docs, what="", call=None):
+    """docs: str documents.  call(data, offs, index) -> (ids, offsets): the entry under test (default: the host entry)."""
+    data, offs = parity.pack([d.encode("utf-8") for d in docs])
+    index = indices(specials, allowed)
+    ids, ooff = (call or enc.encode_batch_special)(data, offs, index)
+    eids, eoffs = oracle_docs(oenc, docs, allowed)
+    got_offs = [int(x) for x in ooff]
+    if got_offs != eoffs:
+        d = first_diff(got_offs, eoffs)
+        raise AssertionError("%s: offsets differ at document %d: got %s, expected %s; document %r" % (what, d - 1, got_offs[max(0, d - 1):d + 1], eoffs[max(0, d - 1):d + 1], docs[max(0, d - 1)][:200]))
+    got = [int(x) for x in ids]
+    if got != eids:
+        k = first_diff(got, eids)
+        d = max(0, int(np.searchsorted(np.asarray(eoffs), k, side="right")) - 1)
+        raise AssertionError("%s: ids differ at %d (document %d): got %s, expected %s; document %r" % (what, k, d, got[k:k + 8], eids[k:k + 8], docs[min(d, len(docs) - 1)][:200]))
+    return len(eids)
+
+
+def allowed_choices(specials):
+    names = list(specials)
+    out = [names, names[:1], []]
+    if len(names) > 1:
+        out.append(names[1:])                  # a proper subset that leaves the first registered literal out
+    return out
+
+
+def edge_docs(specials, o200k=False):
+    """Literals at the start / end of a document, the whole document, back to back, around blanks and newlines, between CJK and emoji, around long pieces, cut
+    by a document boundary, beside empty documents; literals that are not allowed simply appear as text under the smaller allowed sets."""
+    names = list(specials)
+    a = names[0]
+    b = names[-1]
+    near = [a[:-1], a[1:], a[:-2] + ">", "<|endoftext|", "<|endoftext>", "<endoftext|>"]
+    docs = [
+        a, a + "hello world", "hello world" + a, a + a, a + b + a, "x" + a + a + a + "y",
+        "a   " + a + "b", "a   " + a + "   b", "a\n\n" + a + "\n\nb", "a \n" + a + " \n b", "tab\t\t" + a + "\t\tx", a + " ", " " + a, "  " + a + "  ",
+        "don't" + a + "'s it", "12345" + a + "6789", "word" + a + "word", "中文" + a + "中文", "\U0001F600" + a + "\U0001F600⭐" + b, "é" + a + "ß",
+        "x" * 1500 + a + "y" * 1500, " " * 1500 + a + " " * 1500, "ab " * 400 + a + "=" * 1200 + a + "q",
+        "", a, "", "", "text only, no literal at all", "", b, "",
+        "".join(near), " ".join(near), near[3] + a + near[3],
+        a[:5], a[5:], a[:-1], ">", "<|", a[2:],             # a literal cut in two by a document boundary: no match
+        "the end" + b,
+    ]
+    if o200k:
+        docs += ["a\r\n/" + a + "\r\n/b", "x \r\n\r\n" + a + "\r\n//" + b + "/", "Ab\r\n" + a + "'S", "aB" + a + "Cd\n/" + a]
+    return docs
+
+
+def boundary_docs(lit, boundaries, shifts=None, fill="ab cd "):
+    """One document per shift: the literal placed so that it crosses (or touches) byte `boundary` of the BATCH at every offset -- the documents are laid out by
+    the caller one per batch.  Returns a list of single-document batches."""
+    out = []
+    n = len(lit.encode("utf-8"))
+    for B in boundaries:
+        for k in (shifts if shifts is not None else range(n + 1)):
+            pre = B - k
+            if pre < 0:
+                continue
+            body = (fill * (pre // len(fill) + 1))[:pre]
+            out.append(body + lit + " tail of the text" + lit)
+    return out
+
+
+def random_docs(rng, specials, n_docs, max_len, kinds=("mix", "runs", "a_mix", "ws", "oth")):
+    names = list(specials)
+    extra = ["<|endoftext|", EOT[:-1], EOT[1:], EOT[:6] + EOT[7:]]
+    docs = []
+    alpha = RC.alphabet()
+    for _ in range(n_docs):
+        n = rng.choice([0, 1, 5, 40, 300, 1000, 1100, 4100]) if rng.random() < 0.6 else rng.randrange(max_len + 1)
+        n = min(n, max_len)
+        text = parity.gen_text(rng, rng.choice(kinds), n, alpha) if n else ""
+        parts, pos = [], 0
+        cuts = sorted(rng.randrange(len(text) + 1) for _ in range(rng.choice([0, 1, 1, 2, 5])))
+        for c in cuts:
+            parts.append(text[pos:c])
+            parts.append(rng.choice(names) if rng.random() < 0.7 else rng.choice(extra))
+            if rng.random() < 0.2:
+                parts.append(rng.choice(names))
+            pos = c
+        parts.append(text[pos:])
+        docs.append("".join(parts))
+    return docs
+
+
+# registration order, overlaps, non-ASCII literals, a literal that is a vocabulary key: (specials, allowed sets, documents)
+def order_cases():
+    runs = ["a" * n for n in (1, 2, 3, 4, 5, 6, 7, 64, 65, 127, 128, 129, 300)] + ["ab" * n for n in (1, 2, 3, 5, 33, 64, 70)] + ["aabaabaaabab" * 20, "ba" * 40 + "a" * 9 + "b"]
+    return [
+        ({"<|x": 1001, "<|x|>": 1002}, [["<|x|>"], ["<|x", "<|x|>"], ["<|x"]], ["<|x|>", "a<|x|>b<|x", "<|x<|x|>", "<|<|x|>|>", " <|x|> <|x "]),
+        ({"<|x|>": 1002, "<|x": 1001}, [["<|x|>"], ["<|x", "<|x|>"], ["<|x"]], ["<|x|>", "a<|x|>b<|x", "<|x<|x|>", "<|<|x|>|>", " <|x|> <|x "]),
+        ({"aa": 2001, "aba": 2002}, [["aa", "aba"], ["aa"], ["aba"]], runs),
+        ({"aba": 2002, "aa": 2001}, [["aa", "aba"], ["aa"], ["aba"]], runs),
+        ({"<|é中\U0001F600|>": 3001, "中": 3002}, [["<|é中\U0001F600|>", "中"], ["中"], ["<|é中\U0001F600|>"]],
+         ["中中中", "x<|é中\U0001F600|>y中", "<|é中\U0001F600|", "é<|é中\U0001F600|>中\U0001F600", "文中文 中 "]),
+        ({" the": 4001, "hello": 4002}, [[" the", "hello"], ["hello"]], ["hello the world the", " thehello", "in the theatre hello hellothe"]),
+    ]

@@ -144,6 +144,10 @@ class Library:
         L.tkz_encoder_counts_device.argtypes = [vp]
         L.tkz_encoder_counts_device.restype = vp
         L.tkz_encoder_set_special_tokens.argtypes = [vp, vp, vp, vp, i32]
+        L.tkz_encode_batch_special_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, vp, i64, vp, vp, pi64]
+        L.tkz_encode_batch_special_utf8.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, pi64]
+        L.tkz_encoder_special_stats.argtypes = [vp, pi64, pi64]
+        L.tkz_encoder_special_stats.restype = None
         L.tkz_decode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
         L.tkz_decode_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
@@ -351,6 +355,40 @@ class Encoder:
         self.lib.check(self.lib.L.tkz_encode_batch_utf8(self._h, _ptr(data), _ptr(offsets), n, _ptr(ids), cap, _ptr(ooff), C.byref(needed)))
         return ids[:needed.value], ooff[:n + 1]
 
+    def encode_batch_special(self, data: np.ndarray, offsets: np.ndarray, allowed, out_cap=None, out=None):
+        """EncodeBatch as ITokenizer.Encode(text, allowedSpecial): the allowed special-token literals are cut out on the device.  allowed: indices into the
+        literals registered by set_special_tokens (registration order).  Buffers as in encode_batch."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = len(data) if out_cap is None else out_cap
+        if out is not None:
+            ids, ooff = out
+            assert ids.dtype == np.int32 and ooff.dtype == np.int64 and ids.flags.c_contiguous and ooff.flags.c_contiguous
+            assert len(ooff) >= n + 1
+            cap = len(ids)
+        else:
+            ids = np.empty(max(1, cap), np.int32)
+            ooff = np.empty(n + 1, np.int64)
+        needed = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_encode_batch_special_utf8(self._h, _ptr(data), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                                _ptr(ids), cap, _ptr(ooff), C.byref(needed)))
+        return ids[:needed.value], ooff[:n + 1]
+
+    def encode_batch_special_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, d_out_ids, out_cap, d_out_offsets, stream=0):
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_encode_batch_special_device(self._h, d_bytes, d_offsets, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                  len(allowed), d_out_ids, out_cap, d_out_offsets, stream or None, C.byref(tot)))
+        return tot.value
+
+    def special_stats(self):
+        """(calls that took the device special path, special-token literals they turned into ids)"""
+        b, l = C.c_int64(0), C.c_int64(0)
+        self.lib.L.tkz_encoder_special_stats(self._h, C.byref(b), C.byref(l))
+        return b.value, l.value
+
     def encode_batch_utf16(self, units: np.ndarray, offsets: np.ndarray, out=None):
         """EncodeBatch on UTF-16 code units (uint16[total], offsets int64[n+1] in units); transcoded on the device.
         `out` = (ids, out_offsets) arrays to fill, as in encode_batch."""
@@ -423,7 +461,8 @@ class Encoder:
 
     # -- Decode --
     def set_special_tokens(self, specials):
-        """specials: {literal str: id}.  Registers SpecialTokensDecoder for Decode (TikTokenizer.cs:79)."""
+        """specials: {literal str: id}.  Registers SpecialTokensDecoder for Decode (TikTokenizer.cs:79) and, in this order, the literals the special
+        entries cut out of the text (encode_batch_special)."""
         items = list(specials.items())
         lits = [k.encode("utf-8") for k, _ in items]
         ids = np.asarray([v for _, v in items], dtype=np.int32)

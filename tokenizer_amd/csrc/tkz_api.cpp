@@ -105,6 +105,7 @@ struct CounterBlock {          // mirrors the device block
     unsigned long long long_log_count;     // a learning batch: records k_merge_long wanted to log (EncodeParams::long_log)
     int64_t lq_total;                      // long misses in the class queue (the scan of EncodeParams::lq_cnt)
     unsigned long long miss_short, miss_long;   // pieces of the batch that missed the key tables as a whole (k_list_stats: the sums of mcount)
+    unsigned long long n_literals;         // the special entries: special-token literals taken (k_lit_resolve)
 };
 
 }  // namespace
@@ -127,6 +128,11 @@ struct Workspace {
     DevView w_counters, w_docbits, w_heavyq;
     DevBuf w_mlist, w_mquad, w_mcount, w_pextra, w_coopq, w_lqcnt, w_lqbase, w_lq;
     bool learn_window_start = false;       // this learning batch opens a window: the hit counters and the log start from zero
+    // the special entries only (allocated on their first use): candidates, segment marks (document marks + starts and ends of the taken literals: what the
+    // pre-tokenizer takes for its isolation boundaries), starts and ends of the taken literals; the segments' offsets for the scanners that take offsets
+    DevBuf w_candbits, w_segbits, w_specbits, w_endbits, w_segoffs;
+    int64_t n_seg = 0;                     // segments of the batch whose marks the workspace holds (w_segoffs)
+    int64_t spec_taken = 0;                // literals taken in that batch
     DevBuf w_counts3;                      // {n_docs, n_bytes, n_tokens} of the batch this workspace is running (tkz_pending_counts_device)
     bool sized = false;                    // a batch has run to its end here: the lists and the record buffer have seen real text (encode_device: the sizing attempt)
     int32_t mcap = tkz::kMissCapMin;       // entries of a sub-tile's miss list; grows (once, to what the batch needed) when a sub-tile overflows it
@@ -182,7 +188,7 @@ struct Workspace {
     double ms[tkz::K_COUNT] = {};
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
-        DevBuf* bufs[] = {&w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
+        DevBuf* bufs[] = {&w_candbits, &w_segbits, &w_specbits, &w_endbits, &w_segoffs, &w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
                           &w_doctok, &w_dcount, &w_dbase, &w_pool, &s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2],
                           &s_outoffs[0], &s_outoffs[1], &s_outoffs[2], &u_bytes[0], &u_bytes[1],
                           &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &p_boffs, &p_toffs, &p_docp};
@@ -219,6 +225,13 @@ struct tkz_encoder {
     DevBuf t_decoff, t_decblob, t_decids;
     TkzDecodeTable D{};
     std::vector<std::pair<int32_t, std::string>> dec_vocab, dec_special;   // host copies (id, bytes)
+    // the registered special tokens as the special entries' kernels read them (tkz_kernels.h: TkzLitTable), rebuilt with the decode table.  lit_state: 0 none
+    // registered, 1 table built, -1 the set is beyond what the device path holds (lit_why; the special entries answer TKZ_E_UNSUPPORTED)
+    DevBuf t_lit;
+    tkz::TkzLitTable LIT{};
+    int lit_state = 0;
+    std::string lit_why;
+    std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
     int64_t bytes_allocated = 0;           // tables
     std::atomic<int64_t> last_xcount{0}, last_xcount2{0};   // tkz_encoder_pretok_leftovers
     bool small_ok = false;                 // the device's LDS per workgroup holds k_small's (kSmallLdsBytesNeeded)
@@ -252,6 +265,15 @@ namespace {
 // ONE batch at a time in the whole process runs kernels on side streams behind events (launch_encode's forked form): two such batches at once are six streams with
 // waits on one another's events, on a runtime that maps streams onto a handful of hardware queues -- a call that finds the permission taken keeps the serial form
 std::atomic<int> g_fork_in_flight{0};
+
+// A call of one of the special entries: which registered literals it allows.  The entry sets it for the calling thread (every launch sequence of a call is
+// enqueued by the thread that made it); enqueue_attempt is the one place of the batch path that asks.
+struct SpecialCall { tkz::TkzLitAllowed allowed; };
+thread_local const SpecialCall* g_special = nullptr;
+struct SpecialScope {
+    explicit SpecialScope(const SpecialCall* c) { g_special = c; }
+    ~SpecialScope() { g_special = nullptr; }
+};
 
 // a workspace of the encoder's pool for the duration of one call
 struct Lease {
@@ -362,6 +384,62 @@ constexpr int64_t kLongLogCap = 65536;             // records of merged 17..28-b
 
 // (re)builds the SHORT / MID images from the vocabulary's keys + the promoted pieces and publishes them; `retire`: other calls may be probing the
 // current images (they are kept until the encoder is destroyed), else they are freed
+// The registered special tokens as k_lit_scan / k_probe_special read them (called with e->mu held, behind build_decode_table).  A set the device path does not
+// hold -- more than 256 literals, one that is empty, longer than 128 bytes or not well-formed UTF-8 (a segment mark would fall inside a character), an id a piece
+// record cannot carry beside its flag bits and the promoted pieces' codes -- is no error here (Decode takes any): the special entries then answer TKZ_E_UNSUPPORTED.
+bool well_formed_utf8(const std::string& t) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(t.data());
+    const size_t n = t.size();
+    for (size_t i = 0; i < n;) {
+        const unsigned c = b[i];
+        int len; uint32_t cp, lo;
+        if (c < 0x80) { ++i; continue; }
+        else if ((c & 0xE0) == 0xC0) { len = 2; cp = c & 0x1F; lo = 0x80; }
+        else if ((c & 0xF0) == 0xE0) { len = 3; cp = c & 0x0F; lo = 0x800; }
+        else if ((c & 0xF8) == 0xF0) { len = 4; cp = c & 0x07; lo = 0x10000; }
+        else return false;
+        if (i + len > n) return false;
+        for (int k = 1; k < len; ++k) { if ((b[i + k] & 0xC0) != 0x80) return false; cp = (cp << 6) | (b[i + k] & 0x3F); }
+        if (cp < lo || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
+        i += len;
+    }
+    return true;
+}
+tkz_status build_literal_table(tkz_encoder* e) {
+    using namespace tkz;
+    e->LIT = TkzLitTable{};
+    e->lit_state = 0;
+    e->lit_why.clear();
+    const auto& sp = e->dec_special;
+    if (sp.empty()) return TKZ_OK;
+    auto refuse = [&](const std::string& why) { e->lit_state = -1; e->lit_why = why; return TKZ_OK; };
+    if (sp.size() > (size_t)kLitMax) return refuse("more than 256 special tokens are registered");
+    std::vector<uint32_t> img((size_t)kLitMetaHead + 2 * sp.size(), 0u);
+    std::string blob;
+    for (size_t i = 0; i < sp.size(); ++i) {
+        const std::string& lit = sp[i].second;
+        if (lit.empty()) return refuse("an empty special-token literal is registered");
+        if (lit.size() > (size_t)kLitMaxLen) return refuse("a special-token literal of more than 128 bytes is registered");
+        if (!well_formed_utf8(lit)) return refuse("a special-token literal that is not well-formed UTF-8 is registered");
+        if (sp[i].first < 0 || (uint32_t)sp[i].first >= kPromoFlag) return refuse("a special-token id outside [0, 2^26) is registered: a piece record cannot hold it");
+        const unsigned c = (unsigned char)lit[0];
+        img[c >> 5] |= 1u << (c & 31);
+        img[kLitMetaHead + 2 * i] = (uint32_t)blob.size() | ((uint32_t)lit.size() << 16);
+        img[kLitMetaHead + 2 * i + 1] = (uint32_t)sp[i].first;
+        blob += lit;
+    }
+    const size_t meta_dwords = img.size();
+    img.resize(meta_dwords + (blob.size() + 3) / 4, 0u);
+    memcpy(img.data() + meta_dwords, blob.data(), blob.size());
+    HIP_TRY(upload(e->t_lit, img, &e->bytes_allocated));
+    e->LIT.meta = e->t_lit.as<uint32_t>();
+    e->LIT.blob = reinterpret_cast<const uint8_t*>(e->t_lit.as<uint32_t>() + meta_dwords);
+    e->LIT.n = (int32_t)sp.size();
+    e->LIT.blob_bytes = (int32_t)blob.size();
+    e->lit_state = 1;
+    return TKZ_OK;
+}
+
 struct KeyTablesImage { DevBuf nt, np; size_t short_bytes = 0, n_short_slots = 0, n_mid_slots = 0, n_promo = 0; uint32_t sseed = 0, mseed = 0; };
 // the images on the device, built from the vocabulary's keys + `promo_items` (copies: no lock is held here, the build takes tens of milliseconds)
 tkz_status build_key_tables_image(tkz_encoder* e, const std::vector<tkz::KeyItem>& promo_items, const std::vector<uint32_t>& promo_quads, KeyTablesImage* img) {
@@ -691,6 +769,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
     char* cb = ws->w_counters.as<char>();
     uint64_t* docbits = ws->w_docbits.as<uint64_t>();
     uint64_t* startbits = ws->w_startbits.as<uint64_t>();
+    const SpecialCall* const special = d_bitmap_only || po || !pretok ? nullptr : g_special;
     if (marks_reused) {      // (the counters and the sub-tile flags only)
         HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, 256, stream));
         if (!d_bitmap_only) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
@@ -701,17 +780,43 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
         else if (ws->zero_bytes <= (size_t(8) << 20)) launch_ingest(L, nullptr, 0, nullptr, nullptr, 0, nullptr, ws->w_zero.p, (int64_t)ws->zero_bytes);
         else HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, ws->zero_bytes, stream));
         launch_docmark(L, d_offs, n_docs, total, docbits, counters);
+        // the special entries: the pre-tokenizer splits between SEGMENT marks (the documents cut at the literals taken), from a bitmap or -- the scanners that take
+        // offsets: the sequential one, o200k's last resort -- from the segments' offsets
+        const uint64_t* isobits = docbits;
+        const int64_t* iso_offs = d_offs;
+        int64_t n_iso = n_docs;
+        if (special) {
+            for (DevBuf* b : {&ws->w_candbits, &ws->w_segbits, &ws->w_specbits, &ws->w_endbits}) HIP_TRY(b->ensure((size_t)(nwords + 8) * 8, &ws->bytes_allocated));
+            launch_lit_scan(L, d_bytes, total, docbits, nwords, e->LIT, special->allowed, ws->w_candbits.as<uint64_t>(), ws->w_segbits.as<uint64_t>(),
+                            ws->w_specbits.as<uint64_t>(), ws->w_endbits.as<uint64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, n_literals)));
+            isobits = ws->w_segbits.as<uint64_t>();
+            if (e->pretok_seq || e->pattern == TKZ_PATTERN_O200K || e->pattern == TKZ_PATTERN_O200K_DOTNET) {
+                // (how many segments there are is known on the device only: one wait, as the piece-granular entry has it)
+                int64_t* nseg = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, ndocstarts));
+                launch_doccount2(L, isobits, isobits, nwords, total, ntiles, ws->w_dcount.as<int32_t>(), ws->w_pcount.as<int32_t>());
+                launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), ws->w_dcount.as<int32_t>(), ws->w_dbase.as<int64_t>(), nseg, 1, nullptr, nullptr, nullptr, 1, -1);
+                HIP_TRY(hipMemcpyAsync(&ws->h_counters->ndocstarts, nseg, 8, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                ws->n_seg = ws->h_counters->ndocstarts;
+                HIP_TRY(ws->w_segoffs.ensure((size_t)(ws->n_seg + 2) * 8, &ws->bytes_allocated));
+                launch_seg_offsets(L, isobits, nwords, total, ntiles, ws->w_dbase.as<int64_t>(), ws->n_seg, ws->w_segoffs.as<int64_t>());
+                iso_offs = ws->w_segoffs.as<int64_t>();
+                n_iso = ws->n_seg;
+            }
+        }
         if (!pretok) {
             HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
         } else if (e->pretok_seq) {
-            HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
-            launch_pretok_seq(L, e->pattern, d_bytes, d_offs, n_docs, total, startbits, T.bmp_class, counters);
+            HIP_TRY(hipMemcpyAsync(startbits, isobits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
+            launch_pretok_seq(L, e->pattern, d_bytes, iso_offs, n_iso, total, startbits, T.bmp_class, counters);
         } else {
             HIP_TRY(ws->w_xq.ensure((size_t)(nwords / kRowsPerWave + 4) * 16, &ws->bytes_allocated));     // two queues (launch_pretok_rows)
-            launch_pretok_rows(L, e->pattern, d_bytes, d_offs, n_docs, total, docbits, startbits, nwords, T.bmp_class, counters,
+            launch_pretok_rows(L, e->pattern, d_bytes, iso_offs, n_iso, total, isobits, startbits, nwords, T.bmp_class, counters,
                                ws->w_xq.as<int64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, xcount)));
         }
-        if (pretok && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, docbits, startbits);
+        if (pretok && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, isobits, startbits);
+        // (every taken literal ONE piece: the starts the pre-tokenizer found inside it go)
+        if (special) launch_lit_fix(L, startbits, isobits, ws->w_specbits.as<uint64_t>(), ws->w_endbits.as<uint64_t>(), nwords);
     }
     if (d_bitmap_only) {
         HIP_TRY(hipMemcpyAsync(d_bitmap_only, startbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
@@ -741,6 +846,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             P.long_log = e->t_long_log.as<uint32_t>(); P.long_log_cap = (int32_t)kLongLogCap; P.long_log_sparse = T.memo_hits_sparse ? 1 : 0;
             P.long_log_count = reinterpret_cast<unsigned long long*>(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4);   // (the encoder's: it runs on through the batches of a window)
         }
+        if (special) { P.specbits = ws->w_specbits.as<uint64_t>(); P.lit_meta = e->LIT.meta; P.lit_blob = e->LIT.blob; P.n_lit = e->LIT.n; }
         TKZ_TRY(devprof_arm(&P, stream));
         int64_t* ndocstarts = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, ndocstarts));
         int64_t* npieces = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, npieces));
@@ -965,7 +1071,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
         HIP_TRY(hipGetLastError());
         if (e->profiling) prof_collect(ws);
         if (!d_bitmap_only) TKZ_TRY(devprof_report());
-        if (!marks_reused) { e->last_xcount = (int64_t)ws->h_counters->xcount; e->last_xcount2 = (int64_t)ws->h_counters->xcount2; }
+        if (!marks_reused) { e->last_xcount = (int64_t)ws->h_counters->xcount; e->last_xcount2 = (int64_t)ws->h_counters->xcount2; ws->spec_taken = (int64_t)ws->h_counters->n_literals; }
         bool retry = false;
         TKZ_TRY(check_counters(e, ws, stream, total, attempt, nsample, d_bitmap_only != nullptr, &retry));
         marks_ready = true;
@@ -973,6 +1079,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
         if (d_bitmap_only) return TKZ_OK;
         settle_workspace(ws, ntiles);
         if (pretok) after_batch(e, ws, total);
+        if (g_special && !po) e->spec_literals += ws->spec_taken;
         if (total_tokens) *total_tokens = ws->h_counters->grand;
         if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
         if (ws->h_counters->grand > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
@@ -1418,7 +1525,7 @@ tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* uni
     Lease lease(e);
     Workspace* ws = lease.ws;
     // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
-    if (!u16 && pretok && !bitmap && small_eligible(e, offs, n_docs, total)) {
+    if (!u16 && pretok && !bitmap && !g_special && small_eligible(e, offs, n_docs, total)) {
         bool handled = false;
         st = encode_small(e, ws, bytes, offs, n_docs, total, out_ids, out_cap, out_offsets, needed, &handled);
         if (st != TKZ_OK || handled) return st;
@@ -1668,6 +1775,52 @@ tkz_status tkz_encode_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int
     return encode_host(e, bytes, nullptr, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed, true, nullptr);
 }
 
+namespace {
+// the `allowed` argument of the special entries -> the call's literal set.  *plain: nothing allowed or nothing registered, the call is the plain entry's.
+tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowed, SpecialCall* sc, bool* plain) {
+    if (!e) return fail(TKZ_E_ARG, "null encoder");
+    if (n_allowed < 0 || (n_allowed > 0 && !allowed)) return fail(TKZ_E_ARG, "bad allowed-special arguments");
+    std::lock_guard<std::mutex> lock(e->mu);
+    *plain = n_allowed == 0 || e->lit_state == 0;
+    if (*plain) return TKZ_OK;
+    if (e->lit_state < 0) return fail(TKZ_E_UNSUPPORTED, "special tokens on the device: " + e->lit_why);
+    *sc = SpecialCall{};
+    for (int32_t k = 0; k < n_allowed; ++k) {
+        const int32_t i = allowed[k];
+        if (i < 0 || i >= e->LIT.n) return fail(TKZ_E_ARG, "allowed[] holds an index that is not a registered special token");
+        if ((sc->allowed.m[i >> 6] >> (i & 63)) & 1ull) return fail(TKZ_E_ARG, "allowed[] holds an index twice");
+        sc->allowed.m[i >> 6] |= 1ull << (i & 63);
+    }
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_special_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                           const int32_t* allowed, int32_t n_allowed, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                           void* hip_stream, int64_t* total_tokens) {
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    if (plain) return tkz_encode_batch_device(e, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, hip_stream, total_tokens);
+    SpecialScope scope(&sc);
+    const tkz_status st = tkz_encode_batch_device(e, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, hip_stream, total_tokens);
+    if (st == TKZ_OK) ++e->spec_batches;
+    return st;
+}
+tkz_status tkz_encode_batch_special_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
+                                         int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    if (plain) return tkz_encode_batch_utf8(e, bytes, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed);
+    SpecialScope scope(&sc);
+    const tkz_status st = tkz_encode_batch_utf8(e, bytes, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed);
+    if (st == TKZ_OK) ++e->spec_batches;
+    return st;
+}
+void tkz_encoder_special_stats(const tkz_encoder* e, int64_t* batches, int64_t* literals) {
+    if (batches) *batches = e ? e->spec_batches.load() : 0;
+    if (literals) *literals = e ? e->spec_literals.load() : 0;
+}
+
 tkz_status tkz_encode_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs,
                                    int64_t total_bytes, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
                                    void* hip_stream, int64_t* total_tokens) {
@@ -1858,7 +2011,8 @@ tkz_status tkz_encoder_set_special_tokens(tkz_encoder* e, const int32_t* ids, co
         sp.emplace_back(ids[i], std::string(reinterpret_cast<const char*>(literals_utf8) + literal_offsets[i], (size_t)(literal_offsets[i + 1] - literal_offsets[i])));
     }
     e->dec_special.swap(sp);
-    return build_decode_table(e);
+    st = build_decode_table(e);
+    return st != TKZ_OK ? st : build_literal_table(e);
 }
 
 namespace {
@@ -2110,6 +2264,10 @@ tkz_status tkz_encoder_reserve(tkz_encoder* e, int64_t max_bytes, int64_t max_do
     if (st != TKZ_OK) return st;
     const int64_t nwords = max_bytes / 64 + 1;
     HIP_TRY(ws->w_xq.ensure((size_t)(nwords / kRowsPerWave + 4) * 16, acc));                      // (the o200k scanners' queues)
+    {   // (an encoder with special tokens registered: the special entries' bitmaps)
+        bool lits; { std::lock_guard<std::mutex> lock(e->mu); lits = e->lit_state == 1; }
+        if (lits) for (DevBuf* b : {&ws->w_candbits, &ws->w_segbits, &ws->w_specbits, &ws->w_endbits}) HIP_TRY(b->ensure((size_t)(nwords + 8) * 8, acc));
+    }
     if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
     HIP_TRY(ensure_streams(ws));
     {   // what the host-buffer entry points stage a chunk in (two input sets, three output sets: encode_host cuts a large batch into chunks of at most 32 MB; the

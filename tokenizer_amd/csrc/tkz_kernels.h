@@ -89,7 +89,17 @@ struct EncodeParams {
     const uint4* promo;           // token quads of the promoted pieces (TkzTables::promo of the tables this batch was probed with), or null: k_place
     int32_t tc_atomic;            // k_probe zeroes tile_count and k_merge_short ADDS its counts (atomics) instead of storing them: the long-piece kernels, which add theirs, may run beside it (Launch::side)
     int32_t place128;             // launch k_place<128> (two kept list entries per lane) instead of k_place<64>: the previous batch of the workspace was miss-heavy
+    // the special entries only (null on the plain path, which then launches the k_probe it always did): bit i set <=> a TAKEN special-token literal starts at
+    // byte i -- that piece's record is the literal's id (k_probe_special) --, and the literal table the id is read from (TkzLitTable)
+    const uint64_t* specbits; const uint32_t* lit_meta; const uint8_t* lit_blob; int32_t n_lit;
 };
+
+// ---- special tokens on the device (EncodeInternal / FindNextSpecialToken, TikTokenizer.cs:141-170,230-241) ----
+// The registered literals in registration order (= the reference's alternation order).  meta: [0..7] the first bytes of all literals as a 256-bit set,
+// then two dwords per literal: offset into blob | length << 16, id.
+constexpr int kLitMax = 256, kLitMaxLen = 128, kLitMetaHead = 8;
+struct TkzLitTable { const uint32_t* meta; const uint8_t* blob; int32_t n; int32_t blob_bytes; };
+struct TkzLitAllowed { uint64_t m[kLitMax / 64]; };       // bit i: literal i is allowed in this call
 
 // k_small: one launch for a small batch (tkz_kernels.hip).  Input and output live in page-locked host memory the device reads and writes directly.
 // (k_small's static LDS: 83.5 KB of gfx950's 160 KB per workgroup -- more than the 64 KB of earlier CDNA parts: the host takes the single-launch path only
@@ -138,6 +148,14 @@ void launch_rebase(const Launch& L, int64_t* offs, int64_t n, int64_t base);
 // TKZ_OPT_CASE_EQUIVALENCE: a piece start behind every `'` + U+017F at whose apostrophe a match starts (cl100k on a .NET >= 7 host)
 void launch_case_equiv_fix(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, uint64_t* startbits);
 void launch_miss_stats(const Launch& L, const EncodeParams& P, int64_t nsub);
+// the special entries.  launch_lit_scan: candidates (an ALLOWED literal is the first registered literal that matches here and ends inside the document), then the
+// literals taken left to right; segbits = docbits | starts | ends of the taken literals, specbits = their starts, endbits = their ends; *n_taken += their number.
+// launch_lit_fix (behind the pre-tokenizer, which ran with segbits in the place of docbits): no piece start strictly inside a taken literal.
+// launch_seg_offsets: the offsets of the n_seg segments of segbits (n_seg + 1 entries), for the scanners that take offsets (ord_base: the scan of its counts per sub-tile)
+void launch_lit_scan(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, int64_t nwords, const TkzLitTable& LT, const TkzLitAllowed& A,
+                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken);
+void launch_lit_fix(const Launch& L, uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords);
+void launch_seg_offsets(const Launch& L, const uint64_t* segbits, int64_t nwords, int64_t total, int64_t nsub, const int64_t* ord_base, int64_t n_seg, int64_t* seg_offs);
 void launch_counts3(const Launch& L, int64_t n_docs, int64_t total, const int64_t* grand, int64_t* out3, int64_t* out3b = nullptr, int64_t* out3c = nullptr);
 // UTF-16 documents -> UTF-8 documents (Encoding.UTF8.GetBytes for a batch): lengths + group prefixes, then (after the scan of
 // the tile sums) the bytes and the byte offset of every document

@@ -612,7 +612,7 @@ TKZ_DEV uint32_t tkz_key_dword(const uint32_t* s_bytes, int s, int len, int i) {
 // LDS of one wavefront of the probe stage (+ the mask table, shared by the workgroup)
 constexpr int kProbeLdsBytes = (kSub + kHalo) + 2 * (kSub + 2) + 2 * kMidMax + 4 * kMidMax + 4 * (kSub / 32);     // per wavefront; a multiple of 4
 constexpr int kProbeLdsQuads = (kProbeLdsBytes + 15) / 16;
-struct ProbeLds { uint32_t* bytes; uint16_t* pstart; uint16_t* mid; uint32_t* midres; uint32_t* mark; const uint4* kmask; };
+struct ProbeLds { uint32_t* bytes; uint16_t* pstart; uint16_t* mid; uint32_t* midres; uint32_t* mark; const uint4* kmask; uint32_t* spec /* k_probe_special only */; };
 TKZ_DEV ProbeLds tkz_probe_lds(uint4* wave_quads, const uint4* kmask) {
     ProbeLds L;
     uint8_t* b = reinterpret_cast<uint8_t*>(wave_quads);
@@ -622,6 +622,7 @@ TKZ_DEV ProbeLds tkz_probe_lds(uint4* wave_quads, const uint4* kmask) {
     L.pstart = reinterpret_cast<uint16_t*>(b); b += 2 * (kSub + 2);
     L.mid = reinterpret_cast<uint16_t*>(b);
     L.kmask = kmask;
+    L.spec = nullptr;
     return L;
 }
 // byte mask of a zero-padded key of 0..12 bytes (three dwords): written by threads 0..12 of the workgroup, followed by a barrier
@@ -659,13 +660,30 @@ TKZ_DEV void tkz_probe_request_text(const EncodeParams& P, int64_t sub, ProbeTex
     }
     tx->v0 = v0; tx->v1 = v1;
 }
+// The special entries: the piece at byte s of the sub-tile, len bytes long, is a TAKEN special-token literal (EncodeParams::specbits) -- its id, from the literal
+// table: the first registered literal of that length with those bytes (k_lit_scan took the first registered literal that matches at s: it is this one).
+// Rare (a literal per document): the table is read from memory, the bytes from LDS (sb) or, beyond the staged halo, from the text (gb).
+TKZ_DEV int32_t tkz_lit_id(const EncodeParams& P, const uint8_t* sb, const uint8_t* gb, int s, int len) {
+    const uint8_t* tx = s + len <= kSub + kHalo ? sb + s : gb + s;
+    for (int i = 0; i < P.n_lit; ++i) {
+        const uint32_t m = P.lit_meta[kLitMetaHead + 2 * i];
+        if ((int)(m >> 16) != len) continue;
+        const uint8_t* lit = P.lit_blob + (m & 0xFFFFu);
+        int k = 0;
+        while (k < len && lit[k] == tx[k]) ++k;
+        if (k == len) return (int32_t)P.lit_meta[kLitMetaHead + 2 * i + 1];
+    }
+    return TKZ_RANK_NONE;
+}
 // one sub-tile, by one wavefront (no workgroup barrier inside: every wavefront is on its own).  tx: the sub-tile's text, requested by the
 // caller; on return it holds the request for sub-tile `next` (< 0: none), issued as soon as this one's text had moved into LDS -- a
 // wavefront that probes consecutive sub-tiles never waits for text again.
 // REPORT: a list that does not fit is reported here, by two atomics on the counter block (the single-launch kernel: one workgroup); the batch path
 // leaves that to k_list_stats, which reads the lengths from mcount -- when nearly every sub-tile overflows (the first batch of text that is
 // full of missed pieces) ten million atomics on one line cost 100 ms.
-template <bool REPORT>
+// SPECIAL (k_probe_special, the special entries): a piece whose start is marked in P.specbits is a special-token literal -- its record is the literal's id, it
+// takes part in no lookup and is never a miss (not listed, not merged, not in the memo or the miss share).  SPECIAL == false compiles to the code it always was.
+template <bool REPORT, bool SPECIAL = false>
 TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_t sub, const ProbeLds& LD, ProbeText& tx, int64_t next) {
     const int lane = simt::lane();
     uint32_t* s_bytes = LD.bytes;
@@ -686,9 +704,10 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
     // (the text itself was requested even earlier: by the caller, or while the sub-tile before this one was probed -- tx)
     uint4 v0 = tx.v0, v1 = tx.v1;
     uint64_t myword = 0, mymark = 0;                      // lanes 0..15: piece-start word / mark word of the sub-tile
+    uint64_t myspec = 0;                                  // (SPECIAL: the starts of the taken literals)
     if (lane < kSub / 64) {
         const int64_t w = sub * (kSub / 64) + lane;
-        if (w < P.nwords) { myword = P.startbits[w]; mymark = P.docbits[w]; }
+        if (w < P.nwords) { myword = P.startbits[w]; mymark = P.docbits[w]; if (SPECIAL) myspec = P.specbits[w]; }
     }
     const int64_t from = base + nb, w0 = from >> 6;        // the search for the end of the last piece starts here
     uint64_t ahead = (w0 + lane < P.nwords) ? P.startbits[w0 + lane] : 0ull;
@@ -700,6 +719,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         const int lim = nb - lane * 64;                    // bits at or beyond the end of the corpus are not pieces
         if (lim <= 0) myword = 0; else if (lim < 64) myword &= tkz_lowmask(lim);
         s_mark[2 * lane] = (uint32_t)mymark; s_mark[2 * lane + 1] = (uint32_t)(mymark >> 32);
+        if (SPECIAL) { LD.spec[2 * lane] = (uint32_t)myspec; LD.spec[2 * lane + 1] = (uint32_t)(myspec >> 32); }
     }
     // end of the last piece that starts here = first piece start at or after base+nb (the sentinel at `total` bounds it)
     int64_t last_end;
@@ -758,7 +778,8 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
             s = s_pstart[k];
             len = (int)s_pstart[k + 1] - s;
         }
-        const bool is_mid = valid && len <= TKZ_MID_KEY_MAX;
+        const bool is_lit = SPECIAL && valid && ((LD.spec[s >> 5] >> (s & 31)) & 1u);
+        const bool is_mid = valid && len <= TKZ_MID_KEY_MAX && !is_lit;
         if (is_mid) {
 #pragma unroll
             for (int i = 0; i < 7; ++i) kk[i] = tkz_key_dword(s_bytes, s, len, i);
@@ -769,6 +790,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         const uint4 a0 = tkz_load16(tb0 + oa), a1 = tkz_load16(tb0 + oa + 16u), b0 = tkz_load16(tb0 + ob), b1 = tkz_load16(tb0 + ob + 16u);
         int32_t rank = TKZ_RANK_NONE;
         if (is_mid) rank = tkz_match_mid(kk, (uint32_t)len, a0, a1, b0, b1);
+        else if (is_lit) rank = tkz_lit_id(P, sb, gbase, s, len);
         else if (valid) {
             if (s + len <= kSub + kHalo) rank = tkz_lookup_long(T, [&](int i) -> uint32_t { return sb[s + i]; }, (uint32_t)len);
             else rank = tkz_lookup_long(T, [&](int i) -> uint32_t { return gbase[s + i]; }, (uint32_t)len);
@@ -823,6 +845,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         for (int u = 0; u < U; ++u) {
             const bool is_short = plen[u] >= 1 && plen[u] <= TKZ_SHORT_KEY_MAX;
             rk[u] = tkz_match_short2x(kw0[u], kw1[u], kw2[u], (uint32_t)plen[u], a0[u], a1[u]);       // (a piece that is not short matches no slot: len 0 or > 12)
+            if (SPECIAL && is_short && ((LD.spec[ps[u] >> 5] >> (ps[u] & 31)) & 1u)) rk[u] = tkz_lit_id(P, sb, gbase, ps[u], plen[u]);
             more = more || (is_short && rk[u] == TKZ_RANK_NONE);
         }
         // the second bucket, for the lanes the first one did not settle only (the keys the builder could not keep in their first
@@ -938,6 +961,27 @@ TKZ_KERNEL_OCC(256, TKZ_PROBE_OCC) void k_probe(TkzTables T, EncodeParams P) {
         const int64_t nxt = (it + 1 < kProbePer && sub0 + it + 1 < P.nsub) ? sub0 + it + 1 : -1;
         tkz_probe_subtile<false>(T, P, sub0 + it, LD, tx, nxt);
         (void)simt::ballot(true);                             // (the next sub-tile reuses the wavefront's LDS)
+    }
+}
+
+// the special entries' form: the same sub-tiles, with the starts of the taken literals beside the marks
+TKZ_KERNEL_OCC(256, TKZ_PROBE_OCC) void k_probe_special(TkzTables T, EncodeParams P) {
+    TKZ_SHARED uint4 s_wave[kThreads / 64][kProbeLdsQuads];
+    TKZ_SHARED uint4 s_kmask[TKZ_SHORT_KEY_MAX + 1];
+    TKZ_SHARED uint32_t s_spec[kThreads / 64][kSub / 32];
+    tkz_probe_kmask_init(s_kmask);
+    simt::sync();
+    const int64_t sub0 = (tkz_xcd_block(simt::bid(), simt::nblocks()) * (kThreads / 64) + simt::wave()) * kProbePer;
+    if (sub0 >= P.nsub) return;
+    ProbeLds LD = tkz_probe_lds(s_wave[simt::wave()], s_kmask);
+    LD.spec = s_spec[simt::wave()];
+    ProbeText tx;
+    tkz_probe_request_text(P, sub0, &tx);
+#pragma unroll 1
+    for (int it = 0; it < kProbePer && sub0 + it < P.nsub; ++it) {
+        const int64_t nxt = (it + 1 < kProbePer && sub0 + it + 1 < P.nsub) ? sub0 + it + 1 : -1;
+        tkz_probe_subtile<false, true>(T, P, sub0 + it, LD, tx, nxt);
+        (void)simt::ballot(true);
     }
 }
 
@@ -2441,6 +2485,164 @@ TKZ_KERNEL(256) void k_case_equiv_fix(const uint8_t* bytes, int64_t total, const
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Special tokens (the special entries): EncodeInternal / FindNextSpecialToken (TikTokenizer.cs:141-170,230-241) for a batch.
+//   k_lit_scan     position-parallel over the text: at byte p "the match" is the FIRST registered literal whose bytes are the text at p and that ends inside
+//                  p's document (the reference's alternation); p is a CANDIDATE when that literal is allowed.  One wavefront per 4 KiB, staged in LDS with
+//                  the literal table; a lane looks at a byte, the 256-bit set of first bytes sends nearly all of them on.
+//   k_lit_resolve  the literals TAKEN: left to right inside a document, the first candidate at or after the end of the one before.  A candidate no other
+//                  candidate reaches over is taken whatever came before it: it heads a RUN, which one lane walks to the next head (one step for literals
+//                  that do not overlap -- every `<|endoftext|>` of a corpus heads its own run).  Starts and ends are OR-ed into the bitmaps.
+//   k_lit_fix      behind the pre-tokenizer (which split every stretch between segment marks -- the taken literals too -- as a text of its own): the piece
+//                  starts strictly inside a taken literal are cleared, so that it is ONE piece; k_probe_special makes that piece's record the literal's id.
+// -------------------------------------------------------------------------------------------------
+// bytes from p to the end of p's document (the next document mark behind p; the bitmap ends in a mark at `total`), or kLitMaxLen + 1 when that is further away
+// (never more than the text holds, whatever the bitmap says: offsets that k_docmark refused leave it without its last mark)
+TKZ_DEV int tkz_lit_room(const uint64_t* docbits, int64_t nwords, int64_t total, int64_t p) {
+    const int64_t w = p >> 6;
+    const int b = (int)(p & 63);
+    int r = kLitMaxLen + 1;
+    uint64_t m = b == 63 ? 0ull : docbits[w] >> (b + 1);
+    if (m) r = tkz_ctz64(m) + 1;
+    else if ((m = w + 1 < nwords ? docbits[w + 1] : 0ull) != 0) r = 64 - b + tkz_ctz64(m);
+    else if ((m = w + 2 < nwords ? docbits[w + 2] : 0ull) != 0) r = 128 - b + tkz_ctz64(m);
+    return total - p < r ? (int)(total - p) : r;
+}
+// the first registered literal of at most `room` bytes whose bytes are tx[0 ..): its index, or -1
+TKZ_DEV int tkz_lit_first(const uint32_t* meta, const uint8_t* blob, int n, const uint8_t* tx, int room) {
+    for (int i = 0; i < n; ++i) {
+        const uint32_t m = meta[kLitMetaHead + 2 * i];
+        const int len = (int)(m >> 16);
+        if (len > room) continue;
+        const uint8_t* lit = blob + (m & 0xFFFFu);
+        int k = 0;
+        while (k < len && lit[k] == tx[k]) ++k;
+        if (k == len) return i;
+    }
+    return -1;
+}
+constexpr int kLitBlock = 4096;                            // bytes of text per wavefront of k_lit_scan (64 bitmap words)
+constexpr int kLitTextQuads = (kLitBlock + kLitMaxLen) / 16;
+TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, TkzLitTable LT, TkzLitAllowed A,
+                                uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits) {
+    TKZ_SHARED uint4 s_text[kThreads / 64][kLitTextQuads];
+    TKZ_SHARED uint32_t s_meta[kLitMetaHead + 2 * kLitMax];
+    TKZ_SHARED uint4 s_blob[kLitMax * kLitMaxLen / 16];
+    {   // the literal table (a few hundred bytes as a rule)
+        uint8_t* sb = reinterpret_cast<uint8_t*>(s_blob);
+        for (int i = simt::tid(); i < kLitMetaHead + 2 * LT.n; i += simt::nthreads()) s_meta[i] = LT.meta[i];
+        for (int i = simt::tid(); i < LT.blob_bytes; i += simt::nthreads()) sb[i] = LT.blob[i];
+    }
+    simt::sync();
+    const int lane = simt::lane();
+    const int64_t blk = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t w0 = blk * (kLitBlock / 64), base = blk * kLitBlock;
+    if (w0 >= nwords) return;
+    uint4* const tq = s_text[simt::wave()];
+    for (int q = lane; q < kLitTextQuads; q += 64) {       // the block and the bytes a literal that starts in it may reach; zeros beyond the text
+        const int64_t p = base + 16 * (int64_t)q;
+        uint4 v; v.x = v.y = v.z = v.w = 0;
+        if (p + 16 <= total) v = tkz_load16_nt(bytes + p);
+        else {
+            uint32_t w[4] = {0, 0, 0, 0};
+            for (int k = 0; k < 16; ++k) if (p + k < total) w[k >> 2] |= (uint32_t)bytes[p + k] << (8 * (k & 3));
+            v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+        }
+        tq[q] = v;
+    }
+    (void)simt::ballot(true);
+    const uint8_t* const tx = reinterpret_cast<const uint8_t*>(tq);
+    const uint8_t* const blob = reinterpret_cast<const uint8_t*>(s_blob);
+    uint64_t mine = 0;                                     // lane j keeps word w0 + j
+#pragma unroll 1
+    for (int j = 0; j < kLitBlock / 64; ++j) {
+        if (w0 + j >= nwords) break;                       // (wave-uniform)
+        const int pos = 64 * j + lane;
+        const int64_t p = base + pos;
+        const uint32_t c = tx[pos];
+        bool cand = false;
+        if (p < total && ((s_meta[c >> 5] >> (c & 31)) & 1u)) {
+            const int i = tkz_lit_first(s_meta, blob, LT.n, tx + pos, tkz_lit_room(docbits, nwords, total, p));
+            cand = i >= 0 && ((A.m[i >> 6] >> (i & 63)) & 1ull);
+        }
+        const uint64_t m = simt::ballot(cand);
+        if (lane == j) mine = m;
+    }
+    const int64_t w = w0 + lane;
+    if (w < nwords) { candbits[w] = mine; segbits[w] = docbits[w]; specbits[w] = 0; endbits[w] = 0; }
+}
+// the literal that k_lit_scan matched at candidate p (from the text: candidates are rare): its length
+TKZ_DEV int tkz_lit_len_at(const uint8_t* bytes, const uint64_t* docbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p) {
+    const int i = tkz_lit_first(LT.meta, LT.blob, LT.n, bytes + p, tkz_lit_room(docbits, nwords, total, p));
+    return i < 0 ? 1 : (int)(LT.meta[kLitMetaHead + 2 * i] >> 16);
+}
+// does a candidate in front of p reach over p?  (Only one that starts within kLitMaxLen - 1 bytes can; the nearest first: in a run of overlapping literals it does.)
+TKZ_DEV bool tkz_lit_covered(const uint8_t* bytes, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p) {
+    const int64_t lo = p - (kLitMaxLen - 1) > 0 ? p - (kLitMaxLen - 1) : 0;
+    for (int64_t w = (p - 1) >> 6; p > 0 && w >= (lo >> 6); --w) {
+        uint64_t m = candbits[w];
+        if (w == ((p - 1) >> 6)) m &= tkz_lowmask((int)((p - 1) & 63) + 1);
+        if (w == (lo >> 6)) m &= ~tkz_lowmask((int)(lo & 63));
+        while (m) {
+            const int b = tkz_msb64(m);
+            m &= ~(1ull << b);
+            const int64_t q = (w << 6) + b;
+            if (q + tkz_lit_len_at(bytes, docbits, nwords, total, LT, q) > p) return true;
+        }
+    }
+    return false;
+}
+TKZ_KERNEL(256) void k_lit_resolve(const uint8_t* bytes, int64_t total, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, TkzLitTable LT,
+                                   uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken) {
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    unsigned long long taken = 0;
+    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) {
+        for (uint64_t m = candbits[w]; m; m &= m - 1) {
+            const int64_t head = (w << 6) + tkz_ctz64(m);
+            if (tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, head)) continue;       // (another lane's run)
+            for (int64_t cur = head; cur >= 0;) {
+                const int64_t end = cur + tkz_lit_len_at(bytes, docbits, nwords, total, LT, cur);    // (<= total: the literal ends inside its document)
+                simt::atomic_or64((unsigned long long*)&specbits[cur >> 6], 1ull << (cur & 63));
+                simt::atomic_or64((unsigned long long*)&endbits[end >> 6], 1ull << (end & 63));
+                simt::atomic_or64((unsigned long long*)&segbits[cur >> 6], 1ull << (cur & 63));
+                simt::atomic_or64((unsigned long long*)&segbits[end >> 6], 1ull << (end & 63));
+                ++taken;
+                // the next candidate at or after `end`: part of this run when a candidate in front of it reaches over it -- it then starts less than kLitMaxLen
+                // bytes behind `end` --, the head of a run of its own otherwise
+                int64_t nxt = -1;
+                for (int64_t v = end >> 6; v < nwords && v <= (end + kLitMaxLen) >> 6 && nxt < 0; ++v) {
+                    uint64_t c = candbits[v];
+                    if (v == (end >> 6)) c &= ~tkz_lowmask((int)(end & 63));
+                    if (c) nxt = (v << 6) + tkz_ctz64(c);
+                }
+                cur = nxt >= 0 && nxt < total && tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, nxt) ? nxt : -1;
+            }
+        }
+    }
+    if (taken) simt::atomic_add64(n_taken, taken);
+}
+// one bitmap word a lane.  `inside` = the bytes strictly inside a taken literal: the running XOR of a mark behind every start and one at every end (a literal of
+// one byte: the two cancel); what is open at the word's first bit comes from the last start in the 128 bytes before it.
+TKZ_KERNEL(256) void k_lit_fix(uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords) {
+    static_assert(kLitMaxLen <= 128, "a literal spans at most three bitmap words");
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) {
+        const uint64_t s0 = specbits[w], e0 = endbits[w];
+        const uint64_t s1 = w > 0 ? specbits[w - 1] : 0ull, e1 = w > 0 ? endbits[w - 1] : 0ull;
+        bool open = false;                                 // byte 64 w - 1 is inside a literal that goes on into this word
+        const uint64_t s1lo = s1 & ~(1ull << 63);
+        if (s1lo) { const int b = tkz_msb64(s1lo); open = (e1 >> (b + 1)) == 0; }
+        else if (w > 1 && specbits[w - 2]) {
+            const int b = tkz_msb64(specbits[w - 2]);
+            open = ((b == 63 ? 0ull : endbits[w - 2] >> (b + 1)) | e1) == 0;
+        }
+        uint64_t x = ((s0 << 1) | (s1 >> 63)) ^ e0;
+        x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16; x ^= x << 32;
+        if (open) x = ~x;
+        if (x | segbits[w]) startbits[w] = (startbits[w] & ~x) | segbits[w];
+    }
+}
+
 // document offsets of a chunk cut out of a larger batch: made relative to the chunk's first byte
 // A small host batch on page-locked buffers: the text and the offsets come over PCIe by this kernel's own loads (they are device-visible), into the
 // staging buffers the other kernels read, and the workspace's zero region is cleared by the same launch -- in place of two copy commands, two fills and
@@ -3112,7 +3314,8 @@ static void launch_coop(hipStream_t st, const TkzTables& T, const EncodeParams& 
 constexpr int64_t kSideLongGrid = 2048, kSideCoopGrid = 1024;
 void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsub) {
     hook(L, K_ENCODE, 0);
-    TKZ_LAUNCH(k_probe, xcd_grid(cdiv(nsub, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
+    if (P.specbits) TKZ_LAUNCH(k_probe_special, xcd_grid(cdiv(nsub, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
+    else TKZ_LAUNCH(k_probe, xcd_grid(cdiv(nsub, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
     hook(L, K_ENCODE, 1);
     // (the list statistics and, in the same pass, the giant pieces of the sub-tiles k_probe flagged: queued for k_giant_order / k_giant_merge)
     { const int64_t g = grid_for(nsub); TKZ_LAUNCH(k_list_stats, g < 1024 ? g : 1024, kThreads, L.stream, (const uint32_t*)P.mcount, nsub, P.mcap, P.counters,
@@ -3172,7 +3375,8 @@ void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, i
 void launch_probe_sample(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsample) {
     if (nsample > P.nsub) nsample = P.nsub;
     hook(L, K_ENCODE, 0);
-    TKZ_LAUNCH(k_probe, xcd_grid(cdiv(nsample, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
+    if (P.specbits) TKZ_LAUNCH(k_probe_special, xcd_grid(cdiv(nsample, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
+    else TKZ_LAUNCH(k_probe, xcd_grid(cdiv(nsample, (kThreads / 64) * kProbePer)), kThreads, L.stream, T, P);
     hook(L, K_ENCODE, 1);
     { const int64_t g = grid_for(nsample); TKZ_LAUNCH(k_list_stats, g < 1024 ? g : 1024, kThreads, L.stream, (const uint32_t*)P.mcount, nsample, P.mcap, P.counters,
                                                      (const uint8_t*)P.heavy_flag, P.startbits, P.nwords, P.total, P.giant_q, P.giant_count, P.giant_cap,
@@ -3230,6 +3434,20 @@ void launch_docoffs(const Launch& L, const int64_t* d_offs, int64_t n_docs, int6
 }
 void launch_case_equiv_fix(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, uint64_t* startbits) {
     TKZ_LAUNCH(k_case_equiv_fix, grid_for((total + 7) / 8), kThreads, L.stream, d_bytes, total, docbits, startbits);
+}
+// (the brackets: the scan and the segment bitmap extend K_DOCMARK's, the fix-up K_PRETOK's -- the closing event is recorded again behind them)
+void launch_lit_scan(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, int64_t nwords, const TkzLitTable& LT, const TkzLitAllowed& A,
+                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken) {
+    TKZ_LAUNCH(k_lit_scan, grid1(cdiv(nwords, (kThreads / 64) * (kLitBlock / 64))), kThreads, L.stream, d_bytes, total, docbits, nwords, LT, A, candbits, segbits, specbits, endbits);
+    TKZ_LAUNCH(k_lit_resolve, grid_for(nwords), kThreads, L.stream, d_bytes, total, docbits, (const uint64_t*)candbits, nwords, LT, segbits, specbits, endbits, n_taken);
+    hook(L, K_DOCMARK, 1);
+}
+void launch_lit_fix(const Launch& L, uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords) {
+    TKZ_LAUNCH(k_lit_fix, grid_for(nwords), kThreads, L.stream, startbits, segbits, specbits, endbits, nwords);
+    hook(L, K_PRETOK, 1);
+}
+void launch_seg_offsets(const Launch& L, const uint64_t* segbits, int64_t nwords, int64_t total, int64_t nsub, const int64_t* ord_base, int64_t n_seg, int64_t* seg_offs) {
+    TKZ_LAUNCH(k_piece_index, grid1(cdiv(nsub, kThreads / 64)), kThreads, L.stream, segbits, nwords, total, nsub, ord_base, n_seg, seg_offs);
 }
 void launch_rebase(const Launch& L, int64_t* offs, int64_t n, int64_t base) {
     TKZ_LAUNCH(k_rebase, grid_for(n), kThreads, L.stream, offs, n, base);

@@ -103,6 +103,14 @@ def _utf8_like_dotnet(s: str) -> bytes:
         return s.encode("utf-16-le", "surrogatepass").decode("utf-16-le", "replace").encode("utf-8")
 
 
+def _has_lone_surrogate(s: str) -> bool:
+    try:
+        s.encode("utf-8")
+        return False
+    except UnicodeEncodeError:
+        return True
+
+
 class TikTokenizer:
     """ITokenizer over the MI355X encode path.  Construct through TokenizerBuilder, or directly with the
     bytes of a .tiktoken rank file (the reference takes a Stream, TikTokenizer.cs:60-65)."""
@@ -146,8 +154,10 @@ class TikTokenizer:
         self.SpecialTokens = set(self.SpecialTokensEncoder)
         # alternation of the escaped literals in registration order (TikTokenizer.cs:78): leftmost match, first alternative wins
         self._special_re = re.compile("|".join(re.escape(k) for k in self.SpecialTokensEncoder)) if self.SpecialTokensEncoder else None
+        self._special_on_host = False                         # set when the device's special entries refuse the registered set (UnsupportedError)
+        self._fffd_literal = any("\ufffd" in k for k in self.SpecialTokensEncoder)
         if self.SpecialTokensEncoder:
-            self._encoder.set_special_tokens(self.SpecialTokensEncoder)      # SpecialTokensDecoder (TikTokenizer.cs:79), for Decode
+            self._encoder.set_special_tokens(self.SpecialTokensEncoder)      # SpecialTokensDecoder (TikTokenizer.cs:79) for Decode; the device's literal table
 
     # ---- segmentation (host) ---------------------------------------------------------------------
     def _segments(self, text: str, allowed: Optional[Iterable[str]]):
@@ -193,9 +203,16 @@ class TikTokenizer:
     def EncodeBatchFlat(self, texts: Sequence[str], allowedSpecialOrApply: Union[bool, Sequence[str], None] = True):
         """EncodeBatch without a list per text: (ids int32[total], offsets int64[len(texts) + 1]); text d is ids[offsets[d]:offsets[d+1]].
         When no special token applies (the reference's plain path, TikTokenizer.cs:180-183,196-199) the arrays are the device call's own
-        output, untouched; otherwise the special ids are spliced in between the plain segments' ids with array copies."""
+        output, untouched; with special tokens allowed likewise: ONE call of the device's special entry on the texts as they are (the literals
+        are cut out on the device, tkz_encode_batch_special_utf8).  Only a set of literals the device path does not hold (UnsupportedError), or a text with a
+        lone surrogate while a literal holds U+FFFD, is segmented here and spliced."""
         allowed = self._resolve_allowed(allowedSpecialOrApply)
-        if not allowed or self._special_re is None:
+        plain = not allowed or self._special_re is None
+        device_special = not plain and not self._special_on_host
+        if device_special and self._fffd_literal:
+            # Encoding.UTF8.GetBytes turns a lone surrogate into EF BF BD, which a literal holding U+FFFD would match on bytes but not in the reference's UTF-16 search
+            device_special = not any(_has_lone_surrogate(t) for t in texts)
+        if plain or device_special:
             segs = [_utf8_like_dotnet(t) for t in texts]
             if not segs:
                 return np.zeros(0, np.int32), np.zeros(1, np.int64)
@@ -203,7 +220,14 @@ class TikTokenizer:
             offs = np.zeros(len(segs) + 1, np.int64)
             np.cumsum(lens, out=offs[1:])
             data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
-            return self._encoder.encode_batch(data, offs)
+            if plain:
+                return self._encoder.encode_batch(data, offs)
+            names = set(allowed)
+            index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]       # (registration order = the alternation's)
+            try:
+                return self._encoder.encode_batch_special(data, offs, index)
+            except N.UnsupportedError:
+                self._special_on_host = True                  # (more than 256 literals, one beyond 128 bytes ...: the host segmentation below, from here on)
         plans = [self._segments(t, allowed) for t in texts]
         segs = [_utf8_like_dotnet(s) for plan in plans for kind, s, _ in plan if kind == "t"]
         if segs:
