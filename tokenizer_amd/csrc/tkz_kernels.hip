@@ -143,7 +143,6 @@ TKZ_KERNEL(64) void k_pretok_rows(const uint8_t* bytes, int64_t total, const uin
     // evaluates them all at once (tkz_block_eval); blocks that scheme refuses go through the sequential row loop.
     TKZ_SHARED uint16_t s_aflags[128];
     TKZ_SHARED uint4 s_blk[(65 * kBlockRowStride) / 16];
-    for (int i = simt::tid(); i < 128; i += simt::nthreads()) s_aflags[i] = (uint16_t)tkz_ascii_flags((uint32_t)i, PATTERN == TKZ_PAT_CL100K);
     const int lane = simt::lane();
     const int64_t r0 = simt::bid() * kRowsPerWave;
     const int64_t first = r0 - 1;                          // row of lane 0
@@ -187,6 +186,9 @@ TKZ_KERNEL(64) void k_pretok_rows(const uint8_t* bytes, int64_t total, const uin
         for (int64_t r = r0 + lane; r < r1; r += 64) startbits[r] = docbits[r];
         if (lane == 0) reinterpret_cast<uint8_t*>(xq)[simt::bid()] = 1;
     } else {
+        // the per-byte flag table is read by the row loop only: filled here, behind the block evaluator's refusal
+        for (int i = lane; i < 128; i += 64) s_aflags[i] = (uint16_t)tkz_ascii_flags((uint32_t)i, PATTERN == TKZ_PAT_CL100K);
+        simt::sync();
         TkzSrc S;
         S.bytes = bytes; S.total = total; S.stage = nullptr; S.lo = 0; S.hi = 0;
         tkz_rows_sequential<PATTERN>(S, docbits, startbits, nrows, bmp, s_aflags, r0, r1, counters);

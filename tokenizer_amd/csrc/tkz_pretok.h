@@ -562,10 +562,13 @@ TKZ_DEV uint64_t tkz_row_eval_ascii(const TkzRowMasks& mP, const TkzRowMasks& mC
 // =================================================================================================
 // (2b) one ROW PER LANE: 64 consecutive ASCII rows evaluated at once.
 //
-// Lane j owns row (first_row + j): its 64 bytes are classified with SWAR arithmetic on 16 dwords (no
-// ballots, no per-byte work), giving the same 64-bit class masks as tkz_row_masks_ascii -- but in that
-// lane's VGPRs -- and the rules of tkz_row_eval_ascii are then ordinary per-lane 64-bit arithmetic, 64 rows
-// per instruction instead of one row per scalar instruction.  Every cross-row dependency is brought
+// Lane j owns row (first_row + j): its 16 dwords are transposed into the row's eight BIT PLANES (plane k =
+// bit k of each of the 64 bytes: byte permutes, then masked exchanges between register pairs -- no ballots,
+// no per-byte and no per-class work, no multiply) and every class is a boolean function of the planes on all
+// 64 bytes at once, giving the same 64-bit class masks as tkz_row_masks_ascii -- but in that lane's VGPRs;
+// plane 7 is the "not ASCII" mask, so an ASCII block pays nothing for the multi-byte masks.  The rules of
+// tkz_row_eval_ascii are then ordinary per-lane 64-bit arithmetic, 64 rows per instruction instead of one
+// row per scalar instruction.  Every cross-row dependency is brought
 // down to the nearest neighbour (two lane-shift exchanges) by refusing blocks in which a digit run or a
 // white-space run covers a whole 64-byte row; those blocks, blocks with a non-ASCII byte and blocks that
 // are not entirely inside the corpus are left to the sequential row loop.  Lanes 0 and 63 are context:
@@ -573,60 +576,91 @@ TKZ_DEV uint64_t tkz_row_eval_ascii(const TkzRowMasks& mP, const TkzRowMasks& mC
 // =================================================================================================
 constexpr int kBlockRowStride = 80;       // bytes between rows in LDS: keeps 16-byte alignment, spreads the 4 x b128 row reads over all banks
 
-// bit 7 of every byte of x that lies in [lo, hi]; all bytes of x are < 0x80
-TKZ_HD uint32_t tkz_swar_range(uint32_t x, uint32_t lo, uint32_t hi) {
-    return (x + (0x80u - lo) * 0x01010101u) & ~(x + (0x7Fu - hi) * 0x01010101u) & 0x80808080u;
+// v_perm_b32: byte n of the result is byte sel[n] of the eight bytes {hi, lo} (0..3: lo, 4..7: hi)
+TKZ_HD uint32_t tkz_byte_perm(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int n = 0; n < 4; ++n) r |= (uint32_t)((v >> (8 * ((sel >> (8 * n)) & 7u))) & 0xFFu) << (8 * n);
+    return r;
+#endif
 }
-TKZ_HD uint32_t tkz_swar_eq(uint32_t x, uint32_t c) {
-    const uint32_t z = x ^ (c * 0x01010101u);
-    return ~(z + 0x7F7F7F7Fu) & 0x80808080u;
-}
-// the four bit-7 flags of r as a nibble (byte 0 -> bit 0)
-TKZ_HD uint32_t tkz_swar_nibble(uint32_t r) { return (((r >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
+// the bits of a where m is set, those of b elsewhere (v_bfi_b32)
+TKZ_HD uint32_t tkz_bit_select(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }
 
-struct TkzBlockMasks { uint64_t L, N, O, W, CR, SP, AP, UP, SL, HI, CONT; uint32_t hi; };   // HI: bytes >= 0x80, CONT: 10xxxxxx
-
-// classify the 64 bytes of this lane's row (16 dwords at `row`, 16-byte aligned); CASES: also upper-case letters and '/'
-template <bool CASES>
-TKZ_HD TkzBlockMasks tkz_block_classify(const uint4* row) {
-    uint32_t mL[2] = {0, 0}, mN[2] = {0, 0}, mW[2] = {0, 0}, mC[2] = {0, 0}, mS[2] = {0, 0}, mA[2] = {0, 0}, mU[2] = {0, 0}, mX[2] = {0, 0};
-    uint32_t mH[2] = {0, 0}, mT[2] = {0, 0};
-    uint32_t hi = 0;
+// The eight bit planes of 32 consecutive bytes (8 dwords, byte i = byte i % 4 of d[i / 4]): bit i of p[k] = bit k of byte i.
+// A bit of the input has the address (i4 i3 i2 | i1 i0 | k2 k1 k0) = (register | byte in dword | bit in byte); the planes want
+// (k2 k1 k0 | i4 i3 | i2 i1 i0).  Two rounds of byte permutes bring i4 i3 to the byte position (dword k then holds bytes k, 8 + k,
+// 16 + k, 24 + k); three rounds of exchanges between register pairs then swap each bit-in-byte address bit with a register
+// address bit.  There is no per-class work and no multiply: 16 permutes + 12 exchanges of 4 instructions for all planes at once.
+TKZ_HD void tkz_bit_planes32(const uint32_t* d, uint32_t* p) {
+    uint32_t e[8];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint4 v = row[q];
-        const uint32_t xs[4] = {v.x, v.y, v.z, v.w};
+    for (int g = 0; g < 2; ++g) {                          // 4 x 4 byte transpose of d[g], d[2 + g], d[4 + g], d[6 + g]
+        const uint32_t a = d[g], b = d[2 + g], c = d[4 + g], f = d[6 + g];
+        const uint32_t ab_lo = tkz_byte_perm(b, a, 0x05010400u), ab_hi = tkz_byte_perm(b, a, 0x07030602u);   // a0 b0 a1 b1, a2 b2 a3 b3
+        const uint32_t cf_lo = tkz_byte_perm(f, c, 0x05010400u), cf_hi = tkz_byte_perm(f, c, 0x07030602u);
+        e[4 * g + 0] = tkz_byte_perm(cf_lo, ab_lo, 0x05040100u); e[4 * g + 1] = tkz_byte_perm(cf_lo, ab_lo, 0x07060302u);
+        e[4 * g + 2] = tkz_byte_perm(cf_hi, ab_hi, 0x05040100u); e[4 * g + 3] = tkz_byte_perm(cf_hi, ab_hi, 0x07060302u);
+    }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = 4 * q + t;                       // dword index: bytes 4k .. 4k+3
-            const uint32_t xr = xs[t];
-            hi |= xr;
-            // (the range tests add per byte and must not carry into the next one: they run on the low 7 bits; what they say
-            //  about a byte >= 0x80 is meaningless and masked by the caller with HI)
-            const uint32_t x = xr & 0x7F7F7F7Fu;
-            const uint32_t y = x | 0x20202020u;
-            const int h = k >> 3, sh = 4 * (k & 7);
-            mL[h] |= tkz_swar_nibble(tkz_swar_range(y, 'a', 'z')) << sh;
-            mN[h] |= tkz_swar_nibble(tkz_swar_range(x, '0', '9')) << sh;
-            mW[h] |= tkz_swar_nibble(tkz_swar_range(x, 9, 13) | tkz_swar_eq(x, ' ')) << sh;
-            mC[h] |= tkz_swar_nibble(tkz_swar_eq(x, '\n') | tkz_swar_eq(x, '\r')) << sh;
-            mS[h] |= tkz_swar_nibble(tkz_swar_eq(x, ' ')) << sh;
-            mA[h] |= tkz_swar_nibble(tkz_swar_eq(x, '\'')) << sh;
-            mH[h] |= tkz_swar_nibble(xr & 0x80808080u) << sh;
-            mT[h] |= tkz_swar_nibble(xr & ~(xr << 1) & 0x80808080u) << sh;
-            if (CASES) {
-                mU[h] |= tkz_swar_nibble(tkz_swar_range(x, 'A', 'Z')) << sh;
-                mX[h] |= tkz_swar_nibble(tkz_swar_eq(x, '/')) << sh;
-            }
+    for (int s = 0; s < 3; ++s) {                          // register address bit s <-> bit-in-byte address bit s
+        const int sh = 1 << s;
+        const uint32_t m = s == 0 ? 0x55555555u : s == 1 ? 0x33333333u : 0x0F0F0F0Fu;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k & sh) continue;
+            const uint32_t A = e[k], B = e[k | sh];
+            e[k] = tkz_bit_select(m, A, B << sh);
+            e[k | sh] = tkz_bit_select(m, A >> sh, B);
         }
     }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) p[k] = e[k];
+}
+
+struct TkzBlockMasks { uint64_t L, N, O, W, CR, SP, AP, UP, SL, HI, CONT; uint32_t hi; };   // HI: bytes >= 0x80, CONT: 10xxxxxx; hi != 0: the row has a byte >= 0x80
+
+// classify the 64 bytes of this lane's row (16 dwords at `row`, 16-byte aligned); CASES: also upper-case letters and '/'.
+// The row is turned into its eight bit planes once (tkz_bit_planes32 on each half) and every class is a boolean function of
+// the seven low planes on 64 bytes at a time.  The classes look at the low 7 bits only: what they say about a byte >= 0x80 is
+// meaningless and masked by the caller with HI.  HI is plane 7 itself and CONT one more operation: a caller that reads
+// neither pays for neither.
+template <bool CASES>
+TKZ_HD TkzBlockMasks tkz_block_classify(const uint4* row) {
+    uint32_t lo[8], hi[8];
+    {
+        const uint4 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3];
+        const uint32_t d0[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        const uint32_t d1[8] = {v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+        tkz_bit_planes32(d0, lo);
+        tkz_bit_planes32(d1, hi);
+    }
+#define TKZ_PLANE(k) (((uint64_t)hi[k] << 32) | lo[k])
+    const uint64_t a = TKZ_PLANE(0), b = TKZ_PLANE(1), c = TKZ_PLANE(2), d = TKZ_PLANE(3), e = TKZ_PLANE(4), f = TKZ_PLANE(5), g = TKZ_PLANE(6);
     TkzBlockMasks m;
-    m.L = ((uint64_t)mL[1] << 32) | mL[0]; m.N = ((uint64_t)mN[1] << 32) | mN[0]; m.W = ((uint64_t)mW[1] << 32) | mW[0];
-    m.CR = ((uint64_t)mC[1] << 32) | mC[0]; m.SP = ((uint64_t)mS[1] << 32) | mS[0]; m.AP = ((uint64_t)mA[1] << 32) | mA[0];
-    m.UP = ((uint64_t)mU[1] << 32) | mU[0]; m.SL = ((uint64_t)mX[1] << 32) | mX[0];
-    m.HI = ((uint64_t)mH[1] << 32) | mH[0]; m.CONT = ((uint64_t)mT[1] << 32) | mT[0];
+    m.HI = TKZ_PLANE(7);
+#undef TKZ_PLANE
+    m.CONT = m.HI & ~g;
+    m.hi = (uint32_t)(m.HI | (m.HI >> 32));
+    const uint64_t low3 = a | b | c;                       // bits 0..2 not all clear
+    const uint64_t abc = a & b & c;
+    // letters, either case: 1 <= (x & 31) <= 26 with bit 6 set (27..31 = 11011, 111xx)
+    m.L = g & (low3 | d | e) & ~(e & d & (c | (a & b)));
+    // digits 0x30..0x39: 011 and a low nibble <= 9
+    m.N = f & e & ~g & ~(d & (c | b));
+    // 9..13 = 0001 001 .. 0001 101; CR/LF are the two of them with bit 0 == bit 2 != bit 1
+    const uint64_t ctl = d & ~(e | f | g);
+    const uint64_t pun = f & ~(e | g);                     // 010 ....
+    m.SP = pun & ~(d | low3);
+    m.AP = pun & ~d & abc;
+    m.W = (ctl & low3 & ~(c & b)) | m.SP;
+    m.CR = ctl & ~(a ^ c) & (a ^ b);
+    m.UP = 0; m.SL = 0;
+    if (CASES) { m.UP = m.L & ~f; m.SL = pun & d & abc; }
     m.O = ~(m.L | m.N | m.W);
-    m.hi = hi & 0x80808080u;
     return m;
 }
 
