@@ -4,6 +4,7 @@ specials=...).encode(text, allowed) per document."""
 import random
 
 import numpy as np
+import pytest
 
 import parity
 import regex_crosscheck as RC
@@ -140,3 +141,99 @@ def order_cases():
          ["中中中", "x<|é中\U0001F600|>y中", "<|é中\U0001F600|", "é<|é中\U0001F600|>中\U0001F600", "文中文 中 "]),
         ({" the": 4001, "hello": 4002}, [[" the", "hello"], ["hello"]], ["hello the world the", " thehello", "in the theatre hello hellothe"]),
     ]
+
+
+# ---- special and plain calls side by side: what a call is travels with the call, not with the thread that makes it ----
+
+ROUNDS = 20
+
+
+def side_by_side_inputs():
+    """(a) 8 documents of about 200 bytes, the literal inside each: a plain host call takes the single-launch path.  (b) 160 KiB in 64 documents of 2,560
+    bytes, above the single-launch path's 128 KiB: the batch path; a literal across byte 1024 of the batch (a sub-tile edge), one across byte 4096 (a block
+    edge), one somewhere in every other document.  ASCII throughout: a character is a byte."""
+    rng = random.Random(160)
+    words = ["the", "quick", "brown", "fox", "it's", "2024", "tokens", "=>", "x", "  ", "\n", "don't", "Hello", "12345", "(a+b)"]
+
+    def text(n):
+        s = ""
+        while len(s) < n:
+            s += rng.choice(words) + " "
+        return s[:n]
+    a = [text(90 + 3 * d) + EOT + text(97 - 3 * d) for d in range(8)]
+    b = []
+    for d in range(64):
+        at = {0: 1024 - 6, 1: 4096 - 2560 - 6}.get(d, rng.randrange(2560 - len(EOT)))
+        b.append(text(at) + EOT + text(2560 - len(EOT) - at))
+    assert all(len(d) == 2560 for d in b) and "".join(b)[1018:1031] == EOT and "".join(b)[4090:4103] == EOT
+    return a, b
+
+
+def check_special_beside_plain(lib, O, vocab, ovocab, pattern, upload=None):
+    """Thread A makes special calls (the literal allowed), thread B plain calls of the same buffers, through the host entry and the device entry, ROUNDS times
+    on each input: every result is the oracle's for ITS kind of call.  Then, on one thread: a special call that fails its argument check, a plain call, a plain
+    _begin, a special call, the _end.  tkz_encoder_special_stats counts the successful special calls and nothing else.
+    `upload(np_array) -> (owner, pointer)` as in parity.check_begin_end."""
+    import threading
+    specials = {EOT: 50256}
+    enc, oenc = make_encoders(lib, O, vocab, ovocab, pattern, specials)
+    if upload is None:
+        upload = lambda arr: (arr, arr.ctypes.data)
+    back = lambda o: (o.cpu().numpy() if hasattr(o, "cpu") else o)
+    batches = []
+    for docs in side_by_side_inputs():
+        data, offs = parity.pack([d.encode("utf-8") for d in docs])
+        padded = np.zeros(len(data) + 64, np.uint8); padded[:len(data)] = data
+        batches.append(dict(data=data, offs=offs, n=len(docs), total=len(data), d_bytes=upload(padded), d_offs=upload(offs.astype(np.int64)),
+                            expect={True: oracle_docs(oenc, docs, [EOT]), False: oracle_docs(oenc, docs, [])}))
+        assert batches[-1]["expect"][True] != batches[-1]["expect"][False]
+    assert batches[0]["total"] <= 2048 and batches[1]["total"] == 160 << 10
+
+    def device_outputs(b):
+        return upload(np.zeros(b["total"], np.int32)), upload(np.zeros(b["n"] + 1, np.int64))
+
+    def host_entry(b, special):
+        ids, ooff = enc.encode_batch_special(b["data"], b["offs"], [0]) if special else enc.encode_batch(b["data"], b["offs"])
+        return ids.tolist(), ooff.tolist()
+
+    def device_entry(b, special, out):
+        (ids, p_ids), (ooff, p_ooff) = out
+        args = (b["d_bytes"][1], b["d_offs"][1], b["n"], b["total"])
+        n = enc.encode_batch_special_device(*args, [0], p_ids, b["total"], p_ooff) if special else enc.encode_batch_device(*args, p_ids, b["total"], p_ooff)
+        return back(ids)[:n].tolist(), back(ooff).tolist()
+
+    errors = []
+
+    def work(special):
+        outs = [device_outputs(b) for b in batches]          # (each thread its own output buffers)
+        try:
+            for r in range(ROUNDS):
+                for k, b in enumerate(batches):
+                    for entry, got in (("host", host_entry(b, special)), ("device", device_entry(b, special, outs[k]))):
+                        if got != b["expect"][special]:
+                            errors.append("%s entry, %s call, input %s, round %d: not the oracle's result" % (entry, "special" if special else "plain", "ab"[k], r))
+        except Exception as ex:          # (a thread's exception would otherwise be lost)
+            errors.append(repr(ex))
+    small0 = enc.small_path_calls()[0]
+    threads = [threading.Thread(target=work, args=(s,)) for s in (True, False)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors[:5]
+    n_special = 2 * 2 * ROUNDS                               # thread A: two entries, two inputs
+    assert enc.special_stats()[0] == n_special
+    assert enc.small_path_calls()[0] - small0 == ROUNDS      # the plain host calls of (a), and no special call, took the single-launch path
+
+    # one thread, in order
+    a, b = batches
+    with pytest.raises(N.TkzError) as ei:
+        enc.encode_batch_special(a["data"], a["offs"], [1])
+    assert ei.value.code == N.E_ARG and "allowed[] holds an index that is not a registered special token" in str(ei.value)
+    assert host_entry(b, False) == b["expect"][False]
+    out = device_outputs(b)
+    h = enc.encode_batch_device_begin(b["d_bytes"][1], b["d_offs"][1], b["n"], b["total"], out[0][1], b["total"], out[1][1])
+    assert host_entry(a, True) == a["expect"][True]
+    ntok = enc.encode_batch_device_end(h)
+    assert (back(out[0][0])[:ntok].tolist(), back(out[1][0]).tolist()) == b["expect"][False]
+    assert enc.special_stats()[0] == n_special + 1

@@ -247,3 +247,16 @@ def test_python_mirror(lib, vocab_bytes, oracle_mod):
 def test_reference_unit_tests_through_the_device_path(lib, gpt2_tiktoken_bytes, lib_rs_bytes, oracle_mod, oracle_gpt2):
     import reference_style
     reference_style.run_gpt2_suite(lib, gpt2_tiktoken_bytes, lib_rs_bytes.decode("utf-8"), oracle_mod, oracle_gpt2)
+
+
+@pytest.mark.parametrize("pattern", [N.P1, N.CL100K])
+def test_special_and_plain_calls_side_by_side(lib, vocabs, oracle_mod, pattern):
+    """Special calls on one thread, plain calls of the same buffers on another, and both kinds in turn on one thread around a batch in flight."""
+    import torch
+    dev = torch.device("cuda", 0)
+
+    def upload(a):
+        tns = torch.from_numpy(a).to(dev)
+        return tns, tns.data_ptr()
+    v, ov = vocabs("gpt2")
+    SC.check_special_beside_plain(lib, oracle_mod, v, ov, pattern, upload=upload)

@@ -266,13 +266,58 @@ namespace {
 // waits on one another's events, on a runtime that maps streams onto a handful of hardware queues -- a call that finds the permission taken keeps the serial form
 std::atomic<int> g_fork_in_flight{0};
 
-// A call of one of the special entries: which registered literals it allows.  The entry sets it for the calling thread (every launch sequence of a call is
-// enqueued by the thread that made it); enqueue_attempt is the one place of the batch path that asks.
+// ---- what one call asks for: filled once by its entry point, handed down as it is ----------------------------------------------------------
+
+// A call of one of the special entries: which registered literals it allows (special_call).  It lives in the entry's frame for the length of the call.
 struct SpecialCall { tkz::TkzLitAllowed allowed; };
-thread_local const SpecialCall* g_special = nullptr;
-struct SpecialScope {
-    explicit SpecialScope(const SpecialCall* c) { g_special = c; }
-    ~SpecialScope() { g_special = nullptr; }
+// where the piece-granular entry point wants its arrays (all on the device)
+struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
+// the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
+struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
+
+enum class CallKind {
+    Encode,          // documents -> pre-tokenizer -> ids, a token offset per document
+    OnePiecePerDoc,  // tkz_encode_pieces: no pre-tokenizer, every "document" is one piece
+    BitmapOnly,      // tkz_pretokenize_utf8: the piece-start bitmap and nothing else
+    Pieces           // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
+};
+
+// One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
+// the same one to kCallEnd.
+struct BatchCall {
+    const uint8_t* d_bytes; const int64_t* d_offs; int64_t n_docs, total;
+    int32_t* d_out; int64_t out_cap; int64_t* d_out_offs;
+    hipStream_t stream;
+    CallKind kind = CallKind::Encode;
+    uint64_t* d_bitmap = nullptr;              // BitmapOnly: where the bitmap goes
+    PiecesOut* pieces = nullptr;               // Pieces: where the piece arrays go
+    const SpecialCall* special = nullptr;      // the special entries (an ordinary encode only); null: no literal is looked for
+    int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
+    const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
+    bool pretokenizes() const { return kind != CallKind::OnePiecePerDoc; }
+    bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
+    bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
+    bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
+    const SpecialCall* literals() const { return plain_encode() ? special : nullptr; }
+};
+
+// One batch in the caller's host memory, as the host entries hand it to encode_host.
+struct HostCall {
+    const uint8_t* bytes; const uint16_t* units;       // UTF-8 bytes, or UTF-16 code units (offsets in units then)
+    const int64_t* offs; int64_t n_docs;
+    int32_t* out_ids; int64_t out_cap; int64_t* out_offsets; int64_t* needed;
+    CallKind kind = CallKind::Encode;                  // (never Pieces: that entry stages its own buffers)
+    uint64_t* bitmap = nullptr;                        // BitmapOnly: the caller's words
+    const SpecialCall* special = nullptr;
+    bool u16() const { return units != nullptr; }
+    int64_t total() const { return offs[n_docs]; }     // bytes, or code units
+    bool plain_encode() const { return kind == CallKind::Encode; }
+    // the same call on device buffers
+    BatchCall on_device(const uint8_t* d_bytes, const int64_t* d_offs, int64_t nd, int64_t nbytes, int32_t* d_out, int64_t cap, int64_t* d_out_offs, hipStream_t stream) const {
+        BatchCall c{d_bytes, d_offs, nd, nbytes, d_out, cap, d_out_offs, stream};
+        c.kind = kind; c.special = special;
+        return c;
+    }
 };
 
 // a workspace of the encoder's pool for the duration of one call
@@ -553,8 +598,9 @@ tkz_status drop_promotions(tkz_encoder* e, bool retire) {
 }
 
 // workspace of one batch of `total` bytes / n_docs documents (grow-only buffers: nothing happens once they are large enough)
-tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, bool bitmap_only, bool pieces) {
+tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, CallKind kind) {
     using namespace tkz;
+    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces;
     const int64_t nwords = total / 64 + 1;
     const int64_t ntiles = (total + kSub - 1) / kSub;
     const int64_t nblk = (ntiles + kScanBlock - 1) / kScanBlock;
@@ -602,9 +648,6 @@ tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, bool 
     return TKZ_OK;
 }
 
-// where the piece-granular entry point wants its arrays (all on the device)
-struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
-
 struct SlowCallLog {
     int64_t total; int attempts = 0; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     SlowCallLog(int64_t n) : total(n) { g_alloc_ns = 0; g_alloc_calls = 0; }
@@ -633,8 +676,6 @@ struct HostTrace {
     }
 };
 enum { kCallWhole = 0, kCallBegin = 1, kCallEnd = 2 };
-// the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
-struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 // ---- the stages of one attempt of encode_device ---------------------------------------------------------------------------------------
 
 // a large batch: two more streams, for the two kernels of the long pieces that last as long as their slowest wavefront (launch_encode runs them beside k_merge_short;
@@ -670,13 +711,15 @@ int64_t sizing_sample(int64_t ntiles) {
 
 // The tables as they are NOW, one consistent copy for the whole attempt (a promotion at the end of another call's batch replaces the SHORT / MID images and
 // the promo array together: k_probe and k_place of one attempt must see the same generation) -- and whether this batch counts the memo's hits.
-tkz_status arm_learning(tkz_encoder* e, Workspace* ws, int64_t total, bool first, bool may_learn, hipStream_t stream, TkzTables* T) {
+tkz_status arm_learning(tkz_encoder* e, Workspace* ws, const BatchCall& c, bool first, TkzTables* T) {
     using namespace tkz;
+    const int64_t total = c.total;
+    const hipStream_t stream = c.stream;
     {
         std::lock_guard<std::mutex> lock(e->mu);
         bool others = false;
         for (Workspace* w : e->pool) if (w != ws && w->busy) others = true;
-        const AdaptPolicy::Arm arm = e->policy.may_learn(total, first && !ws->learning, may_learn, e->T.memo_n != 0, e->T.max_rank < (int32_t)kPromoFlag, e->promo_items.size(), others);
+        const AdaptPolicy::Arm arm = e->policy.may_learn(total, first && !ws->learning, c.may_learn(), e->T.memo_n != 0, e->T.max_rank < (int32_t)kPromoFlag, e->promo_items.size(), others);
         if (arm != AdaptPolicy::Arm::No && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
             e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
             // (the memo is cleared under nobody's feet, synchronously, with the encoder's lock held: 16 MB, microseconds, once per drift)
@@ -759,22 +802,25 @@ tkz_status devprof_report() { return TKZ_OK; }
 // One attempt on the stream: the zero region and the text (k_ingest), the document marks and the pre-tokenizer (or, on a re-run, the counters and the
 // sub-tile flags only: it starts behind the pre-tokenizer), the counts of the marks and pieces and their scan, the piece index, then the sizing probe
 // (nsample >= 0) or the whole launch sequence, and the counter block back to the host.
-tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, const TkzTables& T, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs,
-                           int64_t total, int32_t* d_out, int64_t out_cap, int64_t* d_out_offs, bool pretok, uint64_t* d_bitmap_only, PiecesOut* po,
-                           int64_t* d_counts3, const IngestSrc* ingest, bool marks_reused, int64_t nsample, bool* pieces_over) {
+tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, const TkzTables& T, const BatchCall& c, bool marks_reused, int64_t nsample,
+                           bool* pieces_over) {
     using namespace tkz;
     const hipStream_t stream = L.stream;
+    const uint8_t* const d_bytes = c.d_bytes;
+    const int64_t* const d_offs = c.d_offs;
+    const int64_t n_docs = c.n_docs, total = c.total;
+    PiecesOut* const po = c.pieces;
     const int64_t nwords = total / 64 + 1, ntiles = (total + kSub - 1) / kSub;
     int32_t* counters = ws->w_counters.as<int32_t>();
     char* cb = ws->w_counters.as<char>();
     uint64_t* docbits = ws->w_docbits.as<uint64_t>();
     uint64_t* startbits = ws->w_startbits.as<uint64_t>();
-    const SpecialCall* const special = d_bitmap_only || po || !pretok ? nullptr : g_special;
+    const SpecialCall* const special = c.literals();
     if (marks_reused) {      // (the counters and the sub-tile flags only)
         HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, 256, stream));
-        if (!d_bitmap_only) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
+        if (!c.bitmap_only()) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
     } else {
-        if (ingest) launch_ingest(L, ingest->h_bytes, total, const_cast<uint8_t*>(d_bytes), ingest->h_offs, n_docs + 1, const_cast<int64_t*>(d_offs), ws->w_zero.p, (int64_t)ws->zero_bytes);
+        if (c.ingest) launch_ingest(L, c.ingest->h_bytes, total, const_cast<uint8_t*>(d_bytes), c.ingest->h_offs, n_docs + 1, const_cast<int64_t*>(d_offs), ws->w_zero.p, (int64_t)ws->zero_bytes);
         // counters, document-start bits, sub-tile flags.  (A chunk of a host batch clears them with a kernel of its own, not a fill command: the runtime's fill is
         //  a blit kernel that queued behind its D2H blit of the chunk before -- the 16 MB call's second chunk started when the first one's download ended.)
         else if (ws->zero_bytes <= (size_t(8) << 20)) launch_ingest(L, nullptr, 0, nullptr, nullptr, 0, nullptr, ws->w_zero.p, (int64_t)ws->zero_bytes);
@@ -804,7 +850,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                 n_iso = ws->n_seg;
             }
         }
-        if (!pretok) {
+        if (!c.pretokenizes()) {
             HIP_TRY(hipMemcpyAsync(startbits, docbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
         } else if (e->pretok_seq) {
             HIP_TRY(hipMemcpyAsync(startbits, isobits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
@@ -814,12 +860,12 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             launch_pretok_rows(L, e->pattern, d_bytes, iso_offs, n_iso, total, isobits, startbits, nwords, T.bmp_class, counters,
                                ws->w_xq.as<int64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, xcount)));
         }
-        if (pretok && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, isobits, startbits);
+        if (c.pretokenizes() && e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) launch_case_equiv_fix(L, d_bytes, total, isobits, startbits);
         // (every taken literal ONE piece: the starts the pre-tokenizer found inside it go)
         if (special) launch_lit_fix(L, startbits, isobits, ws->w_specbits.as<uint64_t>(), ws->w_endbits.as<uint64_t>(), nwords);
     }
-    if (d_bitmap_only) {
-        HIP_TRY(hipMemcpyAsync(d_bitmap_only, startbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
+    if (c.bitmap_only()) {
+        HIP_TRY(hipMemcpyAsync(c.d_bitmap, startbits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, stream));
     } else {
         EncodeParams P = bind_params(ws, d_bytes, d_offs, n_docs, total);
         // (a batch of at most 16 MB waits for the slowest wavefront of every kernel, not for throughput: TKZ_OPT_LATENCY_BYTES, launch_encode.  Handing its
@@ -875,13 +921,13 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             launch_encode(L, T, P, ntiles);
             if (P.stats) launch_miss_stats(L, P, ntiles);
             launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), P.tile_count, ws->w_tbase.as<int64_t>(), grand, 1, nullptr, nullptr, nullptr, 1, K_SCAN);
-            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, d_out, out_cap);
+            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.d_out, c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
-                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
+                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
-                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, d_out_offs,
-                               n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3);
+                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
+                               n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
         }
     }
     HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, sizeof(CounterBlock), hipMemcpyDeviceToHost, stream));
@@ -890,9 +936,11 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
 
 // The counter block of an attempt that has run: a failure status for input that is wrong or a buffer that cannot grow; TKZ_OK with *retry when a buffer
 // was grown (or, after the sizing attempt, sized) and the batch runs again; TKZ_OK alone when the batch is done.
-tkz_status check_counters(tkz_encoder* e, Workspace* ws, hipStream_t stream, int64_t total, int attempt, int64_t nsample, bool bitmap_only, bool* retry) {
+tkz_status check_counters(tkz_encoder* e, Workspace* ws, const BatchCall& call, int attempt, int64_t nsample, bool* retry) {
     using namespace tkz;
     const CounterBlock& c = *ws->h_counters;
+    const int64_t total = call.total;
+    const bool bitmap_only = call.bitmap_only();
     const int64_t ntiles = (total + kSub - 1) / kSub;
     int64_t* acc = &ws->bytes_allocated;
     const int32_t err = c.err;
@@ -945,7 +993,7 @@ tkz_status check_counters(tkz_encoder* e, Workspace* ws, hipStream_t stream, int
         return TKZ_OK;
     }
     // the statistics block as it was before this attempt (enqueue_attempt): the batch is counted once
-    if (e->piece_stats && e->t_stats.p && !bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, stream));
+    if (e->piece_stats && e->t_stats.p && !bitmap_only) HIP_TRY(hipMemcpyAsync(e->t_stats.p, e->t_stats.as<char>() + 64, 64, hipMemcpyDeviceToDevice, call.stream));
     *retry = true;
     return TKZ_OK;
 }
@@ -1018,23 +1066,22 @@ void after_batch(tkz_encoder* e, Workspace* ws, int64_t total) {
     if (!started) { const std::string keep_msg = g_err; promote_or_drop(e, promote); g_err = keep_msg; }
 }
 
-// The batch on the device; when pretok == false every "document" is taken as one piece.
+// The batch on the device.
 // phase: kCallWhole -- enqueue, wait, evaluate (and again if a buffer had to grow); kCallBegin -- enqueue the first attempt and
 // return; kCallEnd -- wait for that attempt, evaluate, and carry on as kCallWhole does (tkz_encode_batch_device_begin / _end)
-tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs, int64_t total,
-                         int32_t* d_out, int64_t out_cap, int64_t* d_out_offs, hipStream_t stream, bool pretok,
-                         uint64_t* d_bitmap_only, int64_t* total_tokens, PiecesOut* po = nullptr, int phase = kCallWhole, int64_t* d_counts3 = nullptr,
-                         const IngestSrc* ingest = nullptr) {
+tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int phase, int64_t* total_tokens) {
     using namespace tkz;
-    if (n_docs < 0 || total < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    const int64_t n_docs = c.n_docs, total = c.total;
+    const hipStream_t stream = c.stream;
+    if (n_docs < 0 || total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
     if (total_tokens) *total_tokens = 0;
     if (n_docs == 0 && total != 0) return fail(TKZ_E_ARG, "bytes without documents");
     if (total == 0) {
         if (phase != kCallEnd) {                                  // (kCallEnd: enqueued when it began)
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
-            { Launch L0{stream, nullptr, ws}; launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), d_counts3); }
-            if (d_out_offs) HIP_TRY(hipMemsetAsync(d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
-            if (d_bitmap_only) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(d_bitmap_only, &one, 8, hipMemcpyHostToDevice, stream)); }
+            { Launch L0{stream, nullptr, ws}; launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3); }
+            if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
+            if (c.d_bitmap) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(c.d_bitmap, &one, 8, hipMemcpyHostToDevice, stream)); }
             if (phase == kCallBegin) return TKZ_OK;               // (_begin returns without waiting)
         }
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1042,7 +1089,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
     }
     const int64_t ntiles = (total + kSub - 1) / kSub;       // sub-tiles: one wavefront each
     SlowCallLog slow_log(total);
-    TKZ_TRY(prepare_workspace(ws, total, n_docs, d_bitmap_only != nullptr, po != nullptr));
+    TKZ_TRY(prepare_workspace(ws, total, n_docs, c.kind));
     if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
 
     // a learning batch that ends any other way than with its promotion gives the encoder's one learning slot back
@@ -1056,33 +1103,32 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const uint8_t* d_bytes, 
     for (int attempt = 0; attempt < 5; ++attempt) {
         slow_log.attempts = attempt + 1;
         bool pieces_over = false;
-        const int64_t nsample = attempt == 0 && phase == kCallWhole && !ws->sized && pretok && !d_bitmap_only && !po ? sizing_sample(ntiles) : -1;
+        const int64_t nsample = attempt == 0 && phase == kCallWhole && !ws->sized && c.plain_encode() ? sizing_sample(ntiles) : -1;
         const bool marks_reused = marks_ready;
         Launch L{stream, e->profiling ? prof_hook : nullptr, ws};
         side_streams(e, ws, total, &L);
         if (!(phase == kCallEnd && attempt == 0)) {              // (kCallEnd: the first attempt is in flight already)
             TkzTables T;
-            TKZ_TRY(arm_learning(e, ws, total, attempt == 0, pretok && !d_bitmap_only, stream, &T));
-            TKZ_TRY(enqueue_attempt(e, ws, L, T, d_bytes, d_offs, n_docs, total, d_out, out_cap, d_out_offs, pretok, d_bitmap_only, po, d_counts3, ingest,
-                                    marks_reused, nsample, &pieces_over));
+            TKZ_TRY(arm_learning(e, ws, c, attempt == 0, &T));
+            TKZ_TRY(enqueue_attempt(e, ws, L, T, c, marks_reused, nsample, &pieces_over));
         }
         if (phase == kCallBegin) { learn_guard.keep = true; return TKZ_OK; }
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipGetLastError());
         if (e->profiling) prof_collect(ws);
-        if (!d_bitmap_only) TKZ_TRY(devprof_report());
+        if (!c.bitmap_only()) TKZ_TRY(devprof_report());
         if (!marks_reused) { e->last_xcount = (int64_t)ws->h_counters->xcount; e->last_xcount2 = (int64_t)ws->h_counters->xcount2; ws->spec_taken = (int64_t)ws->h_counters->n_literals; }
         bool retry = false;
-        TKZ_TRY(check_counters(e, ws, stream, total, attempt, nsample, d_bitmap_only != nullptr, &retry));
+        TKZ_TRY(check_counters(e, ws, c, attempt, nsample, &retry));
         marks_ready = true;
         if (retry) continue;
-        if (d_bitmap_only) return TKZ_OK;
+        if (c.bitmap_only()) return TKZ_OK;
         settle_workspace(ws, ntiles);
-        if (pretok) after_batch(e, ws, total);
-        if (g_special && !po) e->spec_literals += ws->spec_taken;
+        if (c.pretokenizes()) after_batch(e, ws, total);
+        if (c.literals()) e->spec_literals += ws->spec_taken;
         if (total_tokens) *total_tokens = ws->h_counters->grand;
         if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
-        if (ws->h_counters->grand > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+        if (ws->h_counters->grand > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
         return TKZ_OK;
     }
     return fail(TKZ_E_DEVICE, "unreachable");
@@ -1105,26 +1151,26 @@ bool small_eligible(const tkz_encoder* e, const int64_t* offs, int64_t n_docs, i
         for (int64_t d = 0; d < n_docs; ++d) { const int64_t len = offs[d + 1] - offs[d]; if (len < 0 || len > tkz::kSmallMaxDoc) return false; }
     return true;
 }
-tkz_status encode_small(tkz_encoder* e, Workspace* ws, const uint8_t* bytes, const int64_t* offs, int64_t n_docs, int64_t total,
-                        int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed, bool* handled) {
+tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* handled) {
     using namespace tkz;
+    const int64_t n_docs = c.n_docs, total = c.total();
     *handled = false;
-    { const tkz_status ps = prepare_workspace(ws, total, n_docs, false, false); if (ps != TKZ_OK) return ps; }
+    { const tkz_status ps = prepare_workspace(ws, total, n_docs, CallKind::Encode); if (ps != TKZ_OK) return ps; }
     int64_t* acc = &ws->bytes_allocated;
     HIP_TRY(ws->s_bytes[0].ensure((size_t)kSmallMaxBytes + 64, acc));
     HIP_TRY(ws->s_offs[0].ensure((size_t)(kSmallMaxDocs + 1) * 8, acc));
     if (!ws->h_small) HIP_TRY(hipHostMalloc((void**)&ws->h_small, kSmallBlock, 0));
     if (!ws->st_small) HIP_TRY(hipStreamCreateWithFlags(&ws->st_small, hipStreamNonBlocking));
     uint8_t* H = ws->h_small;
-    memcpy(H + kSmallOffBytes, bytes, (size_t)total);
-    memcpy(H + kSmallOffOffs, offs, (size_t)(n_docs + 1) * 8);
+    memcpy(H + kSmallOffBytes, c.bytes, (size_t)total);
+    memcpy(H + kSmallOffOffs, c.offs, (size_t)(n_docs + 1) * 8);
     int64_t* h_res = reinterpret_cast<int64_t*>(H + kSmallOffRes);
     h_res[0] = -1; h_res[1] = 0; h_res[2] = 0;
     EncodeParams P = bind_params(ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total);
     P.lane_piece = kSmallLanePiece;
     SmallArgs A{};
     A.h_bytes = H + kSmallOffBytes; A.h_offs = reinterpret_cast<const int64_t*>(H + kSmallOffOffs);
-    A.out = reinterpret_cast<int32_t*>(H + kSmallOffIds); A.out_cap = std::min<int64_t>(out_cap, kSmallMaxBytes); A.out_offs = reinterpret_cast<int64_t*>(H + kSmallOffOut);
+    A.out = reinterpret_cast<int32_t*>(H + kSmallOffIds); A.out_cap = std::min<int64_t>(c.out_cap, kSmallMaxBytes); A.out_offs = reinterpret_cast<int64_t*>(H + kSmallOffOut);
     A.h_result = h_res;
     A.docbits = ws->w_docbits.as<uint64_t>(); A.startbits = ws->w_startbits.as<uint64_t>();
     A.pcount = ws->w_pcount.as<int32_t>(); A.pbase = ws->w_pbase.as<int64_t>(); A.docord_base = ws->w_dbase.as<int64_t>(); A.tile_base = ws->w_tbase.as<int64_t>();
@@ -1141,11 +1187,11 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const uint8_t* bytes, con
     { std::lock_guard<std::mutex> lock(e->mu); memcpy(ws->small_clocks, h_res + 4, sizeof ws->small_clocks); }
     if (h_res[0] != 0) { ws->small_fallbacks.fetch_add(1, std::memory_order_relaxed); return TKZ_OK; }          // (handled stays false)
     const int64_t tokens = h_res[2];
-    if (needed) *needed = tokens;
+    if (c.needed) *c.needed = tokens;
     *handled = true;
-    if (tokens > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
-    if (tokens) memcpy(out_ids, H + kSmallOffIds, (size_t)tokens * 4);
-    memcpy(out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
+    if (tokens > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+    if (tokens) memcpy(c.out_ids, H + kSmallOffIds, (size_t)tokens * 4);
+    memcpy(c.out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
     return TKZ_OK;
 }
 
@@ -1203,12 +1249,13 @@ struct HostPlan {
     int nout = 1;                                      // output staging sets in use
     int64_t max_units = 0, max_docs = 0;               // the largest chunk
 };
-HostPlan plan_host_batch(const void* in, bool u16, const int64_t* offs, int64_t n_docs, const int32_t* out_ids, int64_t out_cap, const int64_t* out_offsets,
-                         bool pretok, const uint64_t* bitmap) {
+HostPlan plan_host_batch(const HostCall& c) {
     HostPlan p;
-    const int64_t total = offs[n_docs];
-    p.pin_in = pinned_host(in, &p.dv_in) && pinned_host(offs, &p.dv_offs);
-    p.pin_out = !bitmap && pinned_host(out_offsets, &p.dv_ooffs) && (out_cap == 0 || pinned_host(out_ids, &p.dv_ids));
+    const bool u16 = c.u16();
+    const int64_t* const offs = c.offs;
+    const int64_t n_docs = c.n_docs, total = c.total();
+    p.pin_in = pinned_host(u16 ? (const void*)c.units : (const void*)c.bytes, &p.dv_in) && pinned_host(offs, &p.dv_offs);
+    p.pin_out = !c.bitmap && pinned_host(c.out_offsets, &p.dv_ooffs) && (c.out_cap == 0 || pinned_host(c.out_ids, &p.dv_ids));
     // (16 MB of upload a chunk.  Until round 6 a chunk's kernels were launched when the chunk before had drained, every chunk paid its launch sequence's
     //  floor of ~0.4 ms and 32 MB chunks were the optimum; with two launch sequences enqueued ahead and the downloads on a copy engine of their own the
     //  floor is hidden: profiles/r06/host_batches_ab.txt.  Pageable buffers keep 32 MB: the runtime stages their copies itself, synchronously, a cost per copy)
@@ -1219,7 +1266,7 @@ HostPlan plan_host_batch(const void* in, bool u16, const int64_t* offs, int64_t 
     p.up_bytes = total * p.unit;
     // (from 12 MB up a batch is two chunks at least, of 8 MB or more: the second chunk's upload runs beside the first one's kernels)
     p.chunk_bytes = std::min(kChunkBytes, std::max(std::min(kChunkBytes, kHostChunkMin), p.up_bytes / 2));
-    p.nchunks = (bitmap || !pretok || 2 * p.up_bytes < 3 * p.chunk_bytes) ? 1 : std::min<int64_t>(1024, std::max<int64_t>(2, (p.up_bytes + p.chunk_bytes / 2) / p.chunk_bytes));
+    p.nchunks = (!c.plain_encode() || 2 * p.up_bytes < 3 * p.chunk_bytes) ? 1 : std::min<int64_t>(1024, std::max<int64_t>(2, (p.up_bytes + p.chunk_bytes / 2) / p.chunk_bytes));
     // chunk boundaries on documents.  Offsets that are not monotone cannot be cut: the whole batch then goes as one chunk and the device reports them (k_docmark)
     std::vector<int64_t>& cut = p.cut;
     cut.assign((size_t)p.nchunks + 1, 0);
@@ -1230,7 +1277,7 @@ HostPlan plan_host_batch(const void* in, bool u16, const int64_t* offs, int64_t 
         if (cut[(size_t)k] < cut[(size_t)k - 1] || offs[cut[(size_t)k]] < offs[cut[(size_t)k - 1]]) { p.nchunks = 1; break; }
     }
     if (p.nchunks == 1) { cut.assign(2, 0); cut[1] = n_docs; }
-    p.blocking = !u16 && p.nchunks == 1 && !(p.pin_in && p.pin_out && pretok && !bitmap && total > 0);
+    p.blocking = !u16 && p.nchunks == 1 && !(p.pin_in && p.pin_out && c.plain_encode() && total > 0);
     // the kernels write the caller's page-locked ids and offsets themselves -- up to 8 MB of text: beyond that a DMA download beats k_place's stores over PCIe
     // (measured, round 5: 16 MB 1.08 ms direct, 1.00 ms staged)
     p.direct_out = p.nchunks == 1 && p.pin_out && p.up_bytes <= (int64_t(8) << 20) * p.unit;
@@ -1245,32 +1292,33 @@ HostPlan plan_host_batch(const void* in, bool u16, const int64_t* offs, int64_t 
 }
 
 // one chunk, ordinary (pageable) buffers: blocking copies either side of the launch sequence
-tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const uint8_t* bytes, const int64_t* offs, int64_t n_docs, int32_t* out_ids, int64_t out_cap,
-                                int64_t* out_offsets, int64_t* needed, bool pretok, uint64_t* bitmap) {
+tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const HostCall& c) {
     int64_t* acc = &ws->bytes_allocated;
-    const int64_t total = offs[n_docs];
+    uint64_t* const bitmap = c.bitmap;
+    const int64_t n_docs = c.n_docs, total = c.total();
     HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
     HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    const int64_t cap = bitmap ? 0 : std::min<int64_t>(out_cap, total);   // tokens <= bytes: more capacity is never used
+    const int64_t cap = bitmap ? 0 : std::min<int64_t>(c.out_cap, total);   // tokens <= bytes: more capacity is never used
     if (!bitmap) {
         HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
         HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
     } else {
         HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, acc));
     }
-    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->s_offs[0].p, offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, c.bytes, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ws->s_offs[0].p, c.offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
     int64_t tokens = 0;
-    const tkz_status st = encode_device(e, ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap,
-                                        ws->s_outoffs[0].as<int64_t>(), nullptr, pretok, bitmap ? ws->s_out[0].as<uint64_t>() : nullptr, &tokens);
-    if (needed) *needed = tokens;
+    BatchCall dc = c.on_device(ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr);
+    if (bitmap) dc.d_bitmap = ws->s_out[0].as<uint64_t>();
+    const tkz_status st = encode_device(e, ws, dc, kCallWhole, &tokens);
+    if (c.needed) *c.needed = tokens;
     if (st != TKZ_OK) return st;
     if (bitmap) {
         HIP_TRY(hipMemcpy(bitmap, ws->s_out[0].p, (size_t)(total / 64 + 1) * 8, hipMemcpyDeviceToHost));
         return TKZ_OK;
     }
-    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (tokens) HIP_TRY(hipMemcpy(c.out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c.out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }
 
@@ -1287,15 +1335,16 @@ tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const uint8_t* by
 // alternate between two leased workspaces, two input staging sets and -- since the download of chunk k is only ISSUED when k has ended -- three output sets.
 struct HostPipeline {
     // the call
-    tkz_encoder* e; Workspace* ws; const HostPlan& p;
-    const uint8_t* bytes; const uint16_t* units; const int64_t* offs; int64_t n_docs; int32_t* out_ids; int64_t out_cap; int64_t* out_offsets; int64_t* needed;
-    const bool u16 = units != nullptr;
+    tkz_encoder* e; Workspace* ws; const HostPlan& p; const HostCall& c;
+    const bool u16 = c.u16();
+    const int64_t* const offs = c.offs;
     int64_t* const acc = &ws->bytes_allocated;
     // its state
     std::unique_ptr<Lease> lease_b;
     Workspace* W[2] = {ws, ws};
-    // what encode_device was given for the chunk in flight on W[q] (kCallEnd is handed the same)
-    struct InFlight { const uint8_t* cb; const int64_t* co; int64_t cbytes, nd, cap; int32_t* dst_ids; int64_t* dst_offs; } fl[2] = {};
+    // what encode_device was given for the chunk in flight on W[q]: kCallEnd is handed the same.  (`ingest` stays set there.  It is read when the marks are not
+    // reused only, and a chunk that is ended has its first attempt -- the one that makes the marks -- behind it.)
+    BatchCall fl[2] = {};
     const IngestSrc ingest_src{static_cast<const uint8_t*>(p.dv_in), static_cast<const int64_t*>(p.dv_offs)};
     std::vector<int64_t> tok_base = std::vector<int64_t>((size_t)p.nchunks + 1, 0);
     bool over = false;                                       // out_cap exceeded: the remaining chunks are only counted
@@ -1325,7 +1374,7 @@ struct HostPipeline {
             }
         }
         if (!p.direct_out) for (int o = 0; o < p.nout; ++o) {
-            HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
+            HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(c.out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
             HIP_TRY(ws->s_outoffs[o].ensure((size_t)(max_docs + 1) * 8, acc));
         }
         // downloads by copy engine: page-locked results whose device-side address is their host address (hipHostMalloc, tkz_host_alloc, torch's pinned tensors --
@@ -1335,7 +1384,7 @@ struct HostPipeline {
             for (int o = 0; o < 3 && ok; ++o) ok = sdma_signal_create(&ws->sig_out[o]) && sdma_signal_create(&ws->sig_outoffs[o]);
             ws->sdma_state = ok ? 1 : -1;
         }
-        sdma_out = ws->sdma_state == 1 && !p.direct_out && p.pin_out && p.dv_ooffs == (void*)out_offsets && (out_cap == 0 || p.dv_ids == (void*)out_ids);
+        sdma_out = ws->sdma_state == 1 && !p.direct_out && p.pin_out && p.dv_ooffs == (void*)c.out_offsets && (c.out_cap == 0 || p.dv_ids == (void*)c.out_ids);
         return TKZ_OK;
     }
     // the input of chunk k, on its way to the device (stream st_in); for UTF-16 also its document marks, the UTF-8 length of every unit and their scan
@@ -1347,7 +1396,7 @@ struct HostPipeline {
         Launch L{ws->st_in, nullptr, ws};
         if (u16) {
             Workspace::U16Stage& U = ws->u16[q];
-            if (nu) HIP_TRY(hipMemcpyAsync(U.units.p, units + u0, (size_t)nu * 2, hipMemcpyHostToDevice, ws->st_in));
+            if (nu) HIP_TRY(hipMemcpyAsync(U.units.p, c.units + u0, (size_t)nu * 2, hipMemcpyHostToDevice, ws->st_in));
             HIP_TRY(hipMemcpyAsync(U.offs.p, offs + d0, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, ws->st_in));
             if (u0) launch_rebase(L, U.offs.as<int64_t>(), nd + 1, u0);
             const int64_t nw = nu / 64 + 1, nt = u16_tiles(nu);
@@ -1358,7 +1407,7 @@ struct HostPipeline {
             launch_scan(L, U.tsum.as<int32_t>(), nt, U.bsum.as<int64_t>(), U.tbase.as<int64_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), -1);
             HIP_TRY(hipMemcpyAsync(U.h, U.counters.p, 16, hipMemcpyDeviceToHost, ws->st_in));
         } else {
-            if (nu) HIP_TRY(hipMemcpyAsync(ws->s_bytes[q].p, bytes + u0, (size_t)nu, hipMemcpyHostToDevice, ws->st_in));
+            if (nu) HIP_TRY(hipMemcpyAsync(ws->s_bytes[q].p, c.bytes + u0, (size_t)nu, hipMemcpyHostToDevice, ws->st_in));
             HIP_TRY(hipMemcpyAsync(ws->s_offs[q].p, offs + d0, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, ws->st_in));
             if (u0) launch_rebase(L, ws->s_offs[q].as<int64_t>(), nd + 1, u0);
         }
@@ -1378,38 +1427,35 @@ struct HostPipeline {
         const int q = (int)(k & 1), o = (int)(k % p.nout);
         Workspace* w = W[q];
         const int64_t d0 = cut[(size_t)k], d1 = cut[(size_t)k + 1], nu = offs[d1] - offs[d0], nd = d1 - d0;
-        InFlight& F = fl[q];
-        F.nd = nd;
+        const uint8_t* cb; const int64_t* co; int64_t cbytes;      // the chunk as UTF-8 on the device
         if (u16) {
             // the UTF-8 size of the chunk is known once its length pass is through (the host needs it: the launch shapes of the encode path)
             Workspace::U16Stage& U = ws->u16[q];
             PIPELINE_TRY(hipEventSynchronize(ws->ev_in[q]));
             if (U.h->err & kErrOffsets) return note(fail(TKZ_E_ARG, kMsgUnitOffsets));
-            F.cbytes = U.h->grand;
-            PIPELINE_TRY(ws->u_bytes[q].ensure((size_t)F.cbytes + 64, acc));
+            cbytes = U.h->grand;
+            PIPELINE_TRY(ws->u_bytes[q].ensure((size_t)cbytes + 64, acc));
             Launch L{w->st_compute, nullptr, w};
             launch_u16_write(L, U.units.as<uint16_t>(), nu, U.docbits.as<uint64_t>(), u16_tiles(nu), U.tbase.as<int64_t>(), ws->u_bytes[q].as<uint8_t>(),
                              U.offs.as<int64_t>(), nd, U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>());
-            F.cb = ws->u_bytes[q].as<uint8_t>(); F.co = U.boffs.as<int64_t>();
+            cb = ws->u_bytes[q].as<uint8_t>(); co = U.boffs.as<int64_t>();
         } else {
             if (!p.ingest_in) PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_in[q], 0));
-            F.cb = ws->s_bytes[q].as<uint8_t>(); F.co = ws->s_offs[q].as<int64_t>(); F.cbytes = nu;
+            cb = ws->s_bytes[q].as<uint8_t>(); co = ws->s_offs[q].as<int64_t>(); cbytes = nu;
         }
         // the download of chunk k - nout has left this chunk's output set
         if (!wait_engine(o)) return note(fail(TKZ_E_DEVICE, kMsgEngineDownload));
         if (ev_pending[o]) { ev_pending[o] = false; PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_out[o], 0)); }
-        F.dst_ids = p.direct_out ? static_cast<int32_t*>(p.dv_ids) : ws->s_out[o].as<int32_t>();
-        F.dst_offs = p.direct_out ? static_cast<int64_t*>(p.dv_ooffs) : ws->s_outoffs[o].as<int64_t>();
+        int32_t* const dst_ids = p.direct_out ? static_cast<int32_t*>(p.dv_ids) : ws->s_out[o].as<int32_t>();
+        int64_t* const dst_offs = p.direct_out ? static_cast<int64_t*>(p.dv_ooffs) : ws->s_outoffs[o].as<int64_t>();
         // (how much of out_cap the chunks before leave is not known yet when a chunk is begun: the staging set holds a chunk's ids whatever their number, and the
         //  sum is checked when the chunk ends)
-        F.cap = over ? 0 : std::min<int64_t>(out_cap, F.cbytes);
-        return encode_device(e, w, F.cb, F.co, F.nd, F.cbytes, F.dst_ids, F.cap, F.dst_offs, w->st_compute, true, nullptr, tokens, nullptr, phase, nullptr,
-                             p.ingest_in ? &ingest_src : nullptr);
+        fl[q] = c.on_device(cb, co, nd, cbytes, dst_ids, over ? 0 : std::min<int64_t>(c.out_cap, cbytes), dst_offs, w->st_compute);
+        if (p.ingest_in) fl[q].ingest = &ingest_src;
+        return encode_device(e, w, fl[q], phase, tokens);
     }
     tkz_status end_chunk(int64_t k, int64_t* tokens) {          // (returns when the chunk's stream has drained)
-        const InFlight& F = fl[k & 1];
-        Workspace* w = W[k & 1];
-        return encode_device(e, w, F.cb, F.co, F.nd, F.cbytes, F.dst_ids, F.cap, F.dst_offs, w->st_compute, true, nullptr, tokens, nullptr, kCallEnd, nullptr, nullptr);
+        return encode_device(e, W[k & 1], fl[k & 1], kCallEnd, tokens);
     }
     // (an engine that refuses a copy is not asked again: that copy and the rest of the call go through the runtime)
     bool by_engine(void* dst, const void* src, size_t nb, tkz::SdmaSignal sg, bool* pending) {
@@ -1429,11 +1475,11 @@ struct HostPipeline {
         const int64_t d0 = p.cut[(size_t)k], nd = p.cut[(size_t)k + 1] - d0;
         bool ids_sent = tokens == 0, offs_sent = false;
         const size_t nb_ids = (size_t)tokens * 4, nb_offs = (size_t)(nd + 1) * 8;
-        if (tokens) ids_sent = by_engine(out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
-        offs_sent = by_engine(out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
+        if (tokens) ids_sent = by_engine(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
+        offs_sent = by_engine(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
         if (!ids_sent || !offs_sent) {
-            if (!ids_sent) PIPELINE_TRY(hipMemcpyAsync(out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
-            if (!offs_sent) PIPELINE_TRY(hipMemcpyAsync(out_offsets + d0, ws->s_outoffs[o].p, nb_offs, hipMemcpyDeviceToHost, ws->st_out));
+            if (!ids_sent) PIPELINE_TRY(hipMemcpyAsync(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
+            if (!offs_sent) PIPELINE_TRY(hipMemcpyAsync(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, hipMemcpyDeviceToHost, ws->st_out));
             PIPELINE_TRY(hipEventRecord(ws->ev_out[o], ws->st_out));
             ev_pending[o] = true;
         }
@@ -1441,7 +1487,7 @@ struct HostPipeline {
     }
     bool finish(int64_t k, tkz_status cs, int64_t tokens) {      // chunk k has ended with status cs: its place in the output, its download; false: stop
         tok_base[(size_t)k + 1] = tok_base[(size_t)k] + tokens;
-        if (cs == TKZ_E_CAPACITY || (cs == TKZ_OK && tok_base[(size_t)k + 1] > out_cap)) { over = true; return true; }
+        if (cs == TKZ_E_CAPACITY || (cs == TKZ_OK && tok_base[(size_t)k + 1] > c.out_cap)) { over = true; return true; }
         if (cs != TKZ_OK) { note(cs); return false; }
         if (!over && !p.direct_out && download(k, tokens) != TKZ_OK) return false;
         return true;
@@ -1492,49 +1538,76 @@ struct HostPipeline {
         drain();
         if (nchunks > 1) { trace.stamp("downloads arrived", nchunks); trace.print(nchunks); }
         if (first_err != TKZ_OK) return fail(first_err, first_msg);
-        if (needed) *needed = tok_base[(size_t)nchunks];
+        if (c.needed) *c.needed = tok_base[(size_t)nchunks];
         if (over) return fail(TKZ_E_CAPACITY, "output capacity too small");
         // the offsets came back relative to their chunk: add the chunk's token base (chunk 0 needs nothing; the shared boundary entry
         // of two chunks was written by the later one as 0 and gets that chunk's base, which is what the earlier chunk's last entry was)
         for (int64_t k = 1; k < nchunks; ++k) {
             const int64_t tb = tok_base[(size_t)k];
-            for (int64_t d = p.cut[(size_t)k]; d < p.cut[(size_t)k + 1]; ++d) out_offsets[d] += tb;
+            for (int64_t d = p.cut[(size_t)k]; d < p.cut[(size_t)k + 1]; ++d) c.out_offsets[d] += tb;
         }
-        out_offsets[n_docs] = tok_base[(size_t)nchunks];
+        c.out_offsets[c.n_docs] = tok_base[(size_t)nchunks];
         return TKZ_OK;
     }
 };
 #undef PIPELINE_TRY
 
 // validate -> the single-launch path -> plan -> one blocking chunk, or the pipeline
-tkz_status encode_host(tkz_encoder* e, const uint8_t* bytes, const uint16_t* units, const int64_t* offs, int64_t n_docs, int32_t* out_ids,
-                       int64_t out_cap, int64_t* out_offsets, int64_t* needed, bool pretok, uint64_t* bitmap) {
+tkz_status encode_host(tkz_encoder* e, const HostCall& c) {
     DeviceScope scope;
     tkz_status st = check_encoder(e, scope);
     if (st != TKZ_OK) return st;
-    const bool u16 = units != nullptr;
-    if (n_docs < 0 || !offs || (n_docs > 0 && !bytes && !units && offs[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
+    const bool u16 = c.u16();
+    const int64_t* const offs = c.offs;
+    const int64_t n_docs = c.n_docs;
+    if (n_docs < 0 || !offs || (n_docs > 0 && !c.bytes && !c.units && offs[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
     if (offs[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = offs[n_docs];                      // bytes, or code units
+    const int64_t total = c.total();
     if (total < 0) return fail(TKZ_E_ARG, u16 ? "negative unit count" : "negative byte count");
-    if (needed) *needed = 0;
+    if (c.needed) *c.needed = 0;
     if (u16 && total == 0) {
-        for (int64_t d = 0; d <= n_docs; ++d) { if (offs[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); out_offsets[d] = 0; }
+        for (int64_t d = 0; d <= n_docs; ++d) { if (offs[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); c.out_offsets[d] = 0; }
         return TKZ_OK;
     }
     Lease lease(e);
     Workspace* ws = lease.ws;
     // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
-    if (!u16 && pretok && !bitmap && !g_special && small_eligible(e, offs, n_docs, total)) {
+    if (!u16 && c.plain_encode() && !c.special && small_eligible(e, offs, n_docs, total)) {
         bool handled = false;
-        st = encode_small(e, ws, bytes, offs, n_docs, total, out_ids, out_cap, out_offsets, needed, &handled);
+        st = encode_small(e, ws, c, &handled);
         if (st != TKZ_OK || handled) return st;
     }
-    const HostPlan plan = plan_host_batch(u16 ? (const void*)units : (const void*)bytes, u16, offs, n_docs, out_ids, out_cap, out_offsets, pretok, bitmap);
-    if (plan.blocking) return encode_host_blocking(e, ws, bytes, offs, n_docs, out_ids, out_cap, out_offsets, needed, pretok, bitmap);
-    HostPipeline pipe{e, ws, plan, bytes, units, offs, n_docs, out_ids, out_cap, out_offsets, needed};
+    const HostPlan plan = plan_host_batch(c);
+    if (plan.blocking) return encode_host_blocking(e, ws, c);
+    HostPipeline pipe{e, ws, plan, c};
     TKZ_TRY(pipe.reserve_staging());
     return pipe.run();
+}
+
+// tkz_encode_batch_utf8 and its special form; tkz_encode_pieces
+tkz_status encode_host_batch(tkz_encoder* e, const HostCall& c) {
+    if (!c.out_offsets || (c.out_cap > 0 && !c.out_ids)) return fail(TKZ_E_ARG, "null output buffer");
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK && c.special) ++e->spec_batches;
+    return st;
+}
+
+// what the device entries check before they take a workspace
+tkz_status check_device_call(tkz_encoder* e, DeviceScope& scope, const BatchCall& c) {
+    TKZ_TRY(check_encoder(e, scope));
+    if (!c.d_offs || !c.d_out_offs || (c.total > 0 && (!c.d_bytes || !c.d_out))) return fail(TKZ_E_ARG, "null device buffer");
+    if (reinterpret_cast<uintptr_t>(c.d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    return TKZ_OK;
+}
+
+// tkz_encode_batch_device and its special form
+tkz_status encode_device_batch(tkz_encoder* e, const BatchCall& c, int64_t* total_tokens) {
+    DeviceScope scope;
+    TKZ_TRY(check_device_call(e, scope, c));
+    Lease lease(e);
+    const tkz_status st = encode_device(e, lease.ws, c, kCallWhole, total_tokens);
+    if (st == TKZ_OK && c.special) ++e->spec_batches;
+    return st;
 }
 
 const char* const kRegexP1 = "'s|'t|'re|'ve|'m|'ll|'d| ?\\p{L}+| ?\\p{N}+| ?[^\\s\\p{L}\\p{N}]+|\\s+(?!\\S)|\\s+";
@@ -1771,8 +1844,7 @@ void tkz_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
 tkz_status tkz_encode_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs,
                                  int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
-    if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
-    return encode_host(e, bytes, nullptr, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed, true, nullptr);
+    return encode_host_batch(e, HostCall{bytes, nullptr, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed});
 }
 
 namespace {
@@ -1800,21 +1872,17 @@ tkz_status tkz_encode_batch_special_device(tkz_encoder* e, const uint8_t* d_byte
                                            void* hip_stream, int64_t* total_tokens) {
     SpecialCall sc; bool plain = false;
     TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
-    if (plain) return tkz_encode_batch_device(e, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, hip_stream, total_tokens);
-    SpecialScope scope(&sc);
-    const tkz_status st = tkz_encode_batch_device(e, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, hip_stream, total_tokens);
-    if (st == TKZ_OK) ++e->spec_batches;
-    return st;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    if (!plain) c.special = &sc;
+    return encode_device_batch(e, c, total_tokens);
 }
 tkz_status tkz_encode_batch_special_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
                                          int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
     SpecialCall sc; bool plain = false;
     TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
-    if (plain) return tkz_encode_batch_utf8(e, bytes, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed);
-    SpecialScope scope(&sc);
-    const tkz_status st = tkz_encode_batch_utf8(e, bytes, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed);
-    if (st == TKZ_OK) ++e->spec_batches;
-    return st;
+    HostCall c{bytes, nullptr, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
+    if (!plain) c.special = &sc;
+    return encode_host_batch(e, c);
 }
 void tkz_encoder_special_stats(const tkz_encoder* e, int64_t* batches, int64_t* literals) {
     if (batches) *batches = e ? e->spec_batches.load() : 0;
@@ -1824,40 +1892,27 @@ void tkz_encoder_special_stats(const tkz_encoder* e, int64_t* batches, int64_t* 
 tkz_status tkz_encode_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs,
                                    int64_t total_bytes, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
                                    void* hip_stream, int64_t* total_tokens) {
-    DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (!d_doc_offsets || !d_out_offsets || (total_bytes > 0 && (!d_bytes || !d_out_ids))) return fail(TKZ_E_ARG, "null device buffer");
-    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
-    Lease lease(e);
-    Workspace* ws = lease.ws;
-    return encode_device(e, ws, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets,
-                         static_cast<hipStream_t>(hip_stream), true, nullptr, total_tokens);
+    return encode_device_batch(e, BatchCall{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)}, total_tokens);
 }
 
 // The same in two halves: _begin enqueues the batch on the stream and returns, _end waits for it and reports as tkz_encode_batch_device
 // does (a batch that needs a larger buffer than the first attempt had is run again inside _end).  The call keeps a workspace of the
 // encoder from _begin to _end: several batches can be in flight, on one stream or on several.
-struct tkz_pending {
-    tkz_encoder* e; Lease* lease;
-    const uint8_t* d_bytes; const int64_t* d_offs; int64_t n_docs, total; int32_t* d_out; int64_t out_cap; int64_t* d_out_offs; hipStream_t stream;
-    int64_t* d_counts3;                    // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
-};
+struct tkz_pending { tkz_encoder* e; Lease* lease; BatchCall call; };
 tkz_status tkz_encode_batch_device_begin_counts(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs,
                                                 int64_t total_bytes, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
                                                 void* hip_stream, int64_t* d_counts3, tkz_pending** pending) {
     if (!pending) return fail(TKZ_E_ARG, "null pending");
     *pending = nullptr;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    c.d_counts3 = d_counts3;
     DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (!d_doc_offsets || !d_out_offsets || (total_bytes > 0 && (!d_bytes || !d_out_ids))) return fail(TKZ_E_ARG, "null device buffer");
-    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    TKZ_TRY(check_device_call(e, scope, c));
     { std::lock_guard<std::mutex> lock(e->mu); if (e->destroyed) return fail(TKZ_E_ARG, "encoder destroyed"); ++e->pending; }
-    tkz_pending* p = new tkz_pending{e, new Lease(e), d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), d_counts3};
-    st = encode_device(e, p->lease->ws, d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, p->stream, true, nullptr, nullptr, nullptr, kCallBegin, d_counts3);
+    tkz_pending* p = new tkz_pending{e, new Lease(e), c};
+    const tkz_status st = encode_device(e, p->lease->ws, p->call, kCallBegin, nullptr);
     if (st != TKZ_OK) {
-        (void)hipStreamSynchronize(p->stream);
+        (void)hipStreamSynchronize(c.stream);
         delete p->lease; delete p;
         const std::string msg = g_err;
         bool last;
@@ -1876,7 +1931,7 @@ tkz_status tkz_encode_batch_device_begin(tkz_encoder* e, const uint8_t* d_bytes,
 }
 const int64_t* tkz_pending_counts_device(const tkz_pending* p) {
     if (!p) return nullptr;
-    return p->d_counts3 ? p->d_counts3 : p->lease->ws->w_counts3.as<int64_t>();
+    return p->call.d_counts3 ? p->call.d_counts3 : p->lease->ws->w_counts3.as<int64_t>();
 }
 tkz_status tkz_encode_batch_device_end(tkz_pending* p, int64_t* total_tokens) {
     if (!p) return fail(TKZ_E_ARG, "null pending");
@@ -1888,9 +1943,9 @@ tkz_status tkz_encode_batch_device_end(tkz_pending* p, int64_t* total_tokens) {
         bool dead;
         { std::lock_guard<std::mutex> lock(e->mu); dead = e->destroyed; }
         if (st == TKZ_OK && !dead)
-            st = encode_device(e, p->lease->ws, p->d_bytes, p->d_offs, p->n_docs, p->total, p->d_out, p->out_cap, p->d_out_offs, p->stream, true, nullptr, total_tokens, nullptr, kCallEnd, p->d_counts3);
+            st = encode_device(e, p->lease->ws, p->call, kCallEnd, total_tokens);
         else {
-            (void)hipStreamSynchronize(p->stream);
+            (void)hipStreamSynchronize(p->call.stream);
             if (st == TKZ_OK) st = fail(TKZ_E_ARG, "the encoder was destroyed while this batch was in flight");
         }
     }
@@ -1906,7 +1961,7 @@ tkz_status tkz_encode_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, int
     if (len < 0 || !n_out) return fail(TKZ_E_ARG, "bad argument");
     const int64_t offs[2] = {0, len};
     int64_t oo[2] = {0, 0}, needed = 0;
-    tkz_status st = encode_host(e, text, nullptr, offs, 1, out_ids, out_cap, oo, &needed, true, nullptr);
+    tkz_status st = encode_host(e, HostCall{text, nullptr, offs, 1, out_ids, out_cap, oo, &needed});
     *n_out = needed;
     return st;
 }
@@ -1935,18 +1990,21 @@ tkz_status tkz_encode_batch_utf16(tkz_encoder* e, const uint16_t* units, const i
     if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
     if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
     static const uint16_t none = 0;
-    return encode_host(e, nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed, true, nullptr);
+    return encode_host(e, HostCall{nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed});
 }
 
 tkz_status tkz_pretokenize_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, uint64_t* out_bitmap_words) {
     if (!out_bitmap_words) return fail(TKZ_E_ARG, "null output buffer");
-    return encode_host(e, bytes, nullptr, doc_offsets, n_docs, nullptr, 0, nullptr, nullptr, true, out_bitmap_words);
+    HostCall c{bytes, nullptr, doc_offsets, n_docs, nullptr, 0, nullptr, nullptr};
+    c.kind = CallKind::BitmapOnly; c.bitmap = out_bitmap_words;
+    return encode_host(e, c);
 }
 
 tkz_status tkz_encode_pieces(tkz_encoder* e, const uint8_t* bytes, const int64_t* piece_offsets, int64_t n_pieces,
                              int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
-    if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
-    return encode_host(e, bytes, nullptr, piece_offsets, n_pieces, out_ids, out_cap, out_offsets, needed, false, nullptr);
+    HostCall c{bytes, nullptr, piece_offsets, n_pieces, out_ids, out_cap, out_offsets, needed};
+    c.kind = CallKind::OnePiecePerDoc;
+    return encode_host_batch(e, c);
 }
 
 tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs,
@@ -1984,8 +2042,9 @@ tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, co
     HIP_TRY(hipMemcpy(ws->s_offs[0].p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
     PiecesOut po{ws->p_boffs.as<int64_t>(), ws->p_toffs.as<int64_t>(), ws->p_docp.as<int64_t>(), pcap, 0};
     int64_t tokens = 0;
-    st = encode_device(e, ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, nullptr, nullptr, true,
-                       nullptr, &tokens, &po);
+    BatchCall c{ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, nullptr, nullptr};
+    c.kind = CallKind::Pieces; c.pieces = &po;
+    st = encode_device(e, ws, c, kCallWhole, &tokens);
     *n_pieces = po.n_pieces;
     if (needed_ids) *needed_ids = tokens;
     if (st != TKZ_OK) return st;
@@ -2260,7 +2319,7 @@ tkz_status tkz_encoder_reserve(tkz_encoder* e, int64_t max_bytes, int64_t max_do
     Lease lease(e);
     Workspace* ws = lease.ws;
     int64_t* acc = &ws->bytes_allocated;
-    st = prepare_workspace(ws, max_bytes, max_docs, false, false);
+    st = prepare_workspace(ws, max_bytes, max_docs, CallKind::Encode);
     if (st != TKZ_OK) return st;
     const int64_t nwords = max_bytes / 64 + 1;
     HIP_TRY(ws->w_xq.ensure((size_t)(nwords / kRowsPerWave + 4) * 16, acc));                      // (the o200k scanners' queues)
