@@ -59,6 +59,15 @@ namespace Microsoft.DeepDev
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_pieces_utf8(IntPtr encoder, byte* bytes, long* docOffsets, long nDocs, int* outIds, long outCap,
                                                                                          long* docPieceOffsets, long* pieceByteOffsets, long* pieceTokenOffsets,
                                                                                          long pieceCap, out long nPieces, out long neededIds);
+        // EncodeTrimSuffix / EncodeTrimPrefix for a batch, cut on the device (include/tkz.h).  tkz_encode_batch_trim_device is for hosts that hold their text in HBM;
+        // the class uses the host-buffer entry.  (Like the rest of this file: not compiled here.)
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_trim_device(IntPtr encoder, IntPtr dBytes, IntPtr dDocOffsets, long nDocs, long totalBytes,
+                                                                                         int* allowed, int nAllowed, int side, long maxTokens, IntPtr dMaxTokens,
+                                                                                         IntPtr dOutIds, long outCap, IntPtr dOutOffsets, IntPtr dCutBytes, IntPtr dCutUnits,
+                                                                                         IntPtr hipStream, out long totalTokens);
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_trim_utf8(IntPtr encoder, byte* bytes, long* docOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                       int side, long maxTokens, long* maxTokensPerDoc, int* outIds, long outCap, long* outOffsets,
+                                                                                       long* cutBytes, long* cutUnits, out long needed);
 
         /// <summary>A C string argument: the UTF-8 bytes and a terminating zero.</summary>
         internal static byte[] Utf8Z(string s)
@@ -540,7 +549,61 @@ namespace Microsoft.DeepDev
             return items;
         }
 
+        // EncodeTrimSuffix / EncodeTrimPrefix for a batch of texts: ONE device call (tkz_encode_batch_trim_utf8 -- the literals cut out, the pieces counted, the cut
+        // chosen and the kept ids compacted on the device; cutUnits is the reference's encodeLength / actualPrefixStrLength).  Returns null when the host walk over
+        // PieceItems has to do it: a registered set the device path does not hold (TKZ_E_UNSUPPORTED, -7), a text with a lone surrogate while a literal holds U+FFFD
+        // (Encoding.UTF8.GetBytes turns it into EF BF BD, which the literal would match on bytes but not in the reference's UTF-16 search), a negative maximum.
+        private bool specialOnHost;
+        private unsafe List<(List<int> TokenIds, string Text)>? TrimBatchOnDevice(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount, int side)
+        {
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            if (maxTokenCount < 0 || (!plain && specialOnHost)) return null;
+            if (!plain && specialTokensEncoder.Keys.Any(k => k.IndexOf('\uFFFD') >= 0))
+                foreach (string t in texts)
+                    for (int i = 0; i < t.Length; ++i)
+                        if (char.IsSurrogate(t[i]) && !(char.IsHighSurrogate(t[i]) && i + 1 < t.Length && char.IsLowSurrogate(t[i + 1])) && !(char.IsLowSurrogate(t[i]) && i > 0 && char.IsHighSurrogate(t[i - 1])))
+                            return null;
+            var result = new List<(List<int> TokenIds, string Text)>(texts.Count);
+            if (texts.Count == 0) return result;
+            var index = new List<int>();                                              // registration order = the alternation's
+            if (!plain) { int i = 0; foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial!.Contains(k)) index.Add(i); ++i; } }
+            var offsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) offsets[t + 1] = offsets[t] + Encoding.UTF8.GetByteCount(texts[t]);
+            long total = offsets[texts.Count];
+            var bytes = new byte[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) Encoding.UTF8.GetBytes(texts[t], 0, texts[t].Length, bytes, (int)offsets[t]);
+            long cap = Math.Min(total, (long)texts.Count * maxTokenCount);            // (tkz.h: always sufficient)
+            var ids = new int[Math.Max(1, cap)]; var outOffs = new long[texts.Count + 1]; var cutUnits = new long[texts.Count];
+            var allowed = index.Count > 0 ? index.ToArray() : new int[1];
+            int st;
+            fixed (byte* pb = bytes) fixed (long* po = offsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* poo = outOffs) fixed (long* pu = cutUnits)
+                st = Tkz.tkz_encode_batch_trim_utf8(encoder, pb, po, texts.Count, index.Count > 0 ? pa : null, index.Count, side, maxTokenCount, null, pi, cap, poo, null, pu, out _);
+            if (st == -7) { specialOnHost = true; return null; }
+            Tkz.Check(st);
+            for (int t = 0; t < texts.Count; ++t)
+            {
+                var kept = new List<int>((int)(outOffs[t + 1] - outOffs[t]));
+                for (long k = outOffs[t]; k < outOffs[t + 1]; ++k) kept.Add(ids[k]);
+                int u = (int)cutUnits[t];
+                result.Add((kept, side == 0 ? (u == texts[t].Length ? texts[t] : texts[t].Substring(0, u)) : (u == 0 ? texts[t] : texts[t].Substring(u))));
+            }
+            GC.KeepAlive(this);
+            return result;
+        }
+
+        public List<(List<int> TokenIds, string Text)> EncodeTrimSuffixBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
+            => TrimBatchOnDevice(texts, allowedSpecial, maxTokenCount, 0 /* TKZ_TRIM_SUFFIX */) ?? texts.Select(t => TrimSuffixOnHost(t, allowedSpecial, maxTokenCount)).ToList();
+        public List<(List<int> TokenIds, string Text)> EncodeTrimSuffixBatch(IReadOnlyList<string> texts, int maxTokenCount, bool applySpecialTokens = true)
+            => EncodeTrimSuffixBatch(texts, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
+        public List<(List<int> TokenIds, string Text)> EncodeTrimPrefixBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
+            => TrimBatchOnDevice(texts, allowedSpecial, maxTokenCount, 1 /* TKZ_TRIM_PREFIX */) ?? texts.Select(t => TrimPrefixOnHost(t, allowedSpecial, maxTokenCount)).ToList();
+        public List<(List<int> TokenIds, string Text)> EncodeTrimPrefixBatch(IReadOnlyList<string> texts, int maxTokenCount, bool applySpecialTokens = true)
+            => EncodeTrimPrefixBatch(texts, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
+
         public (List<int> TokenIds, string Text) EncodeTrimSuffix(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
+            => EncodeTrimSuffixBatch(new[] { text }, allowedSpecial, maxTokenCount)[0];
+        // the host walk over the pieces: the fallback of the batch methods
+        private (List<int> TokenIds, string Text) TrimSuffixOnHost(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
         {
             var tokenIds = new List<int>();
             int tokenCount = 0, encodeLength = 0;
@@ -558,6 +621,8 @@ namespace Microsoft.DeepDev
             => EncodeTrimSuffix(text, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
 
         public (List<int> TokenIds, string Text) EncodeTrimPrefix(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
+            => EncodeTrimPrefixBatch(new[] { text }, allowedSpecial, maxTokenCount)[0];
+        private (List<int> TokenIds, string Text) TrimPrefixOnHost(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
         {
             var tokenIds = new List<int>();
             int tokenCount = 0, encodeLength = 0;

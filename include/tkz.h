@@ -220,6 +220,36 @@ tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, co
                                         int64_t* piece_token_offsets, int64_t piece_cap,
                                         int64_t* n_pieces, int64_t* needed_ids);
 
+/* EncodeTrimSuffix / EncodeTrimPrefix for a batch, ON THE DEVICE (TikTokenizer.cs:288-579): every document is cut to at most a maximum of tokens exactly as
+ * EncodeTrimSuffix(text, allowedSpecial, maxTokenCount) / EncodeTrimPrefix(...) cut the string it is the UTF-8 form of.  The items of a document are the regex
+ * pieces of its plain stretches and one item of one token per allowed literal, in order; a piece of several tokens is never split.
+ *   TKZ_TRIM_SUFFIX keeps the longest run of leading items whose tokens sum to at most the maximum (the reference's loop with its two `break`s, :296-340,:356-378);
+ *   TKZ_TRIM_PREFIX keeps everything when the document has at most the maximum, else drops the items up to the first item boundary whose cumulative token count
+ *                   is at least count - maximum (TrimPrefix, :470-483).
+ * d_out_ids / d_out_offsets (n_docs + 1): the KEPT ids, compacted, document after document.  d_cut_bytes[d]: bytes of the kept text (suffix) or of the dropped text
+ * (prefix); d_cut_units[d]: the same length in UTF-16 code units -- the reference's encodeLength / actualPrefixStrLength: one per non-continuation byte and one more
+ * per byte >= 0xF0 --; a document kept whole reports its full length for suffix and 0 for prefix.  Either array may be NULL (n_docs entries each, on the device).
+ * The maximum: d_max_tokens == NULL: max_tokens for every document (negative: TKZ_E_ARG -- the reference's prefix variant returns the whole text then: a quirk the
+ * callers keep on the host); else d_max_tokens[d] for document d (device; max_tokens is ignored), where a NEGATIVE ENTRY COUNTS AS 0.
+ * allowed / n_allowed exactly as tkz_encode_batch_special_device (registration order, TKZ_E_ARG for a bad index, TKZ_E_UNSUPPORTED for a set beyond the device
+ * path); n_allowed == 0: no literal is looked for and no literal kernel is launched.
+ * out_cap counts the KEPT ids only -- min(total_bytes, n_docs * maximum) is always sufficient --: the untrimmed ids live in the workspace, never in the caller's
+ * buffer.  On TKZ_E_CAPACITY nothing is in d_out_ids and *total_tokens / *needed hold the kept total; the encoder's {n_docs, n_bytes, n_tokens} block receives the
+ * kept token count.  Errors (invalid UTF-8, TKZ_E_KEY_NOT_FOUND, pieces beyond 2^30 bytes, workspace growth) as tkz_encode_batch_device; a batch that has to be run
+ * again is run again inside the call, which returns after the stream has drained (it also waits once, inside, for the number of pieces).
+ * Workspace: the batch path's ~7 bytes per input byte, and 8 more per input byte (the untrimmed ids and a token mark per possible piece, 4 each), 16 per PIECE
+ * (its byte and token offset: ~3.6 per input byte on English text, at most 16) and 32 per document.  The per-piece arrays never leave the device.
+ * tkz_encode_batch_trim_utf8: the same over host buffers (max_tokens_per_doc is a HOST array, a negative entry is TKZ_E_ARG).  It stages the WHOLE batch on the
+ * device, as tkz_encode_batch_pieces_utf8 does, and copies its result from ONE call of the device entry: no chunk pipeline, no single-launch path. */
+typedef enum tkz_trim_side { TKZ_TRIM_SUFFIX = 0, TKZ_TRIM_PREFIX = 1 } tkz_trim_side;
+tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                        const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens, const int64_t* d_max_tokens,
+                                        int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets, int64_t* d_cut_bytes, int64_t* d_cut_units,
+                                        void* hip_stream, int64_t* total_tokens);
+tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                      int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                      int64_t* cut_bytes, int64_t* cut_units, int64_t* needed);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -342,7 +372,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
 /* When enabled, every kernel launch of tkz_encode_batch_device is bracketed by HIP events on the
  * launch stream; tkz_encoder_kernel_ms returns the accumulated milliseconds and launch counts per
  * kernel since the last reset (arrays of TKZ_K_COUNT).  Not inside any bracket (microseconds each): the fill of the workspace's zero region,
- * k_doccount2 and the scan of its counts, k_list_stats (which also finds the giant pieces and fills k_merge_coop's queue).
+ * k_doccount2 and the scan of its counts, k_list_stats (which also finds the giant pieces and fills k_merge_coop's queue); of a trim call
+ * (tkz_encode_batch_trim_device) k_trim_cut, the scan of the kept lengths and k_trim_gather, which run behind TKZ_K_DOCOFFS.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

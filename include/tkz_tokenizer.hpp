@@ -253,6 +253,30 @@ public:
     using Trimmed = std::pair<std::vector<int32_t>, std::string>;   // (List<int> TokenIds, string Text)
     // EncodeTrimSuffix(string, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)     TikTokenizer.cs:394-403
     Trimmed EncodeTrimSuffix(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        return EncodeTrimSuffixBatch({text}, allowedSpecial, maxTokenCount)[0];
+    }
+    // EncodeTrimSuffix / EncodeTrimPrefix for a batch of texts: ONE device call (tkz_encode_batch_trim_utf8 -- the literals cut out, the pieces counted, the
+    // cut chosen and the kept ids compacted on the device; the text is sliced at the cut's byte position).  The host walk over piece_items() below remains for
+    // a registered set the device path does not hold (TKZ_E_UNSUPPORTED) and for a negative maximum (the reference's prefix variant returns the whole text then).
+    std::vector<Trimmed> EncodeTrimSuffixBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<Trimmed> out;
+        if (trim_batch_device(texts, allowedSpecial, maxTokenCount, TKZ_TRIM_SUFFIX, out)) return out;
+        for (const std::string& t : texts) out.push_back(trim_suffix_host(t, allowedSpecial, maxTokenCount));
+        return out;
+    }
+    std::vector<Trimmed> EncodeTrimSuffixBatch(const std::vector<std::string>& texts, int maxTokenCount, bool applySpecialTokens = true) const {
+        return EncodeTrimSuffixBatch(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount);
+    }
+    std::vector<Trimmed> EncodeTrimPrefixBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<Trimmed> out;
+        if (trim_batch_device(texts, allowedSpecial, maxTokenCount, TKZ_TRIM_PREFIX, out)) return out;
+        for (const std::string& t : texts) out.push_back(trim_prefix_host(t, allowedSpecial, maxTokenCount));
+        return out;
+    }
+    std::vector<Trimmed> EncodeTrimPrefixBatch(const std::vector<std::string>& texts, int maxTokenCount, bool applySpecialTokens = true) const {
+        return EncodeTrimPrefixBatch(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount);
+    }
+    Trimmed trim_suffix_host(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         std::vector<int32_t> ids;
         int64_t tokenCount = 0; size_t encodeLength = 0;
         for (const PieceItem& it : piece_items(text, allowedSpecial)) {            // the walk of :288-341 / :343-392
@@ -270,6 +294,9 @@ public:
     }
     // EncodeTrimPrefix(string, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)     TikTokenizer.cs:529-536
     Trimmed EncodeTrimPrefix(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        return EncodeTrimPrefixBatch({text}, allowedSpecial, maxTokenCount)[0];
+    }
+    Trimmed trim_prefix_host(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         std::vector<int32_t> ids;
         std::vector<std::pair<int64_t, size_t>> boundaries{{0, 0}};               // tokenCountMap (:438-441)
         int64_t tokenCount = 0;
@@ -357,6 +384,35 @@ private:
         std::vector<std::string> all;
         for (const auto& s : specials_) all.push_back(s.first);
         return all;
+    }
+    // the batch on the device's trim entry; false (nothing done): the host walk has to do it
+    bool trim_batch_device(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int32_t side, std::vector<Trimmed>& out) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (maxTokenCount < 0 || (!plain && special_on_host_)) return false;
+        const int64_t n = static_cast<int64_t>(texts.size());
+        if (n == 0) return true;
+        std::vector<int32_t> index;
+        if (!plain)
+            for (size_t i = 0; i < specials_.size(); ++i)
+                for (const auto& a : allowedSpecial) if (a == specials_[i].first) { index.push_back(static_cast<int32_t>(i)); break; }
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const std::string& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        const int64_t total = offs[static_cast<size_t>(n)];
+        const int64_t cap = std::min<int64_t>(total, n * static_cast<int64_t>(maxTokenCount));       // (tkz.h: always sufficient)
+        std::vector<int32_t> ids(static_cast<size_t>(cap) + 1);
+        std::vector<int64_t> ooff(static_cast<size_t>(n) + 1, 0), cut(static_cast<size_t>(n), 0);
+        int64_t needed = 0;
+        if (bytes.empty()) bytes.push_back(0);
+        const tkz_status st = tkz_encode_batch_trim_utf8(enc_, bytes.data(), offs.data(), n, index.empty() ? nullptr : index.data(), static_cast<int32_t>(index.size()), side,
+                                                         maxTokenCount, nullptr, ids.data(), cap, ooff.data(), cut.data(), nullptr, &needed);
+        if (st == TKZ_E_UNSUPPORTED) { special_on_host_ = true; return false; }
+        check(st);
+        for (size_t t = 0; t < texts.size(); ++t) {
+            const size_t c = static_cast<size_t>(cut[t]);             // bytes of the kept text (suffix) / of the dropped text (prefix)
+            out.push_back({std::vector<int32_t>(ids.begin() + ooff[t], ids.begin() + ooff[t + 1]), side == TKZ_TRIM_SUFFIX ? texts[t].substr(0, c) : texts[t].substr(c)});
+        }
+        return true;
     }
     // one item per regex piece of every plain segment and one per special token: its ids and the byte position where it ends
     struct PieceItem { std::vector<int32_t> ids; size_t end; };

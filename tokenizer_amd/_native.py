@@ -19,6 +19,7 @@ OPT_PIECE_MEMO = 2
 OPT_PIECE_STATS = 3
 OPT_PROMOTE_MIN_BYTES, OPT_PROMOTE_CAP = 5, 6
 OPT_CASE_EQUIVALENCE = 7    # cl100k's (?i:...) with .NET >= 7's case-equivalence tables ('ſ is 's)
+TRIM_SUFFIX, TRIM_PREFIX = 0, 1   # tkz_trim_side
 OPT_LATENCY_BYTES = 8       # batches of at most this many bytes merge long missed pieces a wavefront each (tkz.h)
 OPT_ADAPT = 9               # 1 (default): the encoder learns again when the text has drifted; small batches add up to a learning window (tkz.h)
 OPT_PROMOTE = 4        # 0 / 1: automatic promotion of hot memo entries into the key tables off / on; 2: promote now; 3: drop the promotions
@@ -146,6 +147,8 @@ class Library:
         L.tkz_encoder_set_special_tokens.argtypes = [vp, vp, vp, vp, i32]
         L.tkz_encode_batch_special_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, vp, i64, vp, vp, pi64]
         L.tkz_encode_batch_special_utf8.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, pi64]
+        L.tkz_encode_batch_trim_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i64, vp, vp, i64, vp, vp, vp, vp, pi64]
+        L.tkz_encode_batch_trim_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, vp, vp, i64, vp, vp, vp, pi64]
         L.tkz_encoder_special_stats.argtypes = [vp, pi64, pi64]
         L.tkz_encoder_special_stats.restype = None
         L.tkz_decode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
@@ -381,6 +384,43 @@ class Encoder:
         tot = C.c_int64(0)
         self.lib.check(self.lib.L.tkz_encode_batch_special_device(self._h, d_bytes, d_offsets, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
                                                                   len(allowed), d_out_ids, out_cap, d_out_offsets, stream or None, C.byref(tot)))
+        return tot.value
+
+    def encode_batch_trim(self, data: np.ndarray, offsets: np.ndarray, allowed_index, side, max_tokens, per_doc=None, out_cap=None):
+        """EncodeTrimSuffix (side TRIM_SUFFIX) / EncodeTrimPrefix (TRIM_PREFIX) for a batch, cut on the device: (kept ids int32, offsets int64[n+1],
+        cut_bytes int64[n], cut_units int64[n]) -- the byte and UTF-16 length of the kept (suffix) or dropped (prefix) text of every document.  allowed_index as in
+        encode_batch_special; per_doc: a maximum per document (int64[n]) in place of max_tokens.  out_cap counts the kept ids."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed_index, dtype=np.int32)
+        n = len(offsets) - 1
+        if per_doc is not None:
+            per_doc = np.ascontiguousarray(per_doc, dtype=np.int64)
+            assert len(per_doc) == n
+            bound = int(np.minimum(np.maximum(per_doc, 0), np.diff(offsets)).sum()) if n else 0
+        else:
+            bound = min(len(data), n * max(int(max_tokens), 0))
+        cap = bound if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        ooff = np.empty(n + 1, np.int64)
+        cb, cu = np.zeros(max(1, n), np.int64), np.zeros(max(1, n), np.int64)
+        needed = C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_trim_utf8(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None,
+                                                                 len(allowed), int(side), int(max_tokens), _ptr(per_doc) if per_doc is not None and n else None,
+                                                                 _ptr(ids), cap, _ptr(ooff), _ptr(cb), _ptr(cu), C.byref(needed)))
+        except TkzError as ex:
+            ex.needed = needed.value                          # (E_CAPACITY: the kept total)
+            raise
+        return ids[:needed.value], ooff, cb[:n], cu[:n]
+
+    def encode_batch_trim_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, side, max_tokens, d_max_tokens, d_out_ids, out_cap, d_out_offsets,
+                                 d_cut_bytes=0, d_cut_units=0, stream=0):
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_encode_batch_trim_device(self._h, d_bytes, d_offsets, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                               int(side), int(max_tokens), d_max_tokens or None, d_out_ids or None, out_cap, d_out_offsets,
+                                                               d_cut_bytes or None, d_cut_units or None, stream or None, C.byref(tot)))
         return tot.value
 
     def special_stats(self):

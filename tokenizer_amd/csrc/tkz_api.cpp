@@ -106,6 +106,7 @@ struct CounterBlock {          // mirrors the device block
     int64_t lq_total;                      // long misses in the class queue (the scan of EncodeParams::lq_cnt)
     unsigned long long miss_short, miss_long;   // pieces of the batch that missed the key tables as a whole (k_list_stats: the sums of mcount)
     unsigned long long n_literals;         // the special entries: special-token literals taken (k_lit_resolve)
+    int64_t kept_total;                    // the trim entries: ids kept over the whole batch (k_trim_gather)
 };
 
 }  // namespace
@@ -164,6 +165,9 @@ struct Workspace {
     DevBuf d_grp, d_tsum, d_tbase, d_bsum, d_counters, d_ids, d_idoffs, d_out, d_outoffs;
     // piece-granular entry point: piece byte offsets, token offsets, first piece of every document
     DevBuf p_boffs, p_toffs, p_docp;
+    // the trim entries: the untrimmed ids (a token is at least a byte: 4 bytes per input byte), {kept token range, cut position} per document and the
+    // partial sums of their scan; the host entry's staging of the per-document maxima and the two cut arrays
+    DevBuf t_ids, t_keep, t_bsum, t_stage;
     CounterBlock* h_counters = nullptr;   // pinned
     // the single-launch path for small batches (k_small): input, output and status in ONE page-locked block the device reads and writes directly
     uint8_t* h_small = nullptr;
@@ -191,7 +195,7 @@ struct Workspace {
         DevBuf* bufs[] = {&w_candbits, &w_segbits, &w_specbits, &w_endbits, &w_segoffs, &w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
                           &w_doctok, &w_dcount, &w_dbase, &w_pool, &s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2],
                           &s_outoffs[0], &s_outoffs[1], &s_outoffs[2], &u_bytes[0], &u_bytes[1],
-                          &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &p_boffs, &p_toffs, &p_docp};
+                          &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &p_boffs, &p_toffs, &p_docp, &t_ids, &t_keep, &t_bsum, &t_stage};
         for (DevBuf* b : bufs) b->release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
@@ -272,6 +276,8 @@ std::atomic<int> g_fork_in_flight{0};
 struct SpecialCall { tkz::TkzLitAllowed allowed; };
 // where the piece-granular entry point wants its arrays (all on the device)
 struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
+// A call of one of the trim entries: the side, the maximum (uniform, or one per document on the device) and where the cut of every document goes (device, may be null)
+struct TrimCall { int32_t side; int64_t max_tokens; const int64_t* d_max; int64_t* d_cut_bytes; int64_t* d_cut_units; };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -279,7 +285,8 @@ enum class CallKind {
     Encode,          // documents -> pre-tokenizer -> ids, a token offset per document
     OnePiecePerDoc,  // tkz_encode_pieces: no pre-tokenizer, every "document" is one piece
     BitmapOnly,      // tkz_pretokenize_utf8: the piece-start bitmap and nothing else
-    Pieces           // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
+    Pieces,          // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
+    Trim             // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -291,14 +298,15 @@ struct BatchCall {
     CallKind kind = CallKind::Encode;
     uint64_t* d_bitmap = nullptr;              // BitmapOnly: where the bitmap goes
     PiecesOut* pieces = nullptr;               // Pieces: where the piece arrays go
-    const SpecialCall* special = nullptr;      // the special entries (an ordinary encode only); null: no literal is looked for
+    const SpecialCall* special = nullptr;      // the special entries (an ordinary encode or a trim call); null: no literal is looked for
+    const TrimCall* trim = nullptr;            // Trim: what to keep (pieces then points at the workspace's piece arrays)
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     bool pretokenizes() const { return kind != CallKind::OnePiecePerDoc; }
     bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || kind == CallKind::Trim ? special : nullptr; }
 };
 
 // One batch in the caller's host memory, as the host entries hand it to encode_host.
@@ -600,7 +608,7 @@ tkz_status drop_promotions(tkz_encoder* e, bool retire) {
 // workspace of one batch of `total` bytes / n_docs documents (grow-only buffers: nothing happens once they are large enough)
 tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, CallKind kind) {
     using namespace tkz;
-    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces;
+    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces || kind == CallKind::Trim;
     const int64_t nwords = total / 64 + 1;
     const int64_t ntiles = (total + kSub - 1) / kSub;
     const int64_t nblk = (ntiles + kScanBlock - 1) / kScanBlock;
@@ -913,6 +921,10 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             // piece arrays too small: the launch sequence still runs to its end (without the piece arrays), so that the caller
             // learns BOTH required sizes from this one call (tkz.h: *n_pieces and *needed_ids on TKZ_E_CAPACITY)
             *pieces_over = po->n_pieces > po->piece_cap;
+            if (c.trim) {                                               // (the workspace's piece arrays: sized for the pieces there are, not for one per byte)
+                for (DevBuf* b : {&ws->p_boffs, &ws->p_toffs}) HIP_TRY(b->ensure((size_t)(po->n_pieces + 1) * 8, &ws->bytes_allocated));
+                po->piece_boffs = ws->p_boffs.as<int64_t>(); po->piece_toffs = ws->p_toffs.as<int64_t>();
+            }
             if (!*pieces_over) launch_piece_index(L, startbits, nwords, total, ntiles, ws->w_dbase.as<int64_t>(), po->n_pieces, po->piece_boffs, d_offs, n_docs, po->doc_piece);
         }
         if (nsample >= 0) {
@@ -921,10 +933,20 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             launch_encode(L, T, P, ntiles);
             if (P.stats) launch_miss_stats(L, P, ntiles);
             launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), P.tile_count, ws->w_tbase.as<int64_t>(), grand, 1, nullptr, nullptr, nullptr, 1, K_SCAN);
-            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.d_out, c.out_cap);
+            // (a trim call's untrimmed ids stay in the workspace: the caller's buffer holds the kept ones only)
+            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
-                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+                const int64_t* produced = grand;
+                if (c.trim) {
+                    int64_t* const keep = ws->t_keep.as<int64_t>();
+                    int64_t* const kept = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, kept_total));
+                    const TrimParams R{d_bytes, d_offs, n_docs, total, po->doc_piece, po->piece_boffs, po->piece_toffs, c.trim->side, c.trim->max_tokens, c.trim->d_max,
+                                       keep, keep + n_docs, keep + 2 * n_docs, ws->t_bsum.as<int64_t>(), c.trim->d_cut_bytes, c.trim->d_cut_units, counters};
+                    launch_trim(L, R, ws->t_ids.as<int32_t>(), total, c.d_out, c.out_cap, c.d_out_offs, kept);
+                    produced = kept;
+                }
+                launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
                                n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
@@ -1081,6 +1103,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
             { Launch L0{stream, nullptr, ws}; launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3); }
             if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
+            if (c.trim && n_docs > 0) for (int64_t* cut : {c.trim->d_cut_bytes, c.trim->d_cut_units}) if (cut) HIP_TRY(hipMemsetAsync(cut, 0, (size_t)n_docs * sizeof(int64_t), stream));
             if (c.d_bitmap) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(c.d_bitmap, &one, 8, hipMemcpyHostToDevice, stream)); }
             if (phase == kCallBegin) return TKZ_OK;               // (_begin returns without waiting)
         }
@@ -1126,9 +1149,10 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         settle_workspace(ws, ntiles);
         if (c.pretokenizes()) after_batch(e, ws, total);
         if (c.literals()) e->spec_literals += ws->spec_taken;
-        if (total_tokens) *total_tokens = ws->h_counters->grand;
+        const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
+        if (total_tokens) *total_tokens = produced;
         if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
-        if (ws->h_counters->grand > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+        if (produced > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
         return TKZ_OK;
     }
     return fail(TKZ_E_DEVICE, "unreachable");
@@ -2053,6 +2077,93 @@ tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, co
     HIP_TRY(hipMemcpy(piece_byte_offsets, ws->p_boffs.p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(piece_token_offsets, ws->p_toffs.p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(doc_piece_offsets, ws->p_docp.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+
+// ---- EncodeTrimSuffix / EncodeTrimPrefix for a batch (TikTokenizer.cs:288-579) ------------------------
+
+namespace {
+// the trim call on device buffers, on a workspace the entry holds: the piece-granular launch sequence with the piece arrays and the untrimmed ids in the
+// workspace, then the cut, the scan and the kept ids (enqueue_attempt)
+tkz_status trim_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, const TrimCall& tc, const SpecialCall* sc, int64_t* total_tokens) {
+    int64_t* acc = &ws->bytes_allocated;
+    PiecesOut po{nullptr, nullptr, nullptr, c.total, 0};                // (pieces <= bytes: the arrays are sized once the pieces are counted)
+    if (c.total > 0) {
+        HIP_TRY(ws->p_docp.ensure((size_t)(c.n_docs + 1) * 8, acc));
+        HIP_TRY(ws->t_ids.ensure((size_t)c.total * 4, acc));
+        HIP_TRY(ws->t_keep.ensure((size_t)std::max<int64_t>(c.n_docs, 1) * 3 * 8, acc));
+        HIP_TRY(ws->t_bsum.ensure((size_t)(c.n_docs / tkz::kScanBlock + 2) * 8, acc));
+        po.doc_piece = ws->p_docp.as<int64_t>();
+    }
+    c.kind = CallKind::Trim; c.pieces = &po; c.trim = &tc; c.special = sc;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (st == TKZ_OK && sc) ++e->spec_batches;
+    return st;
+}
+tkz_status check_trim_args(int32_t side, int64_t max_tokens, bool per_doc) {
+    if (side != TKZ_TRIM_SUFFIX && side != TKZ_TRIM_PREFIX) return fail(TKZ_E_ARG, "side must be TKZ_TRIM_SUFFIX or TKZ_TRIM_PREFIX");
+    if (!per_doc && max_tokens < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                        const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens, const int64_t* d_max_tokens,
+                                        int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets, int64_t* d_cut_bytes, int64_t* d_cut_units,
+                                        void* hip_stream, int64_t* total_tokens) {
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    TKZ_TRY(check_trim_args(side, max_tokens, d_max_tokens != nullptr));
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    // (a call that can keep nothing -- a maximum of 0 -- needs no id buffer)
+    if (!d_doc_offsets || !d_out_offsets || (total_bytes > 0 && !d_bytes) || (out_cap > 0 && !d_out_ids)) return fail(TKZ_E_ARG, "null device buffer");
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    Lease lease(e);
+    return trim_on_device(e, lease.ws, c, TrimCall{side, max_tokens, d_max_tokens, d_cut_bytes, d_cut_units}, plain ? nullptr : &sc, total_tokens);
+}
+
+tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                      int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                      int64_t* cut_bytes, int64_t* cut_units, int64_t* needed) {
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr));
+    if (!out_offsets || (out_cap > 0 && !out_ids) || out_cap < 0) return fail(TKZ_E_ARG, "null output buffer");
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (n_docs < 0 || !doc_offsets || (n_docs > 0 && !bytes && doc_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
+    if (doc_offsets[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
+    const int64_t total = doc_offsets[n_docs];
+    if (total < 0) return fail(TKZ_E_ARG, "negative size");
+    for (int64_t d = 0; total == 0 && d < n_docs; ++d) if (doc_offsets[d] != 0) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count");
+    for (int64_t d = 0; max_tokens_per_doc && d < n_docs; ++d) if (max_tokens_per_doc[d] < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    if (needed) *needed = 0;
+    // the whole batch is staged (as tkz_encode_batch_pieces_utf8 stages it) and the result copied from ONE call of the device entry
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    int64_t* acc = &ws->bytes_allocated;
+    const int64_t cap = std::min<int64_t>(out_cap, total), nd = std::max<int64_t>(n_docs, 1);
+    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
+    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
+    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
+    HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
+    HIP_TRY(ws->t_stage.ensure((size_t)nd * 3 * 8, acc));
+    int64_t* const d_max = ws->t_stage.as<int64_t>(), * const d_cb = d_max + nd, * const d_cu = d_cb + nd;
+    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ws->s_offs[0].p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    if (max_tokens_per_doc && n_docs) HIP_TRY(hipMemcpy(d_max, max_tokens_per_doc, (size_t)n_docs * 8, hipMemcpyHostToDevice));
+    int64_t tokens = 0;
+    BatchCall c{ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr};
+    const tkz_status st = trim_on_device(e, ws, c, TrimCall{side, max_tokens, max_tokens_per_doc ? d_max : nullptr, cut_bytes ? d_cb : nullptr, cut_units ? d_cu : nullptr},
+                                         plain ? nullptr : &sc, &tokens);
+    if (needed) *needed = tokens;
+    if (st != TKZ_OK) return st;
+    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (cut_bytes && n_docs) HIP_TRY(hipMemcpy(cut_bytes, d_cb, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+    if (cut_units && n_docs) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }
 

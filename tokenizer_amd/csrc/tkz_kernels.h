@@ -166,6 +166,21 @@ void launch_u16_write(const Launch& L, const uint16_t* units, int64_t total, con
 // piece granularity: byte offset of every piece (n_pieces + 1 entries) and first piece of every document, from the bitmap
 void launch_piece_index(const Launch& L, const uint64_t* startbits, int64_t nwords, int64_t total, int64_t nsub, const int64_t* ord_base,
                         int64_t n_pieces, int64_t* piece_offs, const int64_t* d_offs, int64_t n_docs, int64_t* doc_piece);
+// EncodeTrimSuffix / EncodeTrimPrefix for a batch (tkz_encode_batch_trim_device): behind the piece-granular launch sequence -- which leaves the untrimmed ids, the
+// byte and token offset of every piece and the first piece of every document in the workspace -- the cut of every document (k_trim_cut), the scan of the kept
+// lengths into out_offs (n_docs + 1 entries; the kept total also goes to *kept_total) and the kept ids, compacted (k_trim_gather, which also counts cut_units).
+// Nothing is written to `out` when the kept total exceeds out_cap.  side: 0 suffix, 1 prefix.  d_max: null (max_tokens holds for all), or a maximum per document
+// (a negative one counts as 0).  keep_lo / keep_n / cut_pos: n_docs entries each, workspace; bsum: n_docs / kScanBlock + 2 entries.  cut_bytes / cut_units: the
+// caller's, either may be null.  counters: the batch's counter block -- with an error bit set there ([0]) the attempt's offsets mean nothing and nothing is gathered.
+struct TrimParams {
+    const uint8_t* bytes; const int64_t* offs; int64_t n_docs, total;
+    const int64_t* doc_piece; const int64_t* piece_boffs; const int64_t* piece_toffs;
+    int32_t side; int64_t max_tokens; const int64_t* d_max;
+    int64_t* keep_lo; int64_t* keep_n; int64_t* cut_pos; int64_t* bsum;
+    int64_t* cut_bytes; int64_t* cut_units;
+    const int32_t* counters;
+};
+void launch_trim(const Launch& L, const TrimParams& R, const int32_t* ids, int64_t ids_cap, int32_t* out, int64_t out_cap, int64_t* out_offs, int64_t* kept_total);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

@@ -2932,6 +2932,133 @@ TKZ_KERNEL(256) void k_doc_piece(const int64_t* offs, int64_t n_docs, int64_t to
 }
 
 // -------------------------------------------------------------------------------------------------
+// EncodeTrimSuffix / EncodeTrimPrefix for a batch (TikTokenizer.cs:288-579), behind the piece-granular launch sequence: the items of a document are its
+// pieces (a taken special-token literal is ONE piece of ONE token: k_lit_fix, k_probe_special), piece_toffs their cumulative token counts.
+//   k_trim_cut      one lane per document: the cut -- an item boundary, found by binary search over the document's range of piece_toffs --, the kept token
+//                   range, the cut's byte position
+//                     suffix: the longest run of leading items whose tokens sum to at most the maximum (every item has a token: the reference's loop, :296-340)
+//                     prefix: everything when the document has at most the maximum; else the items up to the first boundary whose cumulative count reaches
+//                             count - maximum go (TrimPrefix, :470-483)
+//   (k_scan_partials64, k_scan_top, k_scan_final64: the kept lengths -> the kept ids' offsets.  k_scan_partials / k_scan_final with 64-bit counts: a
+//    document of a batch beyond 2^31 bytes may keep more than 2^31 tokens)
+//   k_trim_gather   the kept ids, compacted; the work is dealt out by OUTPUT position, a wavefront per kTrimTile ids (one long document beside thousands of
+//                   short ones is so many tiles, not one lane's loop).  Then cut_units, dealt out by INPUT position: a wavefront per kTrimByteTile bytes of
+//                   text counts the UTF-16 units (a unit per non-continuation byte, one more for a byte >= 0xF0) of what each of its documents has in front
+//                   of its cut and adds them to the document's entry.
+// An attempt whose counter block holds an error bit has offsets that mean nothing (records that did not fit, offsets that do not ascend ...): its result is
+// thrown away by the host, and these kernels leave the caller's ids alone.
+// -------------------------------------------------------------------------------------------------
+constexpr int kTrimTile = 2048, kTrimByteTile = 4096;
+TKZ_KERNEL(256) void k_trim_cut(TrimParams R) {
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    const bool bad = R.counters[0] != 0;
+    for (int64_t d = simt::bid() * simt::nthreads() + simt::tid(); d < R.n_docs; d += stride) {
+        int64_t lo_t = 0, n_t = 0, cut = 0, a = 0;
+        if (!bad) {
+            a = R.offs[d];
+            const int64_t b = R.offs[d + 1], p0 = R.doc_piece[d], p1 = R.doc_piece[d + 1];      // (an empty document: p0 == p1; the last one ends at `total`, piece n_pieces)
+            const int64_t t0 = R.piece_toffs[p0], count = R.piece_toffs[p1] - t0;
+            int64_t m = R.d_max ? R.d_max[d] : R.max_tokens;
+            if (m < 0) m = 0;
+            int64_t k = p0;                                      // the boundary of the cut: in front of piece k
+            if (R.side == 0) {
+                int64_t lo = p0, hi = p1;                        // the last boundary with at most m tokens in front of it (p0 has none)
+                while (lo < hi) { const int64_t mid = lo + (hi - lo + 1) / 2; if (R.piece_toffs[mid] - t0 <= m) lo = mid; else hi = mid - 1; }
+                k = lo; lo_t = t0; n_t = R.piece_toffs[k] - t0;
+            } else {
+                if (count > m) {
+                    const int64_t need = count - m;              // the first boundary with at least `need` tokens in front of it (p1 has count)
+                    int64_t lo = p0, hi = p1;
+                    while (lo < hi) { const int64_t mid = lo + (hi - lo) / 2; if (R.piece_toffs[mid] - t0 >= need) hi = mid; else lo = mid + 1; }
+                    k = lo;
+                }
+                lo_t = R.piece_toffs[k]; n_t = t0 + count - lo_t;
+            }
+            cut = k >= p1 ? b : (k == p0 ? a : R.piece_boffs[k]);
+        }
+        R.keep_lo[d] = lo_t; R.keep_n[d] = n_t > 0 ? n_t : 0; R.cut_pos[d] = cut;
+        if (R.cut_bytes) R.cut_bytes[d] = cut - a;
+        if (R.cut_units) R.cut_units[d] = 0;
+    }
+}
+TKZ_DEV int64_t tkz_shfl64(int64_t v, int src) {
+    const uint32_t lo = simt::shflu((uint32_t)v, src), hi = simt::shflu((uint32_t)((uint64_t)v >> 32), src);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+TKZ_KERNEL(256) void k_scan_partials64(const int64_t* cnt, int64_t n, int64_t* bsum) {
+    TKZ_SHARED int64_t s_w[4];
+    const int64_t i0 = simt::bid() * kScanBlock;
+    int64_t v = 0;
+    for (int j = simt::tid(); j < kScanBlock; j += kThreads) if (i0 + j < n) v += cnt[i0 + j];
+    for (int d = 32; d >= 1; d >>= 1) v += tkz_shfl64(v, simt::lane() ^ d);
+    if (simt::lane() == 0) s_w[simt::wave()] = v;
+    simt::sync();
+    if (simt::tid() == 0) bsum[simt::bid()] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+TKZ_KERNEL(256) void k_scan_final64(const int64_t* cnt, int64_t n, const int64_t* boff, int64_t* base) {
+    TKZ_SHARED int64_t s_w[kThreads / 64];
+    const int lane = simt::lane(), wave = simt::wave();
+    const int64_t i0 = simt::bid() * kScanBlock;
+    constexpr int per = kScanBlock / kThreads;               // each thread owns `per` consecutive entries
+    int64_t local[per], sum = 0;
+    for (int j = 0; j < per; ++j) { const int64_t i = i0 + (int64_t)simt::tid() * per + j; local[j] = i < n ? cnt[i] : 0; sum += local[j]; }
+    int64_t x = sum;                                         // inclusive scan inside the wavefront, then the wavefronts' totals
+    for (int d = 1; d < 64; d <<= 1) { const int64_t y = tkz_shfl64(x, lane - d < 0 ? lane : lane - d); if (lane >= d) x += y; }
+    if (lane == 63) s_w[wave] = x;
+    simt::sync();
+    int64_t run = boff[simt::bid()] + x - sum;
+    for (int w = 0; w < wave; ++w) run += s_w[w];
+    for (int j = 0; j < per; ++j) { const int64_t i = i0 + (int64_t)simt::tid() * per + j; if (i < n) base[i] = run; run += local[j]; }
+}
+// the last entry of the ascending offs[0 .. n] that is <= x (offs[0] <= x < offs[n]); entries that repeat -- empty documents -- give the last of them
+TKZ_DEV int64_t tkz_last_le(const int64_t* offs, int64_t lo, int64_t hi, int64_t x) {
+    while (lo < hi) { const int64_t mid = lo + (hi - lo + 1) / 2; if (offs[mid] <= x) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+TKZ_KERNEL(256) void k_trim_gather(TrimParams R, const int32_t* ids, int64_t ids_cap, const int64_t* out_offs, int32_t* out, int64_t out_cap, int64_t* kept_total) {
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t kept = out_offs[R.n_docs];
+    if (wave0 == 0 && lane == 0) *kept_total = kept;
+    if (R.counters[0] != 0 || kept < 0) return;
+    if (kept <= out_cap) {
+        const int64_t ntile = (kept + kTrimTile - 1) / kTrimTile;
+        for (int64_t t = wave0; t < ntile; t += nwaves) {
+            const int64_t q0 = t * kTrimTile, q1 = q0 + kTrimTile < kept ? q0 + kTrimTile : kept;
+            const int64_t d0 = tkz_last_le(out_offs, 0, R.n_docs - 1, q0), d1 = tkz_last_le(out_offs, d0, R.n_docs - 1, q1 - 1);     // (wave-uniform)
+            const int64_t shift0 = R.keep_lo[d0] - out_offs[d0];
+            for (int64_t q = q0 + lane; q < q1; q += 64) {
+                // a tile inside one document is a straight copy; else every lane finds the document of its id among the tile's
+                int64_t s = shift0 + q;
+                if (d0 != d1) { const int64_t d = tkz_last_le(out_offs, d0, d1, q); s = R.keep_lo[d] + (q - out_offs[d]); }
+                if (s >= 0 && s < ids_cap) tkz_store_nt(out + q, tkz_load_nt(ids + s));
+            }
+        }
+    }
+    if (!R.cut_units) return;
+    const int64_t nbt = (R.total + kTrimByteTile - 1) / kTrimByteTile;
+    for (int64_t t = wave0; t < nbt; t += nwaves) {
+        const int64_t b0 = t * kTrimByteTile, b1 = b0 + kTrimByteTile < R.total ? b0 + kTrimByteTile : R.total;
+        // the documents with bytes in [b0, b1), 64 at a time: a lane reads one document's range, the wavefront then counts the ranges that are not empty one by one
+        const int64_t d0 = tkz_last_le(R.offs, 0, R.n_docs - 1, b0), d1 = tkz_last_le(R.offs, d0, R.n_docs - 1, b1 - 1);
+        for (int64_t dc = d0; dc <= d1; dc += 64) {
+            const int64_t d = dc + lane;
+            int64_t lo = 0, hi = 0;
+            if (d <= d1) { lo = R.offs[d]; hi = R.cut_pos[d]; if (lo < b0) lo = b0; if (hi > b1) hi = b1; }
+            for (uint64_t m = simt::ballot(lo < hi); m; m &= m - 1) {
+                const int src = tkz_ctz64(m);
+                const int64_t rlo = tkz_shfl64(lo, src), rhi = tkz_shfl64(hi, src);
+                int c = 0;
+                for (int64_t i = rlo + lane; i < rhi; i += 64) { const uint32_t x = R.bytes[i]; c += ((x & 0xC0u) != 0x80u ? 1 : 0) + (x >= 0xF0u ? 1 : 0); }
+                int tot;
+                (void)tkz_wave_scan_sum(c, &tot);
+                if (lane == 0 && tot) simt::atomic_add64(reinterpret_cast<unsigned long long*>(R.cut_units + dc + src), (unsigned long long)tot);
+            }
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // Decode for a batch (TikTokenizer.Decode, TikTokenizer.cs:586-604): id -> bytes through the decoder table, ids that are in
 // neither the vocabulary nor the registered special tokens contribute nothing (:591-599), documents concatenated.
 //   k_dec_len      per 1024-id tile (one wavefront, 16 ids per lane): byte length of every id -> tile sum and the exclusive
@@ -3474,6 +3601,17 @@ void launch_piece_index(const Launch& L, const uint64_t* startbits, int64_t nwor
                         int64_t n_pieces, int64_t* piece_offs, const int64_t* d_offs, int64_t n_docs, int64_t* doc_piece) {
     TKZ_LAUNCH(k_piece_index, grid1(cdiv(nsub, kThreads / 64)), kThreads, L.stream, startbits, nwords, total, nsub, ord_base, n_pieces, piece_offs);
     TKZ_LAUNCH(k_doc_piece, grid_for(n_docs + 1), kThreads, L.stream, d_offs, n_docs, total, startbits, ord_base, n_pieces, doc_piece);
+}
+// (outside the profiling brackets, like k_list_stats: tkz.h at tkz_encoder_set_profiling)
+void launch_trim(const Launch& L, const TrimParams& R, const int32_t* ids, int64_t ids_cap, int32_t* out, int64_t out_cap, int64_t* out_offs, int64_t* kept_total) {
+    TKZ_LAUNCH(k_trim_cut, grid_for(R.n_docs), kThreads, L.stream, R);
+    const int64_t nblk = grid1(cdiv(R.n_docs, kScanBlock));
+    TKZ_LAUNCH(k_scan_partials64, nblk, kThreads, L.stream, (const int64_t*)R.keep_n, R.n_docs, R.bsum);
+    TKZ_LAUNCH(k_scan_top, 1, kThreads, L.stream, R.bsum, nblk, out_offs + R.n_docs);
+    TKZ_LAUNCH(k_scan_final64, nblk, kThreads, L.stream, (const int64_t*)R.keep_n, R.n_docs, (const int64_t*)R.bsum, out_offs);
+    // (a wavefront per tile of the larger of the two ranges -- the kept ids are at most the bytes --, grid-strided beyond 2,048 workgroups)
+    const int64_t tiles = cdiv(R.total, kTrimTile), g = cdiv(tiles, kThreads / 64);
+    TKZ_LAUNCH(k_trim_gather, g < 1 ? 1 : (g > 2048 ? 2048 : g), kThreads, L.stream, R, ids, ids_cap, (const int64_t*)out_offs, out, out_cap, kept_total);
 }
 int64_t dec_tiles(int64_t total_ids) { return cdiv(total_ids, kDecTile); }
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum) {

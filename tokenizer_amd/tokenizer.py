@@ -298,9 +298,54 @@ class TikTokenizer:
             raise TypeError("maxTokenCount is required")
         return (a if a else None), int(b)
 
+    def _trim_batch_device(self, texts: Sequence[str], allowed, max_tokens: int, side: int):
+        """The batch on the device's trim entry (tkz_encode_batch_trim_utf8: the literals cut out, the pieces counted, the cut chosen and the kept ids compacted
+        there): a list of (ids, text), or None when the host walk has to do it -- a set of literals the device path does not hold (UnsupportedError), a text
+        with a lone surrogate while a literal holds U+FFFD, a negative maximum (the reference's prefix variant returns the whole text then)."""
+        if max_tokens < 0:
+            return None
+        plain = not allowed or self._special_re is None
+        if not plain and (self._special_on_host or (self._fffd_literal and any(_has_lone_surrogate(t) for t in texts))):
+            return None
+        if not texts:
+            return []
+        segs = [_utf8_like_dotnet(t) for t in texts]
+        offs = np.zeros(len(segs) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+        data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+        names = set(allowed) if not plain else set()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]           # (registration order = the alternation's)
+        try:
+            ids, ooff, _, units = self._encoder.encode_batch_trim(data, offs, index, side, max_tokens)
+        except N.UnsupportedError:
+            self._special_on_host = True
+            return None
+        flat = ids.tolist()
+        drop = side == N.TRIM_PREFIX
+        return [(flat[ooff[d]:ooff[d + 1]], self._utf16_prefix(t, int(units[d]), drop=drop)) for d, t in enumerate(texts)]
+
+    def EncodeTrimSuffixBatch(self, texts: Sequence[str], a, b=None):
+        """EncodeTrimSuffix for every text, in ONE device call: a list of (ids, text).  The two overload shapes of the single-text method."""
+        allowed, max_tokens = self._trim_args(a, b)
+        out = self._trim_batch_device(texts, allowed, max_tokens, N.TRIM_SUFFIX)
+        return out if out is not None else [self._trim_suffix_host(t, allowed, max_tokens) for t in texts]
+
+    def EncodeTrimPrefixBatch(self, texts: Sequence[str], a, b=None):
+        """EncodeTrimPrefix for every text, in ONE device call: a list of (ids, text)."""
+        allowed, max_tokens = self._trim_args(a, b)
+        out = self._trim_batch_device(texts, allowed, max_tokens, N.TRIM_PREFIX)
+        return out if out is not None else [self._trim_prefix_host(t, allowed, max_tokens) for t in texts]
+
     def EncodeTrimSuffix(self, text: str, a, b=None):
         """Token ids and the text they cover, cut after the last piece / special token that still fits maxTokenCount."""
-        allowed, max_tokens = self._trim_args(a, b)
+        return self.EncodeTrimSuffixBatch([text], a, b)[0]
+
+    def EncodeTrimPrefix(self, text: str, a, b=None):
+        """Token ids and the text they cover, cut before the first piece boundary that leaves at most maxTokenCount tokens."""
+        return self.EncodeTrimPrefixBatch([text], a, b)[0]
+
+    # the host walk over _piece_items: the fallback of the batch methods
+    def _trim_suffix_host(self, text: str, allowed, max_tokens: int):
         token_ids: List[int] = []
         token_count = 0
         encode_length = 0
@@ -315,9 +360,7 @@ class TikTokenizer:
                 break                                          # (:340, :356-359, :375-378)
         return token_ids, self._utf16_prefix(text, encode_length)
 
-    def EncodeTrimPrefix(self, text: str, a, b=None):
-        """Token ids and the text they cover, cut before the first piece boundary that leaves at most maxTokenCount tokens."""
-        allowed, max_tokens = self._trim_args(a, b)
+    def _trim_prefix_host(self, text: str, allowed, max_tokens: int):
         token_ids: List[int] = []
         token_count = 0
         encode_length = 0
