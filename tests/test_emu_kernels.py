@@ -69,6 +69,26 @@ def test_golden_splits(lib, vocab):
         assert [int(i) for i in np.nonzero(got[:len(b)])[0]] == [p[0] for p in rec["pieces"]], rec["text"]
 
 
+@pytest.mark.parametrize("table", ["builtin", "v8"])
+@pytest.mark.parametrize("pattern,sequential", [(1, 0), (2, 0), (3, 0), (1, 1), (2, 1), (3, 1)])
+def test_v8_splits(lib, vocab, pattern, sequential, table):
+    """The device pre-tokenizers against the pieces of V8, the TypeScript reference's regex engine (tests/v8_cases.py), under the built-in class table
+    and under V8's own.  A fixed slice of the fixture (the emulator runs one workgroup at a time): every document of up to 4,097 bytes and every
+    tenth short text; the GPU suite runs all of it."""
+    import v8_cases
+    v8_cases.check_splits(vocab, pattern, sequential, table, v8_cases.slice_for_emulator(v8_cases.records(pattern, table)))
+
+
+def test_v8_table_is_what_decides(lib, vocab, oracle_mod):
+    """The "v8" records do depend on the table handed over: left on the built-in one the device cuts some of them differently; one class changed
+    beyond byte 4096 moves bits in that block and nowhere before it."""
+    import v8_cases
+    for pattern in (1, 2, 3):
+        v8_cases.check_table_read_back(vocab, pattern)
+        v8_cases.check_table_is_honoured(vocab, pattern)
+    v8_cases.check_one_class_flipped(vocab, oracle_mod)
+
+
 @pytest.mark.parametrize("sequential", [0, 1])
 def test_hand_derived_splits(lib, vocab, sequential):
     """The device pre-tokenizers against expected pieces written by hand from the regex semantics (tests/hand_splits.py)."""

@@ -62,6 +62,45 @@ def test_pretok_vs_oracle(lib, vocab, oracle_mod, pattern, sequential):
                         doc_lens=[0, 1, 7, 63, 64, 65, 127, 128, 129, 200, 1000, 5000, 9000, 40000], n_docs_choices=(1, 3, 20, 200))
 
 
+@pytest.mark.parametrize("table", ["builtin", "v8"])
+@pytest.mark.parametrize("pattern,sequential", [(1, 0), (2, 0), (3, 0), (1, 1), (2, 1), (3, 1)])
+def test_v8_splits(lib, vocab, pattern, sequential, table):
+    """The device pre-tokenizers against the pieces of V8, the TypeScript reference's regex engine (tests/v8_cases.py): the whole fixture, packed 1, 3
+    and 20 documents to a batch, under the built-in class table and under V8's own."""
+    import v8_cases
+    v8_cases.check_splits(vocab, pattern, sequential, table, v8_cases.records(pattern, table))
+
+
+@pytest.mark.parametrize("pattern", [1, 2, 3])
+def test_v8_table_read_back(lib, vocab, pattern):
+    import v8_cases
+    v8_cases.check_table_read_back(vocab, pattern)
+
+
+@pytest.mark.parametrize("pattern", [1, 2, 3])
+def test_v8_table_is_honoured(lib, vocab, pattern):
+    import v8_cases
+    v8_cases.check_table_is_honoured(vocab, pattern)
+
+
+def test_v8_one_class_flipped(lib, vocab, oracle_mod):
+    import v8_cases
+    v8_cases.check_one_class_flipped(vocab, oracle_mod)
+
+
+@pytest.mark.parametrize("latency_bytes", [None, 0])
+@pytest.mark.parametrize("table", ["builtin", "v8"])
+@pytest.mark.parametrize("pattern", [1, 2, 3])
+def test_v8_ids(lib, vocab, oracle_gpt2, monkeypatch, pattern, table, latency_bytes):
+    """encode_batch under the gpt2 table against Encode restated over V8's pieces (whole-piece rank, else the oracle's byte-pair merge): short documents
+    one per call (the single launch), then the whole fixture in one batch (the multi-kernel path); again with TKZ_LATENCY_BYTES=0, the form of
+    the large batches (test_throughput_setting_on_small_batches)."""
+    import v8_cases
+    if latency_bytes is not None:
+        monkeypatch.setenv("TKZ_LATENCY_BYTES", str(latency_bytes))
+    v8_cases.check_ids(vocab, oracle_gpt2, pattern, table, v8_cases.records(pattern, table), single_docs=150 if latency_bytes is None else 10)
+
+
 @pytest.mark.parametrize("sequential", [0, 1])
 def test_hand_derived_splits(lib, vocab, sequential):
     """The device pre-tokenizers against expected pieces written by hand from the regex semantics (tests/hand_splits.py)."""

@@ -1,7 +1,12 @@
 """The oracle's hand-written split (oracle/tkz_oracle.c) against an independent backtracking regex
 engine (`regex`) fed UTF-16 code units -- see tests/regex_crosscheck.py for how .NET's code-unit
 semantics are emulated.  This is what stands behind the split for cl100k / o200k, whose id-level
-vectors need vocab files the reference downloads (parity "unpinned at id level" without them)."""
+vectors need vocab files the reference downloads (parity "unpinned at id level" without them).
+
+`regex` is OUR emulation of the two engines.  The split of patterns 1, cl100k and o200k is also pinned on V8 itself, the engine the TypeScript
+reference runs (tests/test_oracle_v8.py, fixtures from tests/golden/make_v8_fixtures.py): for o200k, whose defining engine it is, on any well-formed
+text; for pattern 1 and cl100k on the texts where V8's code-point reading and .NET's code-unit reading coincide.  Pattern 4 (o200k through .NET) and
+the UTF-16 entry with lone surrogates are pinned here alone.  Ids stay pinned through the oracle's BPE: the TypeScript tokenizer needs a newer Node."""
 import random
 
 import pytest
