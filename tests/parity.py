@@ -1409,8 +1409,10 @@ def check_utf16(lib, O, vocab, ovocab):
 
 def check_utf16_batch(lib, O, vocab, ovocab, seed=91, rounds=10, doc_counts=(1, 7, 60), max_units=400):
     """tkz_encode_batch_utf16 (code units transcoded ON THE DEVICE) vs the oracle's UTF-16 entry per document, and vs the UTF-8
-    batch entry fed with the bytes Encoding.UTF8.GetBytes would produce.  Surrogate pairs, lone halves, halves that face each
-    other across a document boundary, pairs straddling the 16-unit lane groups and the 1024-unit tiles, empty documents."""
+    batch entry fed with the bytes Encoding.UTF8.GetBytes would produce.  Surrogate pairs and lone halves at RANDOM positions,
+    one high half that faces a low half across a document boundary in about every other batch, empty documents.  Nothing here
+    places a pair or a document start on an edge of the 16-unit lane groups, the 64-bit bitmap words or the 1024-unit tiles: the
+    positioned cases are tests/u16_cases.py's."""
     rng = random.Random(seed)
     alpha = RC.alphabet()
     for pattern in (N.P1, N.CL100K, N.O200K, N.O200K_DOTNET):
