@@ -65,6 +65,13 @@ namespace Microsoft.DeepDev
                                                                                          int* allowed, int nAllowed, int side, long maxTokens, IntPtr dMaxTokens,
                                                                                          IntPtr dOutIds, long outCap, IntPtr dOutOffsets, IntPtr dCutBytes, IntPtr dCutUnits,
                                                                                          IntPtr hipStream, out long totalTokens);
+        // Encode(text, allowedSpecial) / EncodeTrimSuffix / EncodeTrimPrefix on a batch of strings' own chars: the device transcodes, and searches the literals as
+        // .NET searches the string (a lone surrogate is not U+FFFD).  (Like the rest of this file: not compiled here.)
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_special_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                         int* outIds, long outCap, long* outOffsets, out long needed);
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_trim_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                      int side, long maxTokens, long* maxTokensPerDoc, int* outIds, long outCap, long* outOffsets,
+                                                                                      long* cutUnits, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_trim_utf8(IntPtr encoder, byte* bytes, long* docOffsets, long nDocs, int* allowed, int nAllowed,
                                                                                        int side, long maxTokens, long* maxTokensPerDoc, int* outIds, long outCap, long* outOffsets,
                                                                                        long* cutBytes, long* cutUnits, out long needed);
@@ -289,6 +296,13 @@ namespace Microsoft.DeepDev
         public unsafe (int[] Ids, long[] Offsets) EncodeBatchFlat(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial = null)
         {
             bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            // 0. special tokens: the whole texts to the device's UTF-16 special entry, which cuts the allowed literals out itself.  Only a registered set the device
+            //    path does not hold (TKZ_E_UNSUPPORTED, -7) is segmented here, from then on.
+            if (!plain && !specialOnHost)
+            {
+                var onDevice = SpecialBatchOnDevice(texts, allowedSpecial!);
+                if (onDevice.HasValue) return onDevice.Value;
+            }
             // 1. segmentation on the host: (text index, plain segment) and literal special ids, in order
             var plan = new List<(int text, int special, int segment)>();
             var segments = new List<(string text, int start, int end)>(texts.Count);
@@ -549,35 +563,57 @@ namespace Microsoft.DeepDev
             return items;
         }
 
-        // EncodeTrimSuffix / EncodeTrimPrefix for a batch of texts: ONE device call (tkz_encode_batch_trim_utf8 -- the literals cut out, the pieces counted, the cut
-        // chosen and the kept ids compacted on the device; cutUnits is the reference's encodeLength / actualPrefixStrLength).  Returns null when the host walk over
-        // PieceItems has to do it: a registered set the device path does not hold (TKZ_E_UNSUPPORTED, -7), a text with a lone surrogate while a literal holds U+FFFD
-        // (Encoding.UTF8.GetBytes turns it into EF BF BD, which the literal would match on bytes but not in the reference's UTF-16 search), a negative maximum.
+        // the texts' chars in one array (string.CopyTo: no GetBytes on the host), their offsets in code units, the indices of the allowed literals
+        private (char[] Units, long[] Offsets, int[] Allowed, int NAllowed) GatherUnits(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial, bool plain)
+        {
+            var index = new List<int>();                                              // registration order = the alternation's
+            if (!plain) { int i = 0; foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial!.Contains(k)) index.Add(i); ++i; } }
+            var offsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) offsets[t + 1] = offsets[t] + texts[t].Length;
+            var units = new char[Math.Max(1, offsets[texts.Count])];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)offsets[t], texts[t].Length);
+            return (units, offsets, index.Count > 0 ? index.ToArray() : new int[1], index.Count);
+        }
+
+        // Encode(text, allowedSpecial) for a batch: ONE call of tkz_encode_batch_special_utf16 on the strings' own chars.  null: the registered set is beyond the
+        // device path (-7), the host segmentation of EncodeBatchFlat does it from now on.
+        private unsafe (int[] Ids, long[] Offsets)? SpecialBatchOnDevice(IReadOnlyList<string> texts, IReadOnlyCollection<string> allowedSpecial)
+        {
+            var (units, offsets, allowed, nAllowed) = GatherUnits(texts, allowedSpecial, false);
+            var outOffs = new long[texts.Count + 1];
+            long total = offsets[texts.Count], cap = Math.Max(1, Math.Min(3 * total, total / 2 + 4096));     // (a token per two units first; 3 * units always suffice)
+            while (true)
+            {
+                var ids = new int[cap];
+                int st; long needed;
+                fixed (char* pc = units) fixed (long* po = offsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* poo = outOffs)
+                    st = Tkz.tkz_encode_batch_special_utf16(encoder, pc, po, texts.Count, nAllowed > 0 ? pa : null, nAllowed, pi, cap, poo, out needed);
+                if (st == -7) { specialOnHost = true; return null; }
+                if (st == -4 /* TKZ_E_CAPACITY */ && needed > cap) { cap = needed; continue; }
+                Tkz.Check(st);
+                GC.KeepAlive(this);
+                return (ids, outOffs);
+            }
+        }
+
+        // EncodeTrimSuffix / EncodeTrimPrefix for a batch of texts: ONE device call (tkz_encode_batch_trim_utf16 on the strings' own chars -- transcoded, the literals
+        // cut out, the pieces counted, the cut chosen and the kept ids compacted on the device; cutUnits is the reference's encodeLength / actualPrefixStrLength).
+        // Returns null when the host walk over PieceItems has to do it: a registered set the device path does not hold (TKZ_E_UNSUPPORTED, -7), a negative maximum.
+        // (A lone surrogate under a literal that holds U+FFFD needs no host route any more: the device knows which U+FFFD it wrote itself.)
         private bool specialOnHost;
         private unsafe List<(List<int> TokenIds, string Text)>? TrimBatchOnDevice(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount, int side)
         {
             bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
             if (maxTokenCount < 0 || (!plain && specialOnHost)) return null;
-            if (!plain && specialTokensEncoder.Keys.Any(k => k.IndexOf('\uFFFD') >= 0))
-                foreach (string t in texts)
-                    for (int i = 0; i < t.Length; ++i)
-                        if (char.IsSurrogate(t[i]) && !(char.IsHighSurrogate(t[i]) && i + 1 < t.Length && char.IsLowSurrogate(t[i + 1])) && !(char.IsLowSurrogate(t[i]) && i > 0 && char.IsHighSurrogate(t[i - 1])))
-                            return null;
             var result = new List<(List<int> TokenIds, string Text)>(texts.Count);
             if (texts.Count == 0) return result;
-            var index = new List<int>();                                              // registration order = the alternation's
-            if (!plain) { int i = 0; foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial!.Contains(k)) index.Add(i); ++i; } }
-            var offsets = new long[texts.Count + 1];
-            for (int t = 0; t < texts.Count; ++t) offsets[t + 1] = offsets[t] + Encoding.UTF8.GetByteCount(texts[t]);
+            var (units, offsets, allowed, nAllowed) = GatherUnits(texts, allowedSpecial, plain);
             long total = offsets[texts.Count];
-            var bytes = new byte[Math.Max(1, total)];
-            for (int t = 0; t < texts.Count; ++t) Encoding.UTF8.GetBytes(texts[t], 0, texts[t].Length, bytes, (int)offsets[t]);
-            long cap = Math.Min(total, (long)texts.Count * maxTokenCount);            // (tkz.h: always sufficient)
+            long cap = Math.Min(3 * total, (long)texts.Count * maxTokenCount);        // (tkz.h: always sufficient)
             var ids = new int[Math.Max(1, cap)]; var outOffs = new long[texts.Count + 1]; var cutUnits = new long[texts.Count];
-            var allowed = index.Count > 0 ? index.ToArray() : new int[1];
             int st;
-            fixed (byte* pb = bytes) fixed (long* po = offsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* poo = outOffs) fixed (long* pu = cutUnits)
-                st = Tkz.tkz_encode_batch_trim_utf8(encoder, pb, po, texts.Count, index.Count > 0 ? pa : null, index.Count, side, maxTokenCount, null, pi, cap, poo, null, pu, out _);
+            fixed (char* pc = units) fixed (long* po = offsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* poo = outOffs) fixed (long* pu = cutUnits)
+                st = Tkz.tkz_encode_batch_trim_utf16(encoder, pc, po, texts.Count, nAllowed > 0 ? pa : null, nAllowed, side, maxTokenCount, null, pi, cap, poo, pu, out _);
             if (st == -7) { specialOnHost = true; return null; }
             Tkz.Check(st);
             for (int t = 0; t < texts.Count; ++t)

@@ -197,6 +197,26 @@ tkz_status tkz_encode_batch_utf16(tkz_encoder* e, const uint16_t* units, const i
                                   int64_t n_docs, int32_t* out_ids, int64_t out_cap,
                                   int64_t* out_offsets, int64_t* needed);
 
+/* The special and the trim entries for UTF-16 hosts: every document is encoded or trimmed exactly as ITokenizer.Encode(text, allowedSpecial) /
+ * EncodeTrimSuffix(...) / EncodeTrimPrefix(...) treat the .NET `string` whose code units it is.  The transcode is the device's, as in tkz_encode_batch_utf16, and
+ * the literal search reads what .NET reads: FindNextSpecialToken searches the UTF-16 string, where a lone surrogate -- a high half without its low half, a low
+ * half without its high half, either half of a pair a document boundary cuts -- is NOT U+FFFD, although its bytes after the transcode are EF BF BD.  The
+ * transcoder therefore marks every U+FFFD it wrote itself; a registered literal that holds U+FFFD does not match over such a byte and the alternation goes on to
+ * the next registered literal (a U+FFFD that is in the string matches as ever).  With no such literal registered nothing is marked and nothing is read.
+ *   tkz_encode_batch_special_utf16: allowed / n_allowed, TKZ_E_ARG, TKZ_E_UNSUPPORTED and tkz_encoder_special_stats as tkz_encode_batch_special_utf8; buffers,
+ *     chunks (document ranges: no literal is cut), page-locked fast paths and results as tkz_encode_batch_utf16, which it IS when n_allowed == 0 or nothing is
+ *     registered.  out_cap >= 3 * total units is always sufficient.
+ *   tkz_encode_batch_trim_utf16: side, max_tokens, max_tokens_per_doc (a HOST array, a negative entry is TKZ_E_ARG), out_cap (the KEPT ids), TKZ_E_CAPACITY with
+ *     *needed and every other error as tkz_encode_batch_trim_utf8.  cut_units[d] (n_docs entries, may be NULL): the reference's encodeLength /
+ *     actualPrefixStrLength, i.e. the kept (suffix) or dropped (prefix) text is the first cut_units[d] code units of document d; a replaced surrogate counts as the
+ *     one unit it is.  There is no cut_bytes: the bytes never exist on the host.  The WHOLE batch is staged and transcoded on the device, then ONE trim call.
+ * Host buffers.  No code units (all offsets 0): zero offsets and zero cut_units. */
+tkz_status tkz_encode_batch_special_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed,
+                                          int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed);
+tkz_status tkz_encode_batch_trim_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                       int64_t* cut_units, int64_t* needed);
+
 /* Single-string entries for `string` callers.  UTF-16: the split sees the code units as .NET's Regex
  * does (a supplementary-plane char is two "other" units, a lone surrogate one); each piece is
  * converted as Encoding.UTF8.GetBytes does (lone surrogate -> EF BF BD), TikTokenizer.cs:261. */

@@ -6,7 +6,8 @@
 //                              EncodeTrimSuffix / EncodeTrimPrefix x2   ITokenizer.cs:30-44, TikTokenizer.cs:288-579
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
-// Text is UTF-8 (std::string); EncodeUtf16 takes the code units of a .NET string.  Special-token
+// Text is UTF-8 (std::string); the ...Utf16 methods take the code units of a .NET string (std::u16string) and hand them to the device's UTF-16 entries,
+// special tokens and trimming included (tkz_encode_batch_special_utf16 / tkz_encode_batch_trim_utf16).  Special-token
 // segmentation (EncodeInternal / FindNextSpecialToken, TikTokenizer.cs:141-170,230-241) runs on the host and
 // every plain segment of a batch goes to the GPU in ONE tkz_encode_batch_utf8 call.  Errors are exceptions
 // named after the reference's: FormatException -> tkz::FormatError, ArgumentException -> tkz::DuplicateRankError,
@@ -213,7 +214,9 @@ public:
     // what bindings/csharp/GpuTikTokenizer.EncodeBatchFlat does with `string.CopyTo` + tkz_encode_batch_utf16.  The units are gathered into
     // page-locked memory by `threads` host threads, uploaded as they are (the library cuts the batch into chunks and runs Encoding.UTF8.GetBytes
     // -- TikTokenizer.cs:261 -- on the device while the next chunk is on its way) and the ids come back into page-locked memory.
-    void EncodeBatchFlatUtf16(const std::vector<std::u16string>& texts, FlatBatch& out, int threads = 0) const {
+    void EncodeBatchFlatUtf16(const std::vector<std::u16string>& texts, FlatBatch& out, int threads = 0) const { (void)flat_utf16(texts, out, threads, nullptr); }
+    // allowed: null, or the indices of the allowed special tokens (tkz_encode_batch_special_utf16); false (nothing encoded): that entry refused the registered set
+    bool flat_utf16(const std::vector<std::u16string>& texts, FlatBatch& out, int threads, const std::vector<int32_t>* allowed) const {
         const int64_t n = static_cast<int64_t>(texts.size());
         out.n_texts_ = n;
         int nth = threads > 0 ? threads : static_cast<int>(std::min<int64_t>(16, n >> 14));
@@ -241,13 +244,16 @@ public:
         for (;;) {
             int32_t* ids = static_cast<int32_t*>(out.out_ids_.ensure(static_cast<size_t>(cap) * 4));
             int64_t needed = 0;
-            const tkz_status st = tkz_encode_batch_utf16(enc_, units, offs, n, ids, cap, ooff, &needed);
+            const tkz_status st = allowed ? tkz_encode_batch_special_utf16(enc_, units, offs, n, allowed->data(), static_cast<int32_t>(allowed->size()), ids, cap, ooff, &needed)
+                                          : tkz_encode_batch_utf16(enc_, units, offs, n, ids, cap, ooff, &needed);
+            if (allowed && st == TKZ_E_UNSUPPORTED) return false;
             if (st == TKZ_E_CAPACITY && needed > cap) { cap = needed; continue; }
             check(st);
             if (total > 0) out.tokens_per_byte_ = std::max(out.tokens_per_byte_, static_cast<double>(needed) / static_cast<double>(total));
             break;
         }
         out.ids_ = out.out_ids_.as<int32_t>(); out.offsets_ = out.out_offs_.as<int64_t>();
+        return true;
     }
 
     using Trimmed = std::pair<std::vector<int32_t>, std::string>;   // (List<int> TokenIds, string Text)
@@ -339,6 +345,83 @@ public:
         ids.resize(static_cast<size_t>(n));
         return ids;
     }
+    // ---- std::u16string callers: special tokens and trimming on the code units themselves (tkz_encode_batch_special_utf16 / tkz_encode_batch_trim_utf16) ----
+    // The device transcodes, and searches the literals as .NET searches the string: a lone surrogate is not U+FFFD.  With a registered set the device path does
+    // not hold (TKZ_E_UNSUPPORTED), and for a negative maximum, the host walk over piece_items16() below does the work, as the UTF-8 methods' does.
+    using Trimmed16 = std::pair<std::vector<int32_t>, std::u16string>;
+    void EncodeBatchFlatUtf16(const std::vector<std::u16string>& texts, bool applySpecialTokens, FlatBatch& out, int threads = 0) const {
+        EncodeBatchFlatUtf16(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{}, out, threads);
+    }
+    void EncodeBatchFlatUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, FlatBatch& out, int threads = 0) const {
+        if (allowedSpecial.empty() || specials_.empty()) { EncodeBatchFlatUtf16(texts, out, threads); return; }
+        if (!special_on_host_) {
+            const std::vector<int32_t> index = allowed_index(allowedSpecial);
+            if (flat_utf16(texts, out, threads, &index)) return;
+            special_on_host_ = true;
+        }
+        out.n_texts_ = static_cast<int64_t>(texts.size());
+        out.spliced_ids_.clear();
+        out.spliced_offs_.assign(1, 0);
+        for (const std::u16string& t : texts) {
+            const std::vector<int32_t> ids = encode_host16(t, allowedSpecial);
+            out.spliced_ids_.insert(out.spliced_ids_.end(), ids.begin(), ids.end());
+            out.spliced_offs_.push_back(static_cast<int64_t>(out.spliced_ids_.size()));
+        }
+        out.ids_ = out.spliced_ids_.data(); out.offsets_ = out.spliced_offs_.data();
+    }
+    std::vector<std::vector<int32_t>> EncodeBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial) const {
+        FlatBatch fb;
+        EncodeBatchFlatUtf16(texts, allowedSpecial, fb, 1);
+        std::vector<std::vector<int32_t>> out(texts.size());
+        for (size_t t = 0; t < texts.size(); ++t) out[t] = fb.text(static_cast<int64_t>(t));
+        return out;
+    }
+    std::vector<int32_t> EncodeUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const { return EncodeBatchUtf16({text}, allowedSpecial)[0]; }
+    std::vector<Trimmed16> EncodeTrimSuffixBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<Trimmed16> out;
+        if (trim_batch_device16(texts, allowedSpecial, maxTokenCount, TKZ_TRIM_SUFFIX, out)) return out;
+        for (const std::u16string& t : texts) out.push_back(trim_suffix_host16(t, allowedSpecial, maxTokenCount));
+        return out;
+    }
+    std::vector<Trimmed16> EncodeTrimPrefixBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<Trimmed16> out;
+        if (trim_batch_device16(texts, allowedSpecial, maxTokenCount, TKZ_TRIM_PREFIX, out)) return out;
+        for (const std::u16string& t : texts) out.push_back(trim_prefix_host16(t, allowedSpecial, maxTokenCount));
+        return out;
+    }
+    // the host walk (the reference's loops over the string's code units): Encode, EncodeTrimSuffix, EncodeTrimPrefix
+    std::vector<int32_t> encode_host16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const {
+        std::vector<int32_t> ids;
+        for (const PieceItem& it : piece_items16(text, allowedSpecial)) ids.insert(ids.end(), it.ids.begin(), it.ids.end());
+        return ids;
+    }
+    Trimmed16 trim_suffix_host16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<int32_t> ids;
+        int64_t tokenCount = 0; size_t encodeLength = 0;
+        for (const PieceItem& it : piece_items16(text, allowedSpecial)) {
+            tokenCount += static_cast<int64_t>(it.ids.size());
+            if (tokenCount > maxTokenCount) break;
+            ids.insert(ids.end(), it.ids.begin(), it.ids.end());
+            encodeLength = it.end;
+            if (tokenCount >= maxTokenCount) break;
+        }
+        return {ids, text.substr(0, encodeLength)};
+    }
+    Trimmed16 trim_prefix_host16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<int32_t> ids;
+        std::vector<std::pair<int64_t, size_t>> boundaries{{0, 0}};
+        int64_t tokenCount = 0;
+        for (const PieceItem& it : piece_items16(text, allowedSpecial)) {
+            tokenCount += static_cast<int64_t>(it.ids.size());
+            ids.insert(ids.end(), it.ids.begin(), it.ids.end());
+            boundaries.push_back({tokenCount, it.end});
+        }
+        if (tokenCount <= maxTokenCount) return {ids, text};
+        const int64_t prefix = tokenCount - maxTokenCount;
+        int64_t cutTokens = 0; size_t cutLen = 0;
+        for (const auto& b : boundaries) if (b.first >= prefix) { cutTokens = b.first; cutLen = b.second; break; }
+        return {std::vector<int32_t>(ids.begin() + cutTokens, ids.end()), text.substr(cutLen)};
+    }
     tkz_encoder* native() const { return enc_; }
     // the device workspace of batches of up to max_bytes / max_docs, allocated now instead of inside the first batch call (tkz_encoder_reserve): what
     // TokenizerBuilder.CreateTokenizer (TokenizerBuilder.cs:210-213) is for a drop-in -- construction pays, not the first Encode
@@ -384,6 +467,93 @@ private:
         std::vector<std::string> all;
         for (const auto& s : specials_) all.push_back(s.first);
         return all;
+    }
+    std::vector<int32_t> allowed_index(const std::vector<std::string>& allowedSpecial) const {
+        std::vector<int32_t> index;
+        for (size_t i = 0; i < specials_.size(); ++i)
+            for (const auto& al : allowedSpecial) if (al == specials_[i].first) { index.push_back(static_cast<int32_t>(i)); break; }
+        return index;
+    }
+    // well-formed UTF-8 -> UTF-16 (the registered literals), UTF-16 -> UTF-8 as Encoding.UTF8.GetBytes (a lone surrogate becomes EF BF BD)
+    static std::u16string to_utf16(const std::string& s8) {
+        std::u16string o;
+        for (size_t i = 0; i < s8.size();) {
+            const uint8_t c = static_cast<uint8_t>(s8[i]);
+            const int len = c < 0x80 ? 1 : c < 0xE0 ? 2 : c < 0xF0 ? 3 : 4;
+            uint32_t cp = len == 1 ? c : c & (0xFFu >> (len + 1));
+            for (int k = 1; k < len && i + k < s8.size(); ++k) cp = (cp << 6) | (static_cast<uint8_t>(s8[i + k]) & 0x3Fu);
+            if (cp >= 0x10000) { cp -= 0x10000; o.push_back(static_cast<char16_t>(0xD800 + (cp >> 10))); o.push_back(static_cast<char16_t>(0xDC00 + (cp & 0x3FF))); }
+            else o.push_back(static_cast<char16_t>(cp));
+            i += static_cast<size_t>(len);
+        }
+        return o;
+    }
+    static void append_utf8(const std::u16string& t, size_t begin, size_t end, std::vector<uint8_t>& o) {
+        for (size_t i = begin; i < end; ++i) {
+            uint32_t c = t[i];
+            if (c >= 0xD800 && c <= 0xDBFF && i + 1 < end && t[i + 1] >= 0xDC00 && t[i + 1] <= 0xDFFF) { c = 0x10000 + ((c - 0xD800) << 10) + (t[i + 1] - 0xDC00); ++i; }
+            else if (c >= 0xD800 && c <= 0xDFFF) c = 0xFFFD;
+            if (c < 0x80) o.push_back(static_cast<uint8_t>(c));
+            else if (c < 0x800) { o.push_back(static_cast<uint8_t>(0xC0 | (c >> 6))); o.push_back(static_cast<uint8_t>(0x80 | (c & 0x3F))); }
+            else if (c < 0x10000) { o.push_back(static_cast<uint8_t>(0xE0 | (c >> 12))); o.push_back(static_cast<uint8_t>(0x80 | ((c >> 6) & 0x3F))); o.push_back(static_cast<uint8_t>(0x80 | (c & 0x3F))); }
+            else { o.push_back(static_cast<uint8_t>(0xF0 | (c >> 18))); o.push_back(static_cast<uint8_t>(0x80 | ((c >> 12) & 0x3F))); o.push_back(static_cast<uint8_t>(0x80 | ((c >> 6) & 0x3F))); o.push_back(static_cast<uint8_t>(0x80 | (c & 0x3F))); }
+        }
+    }
+    // EncodeInternal + FindNextSpecialToken on the code units: a literal matches where the string's units are the literal's
+    std::vector<Segment> segments16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const {
+        std::vector<std::u16string> lits;
+        for (const auto& sp : specials_) lits.push_back(to_utf16(sp.first));
+        auto match_at16 = [&](size_t p) { for (size_t i = 0; i < lits.size(); ++i) if (!lits[i].empty() && text.compare(p, lits[i].size(), lits[i]) == 0) return static_cast<int>(i); return -1; };
+        std::vector<Segment> out;
+        size_t start = 0;
+        for (;;) {
+            size_t hit_pos = std::u16string::npos; int hit = -1;
+            if (!allowedSpecial.empty()) {
+                for (size_t find = start;;) {
+                    hit = -1;
+                    size_t p = find;
+                    for (; p < text.size(); ++p) { hit = match_at16(p); if (hit >= 0) break; }
+                    if (hit < 0) break;
+                    bool ok = false;
+                    for (const auto& al : allowedSpecial) if (al == specials_[static_cast<size_t>(hit)].first) { ok = true; break; }
+                    if (ok) { hit_pos = p; break; }
+                    find = p + 1;                                       // startFind = nextSpecial.Index + 1
+                }
+            }
+            const size_t end = hit >= 0 ? hit_pos : text.size();
+            if (end > start) out.push_back({false, 0, start, end});
+            if (hit < 0) break;
+            out.push_back({true, specials_[static_cast<size_t>(hit)].second, hit_pos, hit_pos + lits[static_cast<size_t>(hit)].size()});
+            start = hit_pos + lits[static_cast<size_t>(hit)].size();
+            if (start >= text.size()) break;
+        }
+        return out;
+    }
+    // one item per regex piece of every plain segment and one per special token: its ids and the UNIT position where it ends (PieceItem below)
+    bool trim_batch_device16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int32_t side, std::vector<Trimmed16>& out) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (maxTokenCount < 0 || (!plain && special_on_host_)) return false;
+        const int64_t n = static_cast<int64_t>(texts.size());
+        if (n == 0) return true;
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const std::u16string& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        const int64_t total = offs[static_cast<size_t>(n)];
+        const int64_t cap = std::min<int64_t>(3 * total, n * static_cast<int64_t>(maxTokenCount));
+        std::vector<int32_t> ids(static_cast<size_t>(cap) + 1);
+        std::vector<int64_t> ooff(static_cast<size_t>(n) + 1, 0), cut(static_cast<size_t>(n), 0);
+        int64_t needed = 0;
+        if (units.empty()) units.push_back(0);
+        const tkz_status st = tkz_encode_batch_trim_utf16(enc_, units.data(), offs.data(), n, index.empty() ? nullptr : index.data(), static_cast<int32_t>(index.size()), side,
+                                                          maxTokenCount, nullptr, ids.data(), cap, ooff.data(), cut.data(), &needed);
+        if (st == TKZ_E_UNSUPPORTED) { special_on_host_ = true; return false; }
+        check(st);
+        for (size_t t = 0; t < texts.size(); ++t) {
+            const size_t c = static_cast<size_t>(cut[t]);             // code units of the kept text (suffix) / of the dropped text (prefix)
+            out.push_back({std::vector<int32_t>(ids.begin() + ooff[t], ids.begin() + ooff[t + 1]), side == TKZ_TRIM_SUFFIX ? texts[t].substr(0, c) : texts[t].substr(c)});
+        }
+        return true;
     }
     // the batch on the device's trim entry; false (nothing done): the host walk has to do it
     bool trim_batch_device(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int32_t side, std::vector<Trimmed>& out) const {
@@ -437,6 +607,36 @@ private:
             for (int64_t p = dpo[k]; p < dpo[k + 1]; ++p)
                 out.push_back({std::vector<int32_t>(ids.begin() + pto[p], ids.begin() + pto[p + 1]),
                                g.begin + static_cast<size_t>(pbo[p + 1] - offs[k])});
+            ++k;
+        }
+        return out;
+    }
+    // the same over code units: every plain segment is transcoded here as GetBytes does, its pieces come from the piece-granular entry, and a piece's end
+    // goes back to units (one per non-continuation byte, one more per 4-byte char)
+    std::vector<PieceItem> piece_items16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const {
+        const std::vector<Segment> segs = segments16(text, allowedSpecial);
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const Segment& g : segs)
+            if (!g.special) { append_utf8(text, g.begin, g.end, bytes); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        const int64_t nseg = static_cast<int64_t>(offs.size()) - 1;
+        const size_t cap = bytes.size() ? bytes.size() : 1;
+        std::vector<int32_t> ids(cap);
+        std::vector<int64_t> dpo(static_cast<size_t>(nseg) + 1, 0), pbo(cap + 1, 0), pto(cap + 1, 0);
+        int64_t npieces = 0, needed = 0;
+        if (bytes.empty()) bytes.push_back(0);
+        check(tkz_encode_batch_pieces_utf8(enc_, bytes.data(), offs.data(), nseg, ids.data(), static_cast<int64_t>(cap), dpo.data(), pbo.data(),
+                                           pto.data(), static_cast<int64_t>(cap), &npieces, &needed));
+        std::vector<PieceItem> out;
+        int64_t k = 0;
+        for (const Segment& g : segs) {
+            if (g.special) { out.push_back({{g.id}, g.end}); continue; }
+            size_t unit = g.begin;
+            int64_t b = offs[k];
+            for (int64_t p = dpo[k]; p < dpo[k + 1]; ++p) {
+                for (; b < pbo[p + 1]; ++b) unit += ((bytes[static_cast<size_t>(b)] & 0xC0) != 0x80 ? 1u : 0u) + (bytes[static_cast<size_t>(b)] >= 0xF0 ? 1u : 0u);
+                out.push_back({std::vector<int32_t>(ids.begin() + pto[p], ids.begin() + pto[p + 1]), unit});
+            }
             ++k;
         }
         return out;

@@ -149,6 +149,8 @@ class Library:
         L.tkz_encode_batch_special_utf8.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, pi64]
         L.tkz_encode_batch_trim_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i64, vp, vp, i64, vp, vp, vp, vp, pi64]
         L.tkz_encode_batch_trim_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, vp, vp, i64, vp, vp, vp, pi64]
+        L.tkz_encode_batch_special_utf16.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, pi64]
+        L.tkz_encode_batch_trim_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i64, vp, vp, i64, vp, vp, pi64]
         L.tkz_encoder_special_stats.argtypes = [vp, pi64, pi64]
         L.tkz_encoder_special_stats.restype = None
         L.tkz_decode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
@@ -447,6 +449,59 @@ class Encoder:
         buf = units if len(units) else np.zeros(1, np.uint16)
         self.lib.check(self.lib.L.tkz_encode_batch_utf16(self._h, _ptr(buf), _ptr(offsets), n, _ptr(ids), cap, _ptr(ooff), C.byref(needed)))
         return ids[:needed.value], ooff[:n + 1]
+
+    def encode_batch_special_utf16(self, units: np.ndarray, offsets: np.ndarray, allowed_index, out=None, out_cap=None):
+        """ITokenizer.Encode(text, allowedSpecial) for a batch of UTF-16 documents (uint16[total], offsets int64[n+1] in units): transcoded on the device, the
+        literals searched as .NET searches the string (a lone surrogate is not U+FFFD).  allowed_index as in encode_batch_special.  (ids, offsets)."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed_index, dtype=np.int32)
+        n = len(offsets) - 1
+        if out is not None:
+            ids, ooff = out
+            assert ids.dtype == np.int32 and ooff.dtype == np.int64 and ids.flags.c_contiguous and ooff.flags.c_contiguous and len(ooff) >= n + 1
+            cap = len(ids)
+        else:
+            cap = 3 * len(units) if out_cap is None else out_cap
+            ids = np.empty(max(1, cap), np.int32)
+            ooff = np.empty(n + 1, np.int64)
+        needed = C.c_int64(0)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_special_utf16(self._h, _ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                                     _ptr(ids), cap, _ptr(ooff), C.byref(needed)))
+        except TkzError as ex:
+            ex.needed = needed.value                          # (E_CAPACITY: the total)
+            raise
+        return ids[:needed.value], ooff[:n + 1]
+
+    def encode_batch_trim_utf16(self, units: np.ndarray, offsets: np.ndarray, allowed_index, side, max_tokens, per_doc=None, out_cap=None):
+        """encode_batch_trim for UTF-16 documents: (kept ids int32, offsets int64[n+1], cut_units int64[n]) -- the kept (suffix) or dropped (prefix) text of
+        document d is its first cut_units[d] code units."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed_index, dtype=np.int32)
+        n = len(offsets) - 1
+        if per_doc is not None:
+            per_doc = np.ascontiguousarray(per_doc, dtype=np.int64)
+            assert len(per_doc) == n
+            bound = int(np.minimum(np.maximum(per_doc, 0), 3 * np.diff(offsets)).sum()) if n else 0
+        else:
+            bound = min(3 * len(units), n * max(int(max_tokens), 0))
+        cap = bound if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        ooff = np.empty(n + 1, np.int64)
+        cu = np.zeros(max(1, n), np.int64)
+        needed = C.c_int64(0)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_trim_utf16(self._h, _ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                                  int(side), int(max_tokens), _ptr(per_doc) if per_doc is not None and n else None,
+                                                                  _ptr(ids), cap, _ptr(ooff), _ptr(cu), C.byref(needed)))
+        except TkzError as ex:
+            ex.needed = needed.value                          # (E_CAPACITY: the kept total)
+            raise
+        return ids[:needed.value], ooff, cu[:n]
 
     def encode_pieces(self, data: np.ndarray, offsets: np.ndarray):
         data = np.ascontiguousarray(data, dtype=np.uint8)

@@ -146,7 +146,10 @@ struct Workspace {
     // measured while chunk k is encoded), the UTF-8 batch they become
     struct U16Stage {
         DevBuf units, offs, docbits, grp, tsum, tbase, bsum, counters, boffs; struct Host { int32_t err; int32_t pad; int64_t grand; }* h = nullptr;
-        hipError_t ensure(int64_t max_units, int64_t max_docs, int64_t* acc) {      // room for a chunk of max_units code units in max_docs documents
+        DevBuf repl;       // the replaced-byte bitmap of the chunk's UTF-8 bytes (k_u16_write): special calls with a registered literal that holds U+FFFD only
+        static size_t repl_bytes(int64_t n_bytes) { return (size_t)(n_bytes / 64 + 8) * 8; }
+        hipError_t ensure(int64_t max_units, int64_t max_docs, int64_t* acc, bool with_repl = false) {      // room for a chunk of max_units code units in max_docs documents
+            if (with_repl) { const hipError_t r = repl.ensure(repl_bytes(3 * max_units), acc); if (r != hipSuccess) return r; }      // (a unit is at most three bytes)
             const int64_t nw = max_units / 64 + 1, nt = tkz::u16_tiles(max_units), nblk = (nt + tkz::kScanBlock - 1) / tkz::kScanBlock;
             const std::pair<DevBuf*, size_t> want[] = {{&units, (size_t)(max_units + 64) * 2}, {&offs, (size_t)(max_docs + 1) * 8}, {&docbits, (size_t)(nw + 8) * 8},
                                                        {&grp, (size_t)nt * 64 * 4}, {&tsum, (size_t)nt * 4}, {&tbase, (size_t)nt * 8}, {&bsum, (size_t)(nblk + 1) * 8},
@@ -155,7 +158,7 @@ struct Workspace {
             return h ? hipSuccess : hipHostMalloc((void**)&h, 64, 0);
         }
         void release() {
-            for (DevBuf* b : {&units, &offs, &docbits, &grp, &tsum, &tbase, &bsum, &counters, &boffs}) b->release();
+            for (DevBuf* b : {&units, &offs, &docbits, &grp, &tsum, &tbase, &bsum, &counters, &boffs, &repl}) b->release();
             if (h) (void)hipHostFree(h);
             h = nullptr;
         }
@@ -234,6 +237,7 @@ struct tkz_encoder {
     DevBuf t_lit;
     tkz::TkzLitTable LIT{};
     int lit_state = 0;
+    bool lit_fffd = false;                 // a registered literal holds U+FFFD (TkzLitTable's second 256-bit set is not empty)
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
     int64_t bytes_allocated = 0;           // tables
@@ -273,7 +277,7 @@ std::atomic<int> g_fork_in_flight{0};
 // ---- what one call asks for: filled once by its entry point, handed down as it is ----------------------------------------------------------
 
 // A call of one of the special entries: which registered literals it allows (special_call).  It lives in the entry's frame for the length of the call.
-struct SpecialCall { tkz::TkzLitAllowed allowed; };
+struct SpecialCall { tkz::TkzLitAllowed allowed; bool fffd = false; };      // fffd: a registered literal holds U+FFFD (a UTF-16 entry then keeps the replaced-byte bitmap)
 // where the piece-granular entry point wants its arrays (all on the device)
 struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
 // A call of one of the trim entries: the side, the maximum (uniform, or one per document on the device) and where the cut of every document goes (device, may be null)
@@ -302,6 +306,7 @@ struct BatchCall {
     const TrimCall* trim = nullptr;            // Trim: what to keep (pieces then points at the workspace's piece arrays)
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
+    const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
     bool pretokenizes() const { return kind != CallKind::OnePiecePerDoc; }
     bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
@@ -462,6 +467,7 @@ tkz_status build_literal_table(tkz_encoder* e) {
     using namespace tkz;
     e->LIT = TkzLitTable{};
     e->lit_state = 0;
+    e->lit_fffd = false;
     e->lit_why.clear();
     const auto& sp = e->dec_special;
     if (sp.empty()) return TKZ_OK;
@@ -477,6 +483,7 @@ tkz_status build_literal_table(tkz_encoder* e) {
         if (sp[i].first < 0 || (uint32_t)sp[i].first >= kPromoFlag) return refuse("a special-token id outside [0, 2^26) is registered: a piece record cannot hold it");
         const unsigned c = (unsigned char)lit[0];
         img[c >> 5] |= 1u << (c & 31);
+        if (lit.find("\xEF\xBF\xBD") != std::string::npos) { img[kLitFffdHead + (i >> 5)] |= 1u << (i & 31); e->lit_fffd = true; }
         img[kLitMetaHead + 2 * i] = (uint32_t)blob.size() | ((uint32_t)lit.size() << 16);
         img[kLitMetaHead + 2 * i + 1] = (uint32_t)sp[i].first;
         blob += lit;
@@ -842,7 +849,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
         if (special) {
             for (DevBuf* b : {&ws->w_candbits, &ws->w_segbits, &ws->w_specbits, &ws->w_endbits}) HIP_TRY(b->ensure((size_t)(nwords + 8) * 8, &ws->bytes_allocated));
             launch_lit_scan(L, d_bytes, total, docbits, nwords, e->LIT, special->allowed, ws->w_candbits.as<uint64_t>(), ws->w_segbits.as<uint64_t>(),
-                            ws->w_specbits.as<uint64_t>(), ws->w_endbits.as<uint64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, n_literals)));
+                            ws->w_specbits.as<uint64_t>(), ws->w_endbits.as<uint64_t>(), reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, n_literals)), c.d_repl);
             isobits = ws->w_segbits.as<uint64_t>();
             if (e->pretok_seq || e->pattern == TKZ_PATTERN_O200K || e->pattern == TKZ_PATTERN_O200K_DOTNET) {
                 // (how many segments there are is known on the device only: one wait, as the piece-granular entry has it)
@@ -900,7 +907,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             P.long_log = e->t_long_log.as<uint32_t>(); P.long_log_cap = (int32_t)kLongLogCap; P.long_log_sparse = T.memo_hits_sparse ? 1 : 0;
             P.long_log_count = reinterpret_cast<unsigned long long*>(e->t_long_log.as<char>() + (size_t)kLongLogCap * kLongLogDwords * 4);   // (the encoder's: it runs on through the batches of a window)
         }
-        if (special) { P.specbits = ws->w_specbits.as<uint64_t>(); P.lit_meta = e->LIT.meta; P.lit_blob = e->LIT.blob; P.n_lit = e->LIT.n; }
+        if (special) { P.specbits = ws->w_specbits.as<uint64_t>(); P.lit_meta = e->LIT.meta; P.lit_blob = e->LIT.blob; P.n_lit = e->LIT.n; P.lit_repl = c.d_repl; }
         TKZ_TRY(devprof_arm(&P, stream));
         int64_t* ndocstarts = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, ndocstarts));
         int64_t* npieces = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, npieces));
@@ -1361,6 +1368,7 @@ struct HostPipeline {
     // the call
     tkz_encoder* e; Workspace* ws; const HostPlan& p; const HostCall& c;
     const bool u16 = c.u16();
+    const bool with_repl = u16 && c.special && c.special->fffd;      // the literal search must tell a lone surrogate's U+FFFD from a real one
     const int64_t* const offs = c.offs;
     int64_t* const acc = &ws->bytes_allocated;
     // its state
@@ -1391,7 +1399,7 @@ struct HostPipeline {
         }
         for (int q = 0; q < (nchunks > 1 ? 2 : 1); ++q) {
             if (u16) {
-                HIP_TRY(ws->u16[q].ensure(max_units, max_docs, acc));
+                HIP_TRY(ws->u16[q].ensure(max_units, max_docs, acc, with_repl));
             } else {
                 HIP_TRY(ws->s_bytes[q].ensure((size_t)max_units + 64, acc));
                 HIP_TRY(ws->s_offs[q].ensure((size_t)(max_docs + 1) * 8, acc));
@@ -1460,8 +1468,10 @@ struct HostPipeline {
             cbytes = U.h->grand;
             PIPELINE_TRY(ws->u_bytes[q].ensure((size_t)cbytes + 64, acc));
             Launch L{w->st_compute, nullptr, w};
+            if (with_repl) PIPELINE_TRY(hipMemsetAsync(U.repl.p, 0, Workspace::U16Stage::repl_bytes(cbytes), w->st_compute));
             launch_u16_write(L, U.units.as<uint16_t>(), nu, U.docbits.as<uint64_t>(), u16_tiles(nu), U.tbase.as<int64_t>(), ws->u_bytes[q].as<uint8_t>(),
-                             U.offs.as<int64_t>(), nd, U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>());
+                             U.offs.as<int64_t>(), nd, U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>(),
+                             with_repl ? U.repl.as<uint64_t>() : nullptr);
             cb = ws->u_bytes[q].as<uint8_t>(); co = U.boffs.as<int64_t>();
         } else {
             if (!p.ingest_in) PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_in[q], 0));
@@ -1476,6 +1486,7 @@ struct HostPipeline {
         //  sum is checked when the chunk ends)
         fl[q] = c.on_device(cb, co, nd, cbytes, dst_ids, over ? 0 : std::min<int64_t>(c.out_cap, cbytes), dst_offs, w->st_compute);
         if (p.ingest_in) fl[q].ingest = &ingest_src;
+        if (with_repl) fl[q].d_repl = ws->u16[q].repl.as<uint64_t>();
         return encode_device(e, w, fl[q], phase, tokens);
     }
     tkz_status end_chunk(int64_t k, int64_t* tokens) {          // (returns when the chunk's stream has drained)
@@ -1843,7 +1854,7 @@ void destroy_now(tkz_encoder* e) {
     DeviceScope scope;
     (void)scope.enter(e->device);
     DevBuf* bufs[] = {&e->t_short, &e->t_mid, &e->t_long, &e->t_blob, &e->t_pair, &e->t_byte, &e->t_bpair, &e->t_bmp, &e->t_counts3, &e->t_memo, &e->t_stats, &e->t_decoff, &e->t_decblob, &e->t_decids,
-                      &e->t_memo_hits, &e->t_promo, &e->t_long_log};
+                      &e->t_memo_hits, &e->t_promo, &e->t_long_log, &e->t_lit};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : e->retired) b.release();
     for (Workspace* w : e->pool) { w->release_all(); delete w; }
@@ -1881,6 +1892,7 @@ tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowe
     if (*plain) return TKZ_OK;
     if (e->lit_state < 0) return fail(TKZ_E_UNSUPPORTED, "special tokens on the device: " + e->lit_why);
     *sc = SpecialCall{};
+    sc->fffd = e->lit_fffd;
     for (int32_t k = 0; k < n_allowed; ++k) {
         const int32_t i = allowed[k];
         if (i < 0 || i >= e->LIT.n) return fail(TKZ_E_ARG, "allowed[] holds an index that is not a registered special token");
@@ -2015,6 +2027,20 @@ tkz_status tkz_encode_batch_utf16(tkz_encoder* e, const uint16_t* units, const i
     if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
     static const uint16_t none = 0;
     return encode_host(e, HostCall{nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed});
+}
+
+tkz_status tkz_encode_batch_special_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed,
+                                          int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
+    if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
+    static const uint16_t none = 0;
+    HostCall c{nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
+    if (!plain) c.special = &sc;
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK && c.special) ++e->spec_batches;
+    return st;
 }
 
 tkz_status tkz_pretokenize_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, uint64_t* out_bitmap_words) {
@@ -2164,6 +2190,72 @@ tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, cons
     HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
     if (cut_bytes && n_docs) HIP_TRY(hipMemcpy(cut_bytes, d_cb, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
     if (cut_units && n_docs) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+
+// The same for UTF-16 documents: the whole batch's code units are staged and transcoded on the device (as a chunk of tkz_encode_batch_utf16 is), then ONE trim call
+// on the UTF-8 bytes and byte offsets that leaves.  With a registered literal that holds U+FFFD the transcoder also writes the replaced-byte bitmap.
+tkz_status tkz_encode_batch_trim_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                       int64_t* cut_units, int64_t* needed) {
+    using namespace tkz;
+    SpecialCall sc; bool plain = false;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr));
+    if (!out_offsets || (out_cap > 0 && !out_ids) || out_cap < 0) return fail(TKZ_E_ARG, "null output buffer");
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
+    if (unit_offsets[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
+    const int64_t total = unit_offsets[n_docs];
+    if (total < 0) return fail(TKZ_E_ARG, "negative unit count");
+    for (int64_t d = 0; max_tokens_per_doc && d < n_docs; ++d) if (max_tokens_per_doc[d] < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    if (needed) *needed = 0;
+    if (total == 0) {
+        for (int64_t d = 0; d <= n_docs; ++d) { if (unit_offsets[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); out_offsets[d] = 0; }
+        for (int64_t d = 0; cut_units && d < n_docs; ++d) cut_units[d] = 0;
+        if (!plain) ++e->spec_batches;
+        return TKZ_OK;
+    }
+    // (the workspace keeps what is taken here for its next call; the lease -- and with it every buffer's use -- ends with this frame on every return)
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    int64_t* acc = &ws->bytes_allocated;
+    Workspace::U16Stage& U = ws->u16[0];
+    const bool with_repl = !plain && sc.fffd;
+    HIP_TRY(U.ensure(total, n_docs, acc, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const Launch L{nullptr, nullptr, ws};
+    const int64_t nw = total / 64 + 1, nt = u16_tiles(total);
+    HIP_TRY(hipMemsetAsync(U.counters.p, 0, 64, nullptr));
+    HIP_TRY(hipMemsetAsync(U.docbits.p, 0, (size_t)(nw + 8) * 8, nullptr));
+    launch_docmark(L, U.offs.as<int64_t>(), n_docs, total, U.docbits.as<uint64_t>(), U.counters.as<int32_t>());
+    launch_u16_len(L, U.units.as<uint16_t>(), total, U.docbits.as<uint64_t>(), nt, U.grp.as<int32_t>(), U.tsum.as<int32_t>());
+    launch_scan(L, U.tsum.as<int32_t>(), nt, U.bsum.as<int64_t>(), U.tbase.as<int64_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), -1);
+    HIP_TRY(hipMemcpy(U.h, U.counters.p, 16, hipMemcpyDeviceToHost));
+    if (U.h->err & kErrOffsets) return fail(TKZ_E_ARG, kMsgUnitOffsets);
+    const int64_t nbytes = U.h->grand;                                  // the batch as UTF-8
+    HIP_TRY(ws->u_bytes[0].ensure((size_t)nbytes + 64, acc));
+    if (with_repl) HIP_TRY(hipMemsetAsync(U.repl.p, 0, Workspace::U16Stage::repl_bytes(nbytes), nullptr));
+    launch_u16_write(L, U.units.as<uint16_t>(), total, U.docbits.as<uint64_t>(), nt, U.tbase.as<int64_t>(), ws->u_bytes[0].as<uint8_t>(), U.offs.as<int64_t>(), n_docs,
+                     U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>(), with_repl ? U.repl.as<uint64_t>() : nullptr);
+    const int64_t cap = std::min<int64_t>(out_cap, nbytes), nd = std::max<int64_t>(n_docs, 1);
+    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
+    HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
+    HIP_TRY(ws->t_stage.ensure((size_t)nd * 3 * 8, acc));
+    int64_t* const d_max = ws->t_stage.as<int64_t>(), * const d_cu = d_max + nd;
+    if (max_tokens_per_doc) HIP_TRY(hipMemcpy(d_max, max_tokens_per_doc, (size_t)n_docs * 8, hipMemcpyHostToDevice));
+    int64_t tokens = 0;
+    BatchCall c{ws->u_bytes[0].as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    const tkz_status st = trim_on_device(e, ws, c, TrimCall{side, max_tokens, max_tokens_per_doc ? d_max : nullptr, nullptr, cut_units ? d_cu : nullptr},
+                                         plain ? nullptr : &sc, &tokens);
+    if (needed) *needed = tokens;
+    if (st != TKZ_OK) return st;
+    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (cut_units) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }
 

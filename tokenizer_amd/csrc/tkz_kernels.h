@@ -92,12 +92,13 @@ struct EncodeParams {
     // the special entries only (null on the plain path, which then launches the k_probe it always did): bit i set <=> a TAKEN special-token literal starts at
     // byte i -- that piece's record is the literal's id (k_probe_special) --, and the literal table the id is read from (TkzLitTable)
     const uint64_t* specbits; const uint32_t* lit_meta; const uint8_t* lit_blob; int32_t n_lit;
+    const uint64_t* lit_repl;     // null, or the replaced-byte bitmap of a UTF-16 special call (launch_lit_scan): k_probe_special names the literal k_lit_scan matched
 };
 
 // ---- special tokens on the device (EncodeInternal / FindNextSpecialToken, TikTokenizer.cs:141-170,230-241) ----
 // The registered literals in registration order (= the reference's alternation order).  meta: [0..7] the first bytes of all literals as a 256-bit set,
-// then two dwords per literal: offset into blob | length << 16, id.
-constexpr int kLitMax = 256, kLitMaxLen = 128, kLitMetaHead = 8;
+// [8..15] the literals that hold U+FFFD (EF BF BD) as a 256-bit set over their indices, then two dwords per literal: offset into blob | length << 16, id.
+constexpr int kLitMax = 256, kLitMaxLen = 128, kLitFffdHead = 8, kLitMetaHead = 16;
 struct TkzLitTable { const uint32_t* meta; const uint8_t* blob; int32_t n; int32_t blob_bytes; };
 struct TkzLitAllowed { uint64_t m[kLitMax / 64]; };       // bit i: literal i is allowed in this call
 
@@ -152,17 +153,22 @@ void launch_miss_stats(const Launch& L, const EncodeParams& P, int64_t nsub);
 // literals taken left to right; segbits = docbits | starts | ends of the taken literals, specbits = their starts, endbits = their ends; *n_taken += their number.
 // launch_lit_fix (behind the pre-tokenizer, which ran with segbits in the place of docbits): no piece start strictly inside a taken literal.
 // launch_seg_offsets: the offsets of the n_seg segments of segbits (n_seg + 1 entries), for the scanners that take offsets (ord_base: the scan of its counts per sub-tile)
+// repl: null, or (text transcoded from UTF-16 by launch_u16_write, a registered literal holds U+FFFD) the replaced-byte bitmap, nwords words: bit i set <=> the
+// EF BF BD at byte i stands for a lone surrogate.  The reference searches the UTF-16 string, where a lone surrogate is not U+FFFD: a literal that holds U+FFFD
+// does not match where its bytes cover such a bit, and the alternation goes on to the next registered literal.
 void launch_lit_scan(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, int64_t nwords, const TkzLitTable& LT, const TkzLitAllowed& A,
-                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken);
+                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken, const uint64_t* repl = nullptr);
 void launch_lit_fix(const Launch& L, uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords);
 void launch_seg_offsets(const Launch& L, const uint64_t* segbits, int64_t nwords, int64_t total, int64_t nsub, const int64_t* ord_base, int64_t n_seg, int64_t* seg_offs);
 void launch_counts3(const Launch& L, int64_t n_docs, int64_t total, const int64_t* grand, int64_t* out3, int64_t* out3b = nullptr, int64_t* out3c = nullptr);
 // UTF-16 documents -> UTF-8 documents (Encoding.UTF8.GetBytes for a batch): lengths + group prefixes, then (after the scan of
-// the tile sums) the bytes and the byte offset of every document
+// the tile sums) the bytes and the byte offset of every document.  repl: null, or a zeroed bitmap over the OUTPUT bytes (grand / 64 + 1 words) that receives
+// one bit at the EF of every U+FFFD written for a lone surrogate (the special entries' literal search: launch_lit_scan)
 int64_t u16_tiles(int64_t total_units);
 void launch_u16_len(const Launch& L, const uint16_t* units, int64_t total, const uint64_t* docbits, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);
 void launch_u16_write(const Launch& L, const uint16_t* units, int64_t total, const uint64_t* docbits, int64_t ntiles, const int64_t* tile_base,
-                      uint8_t* out, const int64_t* unit_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs);
+                      uint8_t* out, const int64_t* unit_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs,
+                      uint64_t* repl = nullptr);
 // piece granularity: byte offset of every piece (n_pieces + 1 entries) and first piece of every document, from the bitmap
 void launch_piece_index(const Launch& L, const uint64_t* startbits, int64_t nwords, int64_t total, int64_t nsub, const int64_t* ord_base,
                         int64_t n_pieces, int64_t* piece_offs, const int64_t* d_offs, int64_t n_docs, int64_t* doc_piece);

@@ -665,7 +665,24 @@ TKZ_DEV void tkz_probe_request_text(const EncodeParams& P, int64_t sub, ProbeTex
 // The special entries: the piece at byte s of the sub-tile, len bytes long, is a TAKEN special-token literal (EncodeParams::specbits) -- its id, from the literal
 // table: the first registered literal of that length with those bytes (k_lit_scan took the first registered literal that matches at s: it is this one).
 // Rare (a literal per document): the table is read from memory, the bytes from LDS (sb) or, beyond the staged halo, from the text (gb).
-TKZ_DEV int32_t tkz_lit_id(const EncodeParams& P, const uint8_t* sb, const uint8_t* gb, int s, int len) {
+// (A UTF-16 special call -- P.lit_repl --: a literal that holds U+FFFD and covers a replaced byte is passed over here as k_lit_scan passed it over; `abs` is the
+// piece's byte position in the batch.)
+// does [bit, bit + len) of the bitmap rw (nrw words) hold a set bit?  len <= kLitMaxLen: three words at most
+TKZ_DEV bool tkz_bits_any(const uint64_t* rw, int64_t nrw, int64_t bit, int len) {
+    const int64_t wa = bit >> 6, wb = (bit + len - 1) >> 6;
+    for (int64_t w = wa; w <= wb && w < nrw; ++w) {
+        uint64_t m = rw[w];
+        if (w == wa) m &= ~tkz_lowmask((int)(bit & 63));
+        if (w == wb) m &= tkz_lowmask((int)((bit + len - 1) & 63) + 1);
+        if (m) return true;
+    }
+    return false;
+}
+// literal i of the table holds U+FFFD (meta[kLitFffdHead ..]) and its len bytes at `bit` cover a replaced byte: it does not match there
+TKZ_DEV bool tkz_lit_replaced(const uint32_t* meta, int i, const uint64_t* rw, int64_t nrw, int64_t bit, int len) {
+    return rw && ((meta[kLitFffdHead + (i >> 5)] >> (i & 31)) & 1u) && tkz_bits_any(rw, nrw, bit, len);
+}
+TKZ_DEV int32_t tkz_lit_id(const EncodeParams& P, const uint8_t* sb, const uint8_t* gb, int s, int len, int64_t abs) {
     const uint8_t* tx = s + len <= kSub + kHalo ? sb + s : gb + s;
     for (int i = 0; i < P.n_lit; ++i) {
         const uint32_t m = P.lit_meta[kLitMetaHead + 2 * i];
@@ -673,7 +690,7 @@ TKZ_DEV int32_t tkz_lit_id(const EncodeParams& P, const uint8_t* sb, const uint8
         const uint8_t* lit = P.lit_blob + (m & 0xFFFFu);
         int k = 0;
         while (k < len && lit[k] == tx[k]) ++k;
-        if (k == len) return (int32_t)P.lit_meta[kLitMetaHead + 2 * i + 1];
+        if (k == len && !tkz_lit_replaced(P.lit_meta, i, P.lit_repl, P.nwords, abs, len)) return (int32_t)P.lit_meta[kLitMetaHead + 2 * i + 1];
     }
     return TKZ_RANK_NONE;
 }
@@ -792,7 +809,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         const uint4 a0 = tkz_load16(tb0 + oa), a1 = tkz_load16(tb0 + oa + 16u), b0 = tkz_load16(tb0 + ob), b1 = tkz_load16(tb0 + ob + 16u);
         int32_t rank = TKZ_RANK_NONE;
         if (is_mid) rank = tkz_match_mid(kk, (uint32_t)len, a0, a1, b0, b1);
-        else if (is_lit) rank = tkz_lit_id(P, sb, gbase, s, len);
+        else if (is_lit) rank = tkz_lit_id(P, sb, gbase, s, len, base + s);
         else if (valid) {
             if (s + len <= kSub + kHalo) rank = tkz_lookup_long(T, [&](int i) -> uint32_t { return sb[s + i]; }, (uint32_t)len);
             else rank = tkz_lookup_long(T, [&](int i) -> uint32_t { return gbase[s + i]; }, (uint32_t)len);
@@ -847,7 +864,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         for (int u = 0; u < U; ++u) {
             const bool is_short = plen[u] >= 1 && plen[u] <= TKZ_SHORT_KEY_MAX;
             rk[u] = tkz_match_short2x(kw0[u], kw1[u], kw2[u], (uint32_t)plen[u], a0[u], a1[u]);       // (a piece that is not short matches no slot: len 0 or > 12)
-            if (SPECIAL && is_short && ((LD.spec[ps[u] >> 5] >> (ps[u] & 31)) & 1u)) rk[u] = tkz_lit_id(P, sb, gbase, ps[u], plen[u]);
+            if (SPECIAL && is_short && ((LD.spec[ps[u] >> 5] >> (ps[u] & 31)) & 1u)) rk[u] = tkz_lit_id(P, sb, gbase, ps[u], plen[u], base + ps[u]);
             more = more || (is_short && rk[u] == TKZ_RANK_NONE);
         }
         // the second bucket, for the lanes the first one did not settle only (the keys the builder could not keep in their first
@@ -2510,8 +2527,12 @@ TKZ_DEV int tkz_lit_room(const uint64_t* docbits, int64_t nwords, int64_t total,
     else if ((m = w + 2 < nwords ? docbits[w + 2] : 0ull) != 0) r = 128 - b + tkz_ctz64(m);
     return total - p < r ? (int)(total - p) : r;
 }
-// the first registered literal of at most `room` bytes whose bytes are tx[0 ..): its index, or -1
-TKZ_DEV int tkz_lit_first(const uint32_t* meta, const uint8_t* blob, int n, const uint8_t* tx, int room) {
+// the first registered literal of at most `room` bytes whose bytes are tx[0 ..): its index, or -1.  rw: null, or replaced-byte bitmap words (nrw of them) in
+// which tx[0] is bit `rbit`: a literal that holds U+FFFD does not match over a byte the transcoder put there for a lone surrogate.  (The words are read from
+// memory, by k_lit_scan too, and only once ALL bytes of such a literal have matched: staging 66 words a wavefront beside k_lit_scan's text would take its
+// workgroup from 51.8 KB to 53.9 KB of LDS -- past a third of the CU's 160 KB once rounded to the allocation granule, two workgroups a CU instead of three,
+// for every special call, UTF-8 ones included.)
+TKZ_DEV int tkz_lit_first(const uint32_t* meta, const uint8_t* blob, int n, const uint8_t* tx, int room, const uint64_t* rw, int64_t nrw, int64_t rbit) {
     for (int i = 0; i < n; ++i) {
         const uint32_t m = meta[kLitMetaHead + 2 * i];
         const int len = (int)(m >> 16);
@@ -2519,14 +2540,14 @@ TKZ_DEV int tkz_lit_first(const uint32_t* meta, const uint8_t* blob, int n, cons
         const uint8_t* lit = blob + (m & 0xFFFFu);
         int k = 0;
         while (k < len && lit[k] == tx[k]) ++k;
-        if (k == len) return i;
+        if (k == len && !tkz_lit_replaced(meta, i, rw, nrw, rbit, len)) return i;
     }
     return -1;
 }
 constexpr int kLitBlock = 4096;                            // bytes of text per wavefront of k_lit_scan (64 bitmap words)
 constexpr int kLitTextQuads = (kLitBlock + kLitMaxLen) / 16;
 TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, TkzLitTable LT, TkzLitAllowed A,
-                                uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits) {
+                                uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, const uint64_t* repl) {
     TKZ_SHARED uint4 s_text[kThreads / 64][kLitTextQuads];
     TKZ_SHARED uint32_t s_meta[kLitMetaHead + 2 * kLitMax];
     TKZ_SHARED uint4 s_blob[kLitMax * kLitMaxLen / 16];
@@ -2564,7 +2585,7 @@ TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint6
         const uint32_t c = tx[pos];
         bool cand = false;
         if (p < total && ((s_meta[c >> 5] >> (c & 31)) & 1u)) {
-            const int i = tkz_lit_first(s_meta, blob, LT.n, tx + pos, tkz_lit_room(docbits, nwords, total, p));
+            const int i = tkz_lit_first(s_meta, blob, LT.n, tx + pos, tkz_lit_room(docbits, nwords, total, p), repl, nwords, p);
             cand = i >= 0 && ((A.m[i >> 6] >> (i & 63)) & 1ull);
         }
         const uint64_t m = simt::ballot(cand);
@@ -2574,12 +2595,12 @@ TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint6
     if (w < nwords) { candbits[w] = mine; segbits[w] = docbits[w]; specbits[w] = 0; endbits[w] = 0; }
 }
 // the literal that k_lit_scan matched at candidate p (from the text: candidates are rare): its length
-TKZ_DEV int tkz_lit_len_at(const uint8_t* bytes, const uint64_t* docbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p) {
-    const int i = tkz_lit_first(LT.meta, LT.blob, LT.n, bytes + p, tkz_lit_room(docbits, nwords, total, p));
+TKZ_DEV int tkz_lit_len_at(const uint8_t* bytes, const uint64_t* docbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p, const uint64_t* repl) {
+    const int i = tkz_lit_first(LT.meta, LT.blob, LT.n, bytes + p, tkz_lit_room(docbits, nwords, total, p), repl, nwords, p);
     return i < 0 ? 1 : (int)(LT.meta[kLitMetaHead + 2 * i] >> 16);
 }
 // does a candidate in front of p reach over p?  (Only one that starts within kLitMaxLen - 1 bytes can; the nearest first: in a run of overlapping literals it does.)
-TKZ_DEV bool tkz_lit_covered(const uint8_t* bytes, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p) {
+TKZ_DEV bool tkz_lit_covered(const uint8_t* bytes, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p, const uint64_t* repl) {
     const int64_t lo = p - (kLitMaxLen - 1) > 0 ? p - (kLitMaxLen - 1) : 0;
     for (int64_t w = (p - 1) >> 6; p > 0 && w >= (lo >> 6); --w) {
         uint64_t m = candbits[w];
@@ -2589,21 +2610,21 @@ TKZ_DEV bool tkz_lit_covered(const uint8_t* bytes, const uint64_t* docbits, cons
             const int b = tkz_msb64(m);
             m &= ~(1ull << b);
             const int64_t q = (w << 6) + b;
-            if (q + tkz_lit_len_at(bytes, docbits, nwords, total, LT, q) > p) return true;
+            if (q + tkz_lit_len_at(bytes, docbits, nwords, total, LT, q, repl) > p) return true;
         }
     }
     return false;
 }
 TKZ_KERNEL(256) void k_lit_resolve(const uint8_t* bytes, int64_t total, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, TkzLitTable LT,
-                                   uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken) {
+                                   uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken, const uint64_t* repl) {
     const int64_t stride = simt::nblocks() * simt::nthreads();
     unsigned long long taken = 0;
     for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) {
         for (uint64_t m = candbits[w]; m; m &= m - 1) {
             const int64_t head = (w << 6) + tkz_ctz64(m);
-            if (tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, head)) continue;       // (another lane's run)
+            if (tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, head, repl)) continue;       // (another lane's run)
             for (int64_t cur = head; cur >= 0;) {
-                const int64_t end = cur + tkz_lit_len_at(bytes, docbits, nwords, total, LT, cur);    // (<= total: the literal ends inside its document)
+                const int64_t end = cur + tkz_lit_len_at(bytes, docbits, nwords, total, LT, cur, repl);    // (<= total: the literal ends inside its document)
                 simt::atomic_or64((unsigned long long*)&specbits[cur >> 6], 1ull << (cur & 63));
                 simt::atomic_or64((unsigned long long*)&endbits[end >> 6], 1ull << (end & 63));
                 simt::atomic_or64((unsigned long long*)&segbits[cur >> 6], 1ull << (cur & 63));
@@ -2617,7 +2638,7 @@ TKZ_KERNEL(256) void k_lit_resolve(const uint8_t* bytes, int64_t total, const ui
                     if (v == (end >> 6)) c &= ~tkz_lowmask((int)(end & 63));
                     if (c) nxt = (v << 6) + tkz_ctz64(c);
                 }
-                cur = nxt >= 0 && nxt < total && tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, nxt) ? nxt : -1;
+                cur = nxt >= 0 && nxt < total && tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, nxt, repl) ? nxt : -1;
             }
         }
     }
@@ -2781,7 +2802,8 @@ TKZ_KERNEL(64) void k_counts3(int64_t n_docs, int64_t total, const int64_t* gran
 //   k_u16_len     per 1024-unit tile (one wavefront, 16 units per lane): UTF-8 length of every unit -> tile sum and the
 //                 exclusive prefix of every 16-unit group inside the tile
 //   (scan of the tile sums: k_scan_*)
-//   k_u16_write   the bytes, staged per tile in LDS and copied out coalesced
+//   k_u16_write   the bytes, staged per tile in LDS and copied out coalesced; for the special entries' literal search (a registered literal holds U+FFFD) also
+//                 the replaced-byte bitmap: one bit, over output bytes, at the EF of every U+FFFD that stands for a lone surrogate
 //   k_u16_docoffs byte offset of every document = tile base + group prefix + the units of the group before it
 // -------------------------------------------------------------------------------------------------
 constexpr int kU16Tile = 1024;      // code units per wavefront
@@ -2858,7 +2880,7 @@ TKZ_KERNEL(256) void k_u16_len(const uint16_t* units, int64_t total, const uint6
     if (simt::lane() == 0) tile_sum[tile] = tot;
 }
 TKZ_KERNEL(256) void k_u16_write(const uint16_t* units, int64_t total, const uint64_t* docbits, int64_t ntiles, const int64_t* tile_base,
-                                 uint8_t* out) {
+                                 uint8_t* out, uint64_t* repl) {
     TKZ_SHARED uint8_t s_stage[kThreads / 64][3 * kU16Tile + 16];            // (a unit yields at most 3 bytes: a pair is 4 for 2 units)
     const int64_t tile = simt::bid() * (kThreads / 64) + simt::wave();
     if (tile >= ntiles) return;
@@ -2868,7 +2890,14 @@ TKZ_KERNEL(256) void k_u16_write(const uint16_t* units, int64_t total, const uin
     int pos = tkz_wave_scan_sum(sum, &tot);
     uint8_t* st = s_stage[simt::wave()];
 #pragma unroll
-    for (int k = 0; k < kU16Lane; ++k) pos += tkz_u16_put(L.u[k], L.u[k + 1], L.len[k], st + pos);
+    for (int k = 0; k < kU16Lane; ++k) {
+        // (lone surrogates are rare: an atomic each -- tiles, and lanes, share bitmap words)
+        if (repl && L.len[k] == 3 && L.u[k] - 0xD800u < 0x800u) {
+            const int64_t b = tile_base[tile] + pos;
+            simt::atomic_or64((unsigned long long*)&repl[b >> 6], 1ull << (b & 63));
+        }
+        pos += tkz_u16_put(L.u[k], L.u[k + 1], L.len[k], st + pos);
+    }
     (void)simt::ballot(true);          // (the staging area is private to the wavefront: its LDS accesses are ordered, no barrier)
     uint8_t* dst = out + tile_base[tile];
     for (int i = simt::lane(); i < tot; i += 64) dst[i] = st[i];
@@ -3566,9 +3595,9 @@ void launch_case_equiv_fix(const Launch& L, const uint8_t* d_bytes, int64_t tota
 }
 // (the brackets: the scan and the segment bitmap extend K_DOCMARK's, the fix-up K_PRETOK's -- the closing event is recorded again behind them)
 void launch_lit_scan(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, int64_t nwords, const TkzLitTable& LT, const TkzLitAllowed& A,
-                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken) {
-    TKZ_LAUNCH(k_lit_scan, grid1(cdiv(nwords, (kThreads / 64) * (kLitBlock / 64))), kThreads, L.stream, d_bytes, total, docbits, nwords, LT, A, candbits, segbits, specbits, endbits);
-    TKZ_LAUNCH(k_lit_resolve, grid_for(nwords), kThreads, L.stream, d_bytes, total, docbits, (const uint64_t*)candbits, nwords, LT, segbits, specbits, endbits, n_taken);
+                     uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken, const uint64_t* repl) {
+    TKZ_LAUNCH(k_lit_scan, grid1(cdiv(nwords, (kThreads / 64) * (kLitBlock / 64))), kThreads, L.stream, d_bytes, total, docbits, nwords, LT, A, candbits, segbits, specbits, endbits, repl);
+    TKZ_LAUNCH(k_lit_resolve, grid_for(nwords), kThreads, L.stream, d_bytes, total, docbits, (const uint64_t*)candbits, nwords, LT, segbits, specbits, endbits, n_taken, repl);
     hook(L, K_DOCMARK, 1);
 }
 void launch_lit_fix(const Launch& L, uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords) {
@@ -3592,8 +3621,8 @@ void launch_u16_len(const Launch& L, const uint16_t* units, int64_t total, const
     TKZ_LAUNCH(k_u16_len, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, units, total, docbits, ntiles, grp_prefix, tile_sum);
 }
 void launch_u16_write(const Launch& L, const uint16_t* units, int64_t total, const uint64_t* docbits, int64_t ntiles, const int64_t* tile_base,
-                      uint8_t* out, const int64_t* unit_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs) {
-    TKZ_LAUNCH(k_u16_write, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, units, total, docbits, ntiles, tile_base, out);
+                      uint8_t* out, const int64_t* unit_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs, uint64_t* repl) {
+    TKZ_LAUNCH(k_u16_write, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, units, total, docbits, ntiles, tile_base, out, repl);
     TKZ_LAUNCH(k_u16_docoffs, grid_for(n_docs + 1), kThreads, L.stream, units, total, docbits, unit_offs, n_docs, tile_base, grp_prefix, grand, byte_offs);
 }
 int64_t u16_tiles(int64_t total_units) { return cdiv(total_units, kU16Tile); }
