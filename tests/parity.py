@@ -881,12 +881,8 @@ def check_document_marks(lib, O, vocab, ovocab):
         assert ids.tolist() == exp and ooff.tolist() == eoff, len(docs)
 
 
-def check_sizing_attempt(lib, O, vocab, ovocab, capfd, pattern=N.CL100K, seed=43):
-    """A fresh workspace's first large batch probes a sample of its sub-tiles first (encode_device: the sizing attempt) and every attempt after the first
-    starts behind the pre-tokenizer, on the bitmaps the first one left.  Same ids as the oracle when the sample predicts the lists the batch needs (two
-    attempts), when the crowded text lies behind the sample (three: sample, overflow, again), and on ordinary text (two); the attempts are read off the
-    library's TKZ_LOG_SLOW_MS line.  The threshold is 64 MB of text: TKZ_SIZING_MIN_SUB brings it down to what a test can afford."""
-    import re
+def sizing_corpora(seed=43):
+    """check_sizing_attempt's three corpora with the attempts a PLAIN call on a fresh workspace takes for each: (documents, attempts)"""
     rng = random.Random(seed)
     cons = "bcdfghjklmnpqrstvwxz"
     words = "the of and to in is that for it with as was on be at by this had not are but from or have an they which one you were her all".split()
@@ -902,14 +898,23 @@ def check_sizing_attempt(lib, O, vocab, ovocab, capfd, pattern=N.CL100K, seed=43
         while sum(map(len, out)) < n:
             out.append(" " + rng.choice(words))
         return "".join(out)[:n]
-    oenc = O.Encoder(ovocab, pattern)
     crowded_all = [gib(4000, 2, 3).encode() for _ in range(45)]                                     # every sub-tile overflows a fresh list
     crowded_tail = [plain(4000).encode() for _ in range(40)] + [gib(4000, 2, 2).encode() for _ in range(5)]
     ordinary = [(plain(3000) + gib(300, 4, 9)).encode() for _ in range(50)]
+    return (crowded_all, 2), (crowded_tail, 3), (ordinary, 2)
+
+
+def check_sizing_attempt(lib, O, vocab, ovocab, capfd, pattern=N.CL100K, seed=43):
+    """A fresh workspace's first large batch probes a sample of its sub-tiles first (encode_device: the sizing attempt) and every attempt after the first
+    starts behind the pre-tokenizer, on the bitmaps the first one left.  Same ids as the oracle when the sample predicts the lists the batch needs (two
+    attempts), when the crowded text lies behind the sample (three: sample, overflow, again), and on ordinary text (two); the attempts are read off the
+    library's TKZ_LOG_SLOW_MS line.  The threshold is 64 MB of text: TKZ_SIZING_MIN_SUB brings it down to what a test can afford."""
+    import re
+    oenc = O.Encoder(ovocab, pattern)
     old = {k: os.environ.get(k) for k in ("TKZ_SIZING_MIN_SUB", "TKZ_LOG_SLOW_MS")}
     os.environ["TKZ_SIZING_MIN_SUB"] = "128"; os.environ["TKZ_LOG_SLOW_MS"] = "0"
     try:
-        for docs, attempts in ((crowded_all, 2), (crowded_tail, 3), (ordinary, 2)):
+        for docs, attempts in sizing_corpora(seed):
             enc = N.Encoder(vocab, pattern)
             data, offs = pack(docs)
             assert len(data) > 140000

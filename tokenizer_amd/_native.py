@@ -420,9 +420,13 @@ class Encoder:
                                  d_cut_bytes=0, d_cut_units=0, stream=0):
         allowed = np.ascontiguousarray(allowed, dtype=np.int32)
         tot = C.c_int64(0)
-        self.lib.check(self.lib.L.tkz_encode_batch_trim_device(self._h, d_bytes, d_offsets, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None, len(allowed),
-                                                               int(side), int(max_tokens), d_max_tokens or None, d_out_ids or None, out_cap, d_out_offsets,
-                                                               d_cut_bytes or None, d_cut_units or None, stream or None, C.byref(tot)))
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_trim_device(self._h, d_bytes, d_offsets, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                                   int(side), int(max_tokens), d_max_tokens or None, d_out_ids or None, out_cap, d_out_offsets,
+                                                                   d_cut_bytes or None, d_cut_units or None, stream or None, C.byref(tot)))
+        except TkzError as ex:
+            ex.needed = tot.value                             # (E_CAPACITY: the kept total)
+            raise
         return tot.value
 
     def special_stats(self):
