@@ -13,7 +13,7 @@
 // EncodeInternal / FindNextSpecialToken (TikTokenizer.cs:141-170,230-241) with the plain segments sent to the
 // GPU in one batch.  The trim variants (TikTokenizer.cs:288-579) get the token count and length of every regex piece
 // from tkz_encode_batch_pieces_utf8 and decide the cut on the host; Decode / DecodeBatch run on the device too
-// (tkz_decode_batch).  ShardedEncoder at the end is the multi-GPU form: one process per GPU, contiguous document
+// (tkz_decode_batch_utf16: the code units of every string come from the device, Encoding.UTF8.GetString included).  ShardedEncoder at the end is the multi-GPU form: one process per GPU, contiguous document
 // ranges, ONE RCCL all-gather of the per-rank counts through libtkz's own communicator (tkz_comm_*), token shard files.
 using System;
 using System.Collections.Generic;
@@ -47,6 +47,7 @@ namespace Microsoft.DeepDev
                                                                                    int* outIds, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encoder_set_special_tokens(IntPtr encoder, int* ids, byte* literalsUtf8, long* literalOffsets, int n);
         [DllImport(Lib)] internal static extern unsafe int tkz_decode_batch(IntPtr encoder, int* ids, long* idOffsets, long nDocs, byte* outBytes, long outCap, long* outOffsets, out long needed);
+        [DllImport(Lib)] internal static extern unsafe int tkz_decode_batch_utf16(IntPtr encoder, int* ids, long* idOffsets, long nDocs, char* outUnits, long outCap, long* outOffsets, out long needed);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -677,7 +678,9 @@ namespace Microsoft.DeepDev
         public (List<int> TokenIds, string Text) EncodeTrimPrefix(string text, int maxTokenCount, bool applySpecialTokens = true)
             => EncodeTrimPrefix(text, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
 
-        /// <summary>TikTokenizer.Decode (TikTokenizer.cs:586-604): ids in neither table are dropped; on the device.</summary>
+        /// <summary>TikTokenizer.Decode (TikTokenizer.cs:586-604): ids in neither table are dropped; on the device, Encoding.UTF8.GetString (:603)
+        /// included -- tkz_decode_batch_utf16 hands back the code units of every document, one U+FFFD per maximal subpart of an ill-formed sequence as
+        /// GetString writes them, and each string is built from its unit range.  The strings are those GetString gives on the bytes of tkz_decode_batch.</summary>
         public string Decode(int[] tokens) => DecodeBatch(new[] { tokens })[0];
 
         public unsafe List<string> DecodeBatch(IReadOnlyList<int[]> batches)
@@ -687,18 +690,19 @@ namespace Microsoft.DeepDev
             var flat = new int[Math.Max(1, offs[batches.Count])];
             for (int i = 0; i < batches.Count; ++i) batches[i].CopyTo(flat, offs[i]);
             var outOffs = new long[batches.Count + 1];
-            var bytes = new byte[Math.Max(16, 8 * flat.Length)];
+            var units = new char[Math.Max(16, 8 * flat.Length)];
             while (true)
             {
                 int st; long needed;
-                fixed (int* pi = flat) fixed (long* po = offs) fixed (byte* pb = bytes) fixed (long* poo = outOffs)
-                    st = Tkz.tkz_decode_batch(encoder, pi, po, batches.Count, pb, bytes.Length, poo, out needed);
-                if (st == -4) { bytes = new byte[needed]; continue; }              // TKZ_E_CAPACITY: `needed` is the exact size
+                fixed (int* pi = flat) fixed (long* po = offs) fixed (char* pu = units) fixed (long* poo = outOffs)
+                    st = Tkz.tkz_decode_batch_utf16(encoder, pi, po, batches.Count, pu, units.Length, poo, out needed);
+                if (st == -4) { units = new char[needed]; continue; }              // TKZ_E_CAPACITY: `needed` is the exact size, in code units
                 Tkz.Check(st);
                 break;
             }
             var result = new List<string>(batches.Count);
-            for (int i = 0; i < batches.Count; ++i) result.Add(Encoding.UTF8.GetString(bytes, (int)outOffs[i], (int)(outOffs[i + 1] - outOffs[i])));
+            fixed (char* pu = units)
+                for (int i = 0; i < batches.Count; ++i) result.Add(new string(pu, (int)outOffs[i], (int)(outOffs[i + 1] - outOffs[i])));
             return result;
         }
 

@@ -282,6 +282,19 @@ tkz_status tkz_decode_batch_device(tkz_encoder* e, const int32_t* d_ids, const i
                                    uint8_t* d_out_bytes, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_bytes);
 tkz_status tkz_decode_batch(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* out_bytes, int64_t out_cap,
                             int64_t* out_offsets, int64_t* needed);
+/* The same with the second half of Decode, Encoding.UTF8.GetString (:603), done on the device: document d of the result is the UTF-16 string of those bytes,
+ * out_cap and the offsets count CODE UNITS.  The rule is .NET Core 3.0+'s and WHATWG TextDecoder("utf-8")'s (Unicode 3.9, table 3-7): a well-formed sequence
+ * is one unit (a 4-byte one a surrogate pair), every MAXIMAL SUBPART of an ill-formed sequence -- the longest prefix of a well-formed sequence that is present,
+ * or one byte -- is one U+FFFD: F0 90 41 -> FFFD 0041, E0 80 -> FFFD FFFD, ED A0 80 and F4 90 80 80 -> one FFFD per byte, C0 / C1 / F5..FF / a stray 80..BF ->
+ * one FFFD each.  Every document is decoded on its own: a sequence cut by a document boundary is a prefix (one FFFD) and stray continuation bytes (one each).
+ * The units are well-formed UTF-16.  out_cap too small: TKZ_E_CAPACITY and the exact unit total in *total_units / *needed (the bytes of the batch are always
+ * sufficient: a unit stands for at least one byte); bad id offsets: TKZ_E_ARG; no ids: offsets of zero.  The call waits once, inside, for the byte total of the
+ * batch -- the intermediate bytes live in the workspace and are sized from it (1 byte + 1/8 per decoded byte, 4.25 per 16 for the counts) -- and returns after
+ * the stream has drained.  tkz_decode_batch_utf16 stages the whole batch: one upload, one call of the device entry, one download. */
+tkz_status tkz_decode_batch_utf16_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
+                                         uint16_t* d_out_units, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_units);
+tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
+                                  int64_t* out_offsets, int64_t* needed);
 
 /* ---- token shard files -------------------------------------------------------
  * The on-disk form of one rank's EncodeBatch result: a 64-byte header ("TKZSHRD1", version, n_docs, n_tokens, doc_base,

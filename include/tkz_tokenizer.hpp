@@ -1,9 +1,10 @@
-// tkz_tokenizer.hpp -- C++ host mirror of the reference's tokenizer interface for the Encode path, over the
+// tkz_tokenizer.hpp -- C++ host mirror of the reference's tokenizer interface (Encode, and Decode for a batch), over the
 // C ABI of include/tkz.h.  Header-only; link with libtkz.so.
 //
 //   tkz::TikTokenizer          ITokenizer.Encode x2 + EncodeBatch     Tokenizer_C#/TokenizerLib/ITokenizer.cs:12,28
 //                              EncodeBatchFlat: (ids, offsets) in page-locked buffers that are kept from call to call (tkz::FlatBatch)
 //                              EncodeTrimSuffix / EncodeTrimPrefix x2   ITokenizer.cs:30-44, TikTokenizer.cs:288-579
+//                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
 // Text is UTF-8 (std::string); the ...Utf16 methods take the code units of a .NET string (std::u16string) and hand them to the device's UTF-16 entries,
@@ -425,6 +426,18 @@ public:
     tkz_encoder* native() const { return enc_; }
     // the device workspace of batches of up to max_bytes / max_docs, allocated now instead of inside the first batch call (tkz_encoder_reserve): what
     // TokenizerBuilder.CreateTokenizer (TokenizerBuilder.cs:210-213) is for a drop-in -- construction pays, not the first Encode
+    // ---- Decode (ITokenizer.cs:45, TikTokenizer.cs:586-604) ----
+    // Decode / DecodeBatch: the bytes the reference hands to Encoding.UTF8.GetString (tkz_decode_batch) -- a std::string holds them as they are, well-formed or
+    // not.  DecodeUtf16 / DecodeBatchUtf16: the string GetString makes of them, its code units from the device (tkz_decode_batch_utf16: one U+FFFD per maximal
+    // subpart of an ill-formed sequence).  Ids that are neither in the vocabulary nor registered special tokens contribute nothing.
+    std::vector<std::string> DecodeBatch(const std::vector<std::vector<int32_t>>& batches) const {
+        return decode_batch<std::string, uint8_t>(batches, 8, tkz_decode_batch);
+    }
+    std::string Decode(const std::vector<int32_t>& ids) const { return DecodeBatch({ids})[0]; }
+    std::vector<std::u16string> DecodeBatchUtf16(const std::vector<std::vector<int32_t>>& batches) const {
+        return decode_batch<std::u16string, uint16_t>(batches, 8, tkz_decode_batch_utf16);
+    }
+    std::u16string DecodeUtf16(const std::vector<int32_t>& ids) const { return DecodeBatchUtf16({ids})[0]; }
     void Reserve(int64_t max_bytes, int64_t max_docs) { check(tkz_encoder_reserve(enc_, max_bytes, max_docs)); }
     // The split is whatever the HOST's regex engine makes of the pattern (TikTokenizer.cs:77 compiles it in the running process).  A host on another
     // runtime than net6.0 hands its Unicode classification over (classes[cp] in 0..8 for cp < n: 65536 code units or 1114112 code points; nullptr:
@@ -434,6 +447,26 @@ public:
 
 private:
     struct Segment { bool special; int32_t id; size_t begin, end; };          // bytes [begin, end) of the text
+    // one call of a decode entry on the ids of all batches (a second one when the first guess of the capacity, `per_id` elements an id, was too small)
+    template <class Str, class Elem, class Entry>
+    std::vector<Str> decode_batch(const std::vector<std::vector<int32_t>>& batches, size_t per_id, Entry entry) const {
+        std::vector<int32_t> ids;
+        std::vector<int64_t> offs{0};
+        for (const auto& b : batches) { ids.insert(ids.end(), b.begin(), b.end()); offs.push_back(static_cast<int64_t>(ids.size())); }
+        std::vector<Elem> out(ids.size() * per_id + 16);
+        std::vector<int64_t> ooff(batches.size() + 1, 0);
+        int64_t needed = 0;
+        tkz_status st = entry(enc_, ids.data(), offs.data(), static_cast<int64_t>(batches.size()), out.data(), static_cast<int64_t>(out.size()), ooff.data(), &needed);
+        if (st == TKZ_E_CAPACITY) {
+            out.resize(static_cast<size_t>(needed));
+            st = entry(enc_, ids.data(), offs.data(), static_cast<int64_t>(batches.size()), out.data(), static_cast<int64_t>(out.size()), ooff.data(), &needed);
+        }
+        check(st);
+        std::vector<Str> res(batches.size());
+        for (size_t d = 0; d < batches.size(); ++d)
+            res[d].assign(reinterpret_cast<const typename Str::value_type*>(out.data()) + ooff[d], static_cast<size_t>(ooff[d + 1] - ooff[d]));
+        return res;
+    }
     // EncodeInternal + FindNextSpecialToken (TikTokenizer.cs:141-170,230-241): plain segments and special literals in order
     std::vector<Segment> segments(const std::string& text, const std::vector<std::string>& allowedSpecial) const {
         std::vector<Segment> out;

@@ -155,6 +155,8 @@ class Library:
         L.tkz_encoder_special_stats.restype = None
         L.tkz_decode_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
         L.tkz_decode_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
+        L.tkz_decode_batch_utf16_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
+        L.tkz_decode_batch_utf16.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -590,6 +592,29 @@ class Encoder:
         tot = C.c_int64(0)
         self.lib.check(self.lib.L.tkz_decode_batch_device(self._h, d_ids, d_id_offsets, n_docs, total_ids, d_out, out_cap, d_out_offsets,
                                                           stream or None, C.byref(tot)))
+        return tot.value
+
+    def decode_batch_utf16(self, ids: np.ndarray, id_offsets: np.ndarray, out_cap=None):
+        """Batch Decode to UTF-16 on the device (Encoding.UTF8.GetString of every document): (units uint16[total], unit_offsets int64[n+1])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.int64)
+        n = len(id_offsets) - 1
+        cap = out_cap if out_cap is not None else max(16, 8 * len(ids))
+        while True:
+            out = np.empty(max(1, cap), np.uint16)
+            ooff = np.empty(n + 1, np.int64)
+            needed = C.c_int64(0)
+            st = self.lib.L.tkz_decode_batch_utf16(self._h, _ptr(ids) if len(ids) else None, _ptr(id_offsets), n, _ptr(out), cap, _ptr(ooff), C.byref(needed))
+            if st == E_CAPACITY and out_cap is None:
+                cap = needed.value
+                continue
+            self.lib.check(st)
+            return out[:needed.value], ooff
+
+    def decode_batch_utf16_device(self, d_ids, d_id_offsets, n_docs, total_ids, d_out, out_cap, d_out_offsets, stream=0):
+        tot = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_decode_batch_utf16_device(self._h, d_ids, d_id_offsets, n_docs, total_ids, d_out, out_cap, d_out_offsets,
+                                                                stream or None, C.byref(tot)))
         return tot.value
 
     @property

@@ -166,6 +166,9 @@ struct Workspace {
     DevBuf u_bytes[2];
     // Decode
     DevBuf d_grp, d_tsum, d_tbase, d_bsum, d_counters, d_ids, d_idoffs, d_out, d_outoffs;
+    // Decode to UTF-16: the decoded bytes and their document offsets (sized from the length scan's byte total), the document-start bitmap over the bytes,
+    // per-tile / per-group unit counts, the host entry's staging of the units
+    DevBuf d8_bytes, d8_boffs, d8_docbits, d8_grp, d8_tsum, d8_tbase, d8_bsum, d8_units;
     // piece-granular entry point: piece byte offsets, token offsets, first piece of every document
     DevBuf p_boffs, p_toffs, p_docp;
     // the trim entries: the untrimmed ids (a token is at least a byte: 4 bytes per input byte), {kept token range, cut position} per document and the
@@ -198,7 +201,7 @@ struct Workspace {
         DevBuf* bufs[] = {&w_candbits, &w_segbits, &w_specbits, &w_endbits, &w_segoffs, &w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
                           &w_doctok, &w_dcount, &w_dbase, &w_pool, &s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2],
                           &s_outoffs[0], &s_outoffs[1], &s_outoffs[2], &u_bytes[0], &u_bytes[1],
-                          &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &p_boffs, &p_toffs, &p_docp, &t_ids, &t_keep, &t_bsum, &t_stage};
+                          &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &d8_bytes, &d8_boffs, &d8_docbits, &d8_grp, &d8_tsum, &d8_tbase, &d8_bsum, &d8_units, &p_boffs, &p_toffs, &p_docp, &t_ids, &t_keep, &t_bsum, &t_stage};
         for (DevBuf* b : bufs) b->release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
@@ -2353,6 +2356,112 @@ tkz_status tkz_decode_batch(tkz_encoder* e, const int32_t* ids, const int64_t* i
     if (needed) *needed = nbytes;
     if (st != TKZ_OK) return st;
     if (nbytes) HIP_TRY(hipMemcpy(out_bytes, ws->d_out.p, (size_t)nbytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_offsets, ws->d_outoffs.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+
+namespace {
+// Decode + Encoding.UTF8.GetString: the byte decoder's lengths and scan, ONE wait for the byte total (the intermediate bytes are sized from it, not from
+// total_ids x the longest key), the bytes and their offsets into the workspace, the document-start bitmap over them, then unit counts -> scan -> units + unit
+// offsets.  own_units: null (d_out is the caller's), or the workspace buffer the host entry's units go to: sized here, to min(out_cap, bytes) -- a unit
+// stands for at least one byte.
+tkz_status decode_utf16_device(tkz_encoder* e, Workspace* ws, const int32_t* d_ids, const int64_t* d_id_offs, int64_t n_docs, int64_t total_ids, uint16_t* d_out,
+                               int64_t out_cap, int64_t* d_out_offs, hipStream_t stream, int64_t* total_units, DevBuf* own_units = nullptr) {
+    using namespace tkz;
+    if (total_units) *total_units = 0;
+    if (n_docs < 0 || total_ids < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    if (n_docs == 0 && total_ids != 0) return fail(TKZ_E_ARG, "ids without documents");
+    int64_t* acc = &ws->bytes_allocated;
+    const int64_t ntiles = std::max<int64_t>(1, dec_tiles(total_ids)), nblk = (ntiles + kScanBlock - 1) / kScanBlock;
+    HIP_TRY(ws->d_grp.ensure((size_t)ntiles * 64 * 4, acc));
+    HIP_TRY(ws->d_tsum.ensure((size_t)ntiles * 4, acc));
+    HIP_TRY(ws->d_tbase.ensure((size_t)ntiles * 8, acc));
+    HIP_TRY(ws->d_bsum.ensure((size_t)(nblk + 1) * 8, acc));
+    HIP_TRY(ws->d_counters.ensure(64, acc));
+    HIP_TRY(ws->d8_boffs.ensure((size_t)(n_docs + 1) * 8, acc));
+    if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
+    Launch L{stream, nullptr, ws};
+    // the counter block: [0] error bits, +8 the byte total, +16 the unit total
+    int32_t* counters = ws->d_counters.as<int32_t>();
+    int64_t* grand = reinterpret_cast<int64_t*>(ws->d_counters.as<char>() + 8), * grand16 = grand + 1;
+    struct { int32_t err; int32_t pad; int64_t grand; int64_t grand16; } h{};
+    HIP_TRY(hipMemsetAsync(counters, 0, 64, stream));
+    launch_dec_len(L, e->D, d_ids, total_ids, ntiles, ws->d_grp.as<int32_t>(), ws->d_tsum.as<int32_t>());
+    launch_scan(L, ws->d_tsum.as<int32_t>(), ntiles, ws->d_bsum.as<int64_t>(), ws->d_tbase.as<int64_t>(), grand, -1);
+    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    memcpy(&h, ws->h_counters, 16);
+    const int64_t nbytes = h.grand;                                     // the batch as (not necessarily well-formed) UTF-8
+    const int64_t nw = nbytes / 64 + 1, nt8 = std::max<int64_t>(1, u8_tiles(nbytes)), nblk8 = (nt8 + kScanBlock - 1) / kScanBlock;
+    HIP_TRY(ws->d8_bytes.ensure((size_t)nbytes + 64, acc));
+    HIP_TRY(ws->d8_docbits.ensure((size_t)(nw + 8) * 8, acc));
+    HIP_TRY(ws->d8_grp.ensure((size_t)nt8 * 64 * 4, acc));
+    HIP_TRY(ws->d8_tsum.ensure((size_t)nt8 * 4, acc));
+    HIP_TRY(ws->d8_tbase.ensure((size_t)nt8 * 8, acc));
+    HIP_TRY(ws->d8_bsum.ensure((size_t)(nblk8 + 1) * 8, acc));
+    if (own_units) {
+        out_cap = std::min<int64_t>(out_cap, nbytes);
+        HIP_TRY(own_units->ensure((size_t)std::max<int64_t>(out_cap, 1) * 2, acc));
+        d_out = own_units->as<uint16_t>();
+    }
+    const uint8_t* bytes = ws->d8_bytes.as<uint8_t>();
+    const uint64_t* docbits = ws->d8_docbits.as<uint64_t>();
+    HIP_TRY(hipMemsetAsync(ws->d8_docbits.p, 0, (size_t)(nw + 8) * 8, stream));
+    launch_dec_write(L, e->D, d_ids, total_ids, ntiles, ws->d_tbase.as<int64_t>(), ws->d8_bytes.as<uint8_t>(), nbytes, d_id_offs, n_docs, ws->d_grp.as<int32_t>(), grand,
+                     ws->d8_boffs.as<int64_t>(), counters);
+    // (empty documents set no bit of their own; bad id offsets have set kErrOffsets above, and what is computed from their byte offsets is never used)
+    launch_docmark(L, ws->d8_boffs.as<int64_t>(), n_docs, nbytes, ws->d8_docbits.as<uint64_t>(), counters);
+    launch_u8_len(L, bytes, nbytes, docbits, nw, nt8, ws->d8_grp.as<int32_t>(), ws->d8_tsum.as<int32_t>());
+    launch_scan(L, ws->d8_tsum.as<int32_t>(), nt8, ws->d8_bsum.as<int64_t>(), ws->d8_tbase.as<int64_t>(), grand16, -1);
+    launch_u8_write(L, bytes, nbytes, docbits, nw, nt8, ws->d8_tbase.as<int64_t>(), d_out, d_out ? out_cap : 0, ws->d8_boffs.as<int64_t>(), n_docs,
+                    ws->d8_grp.as<int32_t>(), grand16, d_out_offs);
+    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, 24, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    memcpy(&h, ws->h_counters, 24);
+    if (h.err & kErrOffsets) return fail(TKZ_E_ARG, "id offsets must start at 0, be non-decreasing and end at the id count");
+    if (total_units) *total_units = h.grand16;
+    if (h.grand16 > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_decode_batch_utf16_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
+                                         uint16_t* d_out_units, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_units) {
+    DeviceScope scope;
+    tkz_status st = check_encoder(e, scope);
+    if (st != TKZ_OK) return st;
+    if (!d_id_offsets || !d_out_offsets || (total_ids > 0 && !d_ids) || (out_cap > 0 && !d_out_units)) return fail(TKZ_E_ARG, "null device buffer");
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    return decode_utf16_device(e, ws, d_ids, d_id_offsets, n_docs, total_ids, d_out_units, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), total_units);
+}
+
+tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
+                                  int64_t* out_offsets, int64_t* needed) {
+    DeviceScope scope;
+    tkz_status st = check_encoder(e, scope);
+    if (st != TKZ_OK) return st;
+    if (n_docs < 0 || !id_offsets || !out_offsets || (out_cap > 0 && !out_units)) return fail(TKZ_E_ARG, "null buffer");
+    if (id_offsets[0] != 0) return fail(TKZ_E_ARG, "id_offsets[0] must be 0");
+    const int64_t total = id_offsets[n_docs];
+    if (total < 0 || (total > 0 && !ids)) return fail(TKZ_E_ARG, "bad id count");
+    if (needed) *needed = 0;
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    int64_t* acc = &ws->bytes_allocated;
+    HIP_TRY(ws->d_ids.ensure((size_t)std::max<int64_t>(total, 1) * 4, acc));
+    HIP_TRY(ws->d_idoffs.ensure((size_t)(n_docs + 1) * 8, acc));
+    HIP_TRY(ws->d_outoffs.ensure((size_t)(n_docs + 1) * 8, acc));
+    if (total) HIP_TRY(hipMemcpy(ws->d_ids.p, ids, (size_t)total * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ws->d_idoffs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    int64_t nunits = 0;
+    st = decode_utf16_device(e, ws, ws->d_ids.as<int32_t>(), ws->d_idoffs.as<int64_t>(), n_docs, total, nullptr, out_cap, ws->d_outoffs.as<int64_t>(), nullptr, &nunits,
+                             &ws->d8_units);
+    if (needed) *needed = nunits;
+    if (st != TKZ_OK) return st;
+    if (nunits) HIP_TRY(hipMemcpy(out_units, ws->d8_units.p, (size_t)nunits * 2, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_offsets, ws->d_outoffs.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }

@@ -192,6 +192,13 @@ int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);
 void launch_dec_write(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, const int64_t* tile_base, uint8_t* out,
                       int64_t out_cap, const int64_t* id_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs, int32_t* counters);
+// decoded UTF-8 documents -> UTF-16 documents (Encoding.UTF8.GetString for a batch: every maximal subpart of an ill-formed sequence one U+FFFD): unit counts +
+// group prefixes, then (after the scan of the tile sums) the units and the unit offset of every document.  docbits: the document-start bitmap over the bytes
+// (launch_docmark over byte_offs), nwords words.  A tile whose units end beyond out_cap is not written.
+int64_t u8_tiles(int64_t total_bytes);
+void launch_u8_len(const Launch& L, const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);
+void launch_u8_write(const Launch& L, const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, const int64_t* tile_base,
+                     uint16_t* out, int64_t out_cap, const int64_t* byte_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* unit_offs);
 void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, int64_t n_docs, int min_len, int max_len,
                    int64_t* d_offs, uint8_t* d_bytes, int64_t cap_bytes, int64_t* d_total);
 

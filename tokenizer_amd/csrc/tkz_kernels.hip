@@ -3170,6 +3170,154 @@ TKZ_KERNEL(256) void k_dec_docoffs(TkzDecodeTable D, const int32_t* ids, int64_t
 }
 
 // -------------------------------------------------------------------------------------------------
+// Decoded documents -> UTF-16 documents on the device (the batch form of Encoding.UTF8.GetString, TikTokenizer.cs:603; WHATWG
+// TextDecoder("utf-8") in the TypeScript reference): the mirror of the k_u16_* family.  The bytes of k_dec_write are routinely
+// not well-formed -- keys are byte fragments, a trimmed id list ends inside a char --, and both references replace every
+// MAXIMAL SUBPART of an ill-formed sequence (Unicode 3.9, table 3-7) by one U+FFFD.  An ITEM is a well-formed char or such a
+// subpart.  Whether a byte starts an item is decidable from the 3 bytes before it: a lead byte or a byte that can start nothing
+// always does; a continuation byte does not iff the first non-continuation byte up to 3 bytes back INSIDE ITS DOCUMENT is a
+// lead that accepts every byte up to and including this one.  A lead looks at most 3 bytes ahead, inside its document, to
+// see whether its sequence completes (a char: one unit, or a pair for 4 bytes) or not (its accepted prefix: one U+FFFD).
+//   k_u8_len      per 1024-byte tile (one wavefront, 16 bytes per lane): units of every byte -> tile sum and the exclusive
+//                 prefix of every 16-byte group inside the tile
+//   (scan of the tile sums: k_scan_*)
+//   k_u8_write    the units, staged per tile in LDS and copied out coalesced
+//   k_u8_docoffs  unit offset of every document = tile base + group prefix + the bytes of the group before it
+// -------------------------------------------------------------------------------------------------
+constexpr int kU8Tile = 1024;       // bytes per wavefront
+constexpr int kU8Lane = 16;         // ... per lane
+constexpr int kU8Stage = kU8Tile + 8;   // units a tile can yield: a byte each, and one more for a 4-byte lead in its last byte (whose pair is 2 units: the rest of it lies in the next tile)
+// continuation bytes a lead asks for (0: no lead -- ASCII, a continuation byte, C0, C1, F5..FF)
+TKZ_HD int tkz_u8_need(uint32_t b) { return b - 0xC2u < 0x1Eu ? 1 : (b - 0xE0u < 0x10u ? 2 : (b - 0xF0u < 5u ? 3 : 0)); }
+TKZ_HD bool tkz_u8_cont(uint32_t b) { return (b & 0xC0u) == 0x80u; }
+// table 3-7: the second byte a lead accepts (the third and fourth: any continuation byte)
+TKZ_HD bool tkz_u8_second(uint32_t lead, uint32_t c) {
+    const uint32_t lo = lead == 0xE0u ? 0xA0u : (lead == 0xF0u ? 0x90u : 0x80u), hi = lead == 0xEDu ? 0x9Fu : (lead == 0xF4u ? 0x8Fu : 0xBFu);
+    return c >= lo && c <= hi;
+}
+// The units of byte b0 at a position q whose neighbours are p3 p2 p1 (q - 3 .. q - 1) and n1 n2 n3 (q + 1 .. q + 3).  ds: the document-start bits of
+// q - 2 .. q + 3 (bit 2 = q itself): a neighbour counts only when no document starts between it and q.  Returns 0 (the byte belongs to the item a lead before
+// it starts), 1 (*u0) or 2 (*u0, *u1: a pair).
+TKZ_HD int tkz_u8_item(uint32_t p3, uint32_t p2, uint32_t p1, uint32_t b0, uint32_t n1, uint32_t n2, uint32_t n3, uint32_t ds, uint32_t* u0, uint32_t* u1) {
+    *u0 = 0xFFFDu; *u1 = 0u;
+    if (b0 < 0x80u) { *u0 = b0; return 1; }
+    if (tkz_u8_cont(b0)) {
+        const bool back1 = !(ds & 4u), back2 = back1 && !(ds & 2u), back3 = back2 && !(ds & 1u);
+        if (!back1) return 1;
+        if (!tkz_u8_cont(p1)) return tkz_u8_need(p1) >= 1 && tkz_u8_second(p1, b0) ? 0 : 1;
+        if (!back2) return 1;
+        if (!tkz_u8_cont(p2)) return tkz_u8_need(p2) >= 2 && tkz_u8_second(p2, p1) ? 0 : 1;
+        if (!back3) return 1;
+        return tkz_u8_need(p3) == 3 && tkz_u8_second(p3, p2) ? 0 : 1;
+    }
+    const int need = tkz_u8_need(b0);
+    if (need == 0) return 1;                                               // C0, C1, F5..FF
+    const bool fwd1 = !(ds & 8u), fwd2 = fwd1 && !(ds & 16u), fwd3 = fwd2 && !(ds & 32u);
+    if (!(fwd1 && tkz_u8_second(b0, n1))) return 1;
+    if (need == 1) { *u0 = ((b0 & 0x1Fu) << 6) | (n1 & 0x3Fu); return 1; }
+    if (!(fwd2 && tkz_u8_cont(n2))) return 1;
+    if (need == 2) { *u0 = ((b0 & 0x0Fu) << 12) | ((n1 & 0x3Fu) << 6) | (n2 & 0x3Fu); return 1; }
+    if (!(fwd3 && tkz_u8_cont(n3))) return 1;
+    const uint32_t c = (((b0 & 0x07u) << 18) | ((n1 & 0x3Fu) << 12) | ((n2 & 0x3Fu) << 6) | (n3 & 0x3Fu)) - 0x10000u;
+    *u0 = 0xD800u + (c >> 10); *u1 = 0xDC00u + (c & 0x3FFu);
+    return 2;
+}
+// the document-start bits of positions q0 - 2 .. q0 + 29 (bit j = position q0 - 2 + j), q0 >= 0; docbits has nwords words
+TKZ_HD uint32_t tkz_u8_bits(const uint64_t* docbits, int64_t nwords, int64_t q0) {
+    if (q0 < 2) return (uint32_t)(docbits[0] << (2 - q0));
+    const int64_t s = q0 - 2, wd = s >> 6; const int sh = (int)(s & 63);
+    uint64_t v = wd < nwords ? docbits[wd] >> sh : 0ull;
+    if (sh > 32 && wd + 1 < nwords) v |= docbits[wd + 1] << (64 - sh);
+    return (uint32_t)v;
+}
+// the bytes of this lane's group with the 3 either side of it (b[3] is the group's first), its document-start bits (tkz_u8_bits of the group's
+// first position: 21 are used); returns the lane sum
+struct TkzU8Lane { uint32_t b[kU8Lane + 6]; uint32_t ds; };
+TKZ_DEV int tkz_u8_lane(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t tile, TkzU8Lane* L) {
+    const int lane = simt::lane();
+    const int64_t p0 = tile * kU8Tile + (int64_t)lane * kU8Lane;
+    uint32_t w[4];
+    if (p0 + kU8Lane <= total) { const uint4 a = tkz_load16(bytes + p0); w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; }
+    else {
+        for (int k = 0; k < 4; ++k) {
+            w[k] = 0u;
+            for (int j = 0; j < 4; ++j) { const int64_t q = p0 + 4 * k + j; if (q < total) w[k] |= (uint32_t)bytes[q] << (8 * j); }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kU8Lane; ++k) L->b[3 + k] = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+    // neighbours across the lane edge: the last 3 bytes of the lane below, the first 3 of the lane above
+    uint32_t prev = simt::shflu(w[3], (lane + 63) & 63) >> 8, next = simt::shflu(w[0], (lane + 1) & 63) & 0xFFFFFFu;
+    if (lane == 0) { prev = 0u; for (int j = 1; j <= 3; ++j) if (p0 - j >= 0 && p0 - j < total) prev |= (uint32_t)bytes[p0 - j] << (8 * (3 - j)); }
+    if (lane == 63) { next = 0u; for (int j = 0; j < 3; ++j) if (p0 + kU8Lane + j < total) next |= (uint32_t)bytes[p0 + kU8Lane + j] << (8 * j); }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { L->b[j] = (prev >> (8 * j)) & 0xFFu; L->b[3 + kU8Lane + j] = (next >> (8 * j)) & 0xFFu; }
+    L->ds = p0 < total ? tkz_u8_bits(docbits, nwords, p0) : 0u;
+    int sum = 0;
+#pragma unroll
+    for (int k = 0; k < kU8Lane; ++k) {
+        uint32_t u0, u1;
+        if (p0 + k < total) sum += tkz_u8_item(L->b[k], L->b[k + 1], L->b[k + 2], L->b[k + 3], L->b[k + 4], L->b[k + 5], L->b[k + 6], L->ds >> k, &u0, &u1);
+    }
+    return sum;
+}
+TKZ_KERNEL(256) void k_u8_len(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum) {
+    const int64_t tile = simt::bid() * (kThreads / 64) + simt::wave();
+    if (tile >= ntiles) return;
+    TkzU8Lane L;
+    const int sum = tkz_u8_lane(bytes, total, docbits, nwords, tile, &L);
+    int tot;
+    const int pre = tkz_wave_scan_sum(sum, &tot);
+    grp_prefix[tile * 64 + simt::lane()] = pre;
+    if (simt::lane() == 0) tile_sum[tile] = tot;
+}
+TKZ_KERNEL(256) void k_u8_write(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, const int64_t* tile_base,
+                                uint16_t* out, int64_t out_cap) {
+    TKZ_SHARED uint16_t s_stage[kThreads / 64][kU8Stage];
+    const int64_t tile = simt::bid() * (kThreads / 64) + simt::wave();
+    if (tile >= ntiles) return;
+    TkzU8Lane L;
+    const int sum = tkz_u8_lane(bytes, total, docbits, nwords, tile, &L);
+    int tot;
+    int pos = tkz_wave_scan_sum(sum, &tot);
+    const int64_t base = tile_base[tile];
+    if (base + tot > out_cap || tot > kU8Stage) return;      // (the host reports TKZ_E_CAPACITY from the grand total)
+    const int64_t p0 = tile * kU8Tile + (int64_t)simt::lane() * kU8Lane;
+    uint16_t* st = s_stage[simt::wave()];
+#pragma unroll
+    for (int k = 0; k < kU8Lane; ++k) {
+        uint32_t u0, u1;
+        if (p0 + k < total) {
+            const int n = tkz_u8_item(L.b[k], L.b[k + 1], L.b[k + 2], L.b[k + 3], L.b[k + 4], L.b[k + 5], L.b[k + 6], L.ds >> k, &u0, &u1);
+            if (n >= 1) st[pos] = (uint16_t)u0;
+            if (n == 2) st[pos + 1] = (uint16_t)u1;
+            pos += n;
+        }
+    }
+    (void)simt::ballot(true);          // (the staging area is private to the wavefront: its LDS accesses are ordered, no barrier)
+    uint16_t* dst = out + base;
+    for (int i = simt::lane(); i < tot; i += 64) dst[i] = st[i];
+}
+// the units of the byte at q, its neighbours and bits read one by one (k_u8_docoffs: the few bytes between a group's start and a document's)
+TKZ_DEV int tkz_u8_units_at(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t q) {
+    uint32_t b[7], u0, u1;
+    for (int j = 0; j < 7; ++j) { const int64_t r = q - 3 + j; b[j] = r >= 0 && r < total ? (uint32_t)bytes[r] : 0u; }
+    return tkz_u8_item(b[0], b[1], b[2], b[3], b[4], b[5], b[6], tkz_u8_bits(docbits, nwords, q), &u0, &u1);
+}
+TKZ_KERNEL(256) void k_u8_docoffs(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, const int64_t* byte_offs, int64_t n_docs,
+                                  const int64_t* tile_base, const int32_t* grp_prefix, const int64_t* grand, int64_t* unit_offs) {
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    for (int64_t d = simt::bid() * simt::nthreads() + simt::tid(); d <= n_docs; d += stride) {
+        const int64_t p = byte_offs[d];
+        if (p >= total) { unit_offs[d] = *grand; continue; }
+        if (p < 0) { unit_offs[d] = 0; continue; }
+        int64_t v = tile_base[p / kU8Tile] + grp_prefix[p / kU8Lane];
+        for (int64_t q = p & ~(int64_t)(kU8Lane - 1); q < p; ++q) v += tkz_u8_units_at(bytes, total, docbits, nwords, q);      // the bytes of the group that belong to the document before
+        unit_offs[d] = v;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // synthetic corpus (tkz_corpus.h): lengths, then bytes
 // -------------------------------------------------------------------------------------------------
 TKZ_KERNEL(256) void k_corpus_lengths(int kind, uint64_t seed, int64_t first_doc, int64_t n_docs, int min_len, int max_len, int64_t* offs) {
@@ -3650,6 +3798,15 @@ void launch_dec_write(const Launch& L, const TkzDecodeTable& D, const int32_t* i
                       int64_t out_cap, const int64_t* id_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* byte_offs, int32_t* counters) {
     TKZ_LAUNCH(k_dec_write, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, D, ids, total, ntiles, tile_base, out, out_cap);
     TKZ_LAUNCH(k_dec_docoffs, grid_for(n_docs + 1), kThreads, L.stream, D, ids, total, id_offs, n_docs, tile_base, grp_prefix, grand, byte_offs, counters);
+}
+int64_t u8_tiles(int64_t total_bytes) { return cdiv(total_bytes, kU8Tile); }
+void launch_u8_len(const Launch& L, const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum) {
+    TKZ_LAUNCH(k_u8_len, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, bytes, total, docbits, nwords, ntiles, grp_prefix, tile_sum);
+}
+void launch_u8_write(const Launch& L, const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, const int64_t* tile_base,
+                     uint16_t* out, int64_t out_cap, const int64_t* byte_offs, int64_t n_docs, const int32_t* grp_prefix, const int64_t* grand, int64_t* unit_offs) {
+    TKZ_LAUNCH(k_u8_write, grid1(cdiv(ntiles, kThreads / 64)), kThreads, L.stream, bytes, total, docbits, nwords, ntiles, tile_base, out, out_cap);
+    TKZ_LAUNCH(k_u8_docoffs, grid_for(n_docs + 1), kThreads, L.stream, bytes, total, docbits, nwords, byte_offs, n_docs, tile_base, grp_prefix, grand, unit_offs);
 }
 void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, int64_t n_docs, int min_len, int max_len,
                    int64_t* d_offs, uint8_t* d_bytes, int64_t cap_bytes, int64_t* d_total) {

@@ -394,6 +394,20 @@ class TikTokenizer:
         raw = data.tobytes()
         return [raw[boffs[d]:boffs[d + 1]].decode("utf-8", "replace") for d in range(len(batches))]
 
+    def DecodeUtf16(self, tokens: Sequence[int]) -> str:
+        """Decode with Encoding.UTF8.GetString done on the device as well: the same string as Decode."""
+        return self.DecodeBatchUtf16([tokens])[0]
+
+    def DecodeBatchUtf16(self, batches: Sequence[Sequence[int]]) -> List[str]:
+        """DecodeBatch through tkz_decode_batch_utf16: the device hands back the UTF-16 code units of every document (malformed sequences already U+FFFD, one
+        per maximal subpart), so the units are well-formed and the conversion below is exact."""
+        flat = np.asarray([t for b in batches for t in b], dtype=np.int64)
+        flat = np.where((flat < -2**31) | (flat >= 2**31), -1, flat).astype(np.int32)      # (an id outside int is in no table)
+        offs = np.cumsum([0] + [len(b) for b in batches]).astype(np.int64)
+        units, uoffs = self._encoder.decode_batch_utf16(flat, offs)
+        units = units.astype("<u2", copy=False)
+        return [units[uoffs[d]:uoffs[d + 1]].tobytes().decode("utf-16-le") for d in range(len(batches))]
+
     # the raw device encoder, for callers that hold documents in HBM (bench.py)
     @property
     def native(self) -> N.Encoder:
