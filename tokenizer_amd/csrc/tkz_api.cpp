@@ -108,6 +108,85 @@ struct CounterBlock {          // mirrors the device block
     unsigned long long n_literals;         // the special entries: special-token literals taken (k_lit_resolve)
     int64_t kept_total;                    // the trim entries: ids kept over the whole batch (k_trim_gather)
 };
+// ... and the 64-byte block of the length scans (the UTF-16 transcoder, the two decoders): k_docmark's / k_dec_write's error bits, the scans' grand totals
+struct LenCounters { int32_t err, pad; int64_t grand /* UTF-8 bytes */, grand16 /* UTF-16 code units (tkz_decode_batch_utf16 only) */; };
+const char* const kMsgByteOffsets = "document offsets must start at 0, be non-decreasing and end at the byte count";
+const char* const kMsgUnitOffsets = "document offsets must start at 0, be non-decreasing and end at the unit count";
+const char* const kMsgIdOffsets = "id offsets must start at 0, be non-decreasing and end at the id count";
+
+void release_each(std::initializer_list<DevBuf*> bufs) { for (DevBuf* b : bufs) b->release(); }
+
+// The buffers of one feature each, with release() directly under the fields: a buffer added to a line is freed by adding it to the line below it.  Workspace
+// is made of them (base structs, so a buffer keeps the one name it has everywhere: ws->d_tsum).
+struct SpecialBufs {   // the special entries (allocated on their first use): candidates, segment marks (the pre-tokenizer's isolation boundaries), starts and ends of the
+    // taken literals; the segments' offsets for the scanners that take offsets
+    DevBuf w_candbits, w_segbits, w_specbits, w_endbits, w_segoffs;
+    void release() { release_each({&w_candbits, &w_segbits, &w_specbits, &w_endbits, &w_segoffs}); }
+};
+struct HostStageBufs {   // the host entries' staging: two input sets (chunk k+1 goes up while chunk k is encoded), three output sets; ONE-call entries use set 0
+    DevBuf s_bytes[2], s_offs[2], s_out[3], s_outoffs[3];
+    void release() { release_each({&s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2], &s_outoffs[0], &s_outoffs[1], &s_outoffs[2]}); }
+};
+struct DecodeBufs {   // Decode: the length scan's buffers (decode_lengths), the host entries' staging of ids, id offsets, bytes and byte (or unit) offsets
+    DevBuf d_grp, d_tsum, d_tbase, d_bsum, d_counters, d_ids, d_idoffs, d_out, d_outoffs;
+    void release() { release_each({&d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs}); }
+};
+struct DecodeUtf16Bufs {   // Decode to UTF-16: the decoded bytes, their document offsets and start bitmap, per-tile / per-group unit counts, the host entry's units
+    DevBuf d8_bytes, d8_boffs, d8_docbits, d8_grp, d8_tsum, d8_tbase, d8_bsum, d8_units;
+    void release() { release_each({&d8_bytes, &d8_boffs, &d8_docbits, &d8_grp, &d8_tsum, &d8_tbase, &d8_bsum, &d8_units}); }
+};
+struct PieceBufs {   // piece-granular entry point: piece byte offsets, token offsets, first piece of every document
+    DevBuf p_boffs, p_toffs, p_docp;
+    void release() { release_each({&p_boffs, &p_toffs, &p_docp}); }
+};
+struct TrimBufs {   // the trim entries: the untrimmed ids, {kept token range, cut position} per document and their scan's partial sums; the host entries' maxima and cuts
+    DevBuf t_ids, t_keep, t_bsum, t_stage;
+    void release() { release_each({&t_ids, &t_keep, &t_bsum, &t_stage}); }
+};
+// The UTF-16 batch entry points: code units, their document marks, per-tile / per-group lengths (two sets: the units of chunk k+1 are uploaded and measured while
+// chunk k is encoded), the UTF-8 batch they become and its byte offsets (u16_measure / u16_write)
+struct U16Stage {
+    DevBuf units, offs, docbits, grp, tsum, tbase, bsum, counters, boffs, bytes; LenCounters* h = nullptr;
+    DevBuf repl;       // the replaced-byte bitmap of the chunk's UTF-8 bytes (k_u16_write): special calls with a registered literal that holds U+FFFD only
+    static size_t repl_bytes(int64_t n_bytes) { return (size_t)(n_bytes / 64 + 8) * 8; }
+    hipError_t ensure(int64_t max_units, int64_t max_docs, int64_t* acc, bool with_repl = false) {      // room for a chunk of max_units code units in max_docs documents
+        if (with_repl) { const hipError_t r = repl.ensure(repl_bytes(3 * max_units), acc); if (r != hipSuccess) return r; }      // (a unit is at most three bytes)
+        const int64_t nw = max_units / 64 + 1, nt = tkz::u16_tiles(max_units), nblk = (nt + tkz::kScanBlock - 1) / tkz::kScanBlock;
+        const std::pair<DevBuf*, size_t> want[] = {{&units, (size_t)(max_units + 64) * 2}, {&offs, (size_t)(max_docs + 1) * 8}, {&docbits, (size_t)(nw + 8) * 8},
+                                                   {&grp, (size_t)nt * 64 * 4}, {&tsum, (size_t)nt * 4}, {&tbase, (size_t)nt * 8}, {&bsum, (size_t)(nblk + 1) * 8},
+                                                   {&counters, 64}, {&boffs, (size_t)(max_docs + 1) * 8}};
+        for (const auto& w : want) { const hipError_t r = w.first->ensure(w.second, acc); if (r != hipSuccess) return r; }
+        return h ? hipSuccess : hipHostMalloc((void**)&h, 64, 0);
+    }
+    void release() {
+        release_each({&units, &offs, &docbits, &grp, &tsum, &tbase, &bsum, &counters, &boffs, &bytes, &repl});
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+    }
+};
+// Encoding.UTF8.GetBytes on the device, in two steps; the caller waits between them in its own way (the chunk pipeline: an event; the trim entry: the null stream).
+// On L's stream: the document marks of the units in U.units / U.offs, the UTF-8 length of every unit, their scan; the error bits and the total on their way to U.h.
+hipError_t u16_measure(U16Stage& U, const tkz::Launch& L, int64_t n_units, int64_t n_docs) {
+    LenCounters* const blk = U.counters.as<LenCounters>();
+    const int64_t nt = tkz::u16_tiles(n_units);
+    hipError_t r = hipMemsetAsync(U.counters.p, 0, 64, L.stream);
+    if (r == hipSuccess) r = hipMemsetAsync(U.docbits.p, 0, (size_t)(n_units / 64 + 1 + 8) * 8, L.stream);
+    if (r != hipSuccess) return r;
+    launch_docmark(L, U.offs.as<int64_t>(), n_docs, n_units, U.docbits.as<uint64_t>(), &blk->err);
+    launch_u16_len(L, U.units.as<uint16_t>(), n_units, U.docbits.as<uint64_t>(), nt, U.grp.as<int32_t>(), U.tsum.as<int32_t>());
+    launch_scan(L, U.tsum.as<int32_t>(), nt, U.bsum.as<int64_t>(), U.tbase.as<int64_t>(), &blk->grand, -1);
+    return hipMemcpyAsync(U.h, U.counters.p, 16, hipMemcpyDeviceToHost, L.stream);
+}
+// Once U.h has arrived: bad unit offsets are refused; else U.bytes is sized for the *n_bytes of UTF-8 and these and their offsets (U.boffs) are written on L's stream.
+tkz_status u16_write(U16Stage& U, const tkz::Launch& L, int64_t n_units, int64_t n_docs, bool with_repl, int64_t* acc, int64_t* n_bytes) {
+    if (U.h->err & kErrOffsets) return fail(TKZ_E_ARG, kMsgUnitOffsets);
+    *n_bytes = U.h->grand;
+    HIP_TRY(U.bytes.ensure((size_t)*n_bytes + 64, acc));
+    if (with_repl) HIP_TRY(hipMemsetAsync(U.repl.p, 0, U16Stage::repl_bytes(*n_bytes), L.stream));
+    launch_u16_write(L, U.units.as<uint16_t>(), n_units, U.docbits.as<uint64_t>(), tkz::u16_tiles(n_units), U.tbase.as<int64_t>(), U.bytes.as<uint8_t>(), U.offs.as<int64_t>(), n_docs,
+                     U.grp.as<int32_t>(), &U.counters.as<LenCounters>()->grand, U.boffs.as<int64_t>(), with_repl ? U.repl.as<uint64_t>() : nullptr);
+    return TKZ_OK;
+}
 
 }  // namespace
 
@@ -120,7 +199,7 @@ struct tkz_vocab { tkz::Vocab v; };
 // call, so host threads sharing one encoder run concurrently, each on its own workspace and streams ("one encoder
 // usable from many host threads") -- the reference's instance is likewise safe to share (its only shared mutable state, the LRU
 // memo, is locked: LRUCache.cs:61,99).
-struct Workspace {
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, PieceBufs, TrimBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -128,52 +207,20 @@ struct Workspace {
     DevBuf w_zero; size_t zero_bytes = 0;
     DevView w_counters, w_docbits, w_heavyq;
     DevBuf w_mlist, w_mquad, w_mcount, w_pextra, w_coopq, w_lqcnt, w_lqbase, w_lq;
+    DevBuf w_counts3;                      // {n_docs, n_bytes, n_tokens} of the batch this workspace is running (tkz_pending_counts_device)
+    void release_core() {
+        release_each({&w_gq, &w_gcnt, &w_xq, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum, &w_doctok, &w_dcount, &w_dbase, &w_pool,
+                      &w_zero, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_counts3});
+    }
+    U16Stage u16[2];
     bool learn_window_start = false;       // this learning batch opens a window: the hit counters and the log start from zero
-    // the special entries only (allocated on their first use): candidates, segment marks (document marks + starts and ends of the taken literals: what the
-    // pre-tokenizer takes for its isolation boundaries), starts and ends of the taken literals; the segments' offsets for the scanners that take offsets
-    DevBuf w_candbits, w_segbits, w_specbits, w_endbits, w_segoffs;
     int64_t n_seg = 0;                     // segments of the batch whose marks the workspace holds (w_segoffs)
     int64_t spec_taken = 0;                // literals taken in that batch
-    DevBuf w_counts3;                      // {n_docs, n_bytes, n_tokens} of the batch this workspace is running (tkz_pending_counts_device)
     bool sized = false;                    // a batch has run to its end here: the lists and the record buffer have seen real text (encode_device: the sizing attempt)
     int32_t mcap = tkz::kMissCapMin;       // entries of a sub-tile's miss list; grows (once, to what the batch needed) when a sub-tile overflows it
     bool place128 = false;                 // a recent batch of this workspace had more than a fifth of its sub-tiles above 64 list entries: k_place<128>
     int low_lists = 0, low_place = 0;      // consecutive batches that would have done with shorter lists / with k_place<64> (hysteresis: kLowBatches)
     bool learning = false;                 // this workspace's batch counts memo hits per slot (TkzTables::memo_hits): the encoder promotes the hottest entries when it ends
-    // staging for the host-buffer entry points (two sets: chunk k+1 is uploaded while chunk k is encoded and chunk k-1 downloaded)
-    DevBuf s_bytes[2], s_offs[2], s_out[3], s_outoffs[3];      // staging of the host-buffer entry points: two input sets, three output sets (encode_host)
-    // the UTF-16 batch entry point: code units, their document marks, per-tile / per-group lengths (two sets: the units of chunk k+1 are uploaded and
-    // measured while chunk k is encoded), the UTF-8 batch they become
-    struct U16Stage {
-        DevBuf units, offs, docbits, grp, tsum, tbase, bsum, counters, boffs; struct Host { int32_t err; int32_t pad; int64_t grand; }* h = nullptr;
-        DevBuf repl;       // the replaced-byte bitmap of the chunk's UTF-8 bytes (k_u16_write): special calls with a registered literal that holds U+FFFD only
-        static size_t repl_bytes(int64_t n_bytes) { return (size_t)(n_bytes / 64 + 8) * 8; }
-        hipError_t ensure(int64_t max_units, int64_t max_docs, int64_t* acc, bool with_repl = false) {      // room for a chunk of max_units code units in max_docs documents
-            if (with_repl) { const hipError_t r = repl.ensure(repl_bytes(3 * max_units), acc); if (r != hipSuccess) return r; }      // (a unit is at most three bytes)
-            const int64_t nw = max_units / 64 + 1, nt = tkz::u16_tiles(max_units), nblk = (nt + tkz::kScanBlock - 1) / tkz::kScanBlock;
-            const std::pair<DevBuf*, size_t> want[] = {{&units, (size_t)(max_units + 64) * 2}, {&offs, (size_t)(max_docs + 1) * 8}, {&docbits, (size_t)(nw + 8) * 8},
-                                                       {&grp, (size_t)nt * 64 * 4}, {&tsum, (size_t)nt * 4}, {&tbase, (size_t)nt * 8}, {&bsum, (size_t)(nblk + 1) * 8},
-                                                       {&counters, 64}, {&boffs, (size_t)(max_docs + 1) * 8}};
-            for (const auto& w : want) { const hipError_t r = w.first->ensure(w.second, acc); if (r != hipSuccess) return r; }
-            return h ? hipSuccess : hipHostMalloc((void**)&h, 64, 0);
-        }
-        void release() {
-            for (DevBuf* b : {&units, &offs, &docbits, &grp, &tsum, &tbase, &bsum, &counters, &boffs, &repl}) b->release();
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-    } u16[2];
-    DevBuf u_bytes[2];
-    // Decode
-    DevBuf d_grp, d_tsum, d_tbase, d_bsum, d_counters, d_ids, d_idoffs, d_out, d_outoffs;
-    // Decode to UTF-16: the decoded bytes and their document offsets (sized from the length scan's byte total), the document-start bitmap over the bytes,
-    // per-tile / per-group unit counts, the host entry's staging of the units
-    DevBuf d8_bytes, d8_boffs, d8_docbits, d8_grp, d8_tsum, d8_tbase, d8_bsum, d8_units;
-    // piece-granular entry point: piece byte offsets, token offsets, first piece of every document
-    DevBuf p_boffs, p_toffs, p_docp;
-    // the trim entries: the untrimmed ids (a token is at least a byte: 4 bytes per input byte), {kept token range, cut position} per document and the
-    // partial sums of their scan; the host entry's staging of the per-document maxima and the two cut arrays
-    DevBuf t_ids, t_keep, t_bsum, t_stage;
     CounterBlock* h_counters = nullptr;   // pinned
     // the single-launch path for small batches (k_small): input, output and status in ONE page-locked block the device reads and writes directly
     uint8_t* h_small = nullptr;
@@ -198,11 +245,8 @@ struct Workspace {
     double ms[tkz::K_COUNT] = {};
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
-        DevBuf* bufs[] = {&w_candbits, &w_segbits, &w_specbits, &w_endbits, &w_segoffs, &w_counts3, &w_mlist, &w_mquad, &w_mcount, &w_pextra, &w_coopq, &w_lqcnt, &w_lqbase, &w_lq, &w_gq, &w_gcnt, &w_xq, &w_zero, &w_startbits, &w_tmp, &w_dense, &w_tcount, &w_prank, &w_pcount, &w_pbase, &w_tbase, &w_bsum,
-                          &w_doctok, &w_dcount, &w_dbase, &w_pool, &s_bytes[0], &s_bytes[1], &s_offs[0], &s_offs[1], &s_out[0], &s_out[1], &s_out[2],
-                          &s_outoffs[0], &s_outoffs[1], &s_outoffs[2], &u_bytes[0], &u_bytes[1],
-                          &d_grp, &d_tsum, &d_tbase, &d_bsum, &d_counters, &d_ids, &d_idoffs, &d_out, &d_outoffs, &d8_bytes, &d8_boffs, &d8_docbits, &d8_grp, &d8_tsum, &d8_tbase, &d8_bsum, &d8_units, &p_boffs, &p_toffs, &p_docp, &t_ids, &t_keep, &t_bsum, &t_stage};
-        for (DevBuf* b : bufs) b->release();
+        release_core();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); PieceBufs::release(); TrimBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -319,13 +363,14 @@ struct BatchCall {
 
 // One batch in the caller's host memory, as the host entries hand it to encode_host.
 struct HostCall {
-    const uint8_t* bytes; const uint16_t* units;       // UTF-8 bytes, or UTF-16 code units (offsets in units then)
+    const uint8_t* bytes; const uint16_t* units;       // UTF-8 bytes, or (utf16) UTF-16 code units (offsets in units then)
     const int64_t* offs; int64_t n_docs;
     int32_t* out_ids; int64_t out_cap; int64_t* out_offsets; int64_t* needed;
     CallKind kind = CallKind::Encode;                  // (never Pieces: that entry stages its own buffers)
     uint64_t* bitmap = nullptr;                        // BitmapOnly: the caller's words
     const SpecialCall* special = nullptr;
-    bool u16() const { return units != nullptr; }
+    bool utf16 = false;
+    bool u16() const { return utf16; }
     int64_t total() const { return offs[n_docs]; }     // bytes, or code units
     bool plain_encode() const { return kind == CallKind::Encode; }
     // the same call on device buffers
@@ -1268,7 +1313,6 @@ bool pinned_host(const void* p, void** dev) {
 //    chunks k+1 and k+2 (enqueued ahead, on two workspaces) and the download of chunk k (page-locked results: on a copy engine of its own, tkz_sdma.h) run at the
 //    same time.  512 MB of page-locked text: 22 -> 37 GB/s, 64 MB: 22 -> 29.5 (profiles/r06/host_batches_ab.txt); what bounds it now is the download of the ids at
 //    the link's duplex rate.
-const char* const kMsgUnitOffsets = "document offsets must start at 0, be non-decreasing and end at the unit count";
 const char* const kMsgEngineDownload = "a copy engine reported an error for a download";
 constexpr int64_t kHostChunkMin = int64_t(8) << 20;      // a chunk is at least this large (smaller ones were measured through an environment knob: profiles/r06/host_batches_ab.txt)
 
@@ -1325,22 +1369,63 @@ HostPlan plan_host_batch(const HostCall& c) {
     return p;
 }
 
+// ---- the steps a host entry is composed from: validate, stage in, (transcode / decode lengths, the device call,) fetch -------------------------------
+// What is said of a host batch's documents: of a first offset that is not 0, of items without a buffer, of a negative total, of an empty batch with other offsets than 0
+struct DocKind { const char* first; const char* no_data; const char* negative; const char* not_empty; };
+const char* const kMsgDocFirst = "doc_offsets[0] must be 0";
+const DocKind kByteDocs{kMsgDocFirst, "null buffer", "negative byte count", kMsgByteOffsets}, kUnitDocs{kMsgDocFirst, "null buffer", "negative unit count", kMsgUnitOffsets},
+              kSizedDocs{kMsgDocFirst, "null buffer", "negative size", kMsgByteOffsets}, kIdDocs{"id_offsets[0] must be 0", "bad id count", "bad id count", nullptr};
+// The caller's offsets before anything is read through them: n_docs, the array, items behind a positive total, a first offset of 0, a total that is not negative.
+tkz_status check_host_docs(const int64_t* offs, int64_t n_docs, bool have_data, const DocKind& kind, int64_t* total) {
+    if (n_docs < 0 || !offs) return fail(TKZ_E_ARG, "null buffer");
+    if (n_docs > 0 && !have_data && offs[n_docs] > 0) return fail(TKZ_E_ARG, kind.no_data);
+    if (offs[0] != 0) return fail(TKZ_E_ARG, kind.first);
+    *total = offs[n_docs];
+    if (*total < 0) return fail(TKZ_E_ARG, kind.negative);
+    return TKZ_OK;
+}
+// ... and of a batch with a total of 0, which no kernel looks at: every offset is 0 -- and so is every offset of the result (out_offsets, or null)
+tkz_status check_empty_docs(const int64_t* offs, int64_t n_docs, const DocKind& kind, int64_t* out_offsets) {
+    for (int64_t d = 0; d < n_docs; ++d) if (offs[d] != 0) return fail(TKZ_E_ARG, kind.not_empty);
+    if (out_offsets) std::fill_n(out_offsets, n_docs + 1, int64_t(0));
+    return TKZ_OK;
+}
+// the caller's result buffers: offsets always, items when there is room for any (trim: a capacity below 0 is refused here as well)
+tkz_status check_host_outputs(const void* out_items, int64_t out_cap, const void* out_offsets, const char* msg = "null output buffer", bool negative_cap_ok = true) {
+    if (!out_offsets || (out_cap > 0 && !out_items) || (out_cap < 0 && !negative_cap_ok)) return fail(TKZ_E_ARG, msg);
+    return TKZ_OK;
+}
+
+// Whole-batch staging, for the entries that run ONE device call on pageable buffers: blocking copies on the null stream into and out of staging set 0.
+tkz_status stage_in(Workspace* ws, const uint8_t* bytes, int64_t total, const int64_t* offs, int64_t n_docs) {
+    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, &ws->bytes_allocated));
+    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, &ws->bytes_allocated));
+    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ws->s_offs[0].p, offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    return TKZ_OK;
+}
+tkz_status stage_out(Workspace* ws, int64_t n_docs, int64_t cap, bool with_offsets = true) {
+    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, &ws->bytes_allocated));
+    if (with_offsets) HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, &ws->bytes_allocated));
+    return TKZ_OK;
+}
+tkz_status fetch(Workspace* ws, int32_t* out_ids, int64_t tokens, int64_t* out_offsets, int64_t n_docs) {      // (out_offsets null: the ids only)
+    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    if (out_offsets) HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+BatchCall staged_call(Workspace* ws, int64_t n_docs, int64_t total, int64_t cap) {      // the batch stage_in / stage_out left on the device
+    return BatchCall{ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr};
+}
+
 // one chunk, ordinary (pageable) buffers: blocking copies either side of the launch sequence
 tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const HostCall& c) {
-    int64_t* acc = &ws->bytes_allocated;
     uint64_t* const bitmap = c.bitmap;
     const int64_t n_docs = c.n_docs, total = c.total();
-    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
-    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
     const int64_t cap = bitmap ? 0 : std::min<int64_t>(c.out_cap, total);   // tokens <= bytes: more capacity is never used
-    if (!bitmap) {
-        HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
-        HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    } else {
-        HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, acc));
-    }
-    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, c.bytes, (size_t)total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->s_offs[0].p, c.offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    TKZ_TRY(stage_in(ws, c.bytes, total, c.offs, n_docs));
+    if (bitmap) HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, &ws->bytes_allocated));
+    else TKZ_TRY(stage_out(ws, n_docs, cap));
     int64_t tokens = 0;
     BatchCall dc = c.on_device(ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr);
     if (bitmap) dc.d_bitmap = ws->s_out[0].as<uint64_t>();
@@ -1351,9 +1436,7 @@ tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const HostCall& c
         HIP_TRY(hipMemcpy(bitmap, ws->s_out[0].p, (size_t)(total / 64 + 1) * 8, hipMemcpyDeviceToHost));
         return TKZ_OK;
     }
-    if (tokens) HIP_TRY(hipMemcpy(c.out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(c.out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
-    return TKZ_OK;
+    return fetch(ws, c.out_ids, tokens, c.out_offsets, n_docs);
 }
 
 // Inside the pipeline a failed runtime call is RECORDED (HostPipeline::note), never returned from encode_host: the upload of a later chunk may still be reading the
@@ -1430,17 +1513,11 @@ struct HostPipeline {
         const int64_t d0 = cut[(size_t)k], d1 = cut[(size_t)k + 1], u0 = offs[d0], nu = offs[d1] - u0, nd = d1 - d0;
         Launch L{ws->st_in, nullptr, ws};
         if (u16) {
-            Workspace::U16Stage& U = ws->u16[q];
+            U16Stage& U = ws->u16[q];
             if (nu) HIP_TRY(hipMemcpyAsync(U.units.p, c.units + u0, (size_t)nu * 2, hipMemcpyHostToDevice, ws->st_in));
             HIP_TRY(hipMemcpyAsync(U.offs.p, offs + d0, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, ws->st_in));
             if (u0) launch_rebase(L, U.offs.as<int64_t>(), nd + 1, u0);
-            const int64_t nw = nu / 64 + 1, nt = u16_tiles(nu);
-            HIP_TRY(hipMemsetAsync(U.counters.p, 0, 64, ws->st_in));
-            HIP_TRY(hipMemsetAsync(U.docbits.p, 0, (size_t)(nw + 8) * 8, ws->st_in));
-            launch_docmark(L, U.offs.as<int64_t>(), nd, nu, U.docbits.as<uint64_t>(), U.counters.as<int32_t>());
-            launch_u16_len(L, U.units.as<uint16_t>(), nu, U.docbits.as<uint64_t>(), nt, U.grp.as<int32_t>(), U.tsum.as<int32_t>());
-            launch_scan(L, U.tsum.as<int32_t>(), nt, U.bsum.as<int64_t>(), U.tbase.as<int64_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), -1);
-            HIP_TRY(hipMemcpyAsync(U.h, U.counters.p, 16, hipMemcpyDeviceToHost, ws->st_in));
+            HIP_TRY(u16_measure(U, L, nu, nd));
         } else {
             if (nu) HIP_TRY(hipMemcpyAsync(ws->s_bytes[q].p, c.bytes + u0, (size_t)nu, hipMemcpyHostToDevice, ws->st_in));
             HIP_TRY(hipMemcpyAsync(ws->s_offs[q].p, offs + d0, (size_t)(nd + 1) * 8, hipMemcpyHostToDevice, ws->st_in));
@@ -1465,17 +1542,10 @@ struct HostPipeline {
         const uint8_t* cb; const int64_t* co; int64_t cbytes;      // the chunk as UTF-8 on the device
         if (u16) {
             // the UTF-8 size of the chunk is known once its length pass is through (the host needs it: the launch shapes of the encode path)
-            Workspace::U16Stage& U = ws->u16[q];
+            U16Stage& U = ws->u16[q];
             PIPELINE_TRY(hipEventSynchronize(ws->ev_in[q]));
-            if (U.h->err & kErrOffsets) return note(fail(TKZ_E_ARG, kMsgUnitOffsets));
-            cbytes = U.h->grand;
-            PIPELINE_TRY(ws->u_bytes[q].ensure((size_t)cbytes + 64, acc));
-            Launch L{w->st_compute, nullptr, w};
-            if (with_repl) PIPELINE_TRY(hipMemsetAsync(U.repl.p, 0, Workspace::U16Stage::repl_bytes(cbytes), w->st_compute));
-            launch_u16_write(L, U.units.as<uint16_t>(), nu, U.docbits.as<uint64_t>(), u16_tiles(nu), U.tbase.as<int64_t>(), ws->u_bytes[q].as<uint8_t>(),
-                             U.offs.as<int64_t>(), nd, U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>(),
-                             with_repl ? U.repl.as<uint64_t>() : nullptr);
-            cb = ws->u_bytes[q].as<uint8_t>(); co = U.boffs.as<int64_t>();
+            { const tkz_status us = u16_write(U, Launch{w->st_compute, nullptr, w}, nu, nd, with_repl, acc, &cbytes); if (us != TKZ_OK) return note(us); }
+            cb = U.bytes.as<uint8_t>(); co = U.boffs.as<int64_t>();
         } else {
             if (!p.ingest_in) PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_in[q], 0));
             cb = ws->s_bytes[q].as<uint8_t>(); co = ws->s_offs[q].as<int64_t>(); cbytes = nu;
@@ -1598,15 +1668,10 @@ tkz_status encode_host(tkz_encoder* e, const HostCall& c) {
     const bool u16 = c.u16();
     const int64_t* const offs = c.offs;
     const int64_t n_docs = c.n_docs;
-    if (n_docs < 0 || !offs || (n_docs > 0 && !c.bytes && !c.units && offs[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    if (offs[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = c.total();
-    if (total < 0) return fail(TKZ_E_ARG, u16 ? "negative unit count" : "negative byte count");
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(offs, n_docs, c.bytes || c.units, u16 ? kUnitDocs : kByteDocs, &total));
     if (c.needed) *c.needed = 0;
-    if (u16 && total == 0) {
-        for (int64_t d = 0; d <= n_docs; ++d) { if (offs[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); c.out_offsets[d] = 0; }
-        return TKZ_OK;
-    }
+    if (u16 && total == 0) return check_empty_docs(offs, n_docs, kUnitDocs, c.out_offsets);
     Lease lease(e);
     Workspace* ws = lease.ws;
     // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
@@ -1624,10 +1689,18 @@ tkz_status encode_host(tkz_encoder* e, const HostCall& c) {
 
 // tkz_encode_batch_utf8 and its special form; tkz_encode_pieces
 tkz_status encode_host_batch(tkz_encoder* e, const HostCall& c) {
-    if (!c.out_offsets || (c.out_cap > 0 && !c.out_ids)) return fail(TKZ_E_ARG, "null output buffer");
+    TKZ_TRY(check_host_outputs(c.out_ids, c.out_cap, c.out_offsets));
     const tkz_status st = encode_host(e, c);
     if (st == TKZ_OK && c.special) ++e->spec_batches;
     return st;
+}
+
+// tkz_encode_batch_utf16 and its special form (sp null: the plain one)
+tkz_status encode_host_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const SpecialCall* sp,
+                                   int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
+    HostCall c{nullptr, units, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
+    c.utf16 = true; c.special = sp;
+    return encode_host_batch(e, c);
 }
 
 // what the device entries check before they take a workspace
@@ -1886,13 +1959,13 @@ tkz_status tkz_encode_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int
 }
 
 namespace {
-// the `allowed` argument of the special entries -> the call's literal set.  *plain: nothing allowed or nothing registered, the call is the plain entry's.
-tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowed, SpecialCall* sc, bool* plain) {
+// the `allowed` argument of the special entries -> the call's literal set, in the entry's *sc.  *sp: sc, or null -- nothing allowed or registered: the plain entry's call
+tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowed, SpecialCall* sc, const SpecialCall** sp) {
+    *sp = nullptr;
     if (!e) return fail(TKZ_E_ARG, "null encoder");
     if (n_allowed < 0 || (n_allowed > 0 && !allowed)) return fail(TKZ_E_ARG, "bad allowed-special arguments");
     std::lock_guard<std::mutex> lock(e->mu);
-    *plain = n_allowed == 0 || e->lit_state == 0;
-    if (*plain) return TKZ_OK;
+    if (n_allowed == 0 || e->lit_state == 0) return TKZ_OK;
     if (e->lit_state < 0) return fail(TKZ_E_UNSUPPORTED, "special tokens on the device: " + e->lit_why);
     *sc = SpecialCall{};
     sc->fffd = e->lit_fffd;
@@ -1902,6 +1975,7 @@ tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowe
         if ((sc->allowed.m[i >> 6] >> (i & 63)) & 1ull) return fail(TKZ_E_ARG, "allowed[] holds an index twice");
         sc->allowed.m[i >> 6] |= 1ull << (i & 63);
     }
+    *sp = sc;
     return TKZ_OK;
 }
 }  // namespace
@@ -1909,18 +1983,18 @@ tkz_status special_call(tkz_encoder* e, const int32_t* allowed, int32_t n_allowe
 tkz_status tkz_encode_batch_special_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
                                            const int32_t* allowed, int32_t n_allowed, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
                                            void* hip_stream, int64_t* total_tokens) {
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
     BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
-    if (!plain) c.special = &sc;
+    c.special = sp;
     return encode_device_batch(e, c, total_tokens);
 }
 tkz_status tkz_encode_batch_special_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
                                          int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
     HostCall c{bytes, nullptr, doc_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
-    if (!plain) c.special = &sc;
+    c.special = sp;
     return encode_host_batch(e, c);
 }
 void tkz_encoder_special_stats(const tkz_encoder* e, int64_t* batches, int64_t* literals) {
@@ -2026,24 +2100,14 @@ tkz_status tkz_encode_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, i
 
 tkz_status tkz_encode_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs,
                                   int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
-    if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
-    if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    static const uint16_t none = 0;
-    return encode_host(e, HostCall{nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed});
+    return encode_host_batch_utf16(e, units, unit_offsets, n_docs, nullptr, out_ids, out_cap, out_offsets, needed);
 }
 
 tkz_status tkz_encode_batch_special_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed,
                                           int32_t n_allowed, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
-    if (!out_offsets || (out_cap > 0 && !out_ids)) return fail(TKZ_E_ARG, "null output buffer");
-    if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    static const uint16_t none = 0;
-    HostCall c{nullptr, units ? units : &none, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
-    if (!plain) c.special = &sc;
-    const tkz_status st = encode_host(e, c);
-    if (st == TKZ_OK && c.special) ++e->spec_batches;
-    return st;
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    return encode_host_batch_utf16(e, units, unit_offsets, n_docs, sp, out_ids, out_cap, out_offsets, needed);
 }
 
 tkz_status tkz_pretokenize_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, uint64_t* out_bitmap_words) {
@@ -2063,48 +2127,40 @@ tkz_status tkz_encode_pieces(tkz_encoder* e, const uint8_t* bytes, const int64_t
 tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs,
                                         int32_t* out_ids, int64_t out_cap, int64_t* doc_piece_offsets, int64_t* piece_byte_offsets,
                                         int64_t* piece_token_offsets, int64_t piece_cap, int64_t* n_pieces, int64_t* needed_ids) {
-    if (!doc_piece_offsets || !piece_byte_offsets || !piece_token_offsets || !n_pieces || (out_cap > 0 && !out_ids))
-        return fail(TKZ_E_ARG, "null output buffer");
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, doc_piece_offsets));
+    if (!piece_byte_offsets || !piece_token_offsets || !n_pieces) return fail(TKZ_E_ARG, "null output buffer");
     DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (n_docs < 0 || !doc_offsets || (n_docs > 0 && !bytes && doc_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    if (doc_offsets[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = doc_offsets[n_docs];
-    if (total < 0 || piece_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (piece_cap < 0) return fail(TKZ_E_ARG, kSizedDocs.negative);
     *n_pieces = 0;
     if (needed_ids) *needed_ids = 0;
     if (total == 0) {                                        // no bytes: no pieces (empty documents have none)
-        for (int64_t d = 0; d <= n_docs; ++d) { if (doc_offsets[d] != 0) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count"); doc_piece_offsets[d] = 0; }
+        TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, doc_piece_offsets));
         piece_byte_offsets[0] = 0; piece_token_offsets[0] = 0;
         return TKZ_OK;
     }
     // ONE launch sequence on the device: Regex.Matches -> piece offsets from the bitmap -> encode with a token mark per piece
     Lease lease(e);
     Workspace* ws = lease.ws;
-    int64_t* acc = &ws->bytes_allocated;
     const int64_t pcap = std::min<int64_t>(piece_cap, total);           // pieces <= bytes
     const int64_t cap = std::min<int64_t>(out_cap, total);
-    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
-    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
-    HIP_TRY(ws->p_boffs.ensure((size_t)(pcap + 1) * 8, acc));
-    HIP_TRY(ws->p_toffs.ensure((size_t)(pcap + 1) * 8, acc));
-    HIP_TRY(ws->p_docp.ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->s_offs[0].p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    TKZ_TRY(stage_out(ws, n_docs, cap, false));
+    for (DevBuf* b : {&ws->p_boffs, &ws->p_toffs}) HIP_TRY(b->ensure((size_t)(pcap + 1) * 8, &ws->bytes_allocated));
+    HIP_TRY(ws->p_docp.ensure((size_t)(n_docs + 1) * 8, &ws->bytes_allocated));
     PiecesOut po{ws->p_boffs.as<int64_t>(), ws->p_toffs.as<int64_t>(), ws->p_docp.as<int64_t>(), pcap, 0};
     int64_t tokens = 0;
-    BatchCall c{ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, nullptr, nullptr};
-    c.kind = CallKind::Pieces; c.pieces = &po;
-    st = encode_device(e, ws, c, kCallWhole, &tokens);
+    BatchCall c = staged_call(ws, n_docs, total, cap);
+    c.d_out_offs = nullptr; c.kind = CallKind::Pieces; c.pieces = &po;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, &tokens);
     *n_pieces = po.n_pieces;
     if (needed_ids) *needed_ids = tokens;
     if (st != TKZ_OK) return st;
-    const int64_t np = po.n_pieces;
-    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(piece_byte_offsets, ws->p_boffs.p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(piece_token_offsets, ws->p_toffs.p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost));
+    TKZ_TRY(fetch(ws, out_ids, tokens, nullptr, n_docs));
+    HIP_TRY(hipMemcpy(piece_byte_offsets, ws->p_boffs.p, (size_t)(po.n_pieces + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(piece_token_offsets, ws->p_toffs.p, (size_t)(po.n_pieces + 1) * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(doc_piece_offsets, ws->p_docp.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }
@@ -2129,9 +2185,30 @@ tkz_status trim_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, const Trim
     if (st == TKZ_OK && sc) ++e->spec_batches;
     return st;
 }
-tkz_status check_trim_args(int32_t side, int64_t max_tokens, bool per_doc) {
+tkz_status check_trim_args(int32_t side, int64_t max_tokens, bool per_doc, const int64_t* h_max = nullptr, int64_t n_docs = 0) {      // (h_max: the maxima, when in host memory)
     if (side != TKZ_TRIM_SUFFIX && side != TKZ_TRIM_PREFIX) return fail(TKZ_E_ARG, "side must be TKZ_TRIM_SUFFIX or TKZ_TRIM_PREFIX");
     if (!per_doc && max_tokens < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    for (int64_t d = 0; h_max && d < n_docs; ++d) if (h_max[d] < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    return TKZ_OK;
+}
+// The second half of a trim host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the kept ids, their offsets and the
+// per-document arrays (the maxima, the two cut arrays), ONE trim call, the results back.
+tkz_status trim_staged(tkz_encoder* e, Workspace* ws, BatchCall c, int32_t side, int64_t max_tokens, const int64_t* per_doc, const SpecialCall* sp,
+                       int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* cut_bytes, int64_t* cut_units, int64_t* needed) {
+    const int64_t n_docs = c.n_docs, nd = std::max<int64_t>(n_docs, 1);
+    c.out_cap = std::min<int64_t>(out_cap, c.total);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap));
+    HIP_TRY(ws->t_stage.ensure((size_t)nd * 3 * 8, &ws->bytes_allocated));
+    int64_t* const d_max = ws->t_stage.as<int64_t>(), * const d_cb = d_max + nd, * const d_cu = d_cb + nd;
+    if (per_doc && n_docs) HIP_TRY(hipMemcpy(d_max, per_doc, (size_t)n_docs * 8, hipMemcpyHostToDevice));
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = ws->s_outoffs[0].as<int64_t>();
+    int64_t tokens = 0;
+    const tkz_status st = trim_on_device(e, ws, c, TrimCall{side, max_tokens, per_doc ? d_max : nullptr, cut_bytes ? d_cb : nullptr, cut_units ? d_cu : nullptr}, sp, &tokens);
+    if (needed) *needed = tokens;
+    if (st != TKZ_OK) return st;
+    TKZ_TRY(fetch(ws, out_ids, tokens, out_offsets, n_docs));
+    if (cut_bytes && n_docs) HIP_TRY(hipMemcpy(cut_bytes, d_cb, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+    if (cut_units && n_docs) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
 }
 }  // namespace
@@ -2140,8 +2217,8 @@ tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, 
                                         const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens, const int64_t* d_max_tokens,
                                         int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets, int64_t* d_cut_bytes, int64_t* d_cut_units,
                                         void* hip_stream, int64_t* total_tokens) {
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
     TKZ_TRY(check_trim_args(side, max_tokens, d_max_tokens != nullptr));
     BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
     DeviceScope scope;
@@ -2150,50 +2227,27 @@ tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, 
     if (!d_doc_offsets || !d_out_offsets || (total_bytes > 0 && !d_bytes) || (out_cap > 0 && !d_out_ids)) return fail(TKZ_E_ARG, "null device buffer");
     if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
     Lease lease(e);
-    return trim_on_device(e, lease.ws, c, TrimCall{side, max_tokens, d_max_tokens, d_cut_bytes, d_cut_units}, plain ? nullptr : &sc, total_tokens);
+    return trim_on_device(e, lease.ws, c, TrimCall{side, max_tokens, d_max_tokens, d_cut_bytes, d_cut_units}, sp, total_tokens);
 }
 
 tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
                                       int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
                                       int64_t* cut_bytes, int64_t* cut_units, int64_t* needed) {
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
-    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr));
-    if (!out_offsets || (out_cap > 0 && !out_ids) || out_cap < 0) return fail(TKZ_E_ARG, "null output buffer");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr, max_tokens_per_doc, n_docs));
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
     DeviceScope scope;
     TKZ_TRY(check_encoder(e, scope));
-    if (n_docs < 0 || !doc_offsets || (n_docs > 0 && !bytes && doc_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    if (doc_offsets[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = doc_offsets[n_docs];
-    if (total < 0) return fail(TKZ_E_ARG, "negative size");
-    for (int64_t d = 0; total == 0 && d < n_docs; ++d) if (doc_offsets[d] != 0) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count");
-    for (int64_t d = 0; max_tokens_per_doc && d < n_docs; ++d) if (max_tokens_per_doc[d] < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
     if (needed) *needed = 0;
     // the whole batch is staged (as tkz_encode_batch_pieces_utf8 stages it) and the result copied from ONE call of the device entry
     Lease lease(e);
     Workspace* ws = lease.ws;
-    int64_t* acc = &ws->bytes_allocated;
-    const int64_t cap = std::min<int64_t>(out_cap, total), nd = std::max<int64_t>(n_docs, 1);
-    HIP_TRY(ws->s_bytes[0].ensure((size_t)total + 64, acc));
-    HIP_TRY(ws->s_offs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
-    HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->t_stage.ensure((size_t)nd * 3 * 8, acc));
-    int64_t* const d_max = ws->t_stage.as<int64_t>(), * const d_cb = d_max + nd, * const d_cu = d_cb + nd;
-    if (total) HIP_TRY(hipMemcpy(ws->s_bytes[0].p, bytes, (size_t)total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->s_offs[0].p, doc_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-    if (max_tokens_per_doc && n_docs) HIP_TRY(hipMemcpy(d_max, max_tokens_per_doc, (size_t)n_docs * 8, hipMemcpyHostToDevice));
-    int64_t tokens = 0;
-    BatchCall c{ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr};
-    const tkz_status st = trim_on_device(e, ws, c, TrimCall{side, max_tokens, max_tokens_per_doc ? d_max : nullptr, cut_bytes ? d_cb : nullptr, cut_units ? d_cu : nullptr},
-                                         plain ? nullptr : &sc, &tokens);
-    if (needed) *needed = tokens;
-    if (st != TKZ_OK) return st;
-    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
-    if (cut_bytes && n_docs) HIP_TRY(hipMemcpy(cut_bytes, d_cb, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
-    if (cut_units && n_docs) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
-    return TKZ_OK;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return trim_staged(e, ws, staged_call(ws, n_docs, total, 0), side, max_tokens, max_tokens_per_doc, sp, out_ids, out_cap, out_offsets, cut_bytes, cut_units, needed);
 }
 
 // The same for UTF-16 documents: the whole batch's code units are staged and transcoded on the device (as a chunk of tkz_encode_batch_utf16 is), then ONE trim call
@@ -2201,65 +2255,37 @@ tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, cons
 tkz_status tkz_encode_batch_trim_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
                                        int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
                                        int64_t* cut_units, int64_t* needed) {
-    using namespace tkz;
-    SpecialCall sc; bool plain = false;
-    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &plain));
-    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr));
-    if (!out_offsets || (out_cap > 0 && !out_ids) || out_cap < 0) return fail(TKZ_E_ARG, "null output buffer");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_trim_args(side, max_tokens, max_tokens_per_doc != nullptr, max_tokens_per_doc, n_docs));
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
     DeviceScope scope;
     TKZ_TRY(check_encoder(e, scope));
-    if (n_docs < 0 || !unit_offsets || (n_docs > 0 && !units && unit_offsets[n_docs] > 0)) return fail(TKZ_E_ARG, "null buffer");
-    if (unit_offsets[0] != 0) return fail(TKZ_E_ARG, "doc_offsets[0] must be 0");
-    const int64_t total = unit_offsets[n_docs];
-    if (total < 0) return fail(TKZ_E_ARG, "negative unit count");
-    for (int64_t d = 0; max_tokens_per_doc && d < n_docs; ++d) if (max_tokens_per_doc[d] < 0) return fail(TKZ_E_ARG, "negative maximum token count");
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
     if (needed) *needed = 0;
     if (total == 0) {
-        for (int64_t d = 0; d <= n_docs; ++d) { if (unit_offsets[d] != 0) return fail(TKZ_E_ARG, kMsgUnitOffsets); out_offsets[d] = 0; }
-        for (int64_t d = 0; cut_units && d < n_docs; ++d) cut_units[d] = 0;
-        if (!plain) ++e->spec_batches;
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, out_offsets));
+        if (cut_units) std::fill_n(cut_units, n_docs, int64_t(0));
+        if (sp) ++e->spec_batches;                                      // (the one counted special batch that does not reach trim_on_device)
         return TKZ_OK;
     }
     // (the workspace keeps what is taken here for its next call; the lease -- and with it every buffer's use -- ends with this frame on every return)
     Lease lease(e);
     Workspace* ws = lease.ws;
-    int64_t* acc = &ws->bytes_allocated;
-    Workspace::U16Stage& U = ws->u16[0];
-    const bool with_repl = !plain && sc.fffd;
-    HIP_TRY(U.ensure(total, n_docs, acc, with_repl));
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
     HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-    const Launch L{nullptr, nullptr, ws};
-    const int64_t nw = total / 64 + 1, nt = u16_tiles(total);
-    HIP_TRY(hipMemsetAsync(U.counters.p, 0, 64, nullptr));
-    HIP_TRY(hipMemsetAsync(U.docbits.p, 0, (size_t)(nw + 8) * 8, nullptr));
-    launch_docmark(L, U.offs.as<int64_t>(), n_docs, total, U.docbits.as<uint64_t>(), U.counters.as<int32_t>());
-    launch_u16_len(L, U.units.as<uint16_t>(), total, U.docbits.as<uint64_t>(), nt, U.grp.as<int32_t>(), U.tsum.as<int32_t>());
-    launch_scan(L, U.tsum.as<int32_t>(), nt, U.bsum.as<int64_t>(), U.tbase.as<int64_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), -1);
-    HIP_TRY(hipMemcpy(U.h, U.counters.p, 16, hipMemcpyDeviceToHost));
-    if (U.h->err & kErrOffsets) return fail(TKZ_E_ARG, kMsgUnitOffsets);
-    const int64_t nbytes = U.h->grand;                                  // the batch as UTF-8
-    HIP_TRY(ws->u_bytes[0].ensure((size_t)nbytes + 64, acc));
-    if (with_repl) HIP_TRY(hipMemsetAsync(U.repl.p, 0, Workspace::U16Stage::repl_bytes(nbytes), nullptr));
-    launch_u16_write(L, U.units.as<uint16_t>(), total, U.docbits.as<uint64_t>(), nt, U.tbase.as<int64_t>(), ws->u_bytes[0].as<uint8_t>(), U.offs.as<int64_t>(), n_docs,
-                     U.grp.as<int32_t>(), reinterpret_cast<int64_t*>(U.counters.as<char>() + 8), U.boffs.as<int64_t>(), with_repl ? U.repl.as<uint64_t>() : nullptr);
-    const int64_t cap = std::min<int64_t>(out_cap, nbytes), nd = std::max<int64_t>(n_docs, 1);
-    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, acc));
-    HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->t_stage.ensure((size_t)nd * 3 * 8, acc));
-    int64_t* const d_max = ws->t_stage.as<int64_t>(), * const d_cu = d_max + nd;
-    if (max_tokens_per_doc) HIP_TRY(hipMemcpy(d_max, max_tokens_per_doc, (size_t)n_docs * 8, hipMemcpyHostToDevice));
-    int64_t tokens = 0;
-    BatchCall c{ws->u_bytes[0].as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr};
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
     if (with_repl) c.d_repl = U.repl.as<uint64_t>();
-    const tkz_status st = trim_on_device(e, ws, c, TrimCall{side, max_tokens, max_tokens_per_doc ? d_max : nullptr, nullptr, cut_units ? d_cu : nullptr},
-                                         plain ? nullptr : &sc, &tokens);
-    if (needed) *needed = tokens;
-    if (st != TKZ_OK) return st;
-    if (tokens) HIP_TRY(hipMemcpy(out_ids, ws->s_out[0].p, (size_t)tokens * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_offsets, ws->s_outoffs[0].p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
-    if (cut_units) HIP_TRY(hipMemcpy(cut_units, d_cu, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
-    return TKZ_OK;
+    return trim_staged(e, ws, c, side, max_tokens, max_tokens_per_doc, sp, out_ids, out_cap, out_offsets, nullptr, cut_units, needed);
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------
@@ -2281,11 +2307,10 @@ tkz_status tkz_encoder_set_special_tokens(tkz_encoder* e, const int32_t* ids, co
 }
 
 namespace {
-// lengths -> scan -> bytes + document offsets, all on `stream`; d_out may be null when only the size is wanted
-tkz_status decode_device(tkz_encoder* e, Workspace* ws, const int32_t* d_ids, const int64_t* d_id_offs, int64_t n_docs, int64_t total_ids, uint8_t* d_out, int64_t out_cap,
-                         int64_t* d_out_offs, hipStream_t stream, int64_t* total_bytes) {
+// The head of both decoders, on `stream`: the checks of the sizes, the length scan's buffers, the byte length of every id and their scan.  What it leaves:
+// d_grp / d_tbase (the per-group and per-tile bases dec_write places by) and, in the counter block d_counters (a LenCounters), the byte total.
+tkz_status decode_lengths(tkz_encoder* e, Workspace* ws, const int32_t* d_ids, int64_t n_docs, int64_t total_ids, int64_t out_cap, hipStream_t stream) {
     using namespace tkz;
-    if (total_bytes) *total_bytes = 0;
     if (n_docs < 0 || total_ids < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
     if (n_docs == 0 && total_ids != 0) return fail(TKZ_E_ARG, "ids without documents");
     int64_t* acc = &ws->bytes_allocated;
@@ -2296,71 +2321,39 @@ tkz_status decode_device(tkz_encoder* e, Workspace* ws, const int32_t* d_ids, co
     HIP_TRY(ws->d_bsum.ensure((size_t)(nblk + 1) * 8, acc));
     HIP_TRY(ws->d_counters.ensure(64, acc));
     if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
-    Launch L{stream, nullptr, ws};
-    int32_t* counters = ws->d_counters.as<int32_t>();
-    int64_t* grand = reinterpret_cast<int64_t*>(ws->d_counters.as<char>() + 8);
-    HIP_TRY(hipMemsetAsync(counters, 0, 64, stream));
+    const Launch L{stream, nullptr, ws};
+    HIP_TRY(hipMemsetAsync(ws->d_counters.p, 0, 64, stream));
     launch_dec_len(L, e->D, d_ids, total_ids, ntiles, ws->d_grp.as<int32_t>(), ws->d_tsum.as<int32_t>());
-    launch_scan(L, ws->d_tsum.as<int32_t>(), ntiles, ws->d_bsum.as<int64_t>(), ws->d_tbase.as<int64_t>(), grand, -1);
-    launch_dec_write(L, e->D, d_ids, total_ids, ntiles, ws->d_tbase.as<int64_t>(), d_out, d_out ? out_cap : 0, d_id_offs, n_docs, ws->d_grp.as<int32_t>(), grand,
-                     d_out_offs, counters);
-    struct { int32_t err; int32_t pad; int64_t grand; } h{};
-    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, 16, hipMemcpyDeviceToHost, stream));
+    launch_scan(L, ws->d_tsum.as<int32_t>(), ntiles, ws->d_bsum.as<int64_t>(), ws->d_tbase.as<int64_t>(), &ws->d_counters.as<LenCounters>()->grand, -1);
+    return TKZ_OK;
+}
+// the first n bytes of that block on the host, once the stream has drained
+tkz_status fetch_len_counters(Workspace* ws, hipStream_t stream, size_t n, LenCounters* h) {
+    HIP_TRY(hipMemcpyAsync(ws->h_counters, ws->d_counters.p, n, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipGetLastError());
-    memcpy(&h, ws->h_counters, 16);
-    if (h.err & kErrOffsets) return fail(TKZ_E_ARG, "id offsets must start at 0, be non-decreasing and end at the id count");
+    memcpy(h, ws->h_counters, n);
+    return TKZ_OK;
+}
+
+// lengths -> scan -> bytes + document offsets, all on `stream` with ONE wait at the end; d_out may be null when only the size is wanted
+tkz_status decode_device(tkz_encoder* e, Workspace* ws, const int32_t* d_ids, const int64_t* d_id_offs, int64_t n_docs, int64_t total_ids, uint8_t* d_out, int64_t out_cap,
+                         int64_t* d_out_offs, hipStream_t stream, int64_t* total_bytes) {
+    using namespace tkz;
+    if (total_bytes) *total_bytes = 0;
+    TKZ_TRY(decode_lengths(e, ws, d_ids, n_docs, total_ids, out_cap, stream));
+    LenCounters* const blk = ws->d_counters.as<LenCounters>();
+    launch_dec_write(Launch{stream, nullptr, ws}, e->D, d_ids, total_ids, std::max<int64_t>(1, dec_tiles(total_ids)), ws->d_tbase.as<int64_t>(), d_out, d_out ? out_cap : 0,
+                     d_id_offs, n_docs, ws->d_grp.as<int32_t>(), &blk->grand, d_out_offs, &blk->err);
+    LenCounters h{};
+    TKZ_TRY(fetch_len_counters(ws, stream, 16, &h));
+    if (h.err & kErrOffsets) return fail(TKZ_E_ARG, kMsgIdOffsets);
     if (total_bytes) *total_bytes = h.grand;
     if (h.grand > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
     return TKZ_OK;
 }
-}  // namespace
 
-tkz_status tkz_decode_batch_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
-                                   uint8_t* d_out_bytes, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_bytes) {
-    DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (!d_id_offsets || !d_out_offsets || (total_ids > 0 && !d_ids) || (out_cap > 0 && !d_out_bytes)) return fail(TKZ_E_ARG, "null device buffer");
-    Lease lease(e);
-    Workspace* ws = lease.ws;
-    return decode_device(e, ws, d_ids, d_id_offsets, n_docs, total_ids, d_out_bytes, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), total_bytes);
-}
 
-tkz_status tkz_decode_batch(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* out_bytes, int64_t out_cap,
-                            int64_t* out_offsets, int64_t* needed) {
-    DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (n_docs < 0 || !id_offsets || !out_offsets || (out_cap > 0 && !out_bytes)) return fail(TKZ_E_ARG, "null buffer");
-    if (id_offsets[0] != 0) return fail(TKZ_E_ARG, "id_offsets[0] must be 0");
-    const int64_t total = id_offsets[n_docs];
-    if (total < 0 || (total > 0 && !ids)) return fail(TKZ_E_ARG, "bad id count");
-    if (needed) *needed = 0;
-    Lease lease(e);
-    Workspace* ws = lease.ws;
-    int64_t* acc = &ws->bytes_allocated;
-    HIP_TRY(ws->d_ids.ensure((size_t)std::max<int64_t>(total, 1) * 4, acc));
-    HIP_TRY(ws->d_idoffs.ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->d_outoffs.ensure((size_t)(n_docs + 1) * 8, acc));
-    // (staging no larger than the result can be: an id yields at most the longest registered byte string, however large a hint out_cap is)
-    int64_t longest = 1;
-    { std::lock_guard<std::mutex> lock(e->mu); for (const auto& kv : e->dec_special) longest = std::max<int64_t>(longest, (int64_t)kv.second.size()); }
-    longest = std::max<int64_t>(longest, e->max_key_len);
-    out_cap = std::min<int64_t>(out_cap, total * longest);
-    HIP_TRY(ws->d_out.ensure((size_t)std::max<int64_t>(out_cap, 1), acc));
-    if (total) HIP_TRY(hipMemcpy(ws->d_ids.p, ids, (size_t)total * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ws->d_idoffs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-    int64_t nbytes = 0;
-    st = decode_device(e, ws, ws->d_ids.as<int32_t>(), ws->d_idoffs.as<int64_t>(), n_docs, total, ws->d_out.as<uint8_t>(), out_cap, ws->d_outoffs.as<int64_t>(), nullptr, &nbytes);
-    if (needed) *needed = nbytes;
-    if (st != TKZ_OK) return st;
-    if (nbytes) HIP_TRY(hipMemcpy(out_bytes, ws->d_out.p, (size_t)nbytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_offsets, ws->d_outoffs.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
-    return TKZ_OK;
-}
-
-namespace {
 // Decode + Encoding.UTF8.GetString: the byte decoder's lengths and scan, ONE wait for the byte total (the intermediate bytes are sized from it, not from
 // total_ids x the longest key), the bytes and their offsets into the workspace, the document-start bitmap over them, then unit counts -> scan -> units + unit
 // offsets.  own_units: null (d_out is the caller's), or the workspace buffer the host entry's units go to: sized here, to min(out_cap, bytes) -- a unit
@@ -2369,29 +2362,13 @@ tkz_status decode_utf16_device(tkz_encoder* e, Workspace* ws, const int32_t* d_i
                                int64_t out_cap, int64_t* d_out_offs, hipStream_t stream, int64_t* total_units, DevBuf* own_units = nullptr) {
     using namespace tkz;
     if (total_units) *total_units = 0;
-    if (n_docs < 0 || total_ids < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
-    if (n_docs == 0 && total_ids != 0) return fail(TKZ_E_ARG, "ids without documents");
+    TKZ_TRY(decode_lengths(e, ws, d_ids, n_docs, total_ids, out_cap, stream));
     int64_t* acc = &ws->bytes_allocated;
-    const int64_t ntiles = std::max<int64_t>(1, dec_tiles(total_ids)), nblk = (ntiles + kScanBlock - 1) / kScanBlock;
-    HIP_TRY(ws->d_grp.ensure((size_t)ntiles * 64 * 4, acc));
-    HIP_TRY(ws->d_tsum.ensure((size_t)ntiles * 4, acc));
-    HIP_TRY(ws->d_tbase.ensure((size_t)ntiles * 8, acc));
-    HIP_TRY(ws->d_bsum.ensure((size_t)(nblk + 1) * 8, acc));
-    HIP_TRY(ws->d_counters.ensure(64, acc));
     HIP_TRY(ws->d8_boffs.ensure((size_t)(n_docs + 1) * 8, acc));
-    if (!ws->h_counters) HIP_TRY(hipHostMalloc((void**)&ws->h_counters, sizeof(CounterBlock), 0));
-    Launch L{stream, nullptr, ws};
-    // the counter block: [0] error bits, +8 the byte total, +16 the unit total
-    int32_t* counters = ws->d_counters.as<int32_t>();
-    int64_t* grand = reinterpret_cast<int64_t*>(ws->d_counters.as<char>() + 8), * grand16 = grand + 1;
-    struct { int32_t err; int32_t pad; int64_t grand; int64_t grand16; } h{};
-    HIP_TRY(hipMemsetAsync(counters, 0, 64, stream));
-    launch_dec_len(L, e->D, d_ids, total_ids, ntiles, ws->d_grp.as<int32_t>(), ws->d_tsum.as<int32_t>());
-    launch_scan(L, ws->d_tsum.as<int32_t>(), ntiles, ws->d_bsum.as<int64_t>(), ws->d_tbase.as<int64_t>(), grand, -1);
-    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipGetLastError());
-    memcpy(&h, ws->h_counters, 16);
+    const Launch L{stream, nullptr, ws};
+    LenCounters* const blk = ws->d_counters.as<LenCounters>();
+    LenCounters h{};
+    TKZ_TRY(fetch_len_counters(ws, stream, 16, &h));
     const int64_t nbytes = h.grand;                                     // the batch as (not necessarily well-formed) UTF-8
     const int64_t nw = nbytes / 64 + 1, nt8 = std::max<int64_t>(1, u8_tiles(nbytes)), nblk8 = (nt8 + kScanBlock - 1) / kScanBlock;
     HIP_TRY(ws->d8_bytes.ensure((size_t)nbytes + 64, acc));
@@ -2408,62 +2385,82 @@ tkz_status decode_utf16_device(tkz_encoder* e, Workspace* ws, const int32_t* d_i
     const uint8_t* bytes = ws->d8_bytes.as<uint8_t>();
     const uint64_t* docbits = ws->d8_docbits.as<uint64_t>();
     HIP_TRY(hipMemsetAsync(ws->d8_docbits.p, 0, (size_t)(nw + 8) * 8, stream));
-    launch_dec_write(L, e->D, d_ids, total_ids, ntiles, ws->d_tbase.as<int64_t>(), ws->d8_bytes.as<uint8_t>(), nbytes, d_id_offs, n_docs, ws->d_grp.as<int32_t>(), grand,
-                     ws->d8_boffs.as<int64_t>(), counters);
+    launch_dec_write(L, e->D, d_ids, total_ids, std::max<int64_t>(1, dec_tiles(total_ids)), ws->d_tbase.as<int64_t>(), ws->d8_bytes.as<uint8_t>(), nbytes, d_id_offs, n_docs,
+                     ws->d_grp.as<int32_t>(), &blk->grand, ws->d8_boffs.as<int64_t>(), &blk->err);
     // (empty documents set no bit of their own; bad id offsets have set kErrOffsets above, and what is computed from their byte offsets is never used)
-    launch_docmark(L, ws->d8_boffs.as<int64_t>(), n_docs, nbytes, ws->d8_docbits.as<uint64_t>(), counters);
+    launch_docmark(L, ws->d8_boffs.as<int64_t>(), n_docs, nbytes, ws->d8_docbits.as<uint64_t>(), &blk->err);
     launch_u8_len(L, bytes, nbytes, docbits, nw, nt8, ws->d8_grp.as<int32_t>(), ws->d8_tsum.as<int32_t>());
-    launch_scan(L, ws->d8_tsum.as<int32_t>(), nt8, ws->d8_bsum.as<int64_t>(), ws->d8_tbase.as<int64_t>(), grand16, -1);
+    launch_scan(L, ws->d8_tsum.as<int32_t>(), nt8, ws->d8_bsum.as<int64_t>(), ws->d8_tbase.as<int64_t>(), &blk->grand16, -1);
     launch_u8_write(L, bytes, nbytes, docbits, nw, nt8, ws->d8_tbase.as<int64_t>(), d_out, d_out ? out_cap : 0, ws->d8_boffs.as<int64_t>(), n_docs,
-                    ws->d8_grp.as<int32_t>(), grand16, d_out_offs);
-    HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, 24, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipGetLastError());
-    memcpy(&h, ws->h_counters, 24);
-    if (h.err & kErrOffsets) return fail(TKZ_E_ARG, "id offsets must start at 0, be non-decreasing and end at the id count");
+                    ws->d8_grp.as<int32_t>(), &blk->grand16, d_out_offs);
+    TKZ_TRY(fetch_len_counters(ws, stream, sizeof h, &h));
+    if (h.err & kErrOffsets) return fail(TKZ_E_ARG, kMsgIdOffsets);
     if (total_units) *total_units = h.grand16;
     if (h.grand16 > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
     return TKZ_OK;
 }
-}  // namespace
-
-tkz_status tkz_decode_batch_utf16_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
-                                         uint16_t* d_out_units, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_units) {
+// tkz_decode_batch and tkz_decode_batch_utf16 (utf16: `out` holds code units): ids and id offsets in, ONE call of the device decoder, items and offsets out
+tkz_status decode_host(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, void* out, int64_t out_cap, int64_t* out_offsets, int64_t* needed,
+                       bool utf16) {
     DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (!d_id_offsets || !d_out_offsets || (total_ids > 0 && !d_ids) || (out_cap > 0 && !d_out_units)) return fail(TKZ_E_ARG, "null device buffer");
-    Lease lease(e);
-    Workspace* ws = lease.ws;
-    return decode_utf16_device(e, ws, d_ids, d_id_offsets, n_docs, total_ids, d_out_units, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), total_units);
-}
-
-tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
-                                  int64_t* out_offsets, int64_t* needed) {
-    DeviceScope scope;
-    tkz_status st = check_encoder(e, scope);
-    if (st != TKZ_OK) return st;
-    if (n_docs < 0 || !id_offsets || !out_offsets || (out_cap > 0 && !out_units)) return fail(TKZ_E_ARG, "null buffer");
-    if (id_offsets[0] != 0) return fail(TKZ_E_ARG, "id_offsets[0] must be 0");
-    const int64_t total = id_offsets[n_docs];
-    if (total < 0 || (total > 0 && !ids)) return fail(TKZ_E_ARG, "bad id count");
+    TKZ_TRY(check_encoder(e, scope));
+    TKZ_TRY(check_host_outputs(out, out_cap, out_offsets, "null buffer"));
+    int64_t total = 0, n_items = 0;
+    TKZ_TRY(check_host_docs(id_offsets, n_docs, ids != nullptr, kIdDocs, &total));
     if (needed) *needed = 0;
     Lease lease(e);
     Workspace* ws = lease.ws;
     int64_t* acc = &ws->bytes_allocated;
     HIP_TRY(ws->d_ids.ensure((size_t)std::max<int64_t>(total, 1) * 4, acc));
-    HIP_TRY(ws->d_idoffs.ensure((size_t)(n_docs + 1) * 8, acc));
-    HIP_TRY(ws->d_outoffs.ensure((size_t)(n_docs + 1) * 8, acc));
+    for (DevBuf* b : {&ws->d_idoffs, &ws->d_outoffs}) HIP_TRY(b->ensure((size_t)(n_docs + 1) * 8, acc));
     if (total) HIP_TRY(hipMemcpy(ws->d_ids.p, ids, (size_t)total * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ws->d_idoffs.p, id_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-    int64_t nunits = 0;
-    st = decode_utf16_device(e, ws, ws->d_ids.as<int32_t>(), ws->d_idoffs.as<int64_t>(), n_docs, total, nullptr, out_cap, ws->d_outoffs.as<int64_t>(), nullptr, &nunits,
-                             &ws->d8_units);
-    if (needed) *needed = nunits;
+    DevBuf& items = utf16 ? ws->d8_units : ws->d_out;          // (the unit staging is sized inside decode_utf16_device, from the byte total)
+    if (!utf16) {      // staging no larger than the result can be: an id yields at most the longest registered byte string, however large a hint out_cap is
+        int64_t longest = 1;
+        { std::lock_guard<std::mutex> lock(e->mu); for (const auto& kv : e->dec_special) longest = std::max<int64_t>(longest, (int64_t)kv.second.size()); }
+        longest = std::max<int64_t>(longest, e->max_key_len);
+        out_cap = std::min<int64_t>(out_cap, total * longest);
+        HIP_TRY(items.ensure((size_t)std::max<int64_t>(out_cap, 1), acc));
+    }
+    const tkz_status st = utf16 ? decode_utf16_device(e, ws, ws->d_ids.as<int32_t>(), ws->d_idoffs.as<int64_t>(), n_docs, total, nullptr, out_cap, ws->d_outoffs.as<int64_t>(), nullptr, &n_items, &items)
+                                : decode_device(e, ws, ws->d_ids.as<int32_t>(), ws->d_idoffs.as<int64_t>(), n_docs, total, items.as<uint8_t>(), out_cap, ws->d_outoffs.as<int64_t>(), nullptr, &n_items);
+    if (needed) *needed = n_items;
     if (st != TKZ_OK) return st;
-    if (nunits) HIP_TRY(hipMemcpy(out_units, ws->d8_units.p, (size_t)nunits * 2, hipMemcpyDeviceToHost));
+    if (n_items) HIP_TRY(hipMemcpy(out, items.p, (size_t)n_items * (utf16 ? 2 : 1), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_offsets, ws->d_outoffs.p, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
     return TKZ_OK;
+}
+tkz_status check_decode_device(tkz_encoder* e, DeviceScope& scope, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t total_ids, const void* d_out, int64_t out_cap,
+                               const int64_t* d_out_offsets) {
+    TKZ_TRY(check_encoder(e, scope));
+    if (!d_id_offsets || !d_out_offsets || (total_ids > 0 && !d_ids) || (out_cap > 0 && !d_out)) return fail(TKZ_E_ARG, "null device buffer");
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_decode_batch_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
+                                   uint8_t* d_out_bytes, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_bytes) {
+    DeviceScope scope;
+    TKZ_TRY(check_decode_device(e, scope, d_ids, d_id_offsets, total_ids, d_out_bytes, out_cap, d_out_offsets));
+    Lease lease(e);
+    return decode_device(e, lease.ws, d_ids, d_id_offsets, n_docs, total_ids, d_out_bytes, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), total_bytes);
+}
+tkz_status tkz_decode_batch_utf16_device(tkz_encoder* e, const int32_t* d_ids, const int64_t* d_id_offsets, int64_t n_docs, int64_t total_ids,
+                                         uint16_t* d_out_units, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_units) {
+    DeviceScope scope;
+    TKZ_TRY(check_decode_device(e, scope, d_ids, d_id_offsets, total_ids, d_out_units, out_cap, d_out_offsets));
+    Lease lease(e);
+    return decode_utf16_device(e, lease.ws, d_ids, d_id_offsets, n_docs, total_ids, d_out_units, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream), total_units);
+}
+
+tkz_status tkz_decode_batch(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint8_t* out_bytes, int64_t out_cap,
+                            int64_t* out_offsets, int64_t* needed) {
+    return decode_host(e, ids, id_offsets, n_docs, out_bytes, out_cap, out_offsets, needed, false);
+}
+tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
+                                  int64_t* out_offsets, int64_t* needed) {
+    return decode_host(e, ids, id_offsets, n_docs, out_units, out_cap, out_offsets, needed, true);
 }
 
 tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value) {
