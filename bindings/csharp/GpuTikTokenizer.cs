@@ -43,6 +43,7 @@ namespace Microsoft.DeepDev
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_utf8(IntPtr encoder, byte* bytes, long* docOffsets, long nDocs,
                                                                                   int* outIds, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_utf16(IntPtr encoder, char* text, long len, int* outIds, long outCap, out long nOut);
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_special_utf16(IntPtr encoder, char* text, long len, int* allowed, int nAllowed, int* outIds, long outCap, out long nOut);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs,
                                                                                    int* outIds, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encoder_set_special_tokens(IntPtr encoder, int* ids, byte* literalsUtf8, long* literalOffsets, int n);
@@ -270,10 +271,35 @@ namespace Microsoft.DeepDev
         }
 
         public List<int> Encode(string text, IReadOnlyCollection<string> allowedSpecial)
-            => EncodeBatch(new[] { text }, allowedSpecial)[0];
+            => SpecialOnDevice(text, allowedSpecial) ?? EncodeBatch(new[] { text }, allowedSpecial)[0];
 
         public List<int> Encode(string text, bool applySpecialTokens = true)
-            => EncodeBatch(new[] { text }, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null)[0];
+            => Encode(text, applySpecialTokens && specialTokens.Count > 0 ? (IReadOnlyCollection<string>)specialTokens : Array.Empty<string>());
+
+        // Encode(text, allowedSpecial) on one string: ONE call of tkz_encode_special_utf16 on the string's own chars -- one kernel launch for a prompt.  null: nothing
+        // to allow (the plain route of EncodeBatch), or the registered set is beyond the device path (-7): the host segmentation of EncodeBatchFlat from now on.
+        private unsafe List<int>? SpecialOnDevice(string text, IReadOnlyCollection<string>? allowedSpecial)
+        {
+            if (allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0 || specialOnHost) return null;
+            var index = new List<int>();                                              // registration order = the alternation's
+            { int i = 0; foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial.Contains(k)) index.Add(i); ++i; } }
+            int[] allowed = index.Count > 0 ? index.ToArray() : new int[1];
+            long cap = Math.Max(1, Math.Min(3L * text.Length, text.Length / 2 + 4096));   // (a token per two units first; 3 * units always suffice)
+            while (true)
+            {
+                var ids = new int[cap];
+                int st; long n;
+                fixed (char* pc = text) fixed (int* pa = allowed) fixed (int* pi = ids)
+                    st = Tkz.tkz_encode_special_utf16(encoder, pc, text.Length, index.Count > 0 ? pa : null, index.Count, pi, cap, out n);
+                if (st == -7) { specialOnHost = true; return null; }
+                if (st == -4 /* TKZ_E_CAPACITY */ && n > cap) { cap = n; continue; }
+                Tkz.Check(st);
+                GC.KeepAlive(this);
+                var result = new List<int>((int)n);
+                if (n > 0) result.AddRange(new ArraySegment<int>(ids, 0, (int)n));
+                return result;
+            }
+        }
 
         /// <summary>Encodes every text as Encode(text, allowedSpecial) would; all plain segments go to the GPU as one batch.
         /// One List per text, each filled with ONE AddRange over its segment of the flat result.</summary>

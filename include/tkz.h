@@ -225,6 +225,20 @@ tkz_status tkz_encode_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, int
 tkz_status tkz_encode_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, int32_t* out_ids,
                             int64_t out_cap, int64_t* n_out);
 
+/* ITokenizer.Encode(text, allowedSpecial) on ONE string (TikTokenizer.cs:178-207; Encode(text, applySpecialTokens: true) is the call with every registered
+ * literal allowed).  The ids are tkz_encode_batch_special_utf8's / _utf16's for the same text as a batch of one document; allowed / n_allowed, TKZ_E_ARG and
+ * TKZ_E_UNSUPPORTED as there.  A text the plain single entries send through the single-launch kernel (at most 128 KiB of UTF-8; o200k: 1 KiB) goes through
+ * ONE launch here as well -- literal search, split, lookups, merges and ids --; a longer text, and one the kernel hands back (a piece of more than 1 KiB, a
+ * missed piece of more than 256 bytes, an error to report), takes the batch entry's path.  n_allowed == 0 or nothing registered: tkz_encode_utf8 /
+ * tkz_encode_utf16, and tkz_encoder_special_stats does not move.  A successful call counts as one batch there, with the literals it turned into ids; a call
+ * that takes the launch counts in tkz_encoder_small_path_calls.  TKZ_E_CAPACITY: *n_out is the required count.
+ *   tkz_encode_special_utf16: the transcode is the host's, as in tkz_encode_utf16; with a registered literal that holds U+FFFD the same loop notes where a
+ *   U+FFFD stands for a lone surrogate, which such a literal does not match (see tkz_encode_batch_special_utf16). */
+tkz_status tkz_encode_special_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids,
+                                   int64_t out_cap, int64_t* n_out);
+tkz_status tkz_encode_special_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids,
+                                    int64_t out_cap, int64_t* n_out);
+
 /* EncodeBatch with PIECE granularity -- what EncodeTrimSuffix / EncodeTrimPrefix consume
  * (TikTokenizer.cs:288-341 and :483-519 walk the regex matches of a text and need the token count and
  * the length of each).  Every document is split into its pieces and each piece is encoded:

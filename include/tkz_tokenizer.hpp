@@ -114,11 +114,16 @@ public:
     TikTokenizer& operator=(const TikTokenizer&) = delete;
 
     // Encode(string text, IReadOnlyCollection<string> allowedSpecial)        TikTokenizer.cs:178-185
+    // With special tokens allowed: ONE call of the single-text special entry (tkz_encode_special_utf8: one kernel launch for a prompt).  Only a registered set
+    // the device path does not hold (TKZ_E_UNSUPPORTED) is segmented here, as EncodeBatch does it.
     std::vector<int32_t> Encode(const std::string& text, const std::vector<std::string>& allowedSpecial) const {
+        std::vector<int32_t> ids;
+        if (encode_special_single(text, allowedSpecial, ids)) return ids;
         return EncodeBatch({text}, allowedSpecial)[0];
     }
     // Encode(string text, bool applySpecialTokens = true)                     TikTokenizer.cs:193-207
     std::vector<int32_t> Encode(const std::string& text, bool applySpecialTokens = true) const {
+        if (applySpecialTokens && !specials_.empty()) return Encode(text, all_specials());
         return EncodeBatch({text}, applySpecialTokens)[0];
     }
     std::vector<std::vector<int32_t>> EncodeBatch(const std::vector<std::string>& texts, bool applySpecialTokens = true) const {
@@ -377,7 +382,19 @@ public:
         for (size_t t = 0; t < texts.size(); ++t) out[t] = fb.text(static_cast<int64_t>(t));
         return out;
     }
-    std::vector<int32_t> EncodeUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const { return EncodeBatchUtf16({text}, allowedSpecial)[0]; }
+    // (one string: tkz_encode_special_utf16, the single-text special entry)
+    std::vector<int32_t> EncodeUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial) const {
+        if (!allowedSpecial.empty() && !specials_.empty() && !special_on_host_) {
+            const std::vector<int32_t> index = allowed_index(allowedSpecial);
+            std::vector<int32_t> ids(text.size() * 3 + 1);
+            int64_t n = 0;
+            const tkz_status st = tkz_encode_special_utf16(enc_, reinterpret_cast<const uint16_t*>(text.data()), static_cast<int64_t>(text.size()), index.data(),
+                                                           static_cast<int32_t>(index.size()), ids.data(), static_cast<int64_t>(ids.size()), &n);
+            if (st != TKZ_E_UNSUPPORTED) { check(st); ids.resize(static_cast<size_t>(n)); return ids; }
+            special_on_host_ = true;
+        }
+        return EncodeBatchUtf16({text}, allowedSpecial)[0];
+    }
     std::vector<Trimmed16> EncodeTrimSuffixBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         std::vector<Trimmed16> out;
         if (trim_batch_device16(texts, allowedSpecial, maxTokenCount, TKZ_TRIM_SUFFIX, out)) return out;
@@ -500,6 +517,19 @@ private:
         std::vector<std::string> all;
         for (const auto& s : specials_) all.push_back(s.first);
         return all;
+    }
+    // Encode(text, allowedSpecial) through tkz_encode_special_utf8; false (nothing encoded): nothing to allow, or the entry refused the registered set
+    bool encode_special_single(const std::string& text, const std::vector<std::string>& allowedSpecial, std::vector<int32_t>& ids) const {
+        if (allowedSpecial.empty() || specials_.empty() || special_on_host_) return false;
+        const std::vector<int32_t> index = allowed_index(allowedSpecial);
+        ids.resize(text.size() + 1);
+        int64_t n = 0;
+        const tkz_status st = tkz_encode_special_utf8(enc_, reinterpret_cast<const uint8_t*>(text.data()), static_cast<int64_t>(text.size()), index.data(),
+                                                      static_cast<int32_t>(index.size()), ids.data(), static_cast<int64_t>(ids.size()), &n);
+        if (st == TKZ_E_UNSUPPORTED) { special_on_host_ = true; ids.clear(); return false; }
+        check(st);
+        ids.resize(static_cast<size_t>(n));
+        return true;
     }
     std::vector<int32_t> allowed_index(const std::vector<std::string>& allowedSpecial) const {
         std::vector<int32_t> index;

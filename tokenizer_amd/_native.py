@@ -119,6 +119,8 @@ class Library:
         L.tkz_encode_batch_utf16.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_encode_utf8.argtypes = [vp, vp, i64, vp, i64, pi64]
         L.tkz_encode_utf16.argtypes = [vp, vp, i64, vp, i64, pi64]
+        L.tkz_encode_special_utf8.argtypes = [vp, vp, i64, vp, i32, vp, i64, pi64]
+        L.tkz_encode_special_utf16.argtypes = [vp, vp, i64, vp, i32, vp, i64, pi64]
         L.tkz_pretokenize_utf8.argtypes = [vp, vp, vp, i64, vp]
         L.tkz_encode_pieces.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_encode_batch_pieces_utf8.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, pi64, pi64]
@@ -558,6 +560,36 @@ class Encoder:
         ids = np.empty(max(1, 3 * n_units), np.int32)
         n = C.c_int64(0)
         self.lib.check(self.lib.L.tkz_encode_utf16(self._h, _ptr(u), n_units, _ptr(ids), 3 * n_units, C.byref(n)))
+        return ids[:n.value].tolist()
+
+    def encode_special(self, text: bytes, allowed, out_cap=None):
+        """ITokenizer.Encode(text, allowedSpecial) on one string: tkz_encode_special_utf8.  allowed: indices as in encode_batch_special.  A TkzError of this
+        call carries the count the entry reported as `needed` (E_CAPACITY: the required one)."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        cap = len(text) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        n = C.c_int64(0)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_special_utf8(self._h, _ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed), _ptr(ids), cap, C.byref(n)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
+        return ids[:n.value].tolist()
+
+    def encode_special_utf16(self, units, allowed, out_cap=None):
+        """The same for a .NET `string` given as its UTF-16 code units: tkz_encode_special_utf16."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n_units = len(u) - 1
+        cap = 3 * n_units if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        n = C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_special_utf16(self._h, _ptr(u), n_units, _ptr(allowed) if len(allowed) else None, len(allowed), _ptr(ids), cap, C.byref(n)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
         return ids[:n.value].tolist()
 
     # -- Decode --

@@ -370,6 +370,11 @@ struct HostCall {
     uint64_t* bitmap = nullptr;                        // BitmapOnly: the caller's words
     const SpecialCall* special = nullptr;
     bool utf16 = false;
+    // tkz_encode_special_utf8 / _utf16 (ONE text, special tokens): the only special calls that may take the single-launch path.  small_form: null, or (the UTF-16
+    // one) the same text transcoded on the host, which that path takes in the place of this call; repl: its replaced-byte bitmap, or null (utf16_to_utf8)
+    bool single = false;
+    const HostCall* small_form = nullptr;
+    const uint64_t* repl = nullptr;
     bool u16() const { return utf16; }
     int64_t total() const { return offs[n_docs]; }     // bytes, or code units
     bool plain_encode() const { return kind == CallKind::Encode; }
@@ -1221,7 +1226,8 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
 // back into it, one stream synchronisation, memcpy out.  Returns TKZ_OK with *handled = false when the kernel hands the batch back (a
 // piece of more than 1024 bytes, an error to be diagnosed, lists or buffers to be grown): the caller then takes the batch path.
 constexpr size_t kSmallOffBytes = 0, kSmallOffOffs = tkz::kSmallMaxBytes + 64, kSmallOffIds = kSmallOffOffs + (tkz::kSmallMaxDocs + 1) * 8,
-                 kSmallOffOut = kSmallOffIds + tkz::kSmallMaxBytes * 4, kSmallOffRes = kSmallOffOut + (tkz::kSmallMaxDocs + 1) * 8, kSmallBlock = kSmallOffRes + 256;
+                 kSmallOffOut = kSmallOffIds + tkz::kSmallMaxBytes * 4, kSmallOffRes = kSmallOffOut + (tkz::kSmallMaxDocs + 1) * 8, kSmallOffRepl = kSmallOffRes + 256,
+                 kSmallBlock = kSmallOffRepl + tkz::kSmallMaxBytes / 8 + 8;     // (the replaced-byte bitmap of a special call on text transcoded from UTF-16: total / 64 + 1 words)
 bool small_eligible(const tkz_encoder* e, const int64_t* offs, int64_t n_docs, int64_t total) {
     if (!e->small_ok || e->profiling || e->pretok_seq || (e->case_equiv && e->pattern == TKZ_PATTERN_CL100K) || total <= 0 || total > tkz::kSmallMaxBytes || n_docs < 1 || n_docs > tkz::kSmallMaxDocs) return false;
     const bool o200k = e->pattern == TKZ_PATTERN_O200K || e->pattern == TKZ_PATTERN_O200K_DOTNET;
@@ -1244,7 +1250,7 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     memcpy(H + kSmallOffBytes, c.bytes, (size_t)total);
     memcpy(H + kSmallOffOffs, c.offs, (size_t)(n_docs + 1) * 8);
     int64_t* h_res = reinterpret_cast<int64_t*>(H + kSmallOffRes);
-    h_res[0] = -1; h_res[1] = 0; h_res[2] = 0;
+    h_res[0] = -1; h_res[1] = 0; h_res[2] = 0; h_res[3] = 0;
     EncodeParams P = bind_params(ws, ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total);
     P.lane_piece = kSmallLanePiece;
     SmallArgs A{};
@@ -1258,6 +1264,16 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     TkzTables T;
     { std::lock_guard<std::mutex> lock(e->mu); T = e->T; }
     P.promo = T.promo; P.pextra = T.promo ? ws->w_pextra.as<int32_t>() : nullptr;
+    if (c.special) {       // the special form of the launch: the literal search of enqueue_attempt, inside it
+        const int64_t nwords = total / 64 + 1;
+        for (DevBuf* b : {&ws->w_candbits, &ws->w_segbits, &ws->w_specbits, &ws->w_endbits}) HIP_TRY(b->ensure((size_t)(nwords + 8) * 8, acc));
+        A.lit = e->LIT; A.allowed = c.special->allowed;
+        A.candbits = ws->w_candbits.as<uint64_t>(); A.segbits = ws->w_segbits.as<uint64_t>(); A.specbits = ws->w_specbits.as<uint64_t>(); A.endbits = ws->w_endbits.as<uint64_t>();
+        A.n_taken = reinterpret_cast<unsigned long long*>(ws->w_counters.as<char>() + offsetof(CounterBlock, n_literals));
+        if (c.repl) { memcpy(H + kSmallOffRepl, c.repl, (size_t)nwords * 8); A.repl = reinterpret_cast<const uint64_t*>(H + kSmallOffRepl); }
+        P.specbits = A.specbits; P.lit_meta = e->LIT.meta; P.lit_blob = e->LIT.blob; P.n_lit = e->LIT.n; P.lit_repl = A.repl;
+        P.stats = e->piece_stats ? e->t_stats.as<unsigned long long>() : nullptr;
+    }
     Launch L{ws->st_small, nullptr, ws};
     launch_small(L, T, P, A);
     HIP_TRY(hipStreamSynchronize(ws->st_small));
@@ -1268,6 +1284,7 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     const int64_t tokens = h_res[2];
     if (c.needed) *c.needed = tokens;
     *handled = true;
+    if (c.special) e->spec_literals += h_res[3];
     if (tokens > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
     if (tokens) memcpy(c.out_ids, H + kSmallOffIds, (size_t)tokens * 4);
     memcpy(c.out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
@@ -1675,9 +1692,11 @@ tkz_status encode_host(tkz_encoder* e, const HostCall& c) {
     Lease lease(e);
     Workspace* ws = lease.ws;
     // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
-    if (!u16 && c.plain_encode() && !c.special && small_eligible(e, offs, n_docs, total)) {
+    // (of the special calls only the single-text entries': a UTF-16 one brings the text as the host transcoded it)
+    const HostCall* const sm = c.small_form ? c.small_form : u16 ? nullptr : &c;
+    if (sm && sm->plain_encode() && (!sm->special || sm->single) && small_eligible(e, sm->offs, sm->n_docs, sm->total())) {
         bool handled = false;
-        st = encode_small(e, ws, c, &handled);
+        st = encode_small(e, ws, *sm, &handled);
         if (st != TKZ_OK || handled) return st;
     }
     const HostPlan plan = plan_host_batch(c);
@@ -2079,23 +2098,80 @@ tkz_status tkz_encode_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, int
     return st;
 }
 
-tkz_status tkz_encode_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, int32_t* out_ids, int64_t out_cap, int64_t* n_out) {
-    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
-    // Encoding.UTF8.GetBytes semantics: a surrogate pair -> 4 bytes, a lone surrogate -> U+FFFD (EF BF BD).
-    // Splitting is unaffected: a lone surrogate (Cs) and U+FFFD (So) are both one "other" unit under every pattern.
-    std::vector<uint8_t> u8;
+namespace {
+// Encoding.UTF8.GetBytes semantics: a surrogate pair -> 4 bytes, a lone surrogate -> U+FFFD (EF BF BD).
+// Splitting is unaffected: a lone surrogate (Cs) and U+FFFD (So) are both one "other" unit under every pattern.
+// repl: null, or receives the replaced-byte bitmap over the bytes written (size / 64 + 1 words): one bit at the EF of every U+FFFD that stands for a lone
+// surrogate -- what launch_u16_write leaves on the device, for the literal search of a special call (the reference searches the UTF-16 string).
+void utf16_to_utf8(const uint16_t* text, int64_t len, std::vector<uint8_t>* out, std::vector<uint64_t>* repl) {
+    std::vector<uint8_t>& u8 = *out;
+    u8.clear();
     u8.reserve((size_t)len * 3);
+    std::vector<size_t> lone;
     for (int64_t i = 0; i < len; ++i) {
         uint32_t c = text[i];
         if (c >= 0xD800 && c <= 0xDBFF && i + 1 < len && text[i + 1] >= 0xDC00 && text[i + 1] <= 0xDFFF) {
             c = 0x10000 + ((c - 0xD800) << 10) + (text[i + 1] - 0xDC00); ++i;
-        } else if (c >= 0xD800 && c <= 0xDFFF) c = 0xFFFD;
+        } else if (c >= 0xD800 && c <= 0xDFFF) { c = 0xFFFD; if (repl) lone.push_back(u8.size()); }
         if (c < 0x80) u8.push_back((uint8_t)c);
         else if (c < 0x800) { u8.push_back(0xC0 | (c >> 6)); u8.push_back(0x80 | (c & 0x3F)); }
         else if (c < 0x10000) { u8.push_back(0xE0 | (c >> 12)); u8.push_back(0x80 | ((c >> 6) & 0x3F)); u8.push_back(0x80 | (c & 0x3F)); }
         else { u8.push_back(0xF0 | (c >> 18)); u8.push_back(0x80 | ((c >> 12) & 0x3F)); u8.push_back(0x80 | ((c >> 6) & 0x3F)); u8.push_back(0x80 | (c & 0x3F)); }
     }
+    if (repl) {
+        repl->assign(u8.size() / 64 + 1, 0ull);
+        for (size_t p : lone) (*repl)[p >> 6] |= 1ull << (p & 63);
+    }
+}
+}  // namespace
+
+tkz_status tkz_encode_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, int32_t* out_ids, int64_t out_cap, int64_t* n_out) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    std::vector<uint8_t> u8;
+    utf16_to_utf8(text, len, &u8, nullptr);
     return tkz_encode_utf8(e, u8.data(), (int64_t)u8.size(), out_ids, out_cap, n_out);
+}
+
+// ITokenizer.Encode(text, allowedSpecial) on ONE string (TikTokenizer.cs:178-207): the batch special entry's result for a batch of that one document -- from
+// the single-launch kernel's special form where the plain single entries take the single-launch kernel (small_eligible), from the batch path otherwise and when
+// the kernel hands the call back.  Nothing allowed or registered: the plain single entry's call.
+tkz_status tkz_encode_special_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                   int64_t* n_out) {
+    if (len < 0 || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (!sp) return tkz_encode_utf8(e, text, len, out_ids, out_cap, n_out);
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    HostCall c{text, nullptr, offs, 1, out_ids, out_cap, oo, &needed};
+    c.special = sp; c.single = true;
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK) ++e->spec_batches;
+    *n_out = needed;
+    return st;
+}
+
+// The same for a UTF-16 string.  The host transcodes it as tkz_encode_utf16 does -- and, when a registered literal holds U+FFFD, notes where a U+FFFD stands for
+// a lone surrogate -- for the single-launch kernel; a call that does not take it, or that the kernel hands back, is the batch entry's with the code units.
+tkz_status tkz_encode_special_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                    int64_t* n_out) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (!sp) return tkz_encode_utf16(e, text, len, out_ids, out_cap, n_out);
+    std::vector<uint8_t> u8;
+    std::vector<uint64_t> repl;
+    utf16_to_utf8(text, len, &u8, sp->fffd ? &repl : nullptr);
+    const int64_t offs[2] = {0, len}, offs8[2] = {0, (int64_t)u8.size()};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    HostCall c8{u8.data(), nullptr, offs8, 1, out_ids, out_cap, oo, &needed};
+    c8.special = sp; c8.single = true; c8.repl = sp->fffd ? repl.data() : nullptr;
+    HostCall c{nullptr, text, offs, 1, out_ids, out_cap, oo, &needed};
+    c.utf16 = true; c.special = sp; c.single = true; c.small_form = &c8;
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK) ++e->spec_batches;
+    *n_out = needed;
+    return st;
 }
 
 tkz_status tkz_encode_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs,

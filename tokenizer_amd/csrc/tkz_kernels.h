@@ -110,11 +110,19 @@ constexpr int kSmallMaxBytes = 131072, kSmallMaxBytesO200k = 65536, kSmallMaxDoc
 struct SmallArgs {
     const uint8_t* h_bytes; const int64_t* h_offs;          // the batch, in page-locked host memory (h_bytes kSmallMaxBytes + 64 long)
     int32_t* out; int64_t out_cap; int64_t* out_offs;       // ids and document offsets, page-locked host memory
-    int64_t* h_result;                                      // [0] status (0 done, 1 take the batch path), [1] error bits, [2] token count
+    int64_t* h_result;                                      // [0] status (0 done, 1 take the batch path), [1] error bits, [2] token count, [3] literals taken (the special form)
     uint64_t* docbits; uint64_t* startbits;                 // the workspace arrays EncodeParams holds as const, writable
     int32_t* pcount; int64_t* pbase; int64_t* docord_base; int64_t* tile_base;
     int32_t counter_words;                                  // 32-bit words of the counter block to zero
     int64_t* counts3[2];                                    // {n_docs, n_bytes, n_tokens} of the batch, on the device: the encoder's block and the workspace's (either may be null)
+    // the special form (k_small<true>; n_taken null: the plain one, which reads none of these): the registered literals, the ones this call allows, the four
+    // bitmaps of the literal search (nwords + 8 words each), the counter of the literals taken (inside the counter block: zeroed with it; h_result[3] on
+    // return) and -- text transcoded from UTF-16 on the host while a registered literal holds U+FFFD -- the replaced-byte bitmap in page-locked host memory
+    // (launch_lit_scan's `repl`; EncodeParams::lit_repl is the same pointer), or null
+    TkzLitTable lit; TkzLitAllowed allowed;
+    uint64_t* candbits; uint64_t* segbits; uint64_t* specbits; uint64_t* endbits;
+    unsigned long long* n_taken;
+    const uint64_t* repl;
 };
 
 typedef void (*KernelHook)(void* ctx, int kernel_id, int phase /*0 before, 1 after*/, hipStream_t s);

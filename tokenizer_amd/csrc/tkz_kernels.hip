@@ -2546,23 +2546,24 @@ TKZ_DEV int tkz_lit_first(const uint32_t* meta, const uint8_t* blob, int n, cons
 }
 constexpr int kLitBlock = 4096;                            // bytes of text per wavefront of k_lit_scan (64 bitmap words)
 constexpr int kLitTextQuads = (kLitBlock + kLitMaxLen) / 16;
-TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, TkzLitTable LT, TkzLitAllowed A,
-                                uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, const uint64_t* repl) {
-    TKZ_SHARED uint4 s_text[kThreads / 64][kLitTextQuads];
-    TKZ_SHARED uint32_t s_meta[kLitMetaHead + 2 * kLitMax];
-    TKZ_SHARED uint4 s_blob[kLitMax * kLitMaxLen / 16];
-    {   // the literal table (a few hundred bytes as a rule)
-        uint8_t* sb = reinterpret_cast<uint8_t*>(s_blob);
-        for (int i = simt::tid(); i < kLitMetaHead + 2 * LT.n; i += simt::nthreads()) s_meta[i] = LT.meta[i];
-        for (int i = simt::tid(); i < LT.blob_bytes; i += simt::nthreads()) sb[i] = LT.blob[i];
-    }
-    simt::sync();
+constexpr int kLitMetaWords = kLitMetaHead + 2 * kLitMax, kLitBlobQuads = kLitMax * kLitMaxLen / 16;
+// the literal table (a few hundred bytes as a rule) into LDS, by the whole workgroup; the caller's barrier follows
+TKZ_DEV void tkz_lit_stage_table(const TkzLitTable& LT, uint32_t* s_meta, uint4* s_blob) {
+    uint8_t* sb = reinterpret_cast<uint8_t*>(s_blob);
+    for (int i = simt::tid(); i < kLitMetaHead + 2 * LT.n; i += simt::nthreads()) s_meta[i] = LT.meta[i];
+    for (int i = simt::tid(); i < LT.blob_bytes; i += simt::nthreads()) sb[i] = LT.blob[i];
+}
+// block `blk` of BLOCK bytes of text by ONE wavefront (k_lit_scan: a wavefront of each workgroup; k_small: the blocks dealt out to its wavefronts): its candidate
+// words, and the words of the three bitmaps k_lit_resolve ORs into as they start out.  tq: (BLOCK + kLitMaxLen) / 16 quads of LDS of the wavefront's own.
+template <int BLOCK>
+TKZ_DEV void tkz_lit_scan_block(int64_t blk, uint4* tq, const uint32_t* s_meta, const uint4* s_blob, const uint8_t* bytes, int64_t total, const uint64_t* docbits,
+                                int64_t nwords, int n_lit, const TkzLitAllowed& A, uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits,
+                                const uint64_t* repl) {
+    static_assert(BLOCK % 64 == 0 && BLOCK / 64 <= 64 && (BLOCK + kLitMaxLen) % 16 == 0, "a lane keeps a bitmap word of the block");
     const int lane = simt::lane();
-    const int64_t blk = simt::bid() * (kThreads / 64) + simt::wave();
-    const int64_t w0 = blk * (kLitBlock / 64), base = blk * kLitBlock;
+    const int64_t w0 = blk * (BLOCK / 64), base = blk * BLOCK;
     if (w0 >= nwords) return;
-    uint4* const tq = s_text[simt::wave()];
-    for (int q = lane; q < kLitTextQuads; q += 64) {       // the block and the bytes a literal that starts in it may reach; zeros beyond the text
+    for (int q = lane; q < (BLOCK + kLitMaxLen) / 16; q += 64) {       // the block and the bytes a literal that starts in it may reach; zeros beyond the text
         const int64_t p = base + 16 * (int64_t)q;
         uint4 v; v.x = v.y = v.z = v.w = 0;
         if (p + 16 <= total) v = tkz_load16_nt(bytes + p);
@@ -2578,21 +2579,31 @@ TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint6
     const uint8_t* const blob = reinterpret_cast<const uint8_t*>(s_blob);
     uint64_t mine = 0;                                     // lane j keeps word w0 + j
 #pragma unroll 1
-    for (int j = 0; j < kLitBlock / 64; ++j) {
+    for (int j = 0; j < BLOCK / 64; ++j) {
         if (w0 + j >= nwords) break;                       // (wave-uniform)
         const int pos = 64 * j + lane;
         const int64_t p = base + pos;
         const uint32_t c = tx[pos];
         bool cand = false;
         if (p < total && ((s_meta[c >> 5] >> (c & 31)) & 1u)) {
-            const int i = tkz_lit_first(s_meta, blob, LT.n, tx + pos, tkz_lit_room(docbits, nwords, total, p), repl, nwords, p);
+            const int i = tkz_lit_first(s_meta, blob, n_lit, tx + pos, tkz_lit_room(docbits, nwords, total, p), repl, nwords, p);
             cand = i >= 0 && ((A.m[i >> 6] >> (i & 63)) & 1ull);
         }
         const uint64_t m = simt::ballot(cand);
         if (lane == j) mine = m;
     }
     const int64_t w = w0 + lane;
-    if (w < nwords) { candbits[w] = mine; segbits[w] = docbits[w]; specbits[w] = 0; endbits[w] = 0; }
+    if (lane < BLOCK / 64 && w < nwords) { candbits[w] = mine; segbits[w] = docbits[w]; specbits[w] = 0; endbits[w] = 0; }
+}
+TKZ_KERNEL(256) void k_lit_scan(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, TkzLitTable LT, TkzLitAllowed A,
+                                uint64_t* candbits, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, const uint64_t* repl) {
+    TKZ_SHARED uint4 s_text[kThreads / 64][kLitTextQuads];
+    TKZ_SHARED uint32_t s_meta[kLitMetaWords];
+    TKZ_SHARED uint4 s_blob[kLitBlobQuads];
+    tkz_lit_stage_table(LT, s_meta, s_blob);
+    simt::sync();
+    tkz_lit_scan_block<kLitBlock>(simt::bid() * (kThreads / 64) + simt::wave(), s_text[simt::wave()], s_meta, s_blob, bytes, total, docbits, nwords, LT.n, A,
+                                  candbits, segbits, specbits, endbits, repl);
 }
 // the literal that k_lit_scan matched at candidate p (from the text: candidates are rare): its length
 TKZ_DEV int tkz_lit_len_at(const uint8_t* bytes, const uint64_t* docbits, int64_t nwords, int64_t total, const TkzLitTable& LT, int64_t p, const uint64_t* repl) {
@@ -2615,55 +2626,62 @@ TKZ_DEV bool tkz_lit_covered(const uint8_t* bytes, const uint64_t* docbits, cons
     }
     return false;
 }
+// bitmap word w by ONE thread: the runs its candidates head, walked; the number of literals taken
+TKZ_DEV unsigned long long tkz_lit_resolve_word(int64_t w, const uint8_t* bytes, int64_t total, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords,
+                                                const TkzLitTable& LT, uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, const uint64_t* repl) {
+    unsigned long long taken = 0;
+    for (uint64_t m = candbits[w]; m; m &= m - 1) {
+        const int64_t head = (w << 6) + tkz_ctz64(m);
+        if (tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, head, repl)) continue;       // (another lane's run)
+        for (int64_t cur = head; cur >= 0;) {
+            const int64_t end = cur + tkz_lit_len_at(bytes, docbits, nwords, total, LT, cur, repl);    // (<= total: the literal ends inside its document)
+            simt::atomic_or64((unsigned long long*)&specbits[cur >> 6], 1ull << (cur & 63));
+            simt::atomic_or64((unsigned long long*)&endbits[end >> 6], 1ull << (end & 63));
+            simt::atomic_or64((unsigned long long*)&segbits[cur >> 6], 1ull << (cur & 63));
+            simt::atomic_or64((unsigned long long*)&segbits[end >> 6], 1ull << (end & 63));
+            ++taken;
+            // the next candidate at or after `end`: part of this run when a candidate in front of it reaches over it -- it then starts less than kLitMaxLen
+            // bytes behind `end` --, the head of a run of its own otherwise
+            int64_t nxt = -1;
+            for (int64_t v = end >> 6; v < nwords && v <= (end + kLitMaxLen) >> 6 && nxt < 0; ++v) {
+                uint64_t c = candbits[v];
+                if (v == (end >> 6)) c &= ~tkz_lowmask((int)(end & 63));
+                if (c) nxt = (v << 6) + tkz_ctz64(c);
+            }
+            cur = nxt >= 0 && nxt < total && tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, nxt, repl) ? nxt : -1;
+        }
+    }
+    return taken;
+}
 TKZ_KERNEL(256) void k_lit_resolve(const uint8_t* bytes, int64_t total, const uint64_t* docbits, const uint64_t* candbits, int64_t nwords, TkzLitTable LT,
                                    uint64_t* segbits, uint64_t* specbits, uint64_t* endbits, unsigned long long* n_taken, const uint64_t* repl) {
     const int64_t stride = simt::nblocks() * simt::nthreads();
     unsigned long long taken = 0;
-    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) {
-        for (uint64_t m = candbits[w]; m; m &= m - 1) {
-            const int64_t head = (w << 6) + tkz_ctz64(m);
-            if (tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, head, repl)) continue;       // (another lane's run)
-            for (int64_t cur = head; cur >= 0;) {
-                const int64_t end = cur + tkz_lit_len_at(bytes, docbits, nwords, total, LT, cur, repl);    // (<= total: the literal ends inside its document)
-                simt::atomic_or64((unsigned long long*)&specbits[cur >> 6], 1ull << (cur & 63));
-                simt::atomic_or64((unsigned long long*)&endbits[end >> 6], 1ull << (end & 63));
-                simt::atomic_or64((unsigned long long*)&segbits[cur >> 6], 1ull << (cur & 63));
-                simt::atomic_or64((unsigned long long*)&segbits[end >> 6], 1ull << (end & 63));
-                ++taken;
-                // the next candidate at or after `end`: part of this run when a candidate in front of it reaches over it -- it then starts less than kLitMaxLen
-                // bytes behind `end` --, the head of a run of its own otherwise
-                int64_t nxt = -1;
-                for (int64_t v = end >> 6; v < nwords && v <= (end + kLitMaxLen) >> 6 && nxt < 0; ++v) {
-                    uint64_t c = candbits[v];
-                    if (v == (end >> 6)) c &= ~tkz_lowmask((int)(end & 63));
-                    if (c) nxt = (v << 6) + tkz_ctz64(c);
-                }
-                cur = nxt >= 0 && nxt < total && tkz_lit_covered(bytes, docbits, candbits, nwords, total, LT, nxt, repl) ? nxt : -1;
-            }
-        }
-    }
+    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride)
+        taken += tkz_lit_resolve_word(w, bytes, total, docbits, candbits, nwords, LT, segbits, specbits, endbits, repl);
     if (taken) simt::atomic_add64(n_taken, taken);
 }
 // one bitmap word a lane.  `inside` = the bytes strictly inside a taken literal: the running XOR of a mark behind every start and one at every end (a literal of
 // one byte: the two cancel); what is open at the word's first bit comes from the last start in the 128 bytes before it.
-TKZ_KERNEL(256) void k_lit_fix(uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords) {
+TKZ_DEV void tkz_lit_fix_word(int64_t w, uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits) {
     static_assert(kLitMaxLen <= 128, "a literal spans at most three bitmap words");
-    const int64_t stride = simt::nblocks() * simt::nthreads();
-    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) {
-        const uint64_t s0 = specbits[w], e0 = endbits[w];
-        const uint64_t s1 = w > 0 ? specbits[w - 1] : 0ull, e1 = w > 0 ? endbits[w - 1] : 0ull;
-        bool open = false;                                 // byte 64 w - 1 is inside a literal that goes on into this word
-        const uint64_t s1lo = s1 & ~(1ull << 63);
-        if (s1lo) { const int b = tkz_msb64(s1lo); open = (e1 >> (b + 1)) == 0; }
-        else if (w > 1 && specbits[w - 2]) {
-            const int b = tkz_msb64(specbits[w - 2]);
-            open = ((b == 63 ? 0ull : endbits[w - 2] >> (b + 1)) | e1) == 0;
-        }
-        uint64_t x = ((s0 << 1) | (s1 >> 63)) ^ e0;
-        x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16; x ^= x << 32;
-        if (open) x = ~x;
-        if (x | segbits[w]) startbits[w] = (startbits[w] & ~x) | segbits[w];
+    const uint64_t s0 = specbits[w], e0 = endbits[w];
+    const uint64_t s1 = w > 0 ? specbits[w - 1] : 0ull, e1 = w > 0 ? endbits[w - 1] : 0ull;
+    bool open = false;                                 // byte 64 w - 1 is inside a literal that goes on into this word
+    const uint64_t s1lo = s1 & ~(1ull << 63);
+    if (s1lo) { const int b = tkz_msb64(s1lo); open = (e1 >> (b + 1)) == 0; }
+    else if (w > 1 && specbits[w - 2]) {
+        const int b = tkz_msb64(specbits[w - 2]);
+        open = ((b == 63 ? 0ull : endbits[w - 2] >> (b + 1)) | e1) == 0;
     }
+    uint64_t x = ((s0 << 1) | (s1 >> 63)) ^ e0;
+    x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16; x ^= x << 32;
+    if (open) x = ~x;
+    if (x | segbits[w]) startbits[w] = (startbits[w] & ~x) | segbits[w];
+}
+TKZ_KERNEL(256) void k_lit_fix(uint64_t* startbits, const uint64_t* segbits, const uint64_t* specbits, const uint64_t* endbits, int64_t nwords) {
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    for (int64_t w = simt::bid() * simt::nthreads() + simt::tid(); w < nwords; w += stride) tkz_lit_fix_word(w, startbits, segbits, specbits, endbits);
 }
 
 // document offsets of a chunk cut out of a larger batch: made relative to the chunk's first byte
@@ -3363,14 +3381,28 @@ TKZ_KERNEL(256) void k_offsets_scan(int64_t* offs, int64_t n, int64_t* total) {
 //   every document <= kSmallMaxDoc bytes
 //   a giant piece, a missed piece of more than kLanePiece bytes (k_merge_coop's), a miss list or record buffer that is too small: status != 0, and the
 //   host takes the batch path (which has the retries)
+// SPECIAL (tkz_encode_special_utf8 / _utf16: Encode(text, allowedSpecial) on one string): the literal search of the special entries in the same launch --
+//   tkz_lit_scan_block, tkz_lit_resolve_word between the document marks and the pre-tokenizer, which then splits between SEGMENT marks; tkz_lit_fix_word behind
+//   it; tkz_probe_subtile<true, true>.  Each of these phases reads from memory what the one before wrote there (atomic ORs and plain stores of the same
+//   workgroup): a workgroup barrier between them orders that, as it does for the document marks.  The literal phase lives in the one LDS block: the table as
+//   k_lit_scan stages it (2,112 B of meta + 32 KB of blob at their limits) and a text stage per wavefront of kSmallLitBlock + kLitMaxLen bytes -- 2 KiB blocks,
+//   not k_lit_scan's 4 KiB: sixteen of those beside the table are 102 KB, over the 83.5 KB the pre-tokenizer phase needs anyway; sixteen of these are 69.7 KB.
+//   The table stays in LDS because a lane whose byte is in the set of first bytes walks all of it.  SPECIAL == false compiles to the code it always was.
 // -------------------------------------------------------------------------------------------------
+constexpr int kSmallLitBlock = 2048;       // bytes of text per wavefront and round of the literal scan (32 bitmap words)
+constexpr int kSmallLitTextQuads = (kSmallLitBlock + kLitMaxLen) / 16, kSmallLitTableQuads = kLitMetaWords / 4 + kLitBlobQuads;
 constexpr int kSmallWaves = 16;            // the workgroup is 256 threads for up to 4 sub-tiles, 1024 beyond
 constexpr int kSmallLdsQuads = kSmallWaves * kPretokBlkQuads + 16;       // 83.5 KB: the largest phase (a 4 KiB block of the pre-tokenizer per wavefront)
 static_assert(kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX + 1 && kSmallLdsQuads >= 8 * kMsLdsQuads + 32 && kSmallLdsQuads >= kLongLdsQuads &&
               kSmallLdsQuads >= kSmallWaves * kPlaceLdsQuads && kSmallLdsQuads * 16 >= kSmallMaxBytesO200k + 64 && kSmallMaxBytes <= 8 * kGroup * kSub,
               "every phase fits the one LDS block; the o200k text too; at most 8 groups of k_merge_short");
+static_assert(kLitMetaWords % 4 == 0 && kSmallLdsQuads >= kSmallLitTableQuads + kSmallWaves * kSmallLitTextQuads &&
+              kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX + 1 + kSmallWaves * (kSub / 128),
+              "the literal phase fits the one LDS block as well, and the probe phase with the words of the literals' starts");
+template <bool SPECIAL>
 TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     static_assert(kSmallLdsQuads * 16 <= kSmallLdsBytesNeeded, "tkz_kernels.h: what the host checks against the device's LDS per workgroup");
+    static_assert(kSmallLdsBytesNeeded == 86 * 1024, "the special form takes no more LDS than the plain one always did");
     TKZ_SHARED uint4 s_raw[kSmallLdsQuads];
     TKZ_SHARED int s_flag;
     const int tid = simt::tid(), lane = simt::lane(), wave = simt::wave();
@@ -3393,7 +3425,7 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
             v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
         }
         *reinterpret_cast<uint4*>(d_bytes + 16 * i) = v;
-        if (tkz_pat_is_o200k(T.pattern)) s_raw[i] = v;             // (only the sequential matcher reads the text from LDS)
+        if (!SPECIAL && tkz_pat_is_o200k(T.pattern)) s_raw[i] = v;   // (only the sequential matcher reads the text from LDS; SPECIAL: behind the literal phase)
     }
     for (int64_t d = tid; d <= n_docs; d += kThreads) d_offs[d] = A.h_offs[d];
     for (int64_t w = tid; w < nwords + 1; w += kThreads) A.docbits[w] = 0;
@@ -3416,10 +3448,57 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     for (int64_t w = tid; w < nwords; w += kThreads) A.startbits[w] = A.docbits[w];
     simt::sync();
     stamp();
+    // ---- 1s. the literals taken (k_lit_scan: the blocks dealt out to the wavefronts; k_lit_resolve: the words dealt out to the threads) ----
+    const uint64_t* isobits = A.docbits;                          // what the pre-tokenizer splits between: documents, or (SPECIAL) segments
+    if constexpr (SPECIAL) {
+        uint32_t* s_meta = reinterpret_cast<uint32_t*>(s_raw);
+        uint4* s_blob = s_raw + kLitMetaWords / 4;
+        tkz_lit_stage_table(A.lit, s_meta, s_blob);
+        simt::sync();
+        for (int64_t blk = wave; blk * (kSmallLitBlock / 64) < nwords; blk += nwaves) {
+            (void)simt::ballot(true);                             // (the block before this one is no longer read)
+            tkz_lit_scan_block<kSmallLitBlock>(blk, s_raw + kSmallLitTableQuads + wave * kSmallLitTextQuads, s_meta, s_blob, d_bytes, total, A.docbits, nwords, A.lit.n,
+                                               A.allowed, A.candbits, A.segbits, A.specbits, A.endbits, A.repl);
+        }
+        simt::sync();
+        stamp();
+        unsigned long long taken = 0;
+        for (int64_t w = tid; w < nwords; w += kThreads)
+            taken += tkz_lit_resolve_word(w, d_bytes, total, A.docbits, A.candbits, nwords, A.lit, A.segbits, A.specbits, A.endbits, A.repl);
+        if (taken) simt::atomic_add64(A.n_taken, taken);
+        simt::sync();
+        // (the sequential matcher ORs its starts into the segment marks; its text moves into LDS now that the literal table is done with)
+        for (int64_t w = tid; w < nwords; w += kThreads) A.startbits[w] = A.segbits[w];
+        if (tkz_pat_is_o200k(T.pattern)) for (int64_t i = tid; 16 * i < total; i += kThreads) s_raw[i] = *reinterpret_cast<const uint4*>(d_bytes + 16 * i);
+        simt::sync();
+        stamp();
+        isobits = A.segbits;
+    }
     // ---- 2. Regex.Matches.  Pattern 1 / cl100k: the row evaluator (one lane per BYTE of a 64-byte row, rows one after the other, scan state
     // carried: tkz_rows_sequential), the rows dealt out to the four wavefronts -- the sequential matcher took 55 us for a 64-byte prompt
     // (thousands of dependent reads), this takes ~2.  o200k has no row evaluator: the matcher, one lane per document, on the text in LDS ----
-    if (tkz_pat_is_o200k(T.pattern)) {
+    if (SPECIAL && tkz_pat_is_o200k(T.pattern)) {
+        // one lane per SEGMENT: the marks of a bitmap word by one thread, a segment's end from the next mark (the bitmap ends in one at `total`)
+        for (int64_t w = tid; w < nwords; w += kThreads) {
+            for (uint64_t m = isobits[w]; m; m &= m - 1) {
+                const int bit = tkz_ctz64(m);
+                const int64_t a = (w << 6) + bit;
+                if (a >= total) continue;
+                int64_t b = total;
+                uint64_t nx = bit == 63 ? 0ull : isobits[w] & ~tkz_lowmask(bit + 1);
+                for (int64_t v = w; ; nx = isobits[v]) {
+                    if (nx) { b = (v << 6) + tkz_ctz64(nx); break; }
+                    if (++v >= nwords) break;
+                }
+                if (b > total) b = total;
+                TkzDoc doc; doc.b = s_text + a; doc.n = b - a; doc.bmp = T.bmp_class; doc.by_code_point = T.pattern == TKZ_PAT_O200K;
+                int bad = 0;
+                for (int64_t p = 0; p < doc.n;) { const TkzChar c = tkz_doc_char(doc, p); bad |= c.bad; p += c.len; }
+                if (bad) { simt::atomic_or((unsigned*)&P.counters[0], (unsigned)kErrUtf8); continue; }
+                tkz_seq_emit(T.pattern, doc, a, 0, a, b, A.startbits);
+            }
+        }
+    } else if (tkz_pat_is_o200k(T.pattern)) {
         for (int64_t d = tid; d < n_docs; d += kThreads) {
             const int64_t a = d_offs[d], b = d_offs[d + 1];
             if (b <= a || a < 0 || b > total) continue;
@@ -3435,12 +3514,17 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
         for (int i = tid; i < 128; i += kThreads) s_aflags[i] = (uint16_t)tkz_ascii_flags((uint32_t)i, T.pattern == TKZ_PAT_CL100K);
         simt::sync();
         for (int64_t blk = wave; blk * kRowsPerWave < nwords; blk += nwaves) {
-            if (T.pattern == TKZ_PAT_P1) tkz_pretok_block<TKZ_PAT_P1>(blk, s_raw + wave * kPretokBlkQuads, s_aflags, d_bytes, total, A.docbits, A.startbits, nwords, T.bmp_class, P.counters);
-            else tkz_pretok_block<TKZ_PAT_CL100K>(blk, s_raw + wave * kPretokBlkQuads, s_aflags, d_bytes, total, A.docbits, A.startbits, nwords, T.bmp_class, P.counters);
+            if (T.pattern == TKZ_PAT_P1) tkz_pretok_block<TKZ_PAT_P1>(blk, s_raw + wave * kPretokBlkQuads, s_aflags, d_bytes, total, isobits, A.startbits, nwords, T.bmp_class, P.counters);
+            else tkz_pretok_block<TKZ_PAT_CL100K>(blk, s_raw + wave * kPretokBlkQuads, s_aflags, d_bytes, total, isobits, A.startbits, nwords, T.bmp_class, P.counters);
         }
     }
     simt::sync();
     stamp();
+    if constexpr (SPECIAL) {                                      // (every taken literal ONE piece: k_lit_fix)
+        for (int64_t w = tid; w < nwords; w += kThreads) tkz_lit_fix_word(w, A.startbits, A.segbits, A.specbits, A.endbits);
+        simt::sync();
+        stamp();
+    }
     // ---- 3. documents and pieces that start in each sub-tile, their scans (k_doccount2 + k_scan_*): one lane per sub-tile ----
     if (wave == 0) {
         int dcarry = 0, pcarry = 0;
@@ -3474,7 +3558,9 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
         for (int sub = wave; sub < nsub; sub += nwaves) {
             ProbeText tx;
             tkz_probe_request_text(P, sub, &tx);
-            tkz_probe_subtile<true>(T, P, sub, tkz_probe_lds(s_raw + wave * kProbeLdsQuads, s_kmask), tx, -1);
+            ProbeLds LD = tkz_probe_lds(s_raw + wave * kProbeLdsQuads, s_kmask);
+            if constexpr (SPECIAL) LD.spec = reinterpret_cast<uint32_t*>(s_kmask + TKZ_SHORT_KEY_MAX + 1 + wave * (kSub / 128));      // (k_probe_special's s_spec: behind the mask table)
+            tkz_probe_subtile<true, SPECIAL>(T, P, sub, LD, tx, -1);
             (void)simt::ballot(true);
         }
     }
@@ -3540,6 +3626,14 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     stamp();
     if (tid == 0) {
         const int32_t err = P.counters[0]; A.h_result[1] = err; A.h_result[0] = err ? 1 : 0;
+        if constexpr (SPECIAL) {
+            A.h_result[3] = (int64_t)*A.n_taken;
+            if (P.stats && !err) {                                // TKZ_OPT_PIECE_STATS: k_miss_stats
+                unsigned long long ns = 0, nl = 0, np = 0;
+                for (int t = 0; t < nsub; ++t) { const uint32_t m = P.mcount[t]; ns += m & 0xFFFFu; nl += m >> 16; np += (unsigned long long)A.pcount[t]; }
+                simt::atomic_add64(&P.stats[2], ns); simt::atomic_add64(&P.stats[3], nl); simt::atomic_add64(&P.stats[4], np);
+            }
+        }
         // {n_docs, n_bytes, n_tokens} of this batch on the device, as k_counts3 leaves them on the batch path (a batch that is handed back
         // gets them from there)
         if (!err) for (int k = 0; k < 2; ++k) if (A.counts3[k]) { A.counts3[k][0] = n_docs; A.counts3[k][1] = total; A.counts3[k][2] = A.tile_base[nsub]; }
@@ -3694,7 +3788,8 @@ void launch_ingest(const Launch& L, const uint8_t* h_bytes, int64_t total, uint8
     TKZ_LAUNCH(k_ingest, g < 1 ? 1 : (g > 2048 ? 2048 : g), kThreads, L.stream, h_bytes, total, d_bytes, h_offs, n_offs, d_offs, reinterpret_cast<uint4*>(zero), (zero_bytes + 15) / 16);
 }
 void launch_small(const Launch& L, const TkzTables& T, const EncodeParams& P, const SmallArgs& A) {
-    TKZ_LAUNCH(k_small, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+    if (A.n_taken) TKZ_LAUNCH(k_small<true>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+    else TKZ_LAUNCH(k_small<false>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
 }
 void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_base, int64_t nsub, int32_t* out, int64_t out_cap) {
     hook(L, K_GATHER, 0);

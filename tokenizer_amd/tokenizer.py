@@ -193,6 +193,16 @@ class TikTokenizer:
 
     # ---- ITokenizer --------------------------------------------------------------------------------
     def Encode(self, text: str, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True) -> List[int]:
+        """With special tokens allowed: ONE call of the device's single-text special entry (tkz_encode_special_utf8), which is one kernel launch for a prompt,
+        under the conditions in which EncodeBatchFlat takes the device's special entry; everything else is EncodeBatch of the one text."""
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        if allowed and self._special_re is not None and not self._special_on_host and not (self._fffd_literal and _has_lone_surrogate(text)):
+            names = set(allowed)
+            index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]       # (registration order = the alternation's)
+            try:
+                return self._encoder.encode_special(_utf8_like_dotnet(text), index)
+            except N.UnsupportedError:
+                self._special_on_host = True                  # (EncodeBatchFlat's host segmentation, from here on)
         return self.EncodeBatch([text], allowedSpecialOrApply)[0]
 
     def EncodeBatch(self, texts: Sequence[str], allowedSpecialOrApply: Union[bool, Sequence[str], None] = True) -> List[List[int]]:
