@@ -44,6 +44,9 @@ namespace Microsoft.DeepDev
                                                                                   int* outIds, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_utf16(IntPtr encoder, char* text, long len, int* outIds, long outCap, out long nOut);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_special_utf16(IntPtr encoder, char* text, long len, int* allowed, int nAllowed, int* outIds, long outCap, out long nOut);
+        // EncodeTrimSuffix / EncodeTrimPrefix on ONE string: one kernel launch for a prompt (include/tkz.h).  (Like the rest of this file: not compiled here.)
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_trim_utf16(IntPtr encoder, char* text, long len, int* allowed, int nAllowed, int side, long maxTokens,
+                                                                                  int* outIds, long outCap, out long nOut, out long cutUnits);
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs,
                                                                                    int* outIds, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_encoder_set_special_tokens(IntPtr encoder, int* ids, byte* literalsUtf8, long* literalOffsets, int n);
@@ -654,6 +657,29 @@ namespace Microsoft.DeepDev
             return result;
         }
 
+        // ONE text: ONE call of tkz_encode_trim_utf16 on the string's own chars -- one kernel launch for a prompt.  null: the host walk has to do it, in the
+        // cases of TrimBatchOnDevice.  (Like the rest of this file: not compiled here.)
+        private unsafe (List<int> TokenIds, string Text)? TrimOneOnDevice(string text, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount, int side)
+        {
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            if (maxTokenCount < 0 || (!plain && specialOnHost)) return null;
+            var index = new List<int>();                                              // registration order = the alternation's
+            if (!plain) { int i = 0; foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial!.Contains(k)) index.Add(i); ++i; } }
+            int[] allowed = index.Count > 0 ? index.ToArray() : new int[1];
+            long cap = Math.Min(3L * text.Length, maxTokenCount);                     // (the KEPT ids: tkz.h)
+            var ids = new int[Math.Max(1, cap)];
+            int st; long n, cutUnits;
+            fixed (char* pc = text) fixed (int* pa = allowed) fixed (int* pi = ids)
+                st = Tkz.tkz_encode_trim_utf16(encoder, pc, text.Length, index.Count > 0 ? pa : null, index.Count, side, maxTokenCount, pi, cap, out n, out cutUnits);
+            if (st == -7) { specialOnHost = true; return null; }
+            Tkz.Check(st);
+            GC.KeepAlive(this);
+            var kept = new List<int>((int)n);
+            if (n > 0) kept.AddRange(new ArraySegment<int>(ids, 0, (int)n));
+            int u = (int)cutUnits;
+            return (kept, side == 0 ? (u == text.Length ? text : text.Substring(0, u)) : (u == 0 ? text : text.Substring(u)));
+        }
+
         public List<(List<int> TokenIds, string Text)> EncodeTrimSuffixBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
             => TrimBatchOnDevice(texts, allowedSpecial, maxTokenCount, 0 /* TKZ_TRIM_SUFFIX */) ?? texts.Select(t => TrimSuffixOnHost(t, allowedSpecial, maxTokenCount)).ToList();
         public List<(List<int> TokenIds, string Text)> EncodeTrimSuffixBatch(IReadOnlyList<string> texts, int maxTokenCount, bool applySpecialTokens = true)
@@ -664,7 +690,7 @@ namespace Microsoft.DeepDev
             => EncodeTrimPrefixBatch(texts, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
 
         public (List<int> TokenIds, string Text) EncodeTrimSuffix(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
-            => EncodeTrimSuffixBatch(new[] { text }, allowedSpecial, maxTokenCount)[0];
+            => TrimOneOnDevice(text, allowedSpecial, maxTokenCount, 0 /* TKZ_TRIM_SUFFIX */) ?? TrimSuffixOnHost(text, allowedSpecial, maxTokenCount);
         // the host walk over the pieces: the fallback of the batch methods
         private (List<int> TokenIds, string Text) TrimSuffixOnHost(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
         {
@@ -684,7 +710,7 @@ namespace Microsoft.DeepDev
             => EncodeTrimSuffix(text, applySpecialTokens && specialTokens.Count > 0 ? specialTokens : null!, maxTokenCount);
 
         public (List<int> TokenIds, string Text) EncodeTrimPrefix(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
-            => EncodeTrimPrefixBatch(new[] { text }, allowedSpecial, maxTokenCount)[0];
+            => TrimOneOnDevice(text, allowedSpecial, maxTokenCount, 1 /* TKZ_TRIM_PREFIX */) ?? TrimPrefixOnHost(text, allowedSpecial, maxTokenCount);
         private (List<int> TokenIds, string Text) TrimPrefixOnHost(string text, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)
         {
             var tokenIds = new List<int>();

@@ -274,7 +274,8 @@ tkz_status tkz_encode_batch_pieces_utf8(tkz_encoder* e, const uint8_t* bytes, co
  * Workspace: the batch path's ~7 bytes per input byte, and 8 more per input byte (the untrimmed ids and a token mark per possible piece, 4 each), 16 per PIECE
  * (its byte and token offset: ~3.6 per input byte on English text, at most 16) and 32 per document.  The per-piece arrays never leave the device.
  * tkz_encode_batch_trim_utf8: the same over host buffers (max_tokens_per_doc is a HOST array, a negative entry is TKZ_E_ARG).  It stages the WHOLE batch on the
- * device, as tkz_encode_batch_pieces_utf8 does, and copies its result from ONE call of the device entry: no chunk pipeline, no single-launch path. */
+ * device, as tkz_encode_batch_pieces_utf8 does, and copies its result from ONE call of the device entry: no chunk pipeline, no single-launch path (ONE text: see
+ * tkz_encode_trim_utf8 below, which has one). */
 typedef enum tkz_trim_side { TKZ_TRIM_SUFFIX = 0, TKZ_TRIM_PREFIX = 1 } tkz_trim_side;
 tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
                                         const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens, const int64_t* d_max_tokens,
@@ -283,6 +284,24 @@ tkz_status tkz_encode_batch_trim_device(tkz_encoder* e, const uint8_t* d_bytes, 
 tkz_status tkz_encode_batch_trim_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
                                       int32_t side, int64_t max_tokens, const int64_t* max_tokens_per_doc, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
                                       int64_t* cut_bytes, int64_t* cut_units, int64_t* needed);
+
+/* EncodeTrimSuffix / EncodeTrimPrefix on ONE string (TikTokenizer.cs:288-579): "cut this prompt to max_tokens tokens and tell me what text is left".  The kept
+ * ids, *cut_bytes and *cut_units are what tkz_encode_batch_trim_utf8 / _utf16 return for the same text as a batch of one document with the uniform maximum
+ * max_tokens: the kept length for TKZ_TRIM_SUFFIX, the dropped length for TKZ_TRIM_PREFIX; a text kept whole reports its full length for suffix and 0 for
+ * prefix.  side, allowed / n_allowed, TKZ_E_ARG (a bad side, a negative maximum, a bad or repeated index, a null n_out) and TKZ_E_UNSUPPORTED exactly as there.
+ * cut_bytes and cut_units may each be NULL.  out_cap counts the KEPT ids only; on TKZ_E_CAPACITY *n_out is the kept count.  len == 0: TKZ_OK, *n_out == 0, zero
+ * cuts.  n_allowed == 0 or nothing registered: a plain trim, no literal is looked for and tkz_encoder_special_stats does not move; a call with literals moves it
+ * by what the batch trim entry moves it by for that text (a call that fails with TKZ_E_CAPACITY, there as here: the literals taken are counted, the batch is not).
+ * Route: a text of at most 96 KiB of UTF-8 that the plain single entries send through the single-launch kernel (o200k: 1 KiB) is ONE launch here as well --
+ * literal search, split, lookups, merges, ids, the cut and its lengths; the host copies the kept range of the ids out of the page-locked block -- and counts in
+ * tkz_encoder_small_path_calls.  (96 KiB, not the plain entries' 128 KiB: beyond it the batch trim path, which costs the same at every size, is as fast or faster.)  Any other text, and one the kernel hands back (a piece of more than 1 KiB, a missed piece of more than 256 bytes, an error to
+ * diagnose, lists to grow: the second figure of tkz_encoder_small_path_calls), takes the batch trim entry's path with identical results.
+ *   tkz_encode_trim_utf16: the transcode is the host's, as in tkz_encode_special_utf16, the replaced-byte bitmap in the same loop when a registered literal holds
+ *   U+FFFD; a replaced surrogate counts as the one unit it is.  A call that does not take the launch is tkz_encode_batch_trim_utf16's with the code units. */
+tkz_status tkz_encode_trim_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens,
+                                int32_t* out_ids, int64_t out_cap, int64_t* n_out, int64_t* cut_bytes, int64_t* cut_units);
+tkz_status tkz_encode_trim_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens,
+                                 int32_t* out_ids, int64_t out_cap, int64_t* n_out, int64_t* cut_units);
 
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id

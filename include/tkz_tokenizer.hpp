@@ -264,8 +264,10 @@ public:
 
     using Trimmed = std::pair<std::vector<int32_t>, std::string>;   // (List<int> TokenIds, string Text)
     // EncodeTrimSuffix(string, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)     TikTokenizer.cs:394-403
+    // (one string: tkz_encode_trim_utf8, the single-text trim entry -- one kernel launch for a prompt; the host walk where the batch methods take it)
     Trimmed EncodeTrimSuffix(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
-        return EncodeTrimSuffixBatch({text}, allowedSpecial, maxTokenCount)[0];
+        Trimmed out;
+        return trim_one_device(text, allowedSpecial, maxTokenCount, TKZ_TRIM_SUFFIX, out) ? out : trim_suffix_host(text, allowedSpecial, maxTokenCount);
     }
     // EncodeTrimSuffix / EncodeTrimPrefix for a batch of texts: ONE device call (tkz_encode_batch_trim_utf8 -- the literals cut out, the pieces counted, the
     // cut chosen and the kept ids compacted on the device; the text is sliced at the cut's byte position).  The host walk over piece_items() below remains for
@@ -306,7 +308,8 @@ public:
     }
     // EncodeTrimPrefix(string, IReadOnlyCollection<string> allowedSpecial, int maxTokenCount)     TikTokenizer.cs:529-536
     Trimmed EncodeTrimPrefix(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
-        return EncodeTrimPrefixBatch({text}, allowedSpecial, maxTokenCount)[0];
+        Trimmed out;
+        return trim_one_device(text, allowedSpecial, maxTokenCount, TKZ_TRIM_PREFIX, out) ? out : trim_prefix_host(text, allowedSpecial, maxTokenCount);
     }
     Trimmed trim_prefix_host(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         std::vector<int32_t> ids;
@@ -394,6 +397,15 @@ public:
             special_on_host_ = true;
         }
         return EncodeBatchUtf16({text}, allowedSpecial)[0];
+    }
+    // (one string: tkz_encode_trim_utf16, the single-text trim entry)
+    Trimmed16 EncodeTrimSuffixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        Trimmed16 out;
+        return trim_one_device16(text, allowedSpecial, maxTokenCount, TKZ_TRIM_SUFFIX, out) ? out : trim_suffix_host16(text, allowedSpecial, maxTokenCount);
+    }
+    Trimmed16 EncodeTrimPrefixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        Trimmed16 out;
+        return trim_one_device16(text, allowedSpecial, maxTokenCount, TKZ_TRIM_PREFIX, out) ? out : trim_prefix_host16(text, allowedSpecial, maxTokenCount);
     }
     std::vector<Trimmed16> EncodeTrimSuffixBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         std::vector<Trimmed16> out;
@@ -616,6 +628,39 @@ private:
             const size_t c = static_cast<size_t>(cut[t]);             // code units of the kept text (suffix) / of the dropped text (prefix)
             out.push_back({std::vector<int32_t>(ids.begin() + ooff[t], ids.begin() + ooff[t + 1]), side == TKZ_TRIM_SUFFIX ? texts[t].substr(0, c) : texts[t].substr(c)});
         }
+        return true;
+    }
+    // ONE text on the single-text trim entries; false (nothing done): the host walk has to do it -- the cases of trim_batch_device
+    bool trim_one_device(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int32_t side, Trimmed& out) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (maxTokenCount < 0 || (!plain && special_on_host_)) return false;
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = std::min<int64_t>(static_cast<int64_t>(text.size()), maxTokenCount);
+        std::vector<int32_t> ids(static_cast<size_t>(cap) + 1);
+        int64_t n = 0, cut = 0;
+        const tkz_status st = tkz_encode_trim_utf8(enc_, reinterpret_cast<const uint8_t*>(text.data()), static_cast<int64_t>(text.size()), index.empty() ? nullptr : index.data(),
+                                                   static_cast<int32_t>(index.size()), side, maxTokenCount, ids.data(), cap, &n, &cut, nullptr);
+        if (st == TKZ_E_UNSUPPORTED) { special_on_host_ = true; return false; }
+        check(st);
+        ids.resize(static_cast<size_t>(n));
+        const size_t c = static_cast<size_t>(cut);                    // bytes of the kept text (suffix) / of the dropped text (prefix)
+        out = {ids, side == TKZ_TRIM_SUFFIX ? text.substr(0, c) : text.substr(c)};
+        return true;
+    }
+    bool trim_one_device16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int32_t side, Trimmed16& out) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (maxTokenCount < 0 || (!plain && special_on_host_)) return false;
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = std::min<int64_t>(3 * static_cast<int64_t>(text.size()), maxTokenCount);
+        std::vector<int32_t> ids(static_cast<size_t>(cap) + 1);
+        int64_t n = 0, cut = 0;
+        const tkz_status st = tkz_encode_trim_utf16(enc_, reinterpret_cast<const uint16_t*>(text.data()), static_cast<int64_t>(text.size()), index.empty() ? nullptr : index.data(),
+                                                    static_cast<int32_t>(index.size()), side, maxTokenCount, ids.data(), cap, &n, &cut);
+        if (st == TKZ_E_UNSUPPORTED) { special_on_host_ = true; return false; }
+        check(st);
+        ids.resize(static_cast<size_t>(n));
+        const size_t c = static_cast<size_t>(cut);                    // code units of the kept text (suffix) / of the dropped text (prefix)
+        out = {ids, side == TKZ_TRIM_SUFFIX ? text.substr(0, c) : text.substr(c)};
         return true;
     }
     // the batch on the device's trim entry; false (nothing done): the host walk has to do it

@@ -121,6 +121,8 @@ class Library:
         L.tkz_encode_utf16.argtypes = [vp, vp, i64, vp, i64, pi64]
         L.tkz_encode_special_utf8.argtypes = [vp, vp, i64, vp, i32, vp, i64, pi64]
         L.tkz_encode_special_utf16.argtypes = [vp, vp, i64, vp, i32, vp, i64, pi64]
+        L.tkz_encode_trim_utf8.argtypes = [vp, vp, i64, vp, i32, i32, i64, vp, i64, pi64, pi64, pi64]
+        L.tkz_encode_trim_utf16.argtypes = [vp, vp, i64, vp, i32, i32, i64, vp, i64, pi64, pi64]
         L.tkz_pretokenize_utf8.argtypes = [vp, vp, vp, i64, vp]
         L.tkz_encode_pieces.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_encode_batch_pieces_utf8.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, pi64, pi64]
@@ -591,6 +593,39 @@ class Encoder:
             ex.needed = n.value
             raise
         return ids[:n.value].tolist()
+
+    def encode_trim(self, text: bytes, allowed, side, max_tokens, out_cap=None):
+        """EncodeTrimSuffix (side TRIM_SUFFIX) / EncodeTrimPrefix (TRIM_PREFIX) on one string: tkz_encode_trim_utf8.  (kept ids, cut_bytes, cut_units): the byte
+        and UTF-16 length of the kept (suffix) or dropped (prefix) text.  allowed: indices as in encode_batch_special; out_cap counts the kept ids.  A TkzError
+        of this call carries the count the entry reported as `needed` (E_CAPACITY: the kept one)."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        cap = min(len(text), max(int(max_tokens), 0)) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        n, cb, cu = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_trim_utf8(self._h, _ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed), int(side), int(max_tokens),
+                                                           _ptr(ids), cap, C.byref(n), C.byref(cb), C.byref(cu)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
+        return ids[:n.value].tolist(), cb.value, cu.value
+
+    def encode_trim_utf16(self, units, allowed, side, max_tokens, out_cap=None):
+        """The same for a .NET `string` given as its UTF-16 code units: tkz_encode_trim_utf16.  (kept ids, cut_units)."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n_units = len(u) - 1
+        cap = min(3 * n_units, max(int(max_tokens), 0)) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        n, cu = C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_trim_utf16(self._h, _ptr(u), n_units, _ptr(allowed) if len(allowed) else None, len(allowed), int(side), int(max_tokens),
+                                                            _ptr(ids), cap, C.byref(n), C.byref(cu)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
+        return ids[:n.value].tolist(), cu.value
 
     # -- Decode --
     def set_special_tokens(self, specials):

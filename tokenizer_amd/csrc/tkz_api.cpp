@@ -361,6 +361,9 @@ struct BatchCall {
     const SpecialCall* literals() const { return plain_encode() || kind == CallKind::Trim ? special : nullptr; }
 };
 
+// tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
+struct TrimOne { int32_t side; int64_t max_tokens; int64_t* cut_bytes; int64_t* cut_units; };
+
 // One batch in the caller's host memory, as the host entries hand it to encode_host.
 struct HostCall {
     const uint8_t* bytes; const uint16_t* units;       // UTF-8 bytes, or (utf16) UTF-16 code units (offsets in units then)
@@ -375,6 +378,8 @@ struct HostCall {
     bool single = false;
     const HostCall* small_form = nullptr;
     const uint64_t* repl = nullptr;
+    // the single-text trim entries: the single-launch path runs its trim form, out_cap counts the KEPT ids and *needed receives their count
+    const TrimOne* trim = nullptr;
     bool u16() const { return utf16; }
     int64_t total() const { return offs[n_docs]; }     // bytes, or code units
     bool plain_encode() const { return kind == CallKind::Encode; }
@@ -1240,7 +1245,8 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     using namespace tkz;
     const int64_t n_docs = c.n_docs, total = c.total();
     *handled = false;
-    { const tkz_status ps = prepare_workspace(ws, total, n_docs, CallKind::Encode); if (ps != TKZ_OK) return ps; }
+    // (a trim call: a token mark per possible piece, as the batch trim path has them)
+    { const tkz_status ps = prepare_workspace(ws, total, n_docs, c.trim ? CallKind::Trim : CallKind::Encode); if (ps != TKZ_OK) return ps; }
     int64_t* acc = &ws->bytes_allocated;
     HIP_TRY(ws->s_bytes[0].ensure((size_t)kSmallMaxBytes + 64, acc));
     HIP_TRY(ws->s_offs[0].ensure((size_t)(kSmallMaxDocs + 1) * 8, acc));
@@ -1274,6 +1280,12 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
         P.specbits = A.specbits; P.lit_meta = e->LIT.meta; P.lit_blob = e->LIT.blob; P.n_lit = e->LIT.n; P.lit_repl = A.repl;
         P.stats = e->piece_stats ? e->t_stats.as<unsigned long long>() : nullptr;
     }
+    if (c.trim) {          // the trim form: the marks are the piece starts (enqueue_attempt's `markbits = startbits`); the untrimmed ids all fit the block
+        P.docbits = ws->w_startbits.as<uint64_t>();
+        A.out_cap = kSmallMaxBytes;
+        A.trim = 1; A.trim_side = c.trim->side; A.trim_max = c.trim->max_tokens;
+        h_res[20] = 0; h_res[21] = 0; h_res[22] = 0; h_res[23] = 0;
+    }
     Launch L{ws->st_small, nullptr, ws};
     launch_small(L, T, P, A);
     HIP_TRY(hipStreamSynchronize(ws->st_small));
@@ -1281,13 +1293,17 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     ws->small_calls.fetch_add(1, std::memory_order_relaxed);
     { std::lock_guard<std::mutex> lock(e->mu); memcpy(ws->small_clocks, h_res + 4, sizeof ws->small_clocks); }
     if (h_res[0] != 0) { ws->small_fallbacks.fetch_add(1, std::memory_order_relaxed); return TKZ_OK; }          // (handled stays false)
-    const int64_t tokens = h_res[2];
+    const int64_t first = c.trim ? h_res[20] : 0, tokens = c.trim ? h_res[21] : h_res[2];        // (a trim call: the kept ids are [first, first + tokens) of the block's)
     if (c.needed) *c.needed = tokens;
     *handled = true;
     if (c.special) e->spec_literals += h_res[3];
     if (tokens > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
-    if (tokens) memcpy(c.out_ids, H + kSmallOffIds, (size_t)tokens * 4);
-    memcpy(c.out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
+    if (tokens) memcpy(c.out_ids, H + kSmallOffIds + (size_t)first * 4, (size_t)tokens * 4);
+    if (c.trim) {
+        c.out_offsets[0] = 0; c.out_offsets[1] = tokens;
+        if (c.trim->cut_bytes) *c.trim->cut_bytes = h_res[22];
+        if (c.trim->cut_units) *c.trim->cut_units = h_res[23];
+    } else memcpy(c.out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
     return TKZ_OK;
 }
 
@@ -2362,6 +2378,86 @@ tkz_status tkz_encode_batch_trim_utf16(tkz_encoder* e, const uint16_t* units, co
     BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
     if (with_repl) c.d_repl = U.repl.as<uint64_t>();
     return trim_staged(e, ws, c, side, max_tokens, max_tokens_per_doc, sp, out_ids, out_cap, out_offsets, nullptr, cut_units, needed);
+}
+
+// ---- EncodeTrimSuffix / EncodeTrimPrefix on ONE string: the batch trim entries' result for a batch of that one document and a uniform maximum -- from the
+// single-launch kernel's trim form where the plain single entries take the single-launch kernel (small_eligible) and the text has at most kSmallTrimMaxBytes
+// bytes, from the batch trim entries otherwise and when the kernel hands the call back ----
+
+namespace {
+// the launch for the text as UTF-8 (c8: single, with its TrimOne).  *handled false: the text is not eligible, or the kernel handed it back
+tkz_status trim_small(tkz_encoder* e, const HostCall& c8, bool* handled) {
+    *handled = false;
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (c8.total() > tkz::kSmallTrimMaxBytes || !small_eligible(e, c8.offs, 1, c8.total())) return TKZ_OK;     // (beyond it the batch trim path is as fast or faster; UTF-16: the bytes may exceed it)
+    Lease lease(e);
+    const tkz_status st = encode_small(e, lease.ws, c8, handled);
+    if (st == TKZ_OK && *handled && c8.special) ++e->spec_batches;
+    return st;
+}
+}  // namespace
+
+tkz_status tkz_encode_trim_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens,
+                                int32_t* out_ids, int64_t out_cap, int64_t* n_out, int64_t* cut_bytes, int64_t* cut_units) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_trim_args(side, max_tokens, false));
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0, cb = 0, cu = 0;
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, oo, "null output buffer", false));
+    *n_out = 0;
+    if (cut_bytes) *cut_bytes = 0;
+    if (cut_units) *cut_units = 0;
+    if (len == 0) { if (sp) ++e->spec_batches; return TKZ_OK; }
+    const TrimOne t{side, max_tokens, &cb, &cu};
+    HostCall c{text, nullptr, offs, 1, out_ids, out_cap, oo, &needed};
+    c.special = sp; c.single = true; c.trim = &t;
+    bool handled = false;
+    tkz_status st = len <= tkz::kSmallTrimMaxBytes ? trim_small(e, c, &handled) : TKZ_OK;      // (a longer text costs nothing here before the batch entry has it)
+    if (st == TKZ_OK && !handled)
+        st = tkz_encode_batch_trim_utf8(e, text, offs, 1, allowed, n_allowed, side, max_tokens, nullptr, out_ids, out_cap, oo, &cb, &cu, &needed);
+    *n_out = needed;
+    if (cut_bytes) *cut_bytes = cb;
+    if (cut_units) *cut_units = cu;
+    return st;
+}
+
+// The same for a UTF-16 string.  The host transcodes it as tkz_encode_special_utf16 does -- the replaced-byte bitmap in the same loop when a registered literal
+// holds U+FFFD -- for the single-launch kernel, whose unit count needs nothing more: a replacement is the one unit it stands for.  A call that does not take the
+// launch, or that the kernel hands back, is the batch entry's with the code units.
+tkz_status tkz_encode_trim_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens,
+                                 int32_t* out_ids, int64_t out_cap, int64_t* n_out, int64_t* cut_units) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_trim_args(side, max_tokens, false));
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0, cu = 0;
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, oo, "null output buffer", false));
+    *n_out = 0;
+    if (cut_units) *cut_units = 0;
+    if (len == 0) { if (sp) ++e->spec_batches; return TKZ_OK; }
+    tkz_status st = TKZ_OK;
+    bool handled = false;
+    // (a unit is a byte at least: a string that is not eligible at `len` BYTES -- too long, o200k beyond its 1 KiB, a device without the LDS -- is not eligible
+    //  as the bytes it becomes, and is not transcoded here only to be transcoded again by the batch entry)
+    if (len <= tkz::kSmallTrimMaxBytes && small_eligible(e, offs, 1, len)) {
+        std::vector<uint8_t> u8;
+        std::vector<uint64_t> repl;
+        utf16_to_utf8(text, len, &u8, sp && sp->fffd ? &repl : nullptr);
+        const int64_t offs8[2] = {0, (int64_t)u8.size()};
+        const TrimOne t{side, max_tokens, nullptr, &cu};
+        HostCall c8{u8.data(), nullptr, offs8, 1, out_ids, out_cap, oo, &needed};
+        c8.special = sp; c8.single = true; c8.trim = &t; c8.repl = sp && sp->fffd ? repl.data() : nullptr;
+        st = trim_small(e, c8, &handled);
+    }
+    if (st == TKZ_OK && !handled)
+        st = tkz_encode_batch_trim_utf16(e, text, offs, 1, allowed, n_allowed, side, max_tokens, nullptr, out_ids, out_cap, oo, &cu, &needed);
+    *n_out = needed;
+    if (cut_units) *cut_units = cu;
+    return st;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

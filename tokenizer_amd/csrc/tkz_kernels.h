@@ -107,10 +107,22 @@ struct TkzLitAllowed { uint64_t m[kLitMax / 64]; };       // bit i: literal i is
 //  on a device whose sharedMemPerBlock covers it, the batch path otherwise)
 constexpr int kSmallLdsBytesNeeded = 86 * 1024;
 constexpr int kSmallMaxBytes = 131072, kSmallMaxBytesO200k = 65536, kSmallMaxDocs = 8192, kSmallMaxDoc = 1024;
+// the trim form (tkz_encode_trim_utf8 / _utf16) takes the launch up to this many bytes: the route it replaces -- the batch trim path, the whole chip -- costs
+// about the same at every size up to 128 KiB, one workgroup grows with the text.  Scanned on plain text with the launch taken at every size
+// (profiles/small_trim/README.md, crossover.jsonl): a/b 0.52 .. 0.66 at 48 KiB, 0.78 .. 0.96 at 96 KiB -- the largest scanned size with the launch ahead in every
+// row --, 0.86 .. 1.01 at 104 KiB, 0.92 .. 1.04 at 112, 0.94 .. 1.17 at 128.  A conservative choice, not an interpolated crossover: nothing between 96 and 104 KiB
+// was scanned, and the gpt2 rows are still ahead at 112.
+// (development: -DTKZ_SMALL_TRIM_MAX_BYTES=131072 builds the library the scan was taken with: the launch at every size the plain entries allow)
+#ifndef TKZ_SMALL_TRIM_MAX_BYTES
+#define TKZ_SMALL_TRIM_MAX_BYTES 98304
+#endif
+constexpr int kSmallTrimMaxBytes = TKZ_SMALL_TRIM_MAX_BYTES;
+static_assert(kSmallTrimMaxBytes > 0 && kSmallTrimMaxBytes <= kSmallMaxBytes, "the trim form runs inside the single-launch kernel's limits");
 struct SmallArgs {
     const uint8_t* h_bytes; const int64_t* h_offs;          // the batch, in page-locked host memory (h_bytes kSmallMaxBytes + 64 long)
     int32_t* out; int64_t out_cap; int64_t* out_offs;       // ids and document offsets, page-locked host memory
     int64_t* h_result;                                      // [0] status (0 done, 1 take the batch path), [1] error bits, [2] token count, [3] literals taken (the special form)
+                                                            // [4..19] clock stamps; the trim form: [20] first kept token, [21] kept count, [22] cut_bytes, [23] cut_units
     uint64_t* docbits; uint64_t* startbits;                 // the workspace arrays EncodeParams holds as const, writable
     int32_t* pcount; int64_t* pbase; int64_t* docord_base; int64_t* tile_base;
     int32_t counter_words;                                  // 32-bit words of the counter block to zero
@@ -123,6 +135,10 @@ struct SmallArgs {
     uint64_t* candbits; uint64_t* segbits; uint64_t* specbits; uint64_t* endbits;
     unsigned long long* n_taken;
     const uint64_t* repl;
+    // the trim form (k_small<SPECIAL, true>: tkz_encode_trim_utf8 / _utf16, ONE document; trim 0: the other forms, which read none of these): the side
+    // (tkz_trim_side) and the maximum.  EncodeParams::docbits is the PIECE-start bitmap then, doc_tok holds an entry per piece, `out` holds the untrimmed ids
+    // (out_cap kSmallMaxBytes) and the host copies [h_result[20], + h_result[21]) of them
+    int32_t trim; int32_t trim_side; int64_t trim_max;
 };
 
 typedef void (*KernelHook)(void* ctx, int kernel_id, int phase /*0 before, 1 after*/, hipStream_t s);

@@ -3388,6 +3388,15 @@ TKZ_KERNEL(256) void k_offsets_scan(int64_t* offs, int64_t n, int64_t* total) {
 //   k_lit_scan stages it (2,112 B of meta + 32 KB of blob at their limits) and a text stage per wavefront of kSmallLitBlock + kLitMaxLen bytes -- 2 KiB blocks,
 //   not k_lit_scan's 4 KiB: sixteen of those beside the table are 102 KB, over the 83.5 KB the pre-tokenizer phase needs anyway; sixteen of these are 69.7 KB.
 //   The table stays in LDS because a lane whose byte is in the set of first bytes walks all of it.  SPECIAL == false compiles to the code it always was.
+// TRIM (tkz_encode_trim_utf8 / _utf16: EncodeTrimSuffix / EncodeTrimPrefix of ONE string; either SPECIAL): the batch trim path's launch sequence in the same
+//   launch.  The marks the encode phases see are the PIECE starts, behind tkz_lit_fix_word (the host binds EncodeParams::docbits to the piece-start bitmap, as
+//   enqueue_attempt does for CallKind::Pieces): doc_tok receives a token position per piece, a taken literal is one item of one token, and phase 3 counts its
+//   "documents" from that bitmap.  Behind the place phase comes the cut, k_trim_cut's rule: the tokens in front of the piece boundary at byte pos are
+//   tile_base[sub] + doc_tok[ordinal(pos)] -- strictly ascending, every item has a token --; the bitmap words are dealt out to the threads, each walks its set
+//   bits, and a workgroup-wide maximum (suffix: the last boundary with at most `max` in front of it, byte 0 when none) or minimum (prefix: the first with at
+//   least count - max, `total` when none) follows through a few words of the LDS block.  Then cut_units as k_trim_gather counts them, over the quads of
+//   [0, cut).  Nothing is gathered: the untrimmed ids are in the page-locked block and the host copies [first, first + kept).  TRIM == false compiles to the
+//   code it always was.
 // -------------------------------------------------------------------------------------------------
 constexpr int kSmallLitBlock = 2048;       // bytes of text per wavefront and round of the literal scan (32 bitmap words)
 constexpr int kSmallLitTextQuads = (kSmallLitBlock + kLitMaxLen) / 16, kSmallLitTableQuads = kLitMetaWords / 4 + kLitBlobQuads;
@@ -3399,7 +3408,7 @@ static_assert(kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX
 static_assert(kLitMetaWords % 4 == 0 && kSmallLdsQuads >= kSmallLitTableQuads + kSmallWaves * kSmallLitTextQuads &&
               kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX + 1 + kSmallWaves * (kSub / 128),
               "the literal phase fits the one LDS block as well, and the probe phase with the words of the literals' starts");
-template <bool SPECIAL>
+template <bool SPECIAL, bool TRIM = false>
 TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     static_assert(kSmallLdsQuads * 16 <= kSmallLdsBytesNeeded, "tkz_kernels.h: what the host checks against the device's LDS per workgroup");
     static_assert(kSmallLdsBytesNeeded == 86 * 1024, "the special form takes no more LDS than the plain one always did");
@@ -3537,6 +3546,7 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
                     uint64_t md = w < nwords ? A.docbits[w] : 0ull, mp = w < nwords ? A.startbits[w] : 0ull;
                     const int64_t lim = total - (w << 6);                  // (the sentinel bit at `total` is not a start)
                     if (lim <= 0) { md = 0; mp = 0; } else if (lim < 64) { md &= tkz_lowmask((int)lim); mp &= tkz_lowmask((int)lim); }
+                    if constexpr (TRIM) md = mp;                           // (a mark, and a doc_tok entry, per PIECE)
                     dc += tkz_popc64(md); pc += tkz_popc64(mp);
                 }
             }
@@ -3612,18 +3622,81 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     stamp();
     {
         const int64_t grand = A.tile_base[nsub];
+        const uint64_t* const marks = TRIM ? A.startbits : A.docbits;
         for (int64_t d = tid; d <= n_docs; d += kThreads) {
             const int64_t pos = d_offs[d];
             if (pos >= total) { A.out_offs[d] = grand; continue; }
             const int64_t sub = pos / kSub, wpos = pos >> 6;
             int64_t ord = A.docord_base[sub];
-            for (int64_t w = sub * (kSub / 64); w < wpos; ++w) ord += tkz_popc64(A.docbits[w]);
-            ord += tkz_popc64(A.docbits[wpos] & tkz_lowmask((int)(pos & 63)));
+            for (int64_t w = sub * (kSub / 64); w < wpos; ++w) ord += tkz_popc64(marks[w]);
+            ord += tkz_popc64(marks[wpos] & tkz_lowmask((int)(pos & 63)));
             A.out_offs[d] = A.tile_base[sub] + P.doc_tok[ord];
         }
     }
     simt::sync();
     stamp();
+    [[maybe_unused]] int64_t trim_kept = 0;
+    if constexpr (TRIM) {
+        // ---- 7. the cut (k_trim_cut's rule over the piece boundaries of the one document), then cut_units (k_trim_gather's second half) ----
+        int64_t* const s_cut = reinterpret_cast<int64_t*>(s_raw);          // [0 .. 2 nwaves): the wavefronts' boundaries; [32 .. 32 + nwaves): their unit counts
+        const int64_t grand = A.tile_base[nsub], m = A.trim_max, need = grand - m;
+        const bool suffix = A.trim_side == 0, whole = grand <= m;
+        // (the boundary at `total` has `grand` in front of it: a text kept whole is cut there for suffix and at byte 0 for prefix; a text that is cut starts
+        //  from "no boundary qualifies": byte 0 for suffix, `total` -- which qualifies, need <= grand -- for prefix)
+        int64_t bpos = suffix == whole ? total : 0, bcnt = suffix == whole ? grand : 0;
+        if (!whole) {
+            for (int64_t w = tid; w < nwords; w += kThreads) {
+                uint64_t mk = A.startbits[w];
+                const int64_t lim = total - (w << 6);                      // (the sentinel bit at `total` is not a start)
+                if (lim < 64) mk &= tkz_lowmask((int)(lim < 0 ? 0 : lim));
+                if (!mk) continue;
+                const int64_t sub = w / (kSub / 64), tb = A.tile_base[sub];
+                int64_t ord = A.docord_base[sub];
+                for (int64_t v = sub * (kSub / 64); v < w; ++v) ord += tkz_popc64(A.startbits[v]);
+                for (; mk; mk &= mk - 1, ++ord) {
+                    const int64_t pos = (w << 6) + tkz_ctz64(mk), cnt = tb + P.doc_tok[ord];
+                    if (suffix) { if (cnt > m) break; if (pos >= bpos) { bpos = pos; bcnt = cnt; } }
+                    else if (cnt >= need) { if (pos < bpos) { bpos = pos; bcnt = cnt; } break; }
+                }
+            }
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int64_t op = tkz_shfl64(bpos, lane ^ d), oc = tkz_shfl64(bcnt, lane ^ d);
+            if (suffix ? op > bpos : op < bpos) { bpos = op; bcnt = oc; }
+        }
+        if (lane == 0) { s_cut[2 * wave] = bpos; s_cut[2 * wave + 1] = bcnt; }
+        simt::sync();
+        for (int k = 0; k < nwaves; ++k) {
+            const int64_t op = s_cut[2 * k], oc = s_cut[2 * k + 1];
+            if (suffix ? op > bpos : op < bpos) { bpos = op; bcnt = oc; }
+        }
+        stamp();
+        // a unit per non-continuation byte and one more per byte >= 0xF0, a quad of [0, cut) a thread; the bytes of the last quad at and behind the cut count
+        // as continuation bytes
+        int units = 0;
+        for (int64_t q = tid; 16 * q < bpos; q += kThreads) {
+            const uint4 v = *reinterpret_cast<const uint4*>(d_bytes + 16 * q);
+            const uint32_t x4[4] = {v.x, v.y, v.z, v.w};
+            for (int j = 0; j < 4; ++j) {
+                const int64_t r = bpos - 16 * q - 4 * j;                   // bytes of this dword in front of the cut
+                if (r <= 0) break;
+                uint32_t x = x4[j];
+                if (r < 4) x = (x & (0xFFFFFFFFu >> (8 * (4 - (int)r)))) | (0x80808080u << (8 * (int)r));
+                units += 4 - tkz_popc32(x & ~(x << 1) & 0x80808080u) + tkz_popc32(x & (x << 1) & (x << 2) & (x << 3) & 0x80808080u);
+            }
+        }
+        int wtot;
+        (void)tkz_wave_scan_sum(units, &wtot);
+        if (lane == 0) s_cut[32 + wave] = wtot;
+        simt::sync();
+        if (tid == 0) {
+            int64_t cu = 0;
+            for (int k = 0; k < nwaves; ++k) cu += s_cut[32 + k];
+            trim_kept = suffix ? bcnt : grand - bcnt;
+            A.h_result[20] = suffix ? 0 : bcnt; A.h_result[21] = trim_kept; A.h_result[22] = bpos; A.h_result[23] = cu;
+        }
+        stamp();
+    }
     if (tid == 0) {
         const int32_t err = P.counters[0]; A.h_result[1] = err; A.h_result[0] = err ? 1 : 0;
         if constexpr (SPECIAL) {
@@ -3636,7 +3709,7 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
         }
         // {n_docs, n_bytes, n_tokens} of this batch on the device, as k_counts3 leaves them on the batch path (a batch that is handed back
         // gets them from there)
-        if (!err) for (int k = 0; k < 2; ++k) if (A.counts3[k]) { A.counts3[k][0] = n_docs; A.counts3[k][1] = total; A.counts3[k][2] = A.tile_base[nsub]; }
+        if (!err) for (int k = 0; k < 2; ++k) if (A.counts3[k]) { A.counts3[k][0] = n_docs; A.counts3[k][1] = total; A.counts3[k][2] = TRIM ? trim_kept : A.tile_base[nsub]; }
     }
 }
 
@@ -3788,7 +3861,9 @@ void launch_ingest(const Launch& L, const uint8_t* h_bytes, int64_t total, uint8
     TKZ_LAUNCH(k_ingest, g < 1 ? 1 : (g > 2048 ? 2048 : g), kThreads, L.stream, h_bytes, total, d_bytes, h_offs, n_offs, d_offs, reinterpret_cast<uint4*>(zero), (zero_bytes + 15) / 16);
 }
 void launch_small(const Launch& L, const TkzTables& T, const EncodeParams& P, const SmallArgs& A) {
-    if (A.n_taken) TKZ_LAUNCH(k_small<true>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+    if (A.trim && A.n_taken) TKZ_LAUNCH((k_small<true, true>), 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+    else if (A.trim) TKZ_LAUNCH((k_small<false, true>), 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+    else if (A.n_taken) TKZ_LAUNCH(k_small<true>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
     else TKZ_LAUNCH(k_small<false>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
 }
 void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_base, int64_t nsub, int32_t* out, int64_t out_cap) {

@@ -346,13 +346,34 @@ class TikTokenizer:
         out = self._trim_batch_device(texts, allowed, max_tokens, N.TRIM_PREFIX)
         return out if out is not None else [self._trim_prefix_host(t, allowed, max_tokens) for t in texts]
 
+    def _trim_one_device(self, text: str, allowed, max_tokens: int, side: int):
+        """ONE text on the device's single-text trim entry (tkz_encode_trim_utf8: one kernel launch for a prompt): (ids, text), or None when the host walk has to
+        do it -- exactly the cases of _trim_batch_device."""
+        if max_tokens < 0:
+            return None
+        plain = not allowed or self._special_re is None
+        if not plain and (self._special_on_host or (self._fffd_literal and _has_lone_surrogate(text))):
+            return None
+        names = set(allowed) if not plain else set()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]           # (registration order = the alternation's)
+        try:
+            ids, _, units = self._encoder.encode_trim(_utf8_like_dotnet(text), index, side, max_tokens)
+        except N.UnsupportedError:
+            self._special_on_host = True
+            return None
+        return ids, self._utf16_prefix(text, units, drop=side == N.TRIM_PREFIX)
+
     def EncodeTrimSuffix(self, text: str, a, b=None):
         """Token ids and the text they cover, cut after the last piece / special token that still fits maxTokenCount."""
-        return self.EncodeTrimSuffixBatch([text], a, b)[0]
+        allowed, max_tokens = self._trim_args(a, b)
+        out = self._trim_one_device(text, allowed, max_tokens, N.TRIM_SUFFIX)
+        return out if out is not None else self._trim_suffix_host(text, allowed, max_tokens)
 
     def EncodeTrimPrefix(self, text: str, a, b=None):
         """Token ids and the text they cover, cut before the first piece boundary that leaves at most maxTokenCount tokens."""
-        return self.EncodeTrimPrefixBatch([text], a, b)[0]
+        allowed, max_tokens = self._trim_args(a, b)
+        out = self._trim_one_device(text, allowed, max_tokens, N.TRIM_PREFIX)
+        return out if out is not None else self._trim_prefix_host(text, allowed, max_tokens)
 
     # the host walk over _piece_items: the fallback of the batch methods
     def _trim_suffix_host(self, text: str, allowed, max_tokens: int):
