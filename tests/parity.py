@@ -1471,13 +1471,17 @@ def random_vocab_bytes(rng, alphabet=b"abc", n_keys=300, max_len=6, rank_step=1,
     return b"".join(base64.b64encode(k) + b" " + str(rank_base + rank_step * i).encode() + b"\n" for i, k in enumerate(keys))
 
 
-def check_random_vocab(lib, O, seed, n_vocabs, lens, n_pieces, max_len=6):
-    """Every merge path (lean lane, arena lane packed and unpacked, whole-wave rounds in the pool) on adversarial rank tables."""
+def check_random_vocab(lib, O, seed, n_vocabs, lens, n_pieces, max_len=6, band_top=None):
+    """Every merge path (lean lane, arena lane packed and unpacked, whole-wave rounds in the pool) on adversarial rank tables.  band_top (the soaks): the sparse
+    table is a band table instead, its largest rank exactly band_top (tests/rank_band_cases.py)."""
     rng = random.Random(seed)
     for vi in range(n_vocabs):
         big = vi % 3 == 2                                        # every third vocabulary: sparse ranks up to ~2^26
         raw = random_vocab_bytes(rng, alphabet=rng.choice([b"ab", b"abc", b"abcd"]), n_keys=rng.choice([20, 100, 400]), max_len=max_len,
                                  rank_step=97_003 if big else 1, rank_base=4_200_000 if big else 0)
+        if big and band_top is not None:
+            import rank_band_cases
+            raw = rank_band_cases.band_table(band_top, seed=seed)
         vocab, ovocab = N.Vocab(raw, lib), O.Vocab(raw)
         enc = N.Encoder(vocab, N.CL100K)
         pcs = [bytes(rng.choice(b"abcd"[:rng.randint(1, 4)]) for _ in range(rng.choice(lens))) for _ in range(n_pieces)]
