@@ -52,6 +52,9 @@ namespace Microsoft.DeepDev
         [DllImport(Lib)] internal static extern unsafe int tkz_encoder_set_special_tokens(IntPtr encoder, int* ids, byte* literalsUtf8, long* literalOffsets, int n);
         [DllImport(Lib)] internal static extern unsafe int tkz_decode_batch(IntPtr encoder, int* ids, long* idOffsets, long nDocs, byte* outBytes, long outCap, long* outOffsets, out long needed);
         [DllImport(Lib)] internal static extern unsafe int tkz_decode_batch_utf16(IntPtr encoder, int* ids, long* idOffsets, long nDocs, char* outUnits, long outCap, long* outOffsets, out long needed);
+        // Decode(int[]) of ONE id list: one kernel launch for up to 32,768 ids (include/tkz.h).  (Like the rest of this file: not compiled here.)
+        [DllImport(Lib)] internal static extern unsafe int tkz_decode_utf16(IntPtr encoder, int* ids, long nIds, char* outUnits, long outCap, out long nOut);
+        [DllImport(Lib)] internal static extern void tkz_encoder_small_decode_calls(IntPtr encoder, out long calls, out long handedBack);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -732,8 +735,29 @@ namespace Microsoft.DeepDev
 
         /// <summary>TikTokenizer.Decode (TikTokenizer.cs:586-604): ids in neither table are dropped; on the device, Encoding.UTF8.GetString (:603)
         /// included -- tkz_decode_batch_utf16 hands back the code units of every document, one U+FFFD per maximal subpart of an ill-formed sequence as
-        /// GetString writes them, and each string is built from its unit range.  The strings are those GetString gives on the bytes of tkz_decode_batch.</summary>
-        public string Decode(int[] tokens) => DecodeBatch(new[] { tokens })[0];
+        /// GetString writes them, and each string is built from its unit range.  The strings are those GetString gives on the bytes of tkz_decode_batch.
+        /// ONE id list goes through tkz_decode_utf16 -- a single kernel launch for up to 32,768 ids -- into a pooled buffer (a ConcurrentBag of char[], as the
+        /// page-locked sets are pooled: netstandard2.0 has no ArrayPool without a package).  A buffer that was too small is dropped, the larger one is kept.</summary>
+        private readonly System.Collections.Concurrent.ConcurrentBag<char[]> decodePool = new System.Collections.Concurrent.ConcurrentBag<char[]>();
+        public unsafe string Decode(int[] tokens)
+        {
+            if (tokens.Length == 0) return string.Empty;
+            int want = Math.Max(256, 8 * tokens.Length);
+            if (!decodePool.TryTake(out char[] units) || units.Length < want) units = new char[want];
+            try
+            {
+                while (true)
+                {
+                    int st; long n;
+                    fixed (int* pi = tokens) fixed (char* pu = units)
+                        st = Tkz.tkz_decode_utf16(encoder, pi, tokens.Length, pu, units.Length, out n);
+                    if (st == -4) { units = new char[checked((int)n)]; continue; }     // TKZ_E_CAPACITY: `n` is the exact size, in code units
+                    Tkz.Check(st);
+                    return new string(units, 0, (int)n);
+                }
+            }
+            finally { if (!disposed) decodePool.Add(units); }
+        }
 
         public unsafe List<string> DecodeBatch(IReadOnlyList<int[]> batches)
         {

@@ -328,6 +328,20 @@ tkz_status tkz_decode_batch_utf16_device(tkz_encoder* e, const int32_t* d_ids, c
                                          uint16_t* d_out_units, int64_t out_cap, int64_t* d_out_offsets, void* hip_stream, int64_t* total_units);
 tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
                                   int64_t* out_offsets, int64_t* needed);
+/* ITokenizer.Decode(int[] tokens) -- ONE id list, as a host calls it after every generation and a streaming host after every few tokens.  The bytes / code units
+ * are exactly those of tkz_decode_batch / tkz_decode_batch_utf16 for the same ids as one document.  A list of at most 32,768 ids that decodes to at most 131,072
+ * bytes runs as ONE kernel launch on page-locked memory (k_dec_small: no copy commands, one wait), counted by tkz_encoder_small_decode_calls; a longer list, one
+ * the kernel hands back (more bytes than that: the second figure of that counter), a device whose LDS per workgroup does not hold the single-launch kernels' and a
+ * call with profiling on take the batch entry's path with identical results.  n_ids == 0: TKZ_OK, *n_out = 0, nothing is launched.  TKZ_E_ARG: a null encoder, a
+ * null n_out, a negative n_ids or out_cap, null ids with n_ids > 0, a null output with out_cap > 0.  out_cap too small: TKZ_E_CAPACITY and the exact required
+ * total in *n_out (bytes / code units), on either route; nothing is promised about the output buffer then. */
+tkz_status tkz_decode_utf8(tkz_encoder* e, const int32_t* ids, int64_t n_ids, uint8_t* out_bytes, int64_t out_cap, int64_t* n_out);
+tkz_status tkz_decode_utf16(tkz_encoder* e, const int32_t* ids, int64_t n_ids, uint16_t* out_units, int64_t out_cap, int64_t* n_out);
+/* Informational: how many single decode calls took the launch, and how many of those the kernel handed back to the batch path.  (Its own counter: the figures
+ * of tkz_encoder_small_path_calls count encode calls only.) */
+void tkz_encoder_small_decode_calls(const tkz_encoder* e, int64_t* calls, int64_t* handed_back);
+/* development: the shader-clock stamps the last k_dec_small left at the end of each of its phases (16 values, 0 where the form has no such phase; returns how many) */
+int32_t tkz_encoder_small_decode_phases(const tkz_encoder* e, int64_t* clocks16);
 
 /* ---- token shard files -------------------------------------------------------
  * The on-disk form of one rank's EncodeBatch result: a 64-byte header ("TKZSHRD1", version, n_docs, n_tokens, doc_base,

@@ -462,11 +462,12 @@ public:
     std::vector<std::string> DecodeBatch(const std::vector<std::vector<int32_t>>& batches) const {
         return decode_batch<std::string, uint8_t>(batches, 8, tkz_decode_batch);
     }
-    std::string Decode(const std::vector<int32_t>& ids) const { return DecodeBatch({ids})[0]; }
+    // (ONE id list: tkz_decode_utf8 / _utf16, a single kernel launch for up to 32,768 ids)
+    std::string Decode(const std::vector<int32_t>& ids) const { return decode_one<std::string, uint8_t>(ids, 8, tkz_decode_utf8); }
     std::vector<std::u16string> DecodeBatchUtf16(const std::vector<std::vector<int32_t>>& batches) const {
         return decode_batch<std::u16string, uint16_t>(batches, 8, tkz_decode_batch_utf16);
     }
-    std::u16string DecodeUtf16(const std::vector<int32_t>& ids) const { return DecodeBatchUtf16({ids})[0]; }
+    std::u16string DecodeUtf16(const std::vector<int32_t>& ids) const { return decode_one<std::u16string, uint16_t>(ids, 8, tkz_decode_utf16); }
     void Reserve(int64_t max_bytes, int64_t max_docs) { check(tkz_encoder_reserve(enc_, max_bytes, max_docs)); }
     // The split is whatever the HOST's regex engine makes of the pattern (TikTokenizer.cs:77 compiles it in the running process).  A host on another
     // runtime than net6.0 hands its Unicode classification over (classes[cp] in 0..8 for cp < n: 65536 code units or 1114112 code points; nullptr:
@@ -495,6 +496,18 @@ private:
         for (size_t d = 0; d < batches.size(); ++d)
             res[d].assign(reinterpret_cast<const typename Str::value_type*>(out.data()) + ooff[d], static_cast<size_t>(ooff[d + 1] - ooff[d]));
         return res;
+    }
+    template <class Str, class Elem, class Entry>
+    Str decode_one(const std::vector<int32_t>& ids, size_t per_id, Entry entry) const {
+        std::vector<Elem> out(ids.size() * per_id + 16);
+        int64_t n = 0;
+        tkz_status st = entry(enc_, ids.data(), static_cast<int64_t>(ids.size()), out.data(), static_cast<int64_t>(out.size()), &n);
+        if (st == TKZ_E_CAPACITY) {
+            out.resize(static_cast<size_t>(n));
+            st = entry(enc_, ids.data(), static_cast<int64_t>(ids.size()), out.data(), static_cast<int64_t>(out.size()), &n);
+        }
+        check(st);
+        return Str(reinterpret_cast<const typename Str::value_type*>(out.data()), static_cast<size_t>(n));
     }
     // EncodeInternal + FindNextSpecialToken (TikTokenizer.cs:141-170,230-241): plain segments and special literals in order
     std::vector<Segment> segments(const std::string& text, const std::vector<std::string>& allowedSpecial) const {

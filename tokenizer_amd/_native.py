@@ -161,6 +161,11 @@ class Library:
         L.tkz_decode_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
         L.tkz_decode_batch_utf16_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, pi64]
         L.tkz_decode_batch_utf16.argtypes = [vp, vp, vp, i64, vp, i64, vp, pi64]
+        L.tkz_decode_utf8.argtypes = [vp, vp, i64, vp, i64, pi64]
+        L.tkz_decode_utf16.argtypes = [vp, vp, i64, vp, i64, pi64]
+        L.tkz_encoder_small_decode_calls.argtypes = [vp, pi64, pi64]
+        L.tkz_encoder_small_decode_calls.restype = None
+        L.tkz_encoder_small_decode_phases.argtypes = [vp, vp]
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -324,6 +329,18 @@ class Encoder:
         """Shader-clock stamps at the end of the phases of the last single-launch kernel (development)."""
         a = np.zeros(16, np.int64)
         n = self.lib.L.tkz_encoder_small_path_phases(self._h, a.ctypes.data)
+        return a[:n].tolist()
+
+    def small_decode_calls(self):
+        """(single decode calls that took the launch of k_dec_small, how many of those it handed back to the batch path)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self.lib.L.tkz_encoder_small_decode_calls(self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def small_decode_phases(self):
+        """Shader-clock stamps at the end of the phases of the last k_dec_small (development)."""
+        a = np.zeros(16, np.int64)
+        n = self.lib.L.tkz_encoder_small_decode_phases(self._h, a.ctypes.data)
         return a[:n].tolist()
 
     def pretok_leftovers(self):
@@ -677,6 +694,27 @@ class Encoder:
                 continue
             self.lib.check(st)
             return out[:needed.value], ooff
+
+    def _decode_one(self, fn, dtype, ids, out_cap):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        cap = out_cap if out_cap is not None else max(16, 8 * len(ids))
+        while True:
+            out = np.empty(max(1, cap), dtype)
+            n = C.c_int64(0)
+            st = fn(self._h, _ptr(ids) if len(ids) else None, len(ids), _ptr(out), cap, C.byref(n))
+            if st == E_CAPACITY and out_cap is None:
+                cap = n.value
+                continue
+            self.lib.check(st)
+            return out[:n.value]
+
+    def decode(self, ids: np.ndarray, out_cap=None):
+        """Decode of ONE id list (tkz_decode_utf8: a single launch for a list of up to 32,768 ids): bytes uint8[total]."""
+        return self._decode_one(self.lib.L.tkz_decode_utf8, np.uint8, ids, out_cap)
+
+    def decode_utf16(self, ids: np.ndarray, out_cap=None):
+        """The same to UTF-16 (tkz_decode_utf16): units uint16[total]."""
+        return self._decode_one(self.lib.L.tkz_decode_utf16, np.uint16, ids, out_cap)
 
     def decode_batch_utf16_device(self, d_ids, d_id_offsets, n_docs, total_ids, d_out, out_cap, d_out_offsets, stream=0):
         tot = C.c_int64(0)

@@ -135,6 +135,11 @@ struct DecodeUtf16Bufs {   // Decode to UTF-16: the decoded bytes, their documen
     DevBuf d8_bytes, d8_boffs, d8_docbits, d8_grp, d8_tsum, d8_tbase, d8_bsum, d8_units;
     void release() { release_each({&d8_bytes, &d8_boffs, &d8_docbits, &d8_grp, &d8_tsum, &d8_tbase, &d8_bsum, &d8_units}); }
 };
+struct DecodeSmallBufs {   // Decode of ONE id list in a single launch (k_dec_small): the page-locked block -- ids | bytes or units | result record --, and for the
+    // UTF-16 form the decoded bytes and their start bitmap
+    uint8_t* h_dsmall = nullptr; DevBuf ds_bytes, ds_docbits;
+    void release() { release_each({&ds_bytes, &ds_docbits}); if (h_dsmall) (void)hipHostFree(h_dsmall); h_dsmall = nullptr; }
+};
 struct PieceBufs {   // piece-granular entry point: piece byte offsets, token offsets, first piece of every document
     DevBuf p_boffs, p_toffs, p_docp;
     void release() { release_each({&p_boffs, &p_toffs, &p_docp}); }
@@ -199,7 +204,7 @@ struct tkz_vocab { tkz::Vocab v; };
 // call, so host threads sharing one encoder run concurrently, each on its own workspace and streams ("one encoder
 // usable from many host threads") -- the reference's instance is likewise safe to share (its only shared mutable state, the LRU
 // memo, is locked: LRUCache.cs:61,99).
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, PieceBufs, TrimBufs {
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -232,6 +237,8 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Piec
     hipStream_t st_small = nullptr;        // (non-blocking: a small call never waits for another thread's batch on the legacy default stream)
     std::atomic<int64_t> small_calls{0}, small_fallbacks{0};   // (read by tkz_encoder_small_path_calls from other threads)
     int64_t small_clocks[16] = {};         // the phase stamps of the last single-launch call, copied out after its synchronisation
+    std::atomic<int64_t> dsmall_calls{0}, dsmall_fallbacks{0};   // the same for k_dec_small (tkz_encoder_small_decode_calls)
+    int64_t dsmall_clocks[16] = {};
     hipStream_t st_compute = nullptr, st_in = nullptr, st_out = nullptr;   // the host-buffer entry points: kernels / uploads / downloads
     hipEvent_t ev_in[2] = {}, ev_out[3] = {};
     tkz::SdmaSignal sig_out[3], sig_outoffs[3];   // downloads on a copy engine of their own (tkz_sdma.h): the completion signal of each staging set
@@ -246,7 +253,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Piec
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); PieceBufs::release(); TrimBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -2633,6 +2640,98 @@ tkz_status tkz_decode_batch(tkz_encoder* e, const int32_t* ids, const int64_t* i
 tkz_status tkz_decode_batch_utf16(tkz_encoder* e, const int32_t* ids, const int64_t* id_offsets, int64_t n_docs, uint16_t* out_units, int64_t out_cap,
                                   int64_t* out_offsets, int64_t* needed) {
     return decode_host(e, ids, id_offsets, n_docs, out_units, out_cap, out_offsets, needed, true);
+}
+
+// ---- Decode of ONE id list in a single launch (k_dec_small) -----------------------------------------------------------------------------------
+// ITokenizer.Decode(int[]) through the batch entries is two blocking uploads, a dozen launches, two waits and two blocking downloads whatever the size
+// (decode_host + decode_utf16_device).  A list of at most kDecSmallRouteIds ids goes through ONE launch instead, as encode_small does it for a prompt: the ids
+// are memcpy'd into a page-locked block, k_dec_small (one workgroup, all phases) reads them from there and writes the bytes or the code units and a result
+// record back into it, one stream synchronisation, memcpy out.  The entry is validate (check_decode_one) -> the launch (decode_small) -> fetch
+// (fetch_decode_small); a list the launch does not take, or hands back, is decode_host's with one document.
+namespace {
+constexpr size_t kDecSmallOffIds = 0, kDecSmallOffOut = (size_t)tkz::kDecSmallMaxIds * 4, kDecSmallOffRes = kDecSmallOffOut + (size_t)tkz::kDecSmallMaxBytes * 2,
+                 kDecSmallBlock = kDecSmallOffRes + 256;
+tkz_status check_decode_one(tkz_encoder* e, DeviceScope& scope, const int32_t* ids, int64_t n_ids, const void* out, int64_t out_cap, int64_t* n_out) {
+    TKZ_TRY(check_encoder(e, scope));
+    if (!n_out) return fail(TKZ_E_ARG, "null n_out");
+    *n_out = 0;
+    if (n_ids < 0 || out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    if (n_ids > 0 && !ids) return fail(TKZ_E_ARG, "null ids");
+    if (out_cap > 0 && !out) return fail(TKZ_E_ARG, "null buffer");
+    return TKZ_OK;
+}
+// Returns TKZ_OK with *handled = false when the kernel hands the list back (it decodes to more than kDecSmallMaxBytes bytes): the caller takes the batch path.
+tkz_status decode_small(tkz_encoder* e, Workspace* ws, const int32_t* ids, int64_t n_ids, bool utf16, int64_t* n_items, bool* handled) {
+    using namespace tkz;
+    *handled = false;
+    int64_t* acc = &ws->bytes_allocated;
+    if (utf16) {
+        HIP_TRY(ws->ds_bytes.ensure((size_t)kDecSmallMaxBytes + 64, acc));
+        HIP_TRY(ws->ds_docbits.ensure((size_t)(kDecSmallMaxBytes / 64 + 1 + 8) * 8, acc));
+    }
+    if (!ws->h_dsmall) HIP_TRY(hipHostMalloc((void**)&ws->h_dsmall, kDecSmallBlock, 0));
+    if (!ws->st_small) HIP_TRY(hipStreamCreateWithFlags(&ws->st_small, hipStreamNonBlocking));
+    uint8_t* H = ws->h_dsmall;
+    memcpy(H + kDecSmallOffIds, ids, (size_t)n_ids * 4);
+    int64_t* h_res = reinterpret_cast<int64_t*>(H + kDecSmallOffRes);
+    memset(h_res, 0, 256);
+    h_res[0] = -1;
+    DecSmallArgs A{};
+    A.h_ids = reinterpret_cast<const int32_t*>(H + kDecSmallOffIds); A.n_ids = n_ids;
+    A.h_out = H + kDecSmallOffOut; A.h_result = h_res; A.utf16 = utf16 ? 1 : 0;
+    A.d_bytes = utf16 ? ws->ds_bytes.as<uint8_t>() : nullptr; A.d_docbits = utf16 ? ws->ds_docbits.as<uint64_t>() : nullptr;
+    TkzDecodeTable D;
+    { std::lock_guard<std::mutex> lock(e->mu); D = e->D; }
+    launch_dec_small(Launch{ws->st_small, nullptr, ws}, D, A);
+    HIP_TRY(hipStreamSynchronize(ws->st_small));
+    HIP_TRY(hipGetLastError());
+    ws->dsmall_calls.fetch_add(1, std::memory_order_relaxed);
+    { std::lock_guard<std::mutex> lock(e->mu); memcpy(ws->dsmall_clocks, h_res + 4, sizeof ws->dsmall_clocks); }
+    if (h_res[0] < 0) return fail(TKZ_E_DEVICE, "k_dec_small left no result record");      // (the host's -1 is still there: the launch did not run to its end)
+    if (h_res[0] != 0) { ws->dsmall_fallbacks.fetch_add(1, std::memory_order_relaxed); return TKZ_OK; }          // (handled stays false)
+    *n_items = utf16 ? h_res[2] : h_res[1];
+    *handled = true;
+    return TKZ_OK;
+}
+tkz_status fetch_decode_small(Workspace* ws, void* out, int64_t out_cap, int64_t n_items, bool utf16) {
+    if (n_items > out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+    if (n_items) memcpy(out, ws->h_dsmall + kDecSmallOffOut, (size_t)n_items * (utf16 ? 2 : 1));
+    return TKZ_OK;
+}
+tkz_status decode_one(tkz_encoder* e, const int32_t* ids, int64_t n_ids, void* out, int64_t out_cap, int64_t* n_out, bool utf16) {
+    DeviceScope scope;
+    TKZ_TRY(check_decode_one(e, scope, ids, n_ids, out, out_cap, n_out));
+    if (n_ids == 0) return TKZ_OK;
+    if (n_ids <= tkz::kDecSmallRouteIds && e->small_ok && !e->profiling) {
+        Lease lease(e);
+        bool handled = false;
+        TKZ_TRY(decode_small(e, lease.ws, ids, n_ids, utf16, n_out, &handled));
+        if (handled) return fetch_decode_small(lease.ws, out, out_cap, *n_out, utf16);
+    }
+    const int64_t id_offs[2] = {0, n_ids};
+    int64_t out_offs[2] = {0, 0};
+    return decode_host(e, ids, id_offs, 1, out, out_cap, out_offs, n_out, utf16);
+}
+}  // namespace
+
+tkz_status tkz_decode_utf8(tkz_encoder* e, const int32_t* ids, int64_t n_ids, uint8_t* out_bytes, int64_t out_cap, int64_t* n_out) {
+    return decode_one(e, ids, n_ids, out_bytes, out_cap, n_out, false);
+}
+tkz_status tkz_decode_utf16(tkz_encoder* e, const int32_t* ids, int64_t n_ids, uint16_t* out_units, int64_t out_cap, int64_t* n_out) {
+    return decode_one(e, ids, n_ids, out_units, out_cap, n_out, true);
+}
+void tkz_encoder_small_decode_calls(const tkz_encoder* e, int64_t* calls, int64_t* handed_back) {
+    int64_t c = 0, f = 0;
+    if (e) { tkz_encoder* m = const_cast<tkz_encoder*>(e); std::lock_guard<std::mutex> lock(m->mu); for (Workspace* w : e->pool) { c += w->dsmall_calls; f += w->dsmall_fallbacks; } }
+    if (calls) *calls = c;
+    if (handed_back) *handed_back = f;
+}
+int32_t tkz_encoder_small_decode_phases(const tkz_encoder* e, int64_t* clocks16) {       // (the first workspace that has made such a call)
+    if (!e || !clocks16) return 0;
+    tkz_encoder* m = const_cast<tkz_encoder*>(e);
+    std::lock_guard<std::mutex> lock(m->mu);
+    for (Workspace* w : e->pool) if (w->h_dsmall) { memcpy(clocks16, w->dsmall_clocks, 16 * 8); return 16; }
+    return 0;
 }
 
 tkz_status tkz_encoder_set_option(tkz_encoder* e, int32_t option, int64_t value) {

@@ -141,6 +141,27 @@ struct SmallArgs {
     int32_t trim; int32_t trim_side; int64_t trim_max;
 };
 
+// k_dec_small: one launch for Decode of ONE id list (tkz_kernels.hip).  The ids come from, and the bytes (UTF-8 form) or code units (UTF-16 form) go to,
+// page-locked host memory.  The two figures are what the page-locked block holds, not tuned thresholds: a list of more ids takes the batch path, and so does one the
+// kernel hands back because it decodes to more bytes.  (Its static LDS: 81 KB, inside what the host already checks for k_small, kSmallLdsBytesNeeded.)
+constexpr int kDecSmallMaxIds = 32768, kDecSmallMaxBytes = 131072;
+// ... and the route threshold on the id count, measured (profiles/small_decode/README.md): the launch is ahead of the batch path at every size up to the capacity
+// (development: -DTKZ_SMALL_DECODE_MAX_IDS=n builds a library that takes the launch up to n ids)
+#ifndef TKZ_SMALL_DECODE_MAX_IDS
+#define TKZ_SMALL_DECODE_MAX_IDS 32768
+#endif
+constexpr int kDecSmallRouteIds = TKZ_SMALL_DECODE_MAX_IDS;
+static_assert(kDecSmallRouteIds >= 0 && kDecSmallRouteIds <= kDecSmallMaxIds, "the route threshold lies inside the block's capacity");
+struct DecSmallArgs {
+    const int32_t* h_ids; int64_t n_ids;                    // the id list, page-locked host memory (1 .. kDecSmallMaxIds)
+    void* h_out;                                            // page-locked: kDecSmallMaxBytes bytes (UTF-8 form) or as many code units (UTF-16 form)
+    int64_t* h_result;                                      // [0] status (0 done, 1 take the batch path: more than kDecSmallMaxBytes bytes), [1] byte total, [2] unit total
+                                                            // (UTF-16 form), [4..19] clock stamps
+    int32_t utf16;                                          // the output form
+    uint8_t* d_bytes; uint64_t* d_docbits;                  // UTF-16 form only, workspace: the decoded bytes (kDecSmallMaxBytes + 64) and their document-start bitmap
+                                                            // (kDecSmallMaxBytes / 64 + 1 words: bit 0 and the sentinel at the total)
+};
+
 typedef void (*KernelHook)(void* ctx, int kernel_id, int phase /*0 before, 1 after*/, hipStream_t s);
 // side / side2 / ev_fork / ev_join / ev_join2: all null, or two more streams and three events of the workspace -- launch_encode runs k_merge_long_q and k_merge_coop there,
 // beside k_merge_short on `stream` (a large batch only: EncodeParams::tc_atomic says that the token counts of the sub-tiles are summed with atomics from zero)
@@ -157,6 +178,7 @@ void launch_ingest(const Launch& L, const uint8_t* h_bytes, int64_t total, uint8
 void launch_probe_sample(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsample);
 void launch_encode(const Launch& L, const TkzTables& T, const EncodeParams& P, int64_t nsub);
 void launch_small(const Launch& L, const TkzTables& T, const EncodeParams& P, const SmallArgs& A);
+void launch_dec_small(const Launch& L, const TkzDecodeTable& D, const DecSmallArgs& A);
 // exclusive scan int32 -> int64 (+ grand total); kid = profiling id of the bracket, or -1
 // round_to (a power of two): every count is rounded up to a multiple of it before it is summed
 void launch_scan(const Launch& L, const int32_t* tile_count, int64_t ntiles, int64_t* bsum, int64_t* tile_base, int64_t* grand, int kid, int round_to = 1);

@@ -3289,6 +3289,20 @@ TKZ_KERNEL(256) void k_u8_len(const uint8_t* bytes, int64_t total, const uint64_
     grp_prefix[tile * 64 + simt::lane()] = pre;
     if (simt::lane() == 0) tile_sum[tile] = tot;
 }
+// the units of this lane's group into the wavefront's stage, from `pos` -- the lane's exclusive prefix -- on (k_u8_write, k_dec_small)
+TKZ_DEV void tkz_u8_stage(const TkzU8Lane& L, int64_t total, int64_t tile, int pos, uint16_t* st) {
+    const int64_t p0 = tile * kU8Tile + (int64_t)simt::lane() * kU8Lane;
+#pragma unroll
+    for (int k = 0; k < kU8Lane; ++k) {
+        uint32_t u0, u1;
+        if (p0 + k < total) {
+            const int n = tkz_u8_item(L.b[k], L.b[k + 1], L.b[k + 2], L.b[k + 3], L.b[k + 4], L.b[k + 5], L.b[k + 6], L.ds >> k, &u0, &u1);
+            if (n >= 1) st[pos] = (uint16_t)u0;
+            if (n == 2) st[pos + 1] = (uint16_t)u1;
+            pos += n;
+        }
+    }
+}
 TKZ_KERNEL(256) void k_u8_write(const uint8_t* bytes, int64_t total, const uint64_t* docbits, int64_t nwords, int64_t ntiles, const int64_t* tile_base,
                                 uint16_t* out, int64_t out_cap) {
     TKZ_SHARED uint16_t s_stage[kThreads / 64][kU8Stage];
@@ -3300,18 +3314,8 @@ TKZ_KERNEL(256) void k_u8_write(const uint8_t* bytes, int64_t total, const uint6
     int pos = tkz_wave_scan_sum(sum, &tot);
     const int64_t base = tile_base[tile];
     if (base + tot > out_cap || tot > kU8Stage) return;      // (the host reports TKZ_E_CAPACITY from the grand total)
-    const int64_t p0 = tile * kU8Tile + (int64_t)simt::lane() * kU8Lane;
     uint16_t* st = s_stage[simt::wave()];
-#pragma unroll
-    for (int k = 0; k < kU8Lane; ++k) {
-        uint32_t u0, u1;
-        if (p0 + k < total) {
-            const int n = tkz_u8_item(L.b[k], L.b[k + 1], L.b[k + 2], L.b[k + 3], L.b[k + 4], L.b[k + 5], L.b[k + 6], L.ds >> k, &u0, &u1);
-            if (n >= 1) st[pos] = (uint16_t)u0;
-            if (n == 2) st[pos + 1] = (uint16_t)u1;
-            pos += n;
-        }
-    }
+    tkz_u8_stage(L, total, tile, pos, st);
     (void)simt::ballot(true);          // (the staging area is private to the wavefront: its LDS accesses are ordered, no barrier)
     uint16_t* dst = out + base;
     for (int i = simt::lane(); i < tot; i += 64) dst[i] = st[i];
@@ -3713,6 +3717,141 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// k_dec_small: Decode of ONE id list in ONE kernel, one workgroup (ITokenizer.Decode after a generation, TikTokenizer.cs:586-604; a streaming host calls it
+// every few tokens).  The batch entries are two uploads, ~12 launches, two waits and two downloads whatever the size; here the phases are the same device
+// functions (tkz_dec_lane, tkz_u8_lane, tkz_u8_stage), run one after the other by the wavefronts of one workgroup with workgroup barriers between them -- no
+// atomics, nothing spins on memory.  The ids are read straight from page-locked host memory and the result and its record go straight back into it.
+//   1  lengths: the 1024-id tiles dealt out to the wavefronts round-robin (k_dec_len); the tile sums into LDS
+//   2  their exclusive scan in LDS (the first wavefront); more than kDecSmallMaxBytes bytes: status 1, the host takes the batch path
+//   3  the bytes, staged per tile in LDS and stored coalesced; a tile of more than kDecSmallStage bytes is copied directly (k_dec_write).  A wavefront's first
+//      tile keeps its table entries in registers from phase 1.  UTF-8 form: into the page-locked block, done.
+//   UTF-16 form (Encoding.UTF8.GetString, the k_u8_* family): phase 3 writes the bytes to the workspace, with the one document's start bitmap -- bit 0 and the
+//   sentinel at the total, nothing else -- beside them                                                                        | barrier
+//   4  unit counts per 1024-byte tile (k_u8_len), 5 their scan, 6 the units staged in LDS and stored coalesced into the block (k_u8_write)
+// LDS: kDecSmallWaves stages of kDecSmallStage bytes (sixteen of k_dec_write's 12 KiB would be 192 KB; 5 KiB holds a tile of English text, ~4.4 bytes an id, and
+// phase 6's kU8Stage units) + the sums and bases of up to 128 tiles: 82,960 bytes a workgroup in the compiler's report, inside kSmallLdsBytesNeeded, which the host has checked against the device.
+// -------------------------------------------------------------------------------------------------
+constexpr int kDecSmallWaves = 16;         // the workgroup is 256 threads for up to 4 id tiles, 1024 beyond
+constexpr int kDecSmallStage = 5120;       // bytes of LDS stage per wavefront
+constexpr int kDecSmallTiles = kDecSmallMaxBytes / kU8Tile;       // the most tiles either scan sees
+static_assert(kDecSmallMaxIds % kDecTile == 0 && kDecSmallMaxIds / kDecTile <= kDecSmallTiles && kDecSmallMaxBytes % kU8Tile == 0, "whole tiles; one scan buffer serves both families");
+static_assert(kDecSmallStage % 16 == 0 && kU8Stage * 2 <= kDecSmallStage, "a wavefront's stage holds the units of a byte tile as well");
+static_assert(kDecSmallWaves * kDecSmallStage + (2 * kDecSmallTiles + 1) * 4 <= kSmallLdsBytesNeeded, "tkz_kernels.h: what the host checks against the device's LDS per workgroup");
+// exclusive scan of n <= kDecSmallTiles tile sums in LDS by the first wavefront, the total in s_base[n]; a workgroup barrier on either side
+TKZ_DEV void tkz_dec_small_scan(const int* s_sum, int* s_base, int n) {
+    simt::sync();
+    if (simt::wave() == 0) {
+        int carry = 0;
+        for (int q0 = 0; q0 < n; q0 += 64) {
+            const int q = q0 + simt::lane();
+            int tot;
+            const int pre = carry + tkz_wave_scan_sum(q < n ? s_sum[q] : 0, &tot);
+            if (q < n) s_base[q] = pre;
+            carry += tot;
+        }
+        if (simt::lane() == 0) s_base[n] = carry;
+    }
+    simt::sync();
+}
+template <bool UTF16>
+TKZ_KERNEL(1024) void k_dec_small(TkzDecodeTable D, DecSmallArgs A) {
+    TKZ_SHARED uint4 s_stage[kDecSmallWaves * kDecSmallStage / 16];
+    TKZ_SHARED int s_sum[kDecSmallTiles], s_base[kDecSmallTiles + 1];
+    const int tid = simt::tid(), lane = simt::lane(), wave = simt::wave();
+    const int nthreads = simt::nthreads(), nwaves = nthreads >> 6;
+    uint8_t* const st = reinterpret_cast<uint8_t*>(s_stage) + wave * kDecSmallStage;       // (private to the wavefront: its LDS accesses are ordered, no barrier)
+    int stamp_i = 4;                                              // h_result[4..]: the shader clock at the end of every phase (thread 0), as k_small leaves them
+    auto stamp = [&]() { if (tid == 0 && stamp_i < 20) A.h_result[stamp_i] = (int64_t)simt::clock(); ++stamp_i; };
+    stamp();
+    const int64_t n_ids = A.n_ids;
+    const int ntiles = (int)((n_ids + kDecTile - 1) / kDecTile);
+    // ---- 1. byte length of every id (k_dec_len) ----
+    TkzDecLane L0 = {};
+    int sum0 = 0;
+    for (int t = wave; t < ntiles; t += nwaves) {
+        TkzDecLane L;
+        const int sum = tkz_dec_lane(D, A.h_ids, n_ids, t, &L);
+        // (an entry longer than the block -- only a registered literal can be -- hands the list back before any sum of such lengths is formed: the sums below stay
+        //  far inside an int, and phase 3 only ever sees tiles whose bytes end inside the block)
+        bool big = false;
+#pragma unroll
+        for (int k = 0; k < kDecLane; ++k) big = big || L.len[k] > (uint32_t)kDecSmallMaxBytes;
+        const bool anybig = simt::ballot(big) != 0;
+        int tot;
+        (void)tkz_wave_scan_sum(anybig ? 0 : sum, &tot);
+        if (anybig || tot > kDecSmallMaxBytes) tot = kDecSmallMaxBytes + 1;
+        if (lane == 0) s_sum[t] = tot;
+        if (t == wave) { L0 = L; sum0 = sum; }
+    }
+    stamp();
+    // ---- 2. scan of the tile sums ----
+    tkz_dec_small_scan(s_sum, s_base, ntiles);
+    const int nbytes = s_base[ntiles];
+    if (nbytes > kDecSmallMaxBytes) {                             // (workgroup-uniform) more than the block holds: the batch path's business
+        if (tid == 0) { A.h_result[1] = nbytes; A.h_result[0] = 1; }
+        return;
+    }
+    stamp();
+    // ---- 3. the bytes (k_dec_write) ----
+    uint8_t* const out8 = UTF16 ? A.d_bytes : static_cast<uint8_t*>(A.h_out);
+    for (int t = wave; t < ntiles; t += nwaves) {
+        TkzDecLane L;
+        int sum;
+        if (t == wave) { L = L0; sum = sum0; } else sum = tkz_dec_lane(D, A.h_ids, n_ids, t, &L);
+        int tot;
+        int pos = tkz_wave_scan_sum(sum, &tot);
+        uint8_t* const dst = out8 + s_base[t];                    // (s_base[t] + tot <= nbytes <= kDecSmallMaxBytes)
+        if (tot <= kDecSmallStage) {
+#pragma unroll 1
+            for (int k = 0; k < kDecLane; ++k) { const uint8_t* src = D.blob + L.off[k]; for (uint32_t j = 0; j < L.len[k]; ++j) st[pos + (int)j] = src[j]; pos += (int)L.len[k]; }
+            (void)simt::ballot(true);
+            for (int i = lane; i < tot; i += 64) dst[i] = st[i];
+            (void)simt::ballot(true);                             // (the wavefront's next tile stages behind these reads)
+        } else {
+#pragma unroll 1
+            for (int k = 0; k < kDecLane; ++k) { const uint8_t* src = D.blob + L.off[k]; for (uint32_t j = 0; j < L.len[k]; ++j) dst[pos + (int)j] = src[j]; pos += (int)L.len[k]; }
+        }
+    }
+    if constexpr (UTF16) {
+        const int64_t nwords = nbytes / 64 + 1;
+        for (int64_t w = tid; w < nwords; w += nthreads)
+            A.d_docbits[w] = (w == 0 ? 1ull : 0ull) | (w == (nbytes >> 6) ? 1ull << (nbytes & 63) : 0ull);
+        simt::sync();            // the bytes and the bitmap: plain stores of this workgroup, read by it behind the barrier (as k_small's phases are ordered)
+        stamp();
+        // ---- 4. units of every byte (k_u8_len) ----
+        const int nt8 = (nbytes + kU8Tile - 1) / kU8Tile;
+        for (int t = wave; t < nt8; t += nwaves) {
+            TkzU8Lane U;
+            const int sum = tkz_u8_lane(A.d_bytes, nbytes, A.d_docbits, nwords, t, &U);
+            int tot;
+            (void)tkz_wave_scan_sum(sum, &tot);
+            if (lane == 0) s_sum[t] = tot;
+        }
+        stamp();
+        // ---- 5. scan, 6. the units (k_u8_write) ----
+        tkz_dec_small_scan(s_sum, s_base, nt8);
+        stamp();
+        uint16_t* const out16 = static_cast<uint16_t*>(A.h_out);
+        uint16_t* const st16 = reinterpret_cast<uint16_t*>(st);
+        for (int t = wave; t < nt8; t += nwaves) {
+            TkzU8Lane U;
+            const int sum = tkz_u8_lane(A.d_bytes, nbytes, A.d_docbits, nwords, t, &U);
+            int tot;
+            const int pos = tkz_wave_scan_sum(sum, &tot);
+            if (tot > kU8Stage) continue;                         // (cannot be: a tile yields at most kU8Tile + 1 units)
+            tkz_u8_stage(U, nbytes, t, pos, st16);
+            (void)simt::ballot(true);
+            uint16_t* const dst = out16 + s_base[t];              // (units <= bytes <= kDecSmallMaxBytes, the block's capacity in units)
+            for (int i = lane; i < tot; i += 64) dst[i] = st16[i];
+            (void)simt::ballot(true);
+        }
+        stamp();
+        if (tid == 0) A.h_result[2] = s_base[nt8];
+    } else stamp();
+    if (tid == 0) { A.h_result[1] = nbytes; A.h_result[0] = 0; }
+}
+
 // =================================================================================================
 // launchers
 // =================================================================================================
@@ -3865,6 +4004,11 @@ void launch_small(const Launch& L, const TkzTables& T, const EncodeParams& P, co
     else if (A.trim) TKZ_LAUNCH((k_small<false, true>), 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
     else if (A.n_taken) TKZ_LAUNCH(k_small<true>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
     else TKZ_LAUNCH(k_small<false>, 1, P.nsub <= 4 ? 256 : 1024, L.stream, T, P, A);
+}
+void launch_dec_small(const Launch& L, const TkzDecodeTable& D, const DecSmallArgs& A) {
+    const int block = A.n_ids <= 4 * kDecTile ? 256 : 1024;
+    if (A.utf16) TKZ_LAUNCH(k_dec_small<true>, 1, block, L.stream, D, A);
+    else TKZ_LAUNCH(k_dec_small<false>, 1, block, L.stream, D, A);
 }
 void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_base, int64_t nsub, int32_t* out, int64_t out_cap) {
     hook(L, K_GATHER, 0);

@@ -413,8 +413,13 @@ class TikTokenizer:
 
     def Decode(self, tokens: Sequence[int]) -> str:
         """TikTokenizer.cs:586-604: ids that are neither in the vocabulary nor special tokens are dropped; the bytes are decoded as
-        UTF-8 (Encoding.UTF8.GetString: malformed sequences become U+FFFD)."""
-        return self.DecodeBatch([tokens])[0]
+        UTF-8 (Encoding.UTF8.GetString: malformed sequences become U+FFFD).  One id list is one kernel launch (tkz_decode_utf8)."""
+        return self._encoder.decode(self._int32_ids(tokens)).tobytes().decode("utf-8", "replace")
+
+    @staticmethod
+    def _int32_ids(tokens):
+        flat = np.asarray(list(tokens), dtype=np.int64)
+        return np.where((flat < -2**31) | (flat >= 2**31), -1, flat).astype(np.int32)      # (an id outside int is in no table)
 
     def DecodeBatch(self, batches: Sequence[Sequence[int]]) -> List[str]:
         """Decode for a batch, on the device (tkz_decode_batch: id -> bytes gather through the decoder table + scan)."""
@@ -427,7 +432,7 @@ class TikTokenizer:
 
     def DecodeUtf16(self, tokens: Sequence[int]) -> str:
         """Decode with Encoding.UTF8.GetString done on the device as well: the same string as Decode."""
-        return self.DecodeBatchUtf16([tokens])[0]
+        return self._encoder.decode_utf16(self._int32_ids(tokens)).astype("<u2", copy=False).tobytes().decode("utf-16-le")
 
     def DecodeBatchUtf16(self, batches: Sequence[Sequence[int]]) -> List[str]:
         """DecodeBatch through tkz_decode_batch_utf16: the device hands back the UTF-16 code units of every document (malformed sequences already U+FFFD, one
