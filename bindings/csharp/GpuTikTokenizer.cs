@@ -55,6 +55,11 @@ namespace Microsoft.DeepDev
         // Decode(int[]) of ONE id list: one kernel launch for up to 32,768 ids (include/tkz.h).  (Like the rest of this file: not compiled here.)
         [DllImport(Lib)] internal static extern unsafe int tkz_decode_utf16(IntPtr encoder, int* ids, long nIds, char* outUnits, long outCap, out long nOut);
         [DllImport(Lib)] internal static extern void tkz_encoder_small_decode_calls(IntPtr encoder, out long calls, out long handedBack);
+        // Encode(...).Count without the ids: the token offsets (or the one count) come back, no id buffer exists
+        [DllImport(Lib)] internal static extern unsafe int tkz_count_utf16(IntPtr encoder, char* text, long len, int* allowed, int nAllowed, out long nOut);
+        [DllImport(Lib)] internal static extern unsafe int tkz_count_batch_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                  long* outOffsets, out long totalTokens);
+        [DllImport(Lib)] internal static extern void tkz_encoder_count_calls(IntPtr encoder, out long calls, out long singleLaunch);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -305,6 +310,68 @@ namespace Microsoft.DeepDev
                 if (n > 0) result.AddRange(new ArraySegment<int>(ids, 0, (int)n));
                 return result;
             }
+        }
+
+        /// <summary>Encode(text, allowedSpecial).Count without the ids: ONE call of tkz_count_utf16 on the string's own chars (a single kernel launch for a prompt,
+        /// nothing but the count comes back).  With a registered set the device path does not hold (-7) it is Encode(...).Count.</summary>
+        public unsafe int CountTokens(string text, IReadOnlyCollection<string> allowedSpecial)
+        {
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            if (plain || !specialOnHost)
+            {
+                int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+                int st; long n;
+                fixed (char* pc = text) fixed (int* pa = allowed)
+                    st = Tkz.tkz_count_utf16(encoder, pc, text.Length, allowed.Length > 0 ? pa : null, allowed.Length, out n);
+                GC.KeepAlive(this);
+                if (st != -7) { Tkz.Check(st); return checked((int)n); }
+                specialOnHost = true;
+            }
+            return Encode(text, allowedSpecial!).Count;
+        }
+
+        public int CountTokens(string text, bool applySpecialTokens = true)
+            => CountTokens(text, applySpecialTokens && specialTokens.Count > 0 ? (IReadOnlyCollection<string>)specialTokens : Array.Empty<string>());
+
+        /// <summary>The count of every text, as CountTokens(text, allowedSpecial) gives it: the strings' chars go to tkz_count_batch_utf16 as they are (copied into one
+        /// char[] with string.CopyTo), only the offsets come back.</summary>
+        public unsafe int[] CountTokensBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial = null)
+        {
+            var counts = new int[texts.Count];
+            if (texts.Count == 0) return counts;
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            if (plain || !specialOnHost)
+            {
+                var unitOffsets = new long[texts.Count + 1];
+                for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+                var units = new char[Math.Max(1, unitOffsets[texts.Count])];
+                for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+                int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+                var offsets = new long[texts.Count + 1];
+                int st;
+                fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (long* pt = offsets)
+                    st = Tkz.tkz_count_batch_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, pt, out _);
+                GC.KeepAlive(this);
+                if (st != -7)
+                {
+                    Tkz.Check(st);
+                    for (int t = 0; t < texts.Count; ++t) counts[t] = checked((int)(offsets[t + 1] - offsets[t]));
+                    return counts;
+                }
+                specialOnHost = true;
+            }
+            var lists = EncodeBatch(texts, allowedSpecial);
+            for (int t = 0; t < texts.Count; ++t) counts[t] = lists[t].Count;
+            return counts;
+        }
+
+        // the allowed literals as indices into the registered set (registration order = the alternation's)
+        private int[] AllowedIndex(IReadOnlyCollection<string> allowedSpecial)
+        {
+            var index = new List<int>();
+            int i = 0;
+            foreach (string k in specialTokensEncoder.Keys) { if (allowedSpecial.Contains(k)) index.Add(i); ++i; }
+            return index.ToArray();
         }
 
         /// <summary>Encodes every text as Encode(text, allowedSpecial) would; all plain segments go to the GPU as one batch.

@@ -303,6 +303,32 @@ tkz_status tkz_encode_trim_utf8(tkz_encoder* e, const uint8_t* text, int64_t len
 tkz_status tkz_encode_trim_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t side, int64_t max_tokens,
                                  int32_t* out_ids, int64_t out_cap, int64_t* n_out, int64_t* cut_units);
 
+/* ---- Count: Encode(...).Count for a batch or one text, without the ids ------------------------------
+ * What prompt budgeting, length filtering and bucketing ask of a tokenizer: how many tokens every document has.  out_offsets (n_docs + 1 entries) is EXACTLY what the
+ * matching encode entry writes for the same arguments -- tkz_encode_batch_special_* when n_allowed > 0 and literals are registered, the plain entry otherwise --;
+ * the count of document d is out_offsets[d + 1] - out_offsets[d], *total_tokens (may be NULL) the last entry.  No id buffer is taken, none is allocated and no id
+ * is stored or copied: on the device k_tokcount stands where k_place stands in the launch sequence (everything before it -- marks, literals, pre-tokenizer, probe,
+ * merges, scans, retries, learning -- and k_docoffs behind it are the encode call's, so a count call trains and promotes as an encode call does); a sub-tile in which no
+ * document starts is skipped, one with document starts is read up to its last one.  The host entries stage no ids and download none: only the offsets travel back.
+ * allowed / n_allowed, TKZ_E_ARG, TKZ_E_UNSUPPORTED and tkz_encoder_special_stats as tkz_encode_batch_special_device / _utf8 / _utf16.  Every other error as in the
+ * encode entries (TKZ_E_INVALID_UTF8, TKZ_E_KEY_NOT_FOUND, bad offsets or null buffers: TKZ_E_ARG); TKZ_E_CAPACITY is never returned.  An empty batch or text:
+ * TKZ_OK and offsets of zero -- the host entries launch nothing, the device entry clears d_out_offsets on the stream.  d_bytes 16-byte aligned, as for every device entry.
+ *   tkz_count_batch_utf8 / _utf16: the routes of tkz_encode_batch_utf8 / _utf16 -- a small plain UTF-8 batch is ONE launch of the single-launch kernel as it is (its
+ *     ids land in the encoder's page-locked block and stay there; tkz_encoder_small_path_calls moves as for the encode call), anything else the chunk pipeline.
+ *   tkz_count_utf8 / _utf16: ONE text, *n_out its count (n_out may not be NULL).  The routes of tkz_encode_utf8 / tkz_encode_special_utf8 and their UTF-16 forms: the
+ *     UTF-16 text is transcoded on the host, a text with literals takes the special form of the single launch under the same rule.
+ * There is no _begin / _end form. */
+tkz_status tkz_count_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                  const int32_t* allowed, int32_t n_allowed, int64_t* d_out_offsets, void* hip_stream, int64_t* total_tokens);
+tkz_status tkz_count_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                int64_t* out_offsets, int64_t* total_tokens);
+tkz_status tkz_count_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                 int64_t* out_offsets, int64_t* total_tokens);
+tkz_status tkz_count_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t* n_out);
+tkz_status tkz_count_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t* n_out);
+/* informational: successful count calls, and those of them the single-launch kernel answered */
+void tkz_encoder_count_calls(const tkz_encoder* e, int64_t* calls, int64_t* single_launch);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,

@@ -4,6 +4,7 @@
 //   tkz::TikTokenizer          ITokenizer.Encode x2 + EncodeBatch     Tokenizer_C#/TokenizerLib/ITokenizer.cs:12,28
 //                              EncodeBatchFlat: (ids, offsets) in page-locked buffers that are kept from call to call (tkz::FlatBatch)
 //                              EncodeTrimSuffix / EncodeTrimPrefix x2   ITokenizer.cs:30-44, TikTokenizer.cs:288-579
+//                              CountTokens / CountTokensBatch (+ Utf16): Encode(...).Count from the device's count entries, no ids
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -397,6 +398,88 @@ public:
             special_on_host_ = true;
         }
         return EncodeBatchUtf16({text}, allowedSpecial)[0];
+    }
+    // ---- counts: Encode(...).Count without the ids (tkz_count_utf8 / _utf16, tkz_count_batch_utf8 / _utf16: no id buffer, only the offsets come back) ----
+    // The count of every text is the size of what the Encode method of the same arguments returns.  With a registered set the device path does not hold
+    // (TKZ_E_UNSUPPORTED) it IS that size: the host segmentation encodes.
+    int64_t CountTokens(const std::string& text, const std::vector<std::string>& allowedSpecial) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (plain || !special_on_host_) {
+            const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+            const uint8_t zero = 0;
+            int64_t n = 0;
+            const tkz_status st = tkz_count_utf8(enc_, text.empty() ? &zero : reinterpret_cast<const uint8_t*>(text.data()), static_cast<int64_t>(text.size()),
+                                                 index.data(), static_cast<int32_t>(index.size()), &n);
+            if (st != TKZ_E_UNSUPPORTED) { check(st); return n; }
+            special_on_host_ = true;
+        }
+        return static_cast<int64_t>(Encode(text, allowedSpecial).size());
+    }
+    int64_t CountTokens(const std::string& text, bool applySpecialTokens = true) const {
+        return CountTokens(text, applySpecialTokens ? all_specials() : std::vector<std::string>{});
+    }
+    std::vector<int64_t> CountTokensBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial) const {
+        std::vector<int64_t> counts(texts.size(), 0);
+        if (texts.empty()) return counts;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (plain || !special_on_host_) {
+            std::vector<uint8_t> bytes;
+            std::vector<int64_t> offs{0}, ooff(texts.size() + 1, 0);
+            for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+            if (bytes.empty()) bytes.push_back(0);
+            const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+            const tkz_status st = tkz_count_batch_utf8(enc_, bytes.data(), offs.data(), static_cast<int64_t>(texts.size()), index.data(), static_cast<int32_t>(index.size()),
+                                                       ooff.data(), nullptr);
+            if (st != TKZ_E_UNSUPPORTED) {
+                check(st);
+                for (size_t t = 0; t < texts.size(); ++t) counts[t] = ooff[t + 1] - ooff[t];
+                return counts;
+            }
+            special_on_host_ = true;
+        }
+        const std::vector<std::vector<int32_t>> ids = EncodeBatch(texts, allowedSpecial);
+        for (size_t t = 0; t < texts.size(); ++t) counts[t] = static_cast<int64_t>(ids[t].size());
+        return counts;
+    }
+    std::vector<int64_t> CountTokensBatch(const std::vector<std::string>& texts, bool applySpecialTokens = true) const {
+        return CountTokensBatch(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{});
+    }
+    // ... the code units of .NET strings: the batch is transcoded on the device, the one text on the host (as EncodeBatchUtf16 / EncodeUtf16 have it)
+    int64_t CountTokensUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial = {}) const {
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (plain || !special_on_host_) {
+            const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+            const uint16_t zero = 0;
+            int64_t n = 0;
+            const tkz_status st = tkz_count_utf16(enc_, text.empty() ? &zero : reinterpret_cast<const uint16_t*>(text.data()), static_cast<int64_t>(text.size()),
+                                                  index.data(), static_cast<int32_t>(index.size()), &n);
+            if (st != TKZ_E_UNSUPPORTED) { check(st); return n; }
+            special_on_host_ = true;
+        }
+        return static_cast<int64_t>(EncodeUtf16(text, allowedSpecial).size());
+    }
+    std::vector<int64_t> CountTokensBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial = {}) const {
+        std::vector<int64_t> counts(texts.size(), 0);
+        if (texts.empty()) return counts;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        if (plain || !special_on_host_) {
+            std::vector<uint16_t> units;
+            std::vector<int64_t> offs{0}, ooff(texts.size() + 1, 0);
+            for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+            if (units.empty()) units.push_back(0);
+            const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+            const tkz_status st = tkz_count_batch_utf16(enc_, units.data(), offs.data(), static_cast<int64_t>(texts.size()), index.data(), static_cast<int32_t>(index.size()),
+                                                        ooff.data(), nullptr);
+            if (st != TKZ_E_UNSUPPORTED) {
+                check(st);
+                for (size_t t = 0; t < texts.size(); ++t) counts[t] = ooff[t + 1] - ooff[t];
+                return counts;
+            }
+            special_on_host_ = true;
+        }
+        const std::vector<std::vector<int32_t>> ids = EncodeBatchUtf16(texts, allowedSpecial);
+        for (size_t t = 0; t < texts.size(); ++t) counts[t] = static_cast<int64_t>(ids[t].size());
+        return counts;
     }
     // (one string: tkz_encode_trim_utf16, the single-text trim entry)
     Trimmed16 EncodeTrimSuffixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {

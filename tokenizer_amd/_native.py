@@ -166,6 +166,13 @@ class Library:
         L.tkz_encoder_small_decode_calls.argtypes = [vp, pi64, pi64]
         L.tkz_encoder_small_decode_calls.restype = None
         L.tkz_encoder_small_decode_phases.argtypes = [vp, vp]
+        L.tkz_count_batch_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, vp, vp, pi64]
+        L.tkz_count_batch_utf8.argtypes = [vp, vp, vp, i64, vp, i32, vp, pi64]
+        L.tkz_count_batch_utf16.argtypes = [vp, vp, vp, i64, vp, i32, vp, pi64]
+        L.tkz_count_utf8.argtypes = [vp, vp, i64, vp, i32, pi64]
+        L.tkz_count_utf16.argtypes = [vp, vp, i64, vp, i32, pi64]
+        L.tkz_encoder_count_calls.argtypes = [vp, pi64, pi64]
+        L.tkz_encoder_count_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -645,6 +652,62 @@ class Encoder:
         return ids[:n.value].tolist(), cu.value
 
     # -- Decode --
+    # -- counts: Encode(...).Count without the ids --
+    def count_batch(self, data: np.ndarray, offsets: np.ndarray, allowed=()):
+        """Token offsets int64[n+1] of the batch -- exactly encode_batch's / encode_batch_special's -- and no ids: tkz_count_batch_utf8.  The count of document d
+        is offsets[d + 1] - offsets[d] (np.diff).  allowed: indices as in encode_batch_special."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        ooff = np.empty(n + 1, np.int64)
+        tot = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_count_batch_utf8(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                       _ptr(ooff), C.byref(tot)))
+        return ooff
+
+    def count_batch_utf16(self, units: np.ndarray, offsets: np.ndarray, allowed=()):
+        """count_batch for UTF-16 documents (uint16[total], offsets in units): tkz_count_batch_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        ooff = np.empty(n + 1, np.int64)
+        tot = C.c_int64(0)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        self.lib.check(self.lib.L.tkz_count_batch_utf16(self._h, _ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed), _ptr(ooff), C.byref(tot)))
+        return ooff
+
+    def count_batch_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, d_out_offsets, stream=0):
+        """Device buffers in, the token offsets (int64[n_docs + 1]) out, no id buffer: tkz_count_batch_device.  Returns the token total."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_count_batch_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                         d_out_offsets or None, stream or None, C.byref(tot)))
+        return tot.value
+
+    def count(self, text: bytes, allowed=()):
+        """len(encode_special(text, allowed)) without the ids: tkz_count_utf8."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = C.c_int64(0)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        self.lib.check(self.lib.L.tkz_count_utf8(self._h, _ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed), C.byref(n)))
+        return n.value
+
+    def count_utf16(self, units, allowed=()):
+        """The same for a .NET `string` given as its UTF-16 code units: tkz_count_utf16."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n = C.c_int64(0)
+        self.lib.check(self.lib.L.tkz_count_utf16(self._h, _ptr(u), len(u) - 1, _ptr(allowed) if len(allowed) else None, len(allowed), C.byref(n)))
+        return n.value
+
+    def count_calls(self):
+        """(successful count calls, those of them the single-launch kernel answered)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self.lib.L.tkz_encoder_count_calls(self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
     def set_special_tokens(self, specials):
         """specials: {literal str: id}.  Registers SpecialTokensDecoder for Decode (TikTokenizer.cs:79) and, in this order, the literals the special
         entries cut out of the text (encode_batch_special)."""

@@ -294,6 +294,7 @@ struct tkz_encoder {
     bool lit_fffd = false;                 // a registered literal holds U+FFFD (TkzLitTable's second 256-bit set is not empty)
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
+    std::atomic<int64_t> count_calls{0}, count_single{0};                  // tkz_encoder_count_calls: successful count calls, and those of them that took the single launch
     int64_t bytes_allocated = 0;           // tables
     std::atomic<int64_t> last_xcount{0}, last_xcount2{0};   // tkz_encoder_pretok_leftovers
     bool small_ok = false;                 // the device's LDS per workgroup holds k_small's (kSmallLdsBytesNeeded)
@@ -361,6 +362,7 @@ struct BatchCall {
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
+    bool count_only = false;                   // tkz_count_*: Encode only -- the token offsets and no ids (k_tokcount where k_place stands; d_out null, out_cap 0, never TKZ_E_CAPACITY)
     bool pretokenizes() const { return kind != CallKind::OnePiecePerDoc; }
     bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
@@ -387,13 +389,16 @@ struct HostCall {
     const uint64_t* repl = nullptr;
     // the single-text trim entries: the single-launch path runs its trim form, out_cap counts the KEPT ids and *needed receives their count
     const TrimOne* trim = nullptr;
+    // tkz_count_*: the offsets and no ids (out_ids null, out_cap 0); *took_single: null, or set when the single-launch kernel answered the call
+    bool count_only = false;
+    bool* took_single = nullptr;
     bool u16() const { return utf16; }
     int64_t total() const { return offs[n_docs]; }     // bytes, or code units
     bool plain_encode() const { return kind == CallKind::Encode; }
     // the same call on device buffers
     BatchCall on_device(const uint8_t* d_bytes, const int64_t* d_offs, int64_t nd, int64_t nbytes, int32_t* d_out, int64_t cap, int64_t* d_out_offs, hipStream_t stream) const {
         BatchCall c{d_bytes, d_offs, nd, nbytes, d_out, cap, d_out_offs, stream};
-        c.kind = kind; c.special = special;
+        c.kind = kind; c.special = special; c.count_only = count_only;
         return c;
     }
 };
@@ -1006,7 +1011,9 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             if (P.stats) launch_miss_stats(L, P, ntiles);
             launch_scan2(L, ntiles, ws->w_bsum.as<int64_t>(), P.tile_count, ws->w_tbase.as<int64_t>(), grand, 1, nullptr, nullptr, nullptr, 1, K_SCAN);
             // (a trim call's untrimmed ids stay in the workspace: the caller's buffer holds the kept ones only)
-            launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
+            // (a count call: the token position of every mark and no ids)
+            if (c.count_only) launch_tokcount(L, P, ws->w_tbase.as<int64_t>(), ws->w_dcount.as<int32_t>(), ntiles);
+            else launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
                 const int64_t* produced = grand;
@@ -1168,6 +1175,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
     const int64_t n_docs = c.n_docs, total = c.total;
     const hipStream_t stream = c.stream;
     if (n_docs < 0 || total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    if (c.count_only && !c.plain_encode()) return fail(TKZ_E_ARG, "a count call is an encode call");
     if (total_tokens) *total_tokens = 0;
     if (n_docs == 0 && total != 0) return fail(TKZ_E_ARG, "bytes without documents");
     if (total == 0) {
@@ -1224,7 +1232,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
         if (total_tokens) *total_tokens = produced;
         if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
-        if (produced > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
+        if (!c.count_only && produced > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");      // (a count call stores no ids)
         return TKZ_OK;
     }
     return fail(TKZ_E_DEVICE, "unreachable");
@@ -1268,7 +1276,7 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     P.lane_piece = kSmallLanePiece;
     SmallArgs A{};
     A.h_bytes = H + kSmallOffBytes; A.h_offs = reinterpret_cast<const int64_t*>(H + kSmallOffOffs);
-    A.out = reinterpret_cast<int32_t*>(H + kSmallOffIds); A.out_cap = std::min<int64_t>(c.out_cap, kSmallMaxBytes); A.out_offs = reinterpret_cast<int64_t*>(H + kSmallOffOut);
+    A.out = reinterpret_cast<int32_t*>(H + kSmallOffIds); A.out_cap = c.count_only ? (int64_t)kSmallMaxBytes : std::min<int64_t>(c.out_cap, kSmallMaxBytes); A.out_offs = reinterpret_cast<int64_t*>(H + kSmallOffOut);
     A.h_result = h_res;
     A.docbits = ws->w_docbits.as<uint64_t>(); A.startbits = ws->w_startbits.as<uint64_t>();
     A.pcount = ws->w_pcount.as<int32_t>(); A.pbase = ws->w_pbase.as<int64_t>(); A.docord_base = ws->w_dbase.as<int64_t>(); A.tile_base = ws->w_tbase.as<int64_t>();
@@ -1304,6 +1312,11 @@ tkz_status encode_small(tkz_encoder* e, Workspace* ws, const HostCall& c, bool* 
     if (c.needed) *c.needed = tokens;
     *handled = true;
     if (c.special) e->spec_literals += h_res[3];
+    if (c.count_only) {      // (the ids stay in the page-locked block, which holds them whatever their number)
+        memcpy(c.out_offsets, H + kSmallOffOut, (size_t)(n_docs + 1) * 8);
+        if (c.took_single) *c.took_single = true;
+        return TKZ_OK;
+    }
     if (tokens > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");
     if (tokens) memcpy(c.out_ids, H + kSmallOffIds + (size_t)first * 4, (size_t)tokens * 4);
     if (c.trim) {
@@ -1444,8 +1457,8 @@ tkz_status stage_in(Workspace* ws, const uint8_t* bytes, int64_t total, const in
     HIP_TRY(hipMemcpy(ws->s_offs[0].p, offs, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
     return TKZ_OK;
 }
-tkz_status stage_out(Workspace* ws, int64_t n_docs, int64_t cap, bool with_offsets = true) {
-    HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, &ws->bytes_allocated));
+tkz_status stage_out(Workspace* ws, int64_t n_docs, int64_t cap, bool with_offsets = true, bool with_ids = true) {      // (with_ids false: a count call)
+    if (with_ids) HIP_TRY(ws->s_out[0].ensure((size_t)std::max<int64_t>(cap, 1) * 4, &ws->bytes_allocated));
     if (with_offsets) HIP_TRY(ws->s_outoffs[0].ensure((size_t)(n_docs + 1) * 8, &ws->bytes_allocated));
     return TKZ_OK;
 }
@@ -1465,9 +1478,9 @@ tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const HostCall& c
     const int64_t cap = bitmap ? 0 : std::min<int64_t>(c.out_cap, total);   // tokens <= bytes: more capacity is never used
     TKZ_TRY(stage_in(ws, c.bytes, total, c.offs, n_docs));
     if (bitmap) HIP_TRY(ws->s_out[0].ensure((size_t)(total / 64 + 1) * 8, &ws->bytes_allocated));
-    else TKZ_TRY(stage_out(ws, n_docs, cap));
+    else TKZ_TRY(stage_out(ws, n_docs, cap, true, !c.count_only));
     int64_t tokens = 0;
-    BatchCall dc = c.on_device(ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr);
+    BatchCall dc = c.on_device(ws->s_bytes[0].as<uint8_t>(), ws->s_offs[0].as<int64_t>(), n_docs, total, c.count_only ? nullptr : ws->s_out[0].as<int32_t>(), cap, ws->s_outoffs[0].as<int64_t>(), nullptr);
     if (bitmap) dc.d_bitmap = ws->s_out[0].as<uint64_t>();
     const tkz_status st = encode_device(e, ws, dc, kCallWhole, &tokens);
     if (c.needed) *c.needed = tokens;
@@ -1476,7 +1489,7 @@ tkz_status encode_host_blocking(tkz_encoder* e, Workspace* ws, const HostCall& c
         HIP_TRY(hipMemcpy(bitmap, ws->s_out[0].p, (size_t)(total / 64 + 1) * 8, hipMemcpyDeviceToHost));
         return TKZ_OK;
     }
-    return fetch(ws, c.out_ids, tokens, c.out_offsets, n_docs);
+    return fetch(ws, c.out_ids, c.count_only ? 0 : tokens, c.out_offsets, n_docs);
 }
 
 // Inside the pipeline a failed runtime call is RECORDED (HostPipeline::note), never returned from encode_host: the upload of a later chunk may still be reading the
@@ -1532,7 +1545,7 @@ struct HostPipeline {
             }
         }
         if (!p.direct_out) for (int o = 0; o < p.nout; ++o) {
-            HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(c.out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
+            if (!c.count_only) HIP_TRY(ws->s_out[o].ensure((size_t)std::max<int64_t>(std::min<int64_t>(c.out_cap, (u16 ? 3 : 1) * max_units), 1) * 4, acc));      // (a token is at least one byte, a code unit at most three)
             HIP_TRY(ws->s_outoffs[o].ensure((size_t)(max_docs + 1) * 8, acc));
         }
         // downloads by copy engine: page-locked results whose device-side address is their host address (hipHostMalloc, tkz_host_alloc, torch's pinned tensors --
@@ -1593,7 +1606,7 @@ struct HostPipeline {
         // the download of chunk k - nout has left this chunk's output set
         if (!wait_engine(o)) return note(fail(TKZ_E_DEVICE, kMsgEngineDownload));
         if (ev_pending[o]) { ev_pending[o] = false; PIPELINE_TRY(hipStreamWaitEvent(w->st_compute, ws->ev_out[o], 0)); }
-        int32_t* const dst_ids = p.direct_out ? static_cast<int32_t*>(p.dv_ids) : ws->s_out[o].as<int32_t>();
+        int32_t* const dst_ids = c.count_only ? nullptr : p.direct_out ? static_cast<int32_t*>(p.dv_ids) : ws->s_out[o].as<int32_t>();      // (a count call: no ids anywhere)
         int64_t* const dst_offs = p.direct_out ? static_cast<int64_t*>(p.dv_ooffs) : ws->s_outoffs[o].as<int64_t>();
         // (how much of out_cap the chunks before leave is not known yet when a chunk is begun: the staging set holds a chunk's ids whatever their number, and the
         //  sum is checked when the chunk ends)
@@ -1621,9 +1634,9 @@ struct HostPipeline {
     tkz_status download(int64_t k, int64_t tokens) {
         const int o = (int)(k % p.nout);
         const int64_t d0 = p.cut[(size_t)k], nd = p.cut[(size_t)k + 1] - d0;
-        bool ids_sent = tokens == 0, offs_sent = false;
+        bool ids_sent = tokens == 0 || c.count_only, offs_sent = false;      // (a count call: only the offsets travel back)
         const size_t nb_ids = (size_t)tokens * 4, nb_offs = (size_t)(nd + 1) * 8;
-        if (tokens) ids_sent = by_engine(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
+        if (!ids_sent) ids_sent = by_engine(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
         offs_sent = by_engine(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
         if (!ids_sent || !offs_sent) {
             if (!ids_sent) PIPELINE_TRY(hipMemcpyAsync(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
@@ -1635,7 +1648,7 @@ struct HostPipeline {
     }
     bool finish(int64_t k, tkz_status cs, int64_t tokens) {      // chunk k has ended with status cs: its place in the output, its download; false: stop
         tok_base[(size_t)k + 1] = tok_base[(size_t)k] + tokens;
-        if (cs == TKZ_E_CAPACITY || (cs == TKZ_OK && tok_base[(size_t)k + 1] > c.out_cap)) { over = true; return true; }
+        if (cs == TKZ_E_CAPACITY || (cs == TKZ_OK && !c.count_only && tok_base[(size_t)k + 1] > c.out_cap)) { over = true; return true; }
         if (cs != TKZ_OK) { note(cs); return false; }
         if (!over && !p.direct_out && download(k, tokens) != TKZ_OK) return false;
         return true;
@@ -1712,6 +1725,7 @@ tkz_status encode_host(tkz_encoder* e, const HostCall& c) {
     TKZ_TRY(check_host_docs(offs, n_docs, c.bytes || c.units, u16 ? kUnitDocs : kByteDocs, &total));
     if (c.needed) *c.needed = 0;
     if (u16 && total == 0) return check_empty_docs(offs, n_docs, kUnitDocs, c.out_offsets);
+    if (c.count_only && total == 0) return check_empty_docs(offs, n_docs, kByteDocs, c.out_offsets);      // (an empty batch: zero offsets, nothing launched)
     Lease lease(e);
     Workspace* ws = lease.ws;
     // (the single-launch path first: at most 128 KiB, a fraction of a chunk -- and none of the planner's questions are asked of a 64-byte prompt)
@@ -1739,16 +1753,16 @@ tkz_status encode_host_batch(tkz_encoder* e, const HostCall& c) {
 
 // tkz_encode_batch_utf16 and its special form (sp null: the plain one)
 tkz_status encode_host_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const SpecialCall* sp,
-                                   int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed) {
+                                   int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* needed, bool count_only = false) {
     HostCall c{nullptr, units, unit_offsets, n_docs, out_ids, out_cap, out_offsets, needed};
-    c.utf16 = true; c.special = sp;
+    c.utf16 = true; c.special = sp; c.count_only = count_only;
     return encode_host_batch(e, c);
 }
 
 // what the device entries check before they take a workspace
 tkz_status check_device_call(tkz_encoder* e, DeviceScope& scope, const BatchCall& c) {
     TKZ_TRY(check_encoder(e, scope));
-    if (!c.d_offs || !c.d_out_offs || (c.total > 0 && (!c.d_bytes || !c.d_out))) return fail(TKZ_E_ARG, "null device buffer");
+    if (!c.d_offs || !c.d_out_offs || (c.total > 0 && (!c.d_bytes || (!c.d_out && !c.count_only)))) return fail(TKZ_E_ARG, "null device buffer");
     if (reinterpret_cast<uintptr_t>(c.d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
     return TKZ_OK;
 }
@@ -2208,6 +2222,82 @@ tkz_status tkz_encode_batch_special_utf16(tkz_encoder* e, const uint16_t* units,
     TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
     return encode_host_batch_utf16(e, units, unit_offsets, n_docs, sp, out_ids, out_cap, out_offsets, needed);
 }
+
+// ---- count calls: the token offsets of an encode call and no ids (k_tokcount where k_place stands; the single-launch kernel as it is) ----
+namespace {
+// a count call that succeeded, and whether the single launch answered it
+tkz_status count_done(tkz_encoder* e, tkz_status st, bool single) {
+    if (st == TKZ_OK) { ++e->count_calls; if (single) ++e->count_single; }
+    return st;
+}
+}  // namespace
+
+tkz_status tkz_count_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                  const int32_t* allowed, int32_t n_allowed, int64_t* d_out_offsets, void* hip_stream, int64_t* total_tokens) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, nullptr, 0, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    c.special = sp; c.count_only = true;
+    return count_done(e, encode_device_batch(e, c, total_tokens), false);
+}
+tkz_status tkz_count_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                int64_t* out_offsets, int64_t* total_tokens) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    bool single = false;
+    HostCall c{bytes, nullptr, doc_offsets, n_docs, nullptr, 0, out_offsets, total_tokens};
+    c.special = sp; c.count_only = true; c.took_single = &single;
+    const tkz_status st = encode_host_batch(e, c);
+    return count_done(e, st, single);
+}
+tkz_status tkz_count_batch_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                 int64_t* out_offsets, int64_t* total_tokens) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    return count_done(e, encode_host_batch_utf16(e, units, unit_offsets, n_docs, sp, nullptr, 0, out_offsets, total_tokens, true), false);
+}
+// ONE text: the routes of tkz_encode_utf8 / tkz_encode_special_utf8 (the single-launch kernel where they take it, its special form for a text with literals)
+tkz_status tkz_count_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t* n_out) {
+    if (len < 0 || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0;
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    bool single = false;
+    HostCall c{text, nullptr, offs, 1, nullptr, 0, oo, &needed};
+    c.special = sp; c.single = sp != nullptr; c.count_only = true; c.took_single = &single;
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK && sp) ++e->spec_batches;
+    if (st == TKZ_OK) *n_out = oo[1];
+    return count_done(e, st, single);
+}
+// ... a UTF-16 string: transcoded on the host, as tkz_encode_utf16 / tkz_encode_special_utf16 do
+tkz_status tkz_count_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t* n_out) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0;
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    std::vector<uint8_t> u8;
+    std::vector<uint64_t> repl;
+    utf16_to_utf8(text, len, &u8, sp && sp->fffd ? &repl : nullptr);
+    if (!sp) return tkz_count_utf8(e, u8.data(), (int64_t)u8.size(), nullptr, 0, n_out);
+    const int64_t offs[2] = {0, len}, offs8[2] = {0, (int64_t)u8.size()};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    bool single = false;
+    HostCall c8{u8.data(), nullptr, offs8, 1, nullptr, 0, oo, &needed};
+    c8.special = sp; c8.single = true; c8.repl = sp->fffd ? repl.data() : nullptr; c8.count_only = true; c8.took_single = &single;
+    HostCall c{nullptr, text, offs, 1, nullptr, 0, oo, &needed};
+    c.utf16 = true; c.special = sp; c.single = true; c.small_form = &c8; c.count_only = true;
+    const tkz_status st = encode_host(e, c);
+    if (st == TKZ_OK) { ++e->spec_batches; *n_out = oo[1]; }
+    return count_done(e, st, single);
+}
+void tkz_encoder_count_calls(const tkz_encoder* e, int64_t* calls, int64_t* single_launch) {
+    if (calls) *calls = e ? e->count_calls.load() : 0;
+    if (single_launch) *single_launch = e ? e->count_single.load() : 0;
+}
+
 
 tkz_status tkz_pretokenize_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, uint64_t* out_bitmap_words) {
     if (!out_bitmap_words) return fail(TKZ_E_ARG, "null output buffer");

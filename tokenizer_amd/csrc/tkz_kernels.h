@@ -183,6 +183,8 @@ void launch_dec_small(const Launch& L, const TkzDecodeTable& D, const DecSmallAr
 // round_to (a power of two): every count is rounded up to a multiple of it before it is summed
 void launch_scan(const Launch& L, const int32_t* tile_count, int64_t ntiles, int64_t* bsum, int64_t* tile_base, int64_t* grand, int kid, int round_to = 1);
 void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_base, int64_t nsub, int32_t* out, int64_t out_cap);
+// a count call (tkz_count_*): P.doc_tok as launch_place leaves it and nothing else -- no ids.  dcount: the marks of every sub-tile (launch_doccount2)
+void launch_tokcount(const Launch& L, const EncodeParams& P, const int64_t* tile_base, const int32_t* dcount, int64_t nsub);
 // (c3a / c3b / c3c: null, or blocks that receive {c3_docs, total, *grand}: launch_counts3's job done by the same launch)
 void launch_docoffs(const Launch& L, const int64_t* d_offs, int64_t n_docs, int64_t total, const int64_t* tile_base,
                     const uint64_t* docbits, const int64_t* docord_base, const int32_t* doc_tok, const int64_t* grand, int64_t* out_offs,

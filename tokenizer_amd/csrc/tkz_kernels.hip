@@ -2270,6 +2270,145 @@ TKZ_KERNEL_OCC(256, TKZ_PLACE_OCC) void k_place(EncodeParams P, const int64_t* t
     tkz_place_subtiles<SLOTS, PROMO, kStageBatch>(P, tile_base, out, out_cap, sub0, tkz_place_lds<SLOTS, kStageBatch>(s_wave[simt::wave()]));
 }
 
+// k_tokcount: the count form of k_place (a count call, tkz_count_*: the ids are never wanted).  It fills P.doc_tok -- the token index inside its sub-tile of
+// every marked piece -- exactly as k_place does and stores nothing else: no id stage, no flush, no `out`; no atomics and no fence.  k_place's mapping (tkz_xcd_block,
+// kPlacePer consecutive sub-tiles a wavefront, the next sub-tile's scalars requested while this one is counted, four consecutive records a lane from one 16-byte
+// load), with two short cuts the ids do not allow:
+//   * a sub-tile without a mark (dcount[sub] == 0: k_doccount2) is skipped for the price of its scalar loads -- on documents longer than a sub-tile, nearly all;
+//   * a sub-tile with marks is walked until its last mark is written (marks == dcount[sub], wave-uniform): the records behind it are never loaded.
+// The token count of a record is read as k_place reads it -- a hit 1, a promoted piece from its record bits, a missed piece tkz_result_cnt of its list entry, a
+// giant piece giant_cnt[sub] -- and nothing but the count: mquad, dense, tmp and promo are never read.  LDS: one count word per list entry, kCountSlots entries in
+// ONE form (the short list from slot 0 up, the long one from the top down; entries beyond them are read from the list in memory, as on k_place's general path), and
+// slot kCountSlots: "one token".  One wave scan of tokens | marks << 20 per 256 records; a chunk in which a lane's four records stand for more than kCountLaneMax
+// tokens (a giant piece, a long merged one: 64 lanes of at most that fit 20 bits) is taken 64 records at a time with a scan of the tokens alone.
+// With cut lists (ns + nl > mcap) the attempt is redone and nothing of this pass is used: every missed piece counts 1 then, and nothing is read through the lists.
+constexpr int kCountSlots = 128, kCountLaneMax = (1 << 20) / 64 - 1;
+#ifndef TKZ_TOKCOUNT_OCC
+#define TKZ_TOKCOUNT_OCC 8
+#endif
+TKZ_KERNEL_OCC(256, TKZ_TOKCOUNT_OCC) void k_tokcount(EncodeParams P, const int32_t* dcount) {
+    if (tkz_attempt_failed(P)) return;
+    TKZ_SHARED int32_t s_wave[kThreads / 64][kCountSlots + 4];
+    const int lane = simt::lane();
+    int32_t* const s_cnt = s_wave[simt::wave()];
+    const int64_t sub0 = (tkz_xcd_block(simt::bid(), simt::nblocks()) * (kThreads / 64) + simt::wave()) * kPlacePer;
+    if (sub0 >= P.nsub) return;
+    const bool promo = P.promo != nullptr;                 // (a hit record may carry a promo code instead of a rank: tkz_tables.h)
+    struct Sc { int64_t pb, ord0; int np, dc; uint32_t mc, hf; int gc; };
+    auto load_sc = [&](int64_t sub) -> Sc {
+        Sc c;
+        c.dc = dcount[sub]; c.pb = P.pbase[sub]; c.ord0 = P.docord_base[sub]; c.np = P.pcount[sub]; c.mc = P.mcount[sub]; c.hf = P.heavy_flag[sub]; c.gc = P.giant_cnt[sub];
+        return c;
+    };
+    Sc nxt = load_sc(sub0);
+#pragma unroll 1
+    for (int it = 0; it < kPlacePer && sub0 + it < P.nsub; ++it) {
+        const int64_t sub = sub0 + it;
+        const Sc cur = nxt;
+        if (it + 1 < kPlacePer && sub + 1 < P.nsub) nxt = load_sc(sub + 1);
+        const int dc = cur.dc;
+        if (dc <= 0) continue;                               // (wave-uniform) no document starts here: nobody asks for a position inside this sub-tile
+        const int64_t pb = cur.pb, ord0 = cur.ord0;
+        const int np = cur.np;
+        const int ns = (int)(cur.mc & 0xFFFFu), nl = (int)(cur.mc >> 16);
+        const uint32_t* const ml = P.mlist + sub * (int64_t)P.mcap;
+        const bool has_giant = (cur.hf & 2u) != 0;
+        int gcnt = has_giant ? cur.gc : 0;
+        if (gcnt < 0) gcnt = 0;
+        const bool lists_ok = ns + nl <= P.mcap;
+        // slot s holds the count of entry s of the short list (s < ks) or of entry top - s of the long one (s > top - kl); lane l loads slot l and -- only when
+        // more than 64 entries are kept -- slot l + 64
+        const int kl = ns + nl <= kCountSlots ? nl : (nl < kCountSlots / 2 ? nl : kCountSlots / 2), ks = ns < kCountSlots - kl ? ns : kCountSlots - kl;
+        const bool two = ks + kl > 64;
+        const int top = two ? kCountSlots - 1 : 63;
+        {
+            int a[2] = {1, 1};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1 && !two) break;
+                const int slot = lane + 64 * h;
+                const bool shortside = slot < ks;
+                const int e = shortside ? slot : top - slot;
+                if (lists_ok && (shortside || e < kl)) a[h] = tkz_result_cnt(tkz_load_nt(&ml[shortside ? e : P.mcap - 1 - e]));
+            }
+            (void)simt::ballot(true);                            // (the sub-tile before this one is done with them)
+            s_cnt[lane] = a[0]; s_cnt[lane + 64] = a[1];
+            if (lane == 0) s_cnt[kCountSlots] = 1;
+        }
+        (void)simt::ballot(true);
+        const bool all_kept = lists_ok && !has_giant && ns + nl <= kCountSlots;      // every missed piece's count is in LDS: nearly every sub-tile
+        // the token count of a missed piece wherever its answer is
+        auto miss_count = [&](uint32_t rec) -> int {
+            if (rec & kPrGiant) return gcnt;
+            if (!lists_ok) return 1;
+            const int idx = (int)(rec & 1023u);
+            const bool lg = (rec & kPrLong) != 0;
+            if (lg ? idx < kl : idx < ks) return s_cnt[lg ? top - idx : idx];
+            return idx < P.mcap ? tkz_result_cnt(ml[lg ? P.mcap - 1 - idx : idx]) : 1;
+        };
+        int running = 0, marks = 0;
+#pragma unroll 1
+        for (int kk = 0; kk < np && marks < dc; kk += 256) {
+            // ---- 256 records: four consecutive ones a lane, one scan of tokens | marks << 20 ----
+            const int k0 = kk + 4 * lane;
+            uint32_t r[4] = {0u, 0u, 0u, 0u};
+            if (k0 < np) {
+                if (pb + k0 + 4 <= P.prank_cap) { const uint4 v = tkz_load16_nt(&P.prank[pb + k0]); r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; }
+                else for (int j = 0; j < 4; ++j) if (pb + k0 + j < P.prank_cap) r[j] = (uint32_t)P.prank[pb + k0 + j];
+            }
+            int c[4];
+            bool mkd[4];
+            int t = 0, mk = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool ok = k0 + j < np && pb + k0 + j < P.prank_cap;
+                const bool ms = ok && (r[j] & kPrMiss);
+                if (all_kept) {                                  // (wave-uniform) without a branch: a hit reads the "one token" slot
+                    const int idx = ((r[j] & kPrLong) ? top - (int)(r[j] & 1023u) : (int)(r[j] & 1023u)) & (kCountSlots - 1);
+                    c[j] = ok ? s_cnt[ms ? idx : kCountSlots] : 0;
+                } else c[j] = !ok ? 0 : ms ? miss_count(r[j]) : 1;
+                if (promo && ok && !ms && (r[j] & kPromoFlag)) c[j] = (int)((r[j] >> kPromoCntShift) & 3u) + 1;
+                mkd[j] = ok && (r[j] & kPrMark);
+                t += c[j];
+                mk += mkd[j] ? 1 : 0;
+            }
+            if (!simt::ballot(t > kCountLaneMax)) {
+                int both;
+                const int pre = tkz_wave_scan_sum(t | (mk << 20), &both);
+                int pos = running + (pre & 0xFFFFF), mi = marks + (pre >> 20);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (mkd[j] && mi < dc) P.doc_tok[ord0 + mi] = pos;
+                    mi += mkd[j] ? 1 : 0;
+                    pos += c[j];
+                }
+                running += both & 0xFFFFF; marks += both >> 20;
+                continue;
+            }
+            // ---- a chunk whose token sum may not fit 20 bits: 64 records at a time, as on k_place's general path ----
+#pragma unroll 1
+            for (int j = 0; j < 4 && marks < dc; ++j) {
+                const int q0 = kk + 64 * j;
+                if (q0 >= np) break;
+                const int k = q0 + lane;
+                const bool valid = k < np && pb + k < P.prank_cap;
+                const uint32_t rec = valid ? (uint32_t)tkz_load_nt(&P.prank[pb + k]) : 0u;
+                const bool miss = (rec & kPrMiss) != 0;
+                int cnt = !valid ? 0 : miss ? miss_count(rec) : 1;
+                if (promo && valid && !miss && (rec & kPromoFlag)) cnt = (int)((rec >> kPromoCntShift) & 3u) + 1;
+                int tot;
+                const int pos = running + tkz_wave_scan_sum(cnt, &tot);
+                const bool marked = valid && (rec & kPrMark);
+                const uint64_t mm = simt::ballot(marked);
+                const int mi = marks + tkz_popc64(mm & tkz_lowmask(lane));
+                if (marked && mi < dc) P.doc_tok[ord0 + mi] = pos;
+                running += tot;
+                marks += tkz_popc64(mm);
+            }
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------------
 // giant pieces (> kArenaPiece bytes: a run of thousands of letters, of '=' ...): found on the bitmap, merged by a whole
 // 1024-thread workgroup each (tkz_bpe_long, rounds) before the encode kernels run
@@ -4020,6 +4159,14 @@ void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_ba
         if (P.place128) TKZ_LAUNCH((k_place<128, false>), grid, kThreads, L.stream, P, tile_base, out, out_cap);
         else TKZ_LAUNCH((k_place<64, false>), grid, kThreads, L.stream, P, tile_base, out, out_cap);
     }
+    hook(L, K_GATHER, 1);
+}
+// the count form of launch_place, in the same profiling bracket (tile_base: the positions k_tokcount writes are relative to their sub-tile -- k_docoffs adds the
+// base --, so the kernel does not read it; the argument keeps the two launchers interchangeable where the launch sequence chooses between them)
+void launch_tokcount(const Launch& L, const EncodeParams& P, const int64_t* tile_base, const int32_t* dcount, int64_t nsub) {
+    (void)tile_base;
+    hook(L, K_GATHER, 0);
+    TKZ_LAUNCH(k_tokcount, xcd_grid(cdiv(nsub, (kThreads / 64) * kPlacePer)), kThreads, L.stream, P, dcount);
     hook(L, K_GATHER, 1);
 }
 void launch_doccount2(const Launch& L, const uint64_t* bits_a, const uint64_t* bits_b, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt_a, int32_t* cnt_b) {

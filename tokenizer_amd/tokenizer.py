@@ -263,6 +263,40 @@ class TikTokenizer:
             out_offs[d + 1] = w
         return out, out_offs
 
+    # ---- counts: Encode(...).Count without the ids ---------------------------------------------------
+    def CountTokens(self, text: str, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True) -> int:
+        """len(Encode(text, allowedSpecialOrApply)) from the device's count entry (tkz_count_utf8: one kernel launch for a prompt, no ids stored or copied), under
+        the conditions in which Encode takes the device's entries; where the device special path refuses the registered set, len(Encode(...))."""
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if plain or not (self._special_on_host or (self._fffd_literal and _has_lone_surrogate(text))):
+            names = set(allowed) if not plain else ()
+            index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+            try:
+                return self._encoder.count(_utf8_like_dotnet(text), index)
+            except N.UnsupportedError:
+                self._special_on_host = True
+        return len(self.Encode(text, allowedSpecialOrApply))
+
+    def CountTokensBatch(self, texts: Sequence[str], allowedSpecialOrApply: Union[bool, Sequence[str], None] = True) -> List[int]:
+        """[len(x) for x in EncodeBatch(texts, allowedSpecialOrApply)] from the device's batch count entry (tkz_count_batch_utf8): only the offsets come back."""
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not texts:
+            return []
+        if plain or not (self._special_on_host or (self._fffd_literal and any(_has_lone_surrogate(t) for t in texts))):
+            segs = [_utf8_like_dotnet(t) for t in texts]
+            offs = np.zeros(len(segs) + 1, np.int64)
+            np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+            data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+            names = set(allowed) if not plain else ()
+            index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+            try:
+                return np.diff(self._encoder.count_batch(data, offs, index)).tolist()
+            except N.UnsupportedError:
+                self._special_on_host = True
+        return [len(x) for x in self.EncodeBatch(texts, allowedSpecialOrApply)]
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
