@@ -1966,8 +1966,12 @@ TKZ_DEV PlaceLds tkz_place_lds(uint4* wave_quads) {
 // sub-tiles sub0 .. sub0 + kPlacePer - 1, by one wavefront
 // PROMO: the tables hold promoted pieces (tkz_tables.h): a hit record may carry a promo code instead of a rank -- its count is in the record, its
 // tokens are one 16-byte gather from P.promo.  The form without them is the kernel of every batch before the first promotion, instruction for instruction.
+// The seven per-sub-tile arrays of scalars come as restrict parameters of their own: nothing in here stores to them, and a compiler that is told so reads
+// them with scalar loads inside the loop too (a load behind the loop's stores is otherwise a vector load: ten vector registers a set, and a readfirstlane each).
 template <int SLOTS, bool PROMO, int STAGE>
-TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base, int32_t* out, int64_t out_cap, int64_t sub0, const PlaceLds& LD) {
+TKZ_DEV void tkz_place_subtiles_sc(const EncodeParams& P, int32_t* out, int64_t out_cap, int64_t sub0, const PlaceLds& LD,
+                                   const int64_t* __restrict__ pbase, const int64_t* __restrict__ tile_base, const int64_t* __restrict__ docord_base, const int32_t* __restrict__ pcount,
+                                   const uint32_t* __restrict__ mcount, const uint8_t* __restrict__ heavy_flag, const int32_t* __restrict__ giant_cnt) {
     constexpr int kPlaceSlots = SLOTS, kPlaceRes = SLOTS / 2, kStage = STAGE;
     const int lane = simt::lane();
     if (sub0 >= P.nsub) return;
@@ -1975,29 +1979,68 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
     uint32_t* s_res = LD.res;
     uint4* s_quad = LD.quad;
     int32_t* s_pos = LD.pos;
-    // A wavefront places kPlacePer consecutive sub-tiles, one after the other; what it needs to know about a sub-tile before it can ask for
-    // its records (seven wave-uniform words) is requested while the sub-tile before it is placed: one of the sub-tile's three dependent
-    // round trips leaves the chain.
+    // what a wavefront needs to know about a sub-tile before it can ask for its records and answers: seven wave-uniform words
     struct Sc { int64_t pb, tb, ord0; int np; uint32_t mc, hf; int gc; };
     auto load_sc = [&](int64_t sub) -> Sc {
         Sc c;
-        c.pb = P.pbase[sub]; c.tb = tile_base[sub]; c.ord0 = P.docord_base[sub]; c.np = P.pcount[sub]; c.mc = P.mcount[sub]; c.hf = P.heavy_flag[sub]; c.gc = P.giant_cnt[sub];
+        c.pb = pbase[sub]; c.tb = tile_base[sub]; c.ord0 = docord_base[sub]; c.np = pcount[sub]; c.mc = mcount[sub]; c.hf = heavy_flag[sub]; c.gc = giant_cnt[sub];
         return c;
     };
-    Sc nxt = load_sc(sub0);
-    // the lane's four records of the FIRST chunk of a sub-tile (records 4 * lane .. + 3: one 16-byte load)
+    // the lane's four records of a chunk of a sub-tile (records kk + 4 * lane .. + 3: one 16-byte load)
     auto load_recs = [&](int64_t pb_, int np_, int kk, uint32_t* r) {
+        // (a scalar base and a 32-bit lane offset: no 64-bit address or comparison a lane)
         const int k0 = kk + 4 * lane;
+        const int32_t* const recs = P.prank + pb_;
+        const int64_t room64 = P.prank_cap - pb_;
+        const int room = room64 < 0 ? 0 : room64 > (1 << 20) ? (1 << 20) : (int)room64;          // records of this sub-tile (at most 1,024) that the buffer holds
         r[0] = r[1] = r[2] = r[3] = 0u;
         if (k0 < np_) {
-            if (pb_ + k0 + 4 <= P.prank_cap) { const uint4 v = tkz_load16_nt(&P.prank[pb_ + k0]); r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; }
-            else for (int j = 0; j < 4; ++j) if (pb_ + k0 + j < P.prank_cap) r[j] = (uint32_t)P.prank[pb_ + k0 + j];
+            if (k0 + 4 <= room) { const uint4 v = tkz_load16_nt(&recs[(uint32_t)k0]); r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; }
+            else for (int j = 0; j < 4; ++j) if (k0 + j < room) r[j] = (uint32_t)recs[(uint32_t)(k0 + j)];
         }
     };
+    // which list entries of a sub-tile are kept in LDS, from its miss counts alone (all wave-uniform): slots 0 .. ks-1 hold the first ks entries
+    // of the short list, slots top .. top-kl+1 the first kl of the long one
+    static_assert(SLOTS == 64 || SLOTS == 128, "one or two kept entries per lane: slots lane and lane + 64");
+    struct Kept { int ks, kl, top; bool two, lists_ok; };
+    auto kept_of = [&](uint32_t mc_) -> Kept {
+        const int ns_ = (int)(mc_ & 0xFFFFu), nl_ = (int)(mc_ >> 16);
+        Kept k;
+        k.lists_ok = ns_ + nl_ <= P.mcap;                     // (cut lists: the batch is redone, nothing of this pass is used)
+        k.kl = ns_ + nl_ <= kPlaceSlots ? nl_ : (nl_ < kPlaceRes ? nl_ : kPlaceRes);
+        k.ks = ns_ < kPlaceSlots - k.kl ? ns_ : kPlaceSlots - k.kl;
+        k.two = SLOTS == 128 && k.ks + k.kl > 64;             // (wave-uniform: the second slot of every lane is in use; never with 64 slots)
+        k.top = k.two ? kPlaceSlots - 1 : 63;                 // entry e of the long list is kept in slot top - e
+        return k;
+    };
+    // the answer and the quad of the entry kept in slot lane + 64 * h of sub-tile sub_ (zero where the slot keeps none)
+    auto load_ans = [&](int64_t sub_, const Kept& k, int h, uint32_t& a, uint4& qd) {
+        a = 0u; qd.x = qd.y = qd.z = qd.w = 0;
+        const int slot = lane + 64 * h;
+        const bool shortside = slot < k.ks;
+        const int e = shortside ? slot : k.top - slot;
+        const bool want = k.lists_ok && (shortside || e < k.kl);
+        const uint32_t at = (uint32_t)((shortside ? e : P.mcap - 1 - e) & (kMissCapMax - 1));
+        const uint32_t* const ml_ = P.mlist + sub_ * (int64_t)P.mcap;
+        const uint4* const mqd_ = P.mquad + sub_ * (int64_t)P.mcap;
+        if (want) { a = tkz_load_nt(&ml_[at]); qd = tkz_load16_nt(&mqd_[at]); }
+    };
+    // A wavefront places kPlacePer consecutive sub-tiles, one after the other.  A sub-tile's answers and its first 256 records are requested together at its top,
+    // ahead of the LDS fill (one round trip), and then the seven scalars of the sub-tile behind it, which arrive while this one is placed.  (Requesting records
+    // and answers a whole sub-tile ahead, in registers, was built and measured and is not here: profiles/place_pipeline.)
+    Sc nxt = load_sc(sub0);
 #pragma unroll 1
     for (int it = 0; it < kPlacePer && sub0 + it < P.nsub; ++it) {
     const int64_t sub = sub0 + it;
-    const Sc cur = nxt;
+    // (k_small's scalars come through vector loads -- they were stored by this very kernel --: told that they are uniform, they leave the vector registers here)
+    Sc cur;
+    cur.pb = (int64_t)simt::uniform64((uint64_t)nxt.pb); cur.tb = (int64_t)simt::uniform64((uint64_t)nxt.tb); cur.ord0 = (int64_t)simt::uniform64((uint64_t)nxt.ord0);
+    cur.np = simt::first_lane(nxt.np); cur.mc = (uint32_t)simt::first_lane((int)nxt.mc); cur.hf = (uint32_t)simt::first_lane((int)nxt.hf); cur.gc = simt::first_lane(nxt.gc);
+    const Kept kp = kept_of(cur.mc);
+    uint32_t a[2] = {0u, 0u}, r_cur[4];
+    uint4 qd[2];
+    load_ans(sub, kp, 0, a[0], qd[0]);
+    load_recs(cur.pb, cur.np, 0, r_cur);
     if (it + 1 < kPlacePer && sub + 1 < P.nsub) nxt = load_sc(sub + 1);
     const int64_t pb = cur.pb, tb = cur.tb, base = sub * kSub, ord0 = cur.ord0;
     const int np = cur.np;
@@ -2009,32 +2052,15 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
     const bool has_giant = (cur.hf & 2u) != 0;
     int gcnt = has_giant ? cur.gc : 0;
     if (gcnt < 0) gcnt = 0;
-    const bool lists_ok = ns + nl <= P.mcap;               // (cut lists: the batch is redone, nothing of this pass is used)
-    // the answers of the merge kernels, in the same round trip as the first records
-    // slot = lane: slots 0 .. ks-1 hold the first ks entries of the short list, slots 63 .. 64-kl the first kl of the long one
-    static_assert(SLOTS == 64 || SLOTS == 128, "one or two kept entries per lane: slots lane and lane + 64");
-    const int kl = ns + nl <= kPlaceSlots ? nl : (nl < kPlaceRes ? nl : kPlaceRes), ks = ns < kPlaceSlots - kl ? ns : kPlaceSlots - kl;
-    const bool two = SLOTS == 128 && ks + kl > 64;         // (wave-uniform: the second slot of every lane is in use; never with 64 slots)
-    const int top = two ? kPlaceSlots - 1 : 63;           // entry e of the long list is kept in slot top - e
+    const bool lists_ok = kp.lists_ok;
+    const int kl = kp.kl, ks = kp.ks, top = kp.top;
+    const bool two = kp.two;
     bool fast_ok;
     {
-        // slot s holds entry s of the short list (s < ks) or entry top - s of the long one (s > top - kl); lane l loads slot l and -- only when
-        // more than 64 entries are kept (top = 127 then, else 63) -- slot l + 64
-        uint32_t a[2] = {0u, 0u};
-        uint4 qd[2];
-        bool big = false;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            qd[h].x = qd[h].y = qd[h].z = qd[h].w = 0;
-            if (h == 1 && !two) break;
-            const int slot = lane + 64 * h;
-            const bool shortside = slot < ks;
-            const int e = shortside ? slot : top - slot;
-            const bool want = lists_ok && (shortside || e < kl);
-            const int64_t at = shortside ? e : P.mcap - 1 - e;
-            if (want) { a[h] = tkz_load_nt(&ml[at]); qd[h] = tkz_load16_nt(&mqd[at]); }
-            big = big || (want && tkz_result_cnt(a[h]) > kPlaceFastBig);
-        }
+        // lane l fills slot l and -- only when more than 64 entries are kept (top = 127 then, else 63) -- slot l + 64, whose entry is loaded here
+        qd[1].x = qd[1].y = qd[1].z = qd[1].w = 0;
+        if (two) load_ans(sub, kp, 1, a[1], qd[1]);
+        const bool big = tkz_result_cnt(a[0]) > kPlaceFastBig || tkz_result_cnt(a[1]) > kPlaceFastBig;
         (void)simt::ballot(true);                                // (the sub-tile before this one is done with them)
         s_res[lane] = a[0]; s_quad[lane] = qd[0]; s_pos[lane] = -1;
         if constexpr (SLOTS == 128) { s_res[lane + 64] = a[1]; s_quad[lane + 64] = qd[1]; s_pos[lane + 64] = -1; }
@@ -2068,16 +2094,20 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
     auto flush = [&](int upto) {                             // stores tokens [flushed, upto) of the sub-tile
         (void)simt::ballot(true);
         const int lo = flushed - sbase, hi = upto - sbase;
+        // (wave-uniform, and said to be: a lane adds a 32-bit offset to a scalar base -- left to itself the compiler keeps out + 16 * lane in two vector registers across the loop)
+        int32_t* const obase = reinterpret_cast<int32_t*>(simt::uniform64(reinterpret_cast<uintptr_t>(out + tb + sbase)));
+        const int64_t oroom64 = out_cap - tb - sbase;
+        const int oroom = oroom64 < 0 ? 0 : oroom64 > (1 << 20) ? (1 << 20) : (int)oroom64;      // ids of the stage (a few thousand at most) that `out` has room for
         for (int q4 = lane; 4 * q4 < hi; q4 += 64) {
             const int i0 = 4 * q4;
             if (i0 + 4 <= lo) continue;
             const uint4 v = reinterpret_cast<const uint4*>(stage)[q4];
-            int32_t* dst = out + tb + sbase + i0;
-            if (i0 >= lo && i0 + 4 <= hi && tb + sbase + i0 + 4 <= out_cap) tkz_store16_nt(dst, v);
+            int32_t* dst = obase + (uint32_t)i0;
+            if (i0 >= lo && i0 + 4 <= hi && i0 + 4 <= oroom) tkz_store16_nt(dst, v);
             else {
                 const int32_t w[4] = {(int32_t)v.x, (int32_t)v.y, (int32_t)v.z, (int32_t)v.w};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) if (i0 + i >= lo && i0 + i < hi && tb + sbase + i0 + i < out_cap) dst[i] = w[i];
+                for (int i = 0; i < 4; ++i) if (i0 + i >= lo && i0 + i < hi && i0 + i < oroom) dst[i] = w[i];
             }
         }
         (void)simt::ballot(true);
@@ -2088,10 +2118,14 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
     // mostly per-batch overhead.  A record's token count comes from LDS without a branch (a hit reads the "one token" slot); the
     // tokens of a missed piece are written by the lane that OWNS its list entry's slot (slot e: entry e of the short list, slot top - e: entry e
     // of the long one; lane l owns slots l and l + 64): the lane that holds the record only tells it the position. ----
+    const int64_t room64 = P.prank_cap - pb;
+    const int nrec = room64 < np ? (room64 < 0 ? 0 : (int)room64) : np;       // the sub-tile's records that the buffer holds: all of them, unless the attempt is one to be thrown away
+    int32_t* const doc_tok = P.doc_tok + ord0;
+    int32_t* const otile = reinterpret_cast<int32_t*>(simt::uniform64(reinterpret_cast<uintptr_t>(out + tb)));      // (the general path's direct stores: a scalar base too)
     auto place_fast = [&](int kk) -> bool {
         const int k0 = kk + 4 * lane;
-        uint32_t r[4];
-        load_recs(pb, np, kk, r);
+        uint32_t r[4] = {r_cur[0], r_cur[1], r_cur[2], r_cur[3]};     // the first chunk's were requested with the answers
+        if (kk) load_recs(pb, np, kk, r);
         int c[4], idx[4];
         bool ok[4], ms[4], pm[4];
         uint4 pq0;                                               // the token quad of the lane's FIRST promoted record
@@ -2099,7 +2133,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
         int t = 0, mk = 0;
         if constexpr (PROMO) {
 #pragma unroll
-            for (int j = 3; j >= 0; --j) { pm[j] = k0 + j < np && pb + k0 + j < P.prank_cap && !(r[j] & kPrMiss) && (r[j] & kPromoFlag); if (pm[j]) pj = j; }
+            for (int j = 3; j >= 0; --j) { pm[j] = k0 + j < nrec && !(r[j] & kPrMiss) && (r[j] & kPromoFlag); if (pm[j]) pj = j; }
             // One promoted piece in a hundred: a lane's four records hold one at most, nearly always.  ITS quad is requested here, ahead of the scan, and its
             // tokens are staged after the missed pieces' below -- the round trip to the promo array overlaps both (four registers across them; all four
             // records' quads, requested after the scan and waited for at once, were a dependent round trip per 256 records: 1.0 of k_place's 4.75 ms).  A
@@ -2108,7 +2142,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            ok[j] = k0 + j < np && pb + k0 + j < P.prank_cap;
+            ok[j] = k0 + j < nrec;
             ms[j] = ok[j] && (r[j] & kPrMiss);
             idx[j] = ((r[j] & kPrLong) ? top - (int)(r[j] & 1023u) : (int)(r[j] & 1023u)) & (kPlaceSlots - 1);     // the slot of the piece's list entry
             const uint32_t a = s_res[ms[j] ? idx[j] : kPlaceSlots];
@@ -2127,7 +2161,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
         int pos = running + (pre & 0xFFFFF), mi = marks + (pre >> 20);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (ok[j] && (r[j] & kPrMark)) P.doc_tok[ord0 + mi++] = pos;
+            if (ok[j] && (r[j] & kPrMark)) doc_tok[(uint32_t)mi++] = pos;
             if (ms[j]) s_pos[idx[j]] = pos;
             else if (PROMO && pm[j]) {
                 if (j == pj) { pdst = pos - sbase; pcnt = c[j]; }
@@ -2188,8 +2222,8 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
         const int k0 = kk + 64 * j;
         if (k0 >= np) break;
         const int k = k0 + lane;
-        const bool valid = k < np && pb + k < P.prank_cap;
-        const uint32_t rec = valid ? (uint32_t)tkz_load_nt(&P.prank[pb + k]) : 0u;
+        const bool valid = k < nrec;
+        const uint32_t rec = valid ? (uint32_t)tkz_load_nt(&(P.prank + pb)[(uint32_t)k]) : 0u;
         const uint32_t res = (rec & kPrMiss) ? answer(rec) : 0u;           // the merge kernels' answer for a missed piece
         const bool miss = (rec & kPrMiss) != 0;
         const bool promoted = PROMO && valid && !miss && (rec & kPromoFlag);
@@ -2199,7 +2233,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
         int tot;
         const int pos = running + tkz_wave_scan_sum(cnt, &tot);
         const uint64_t mm = simt::ballot(valid && (rec & kPrMark));
-        if (valid && (rec & kPrMark)) P.doc_tok[ord0 + marks + tkz_popc64(mm & tkz_lowmask(lane))] = pos;
+        if (valid && (rec & kPrMark)) doc_tok[(uint32_t)(marks + tkz_popc64(mm & tkz_lowmask(lane)))] = pos;
         const uint64_t big = simt::ballot(valid && miss && cnt > kPlaceBig);
         if (!big) {
             if (running + tot - sbase > kStage) flush(running);
@@ -2229,7 +2263,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
             flush(running);
             const int32_t* src = (miss && !(res & kMrInline)) ? token_src(res) : nullptr;
             if (valid) {
-                int32_t* dst = out + tb + pos;
+                int32_t* dst = otile + (uint32_t)pos;
                 if (promoted) {
                     const int32_t w[4] = {(int32_t)pquad.x, (int32_t)pquad.y, (int32_t)pquad.z, (int32_t)pquad.w};
 #pragma unroll
@@ -2250,7 +2284,7 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
                 const int c = simt::shfl(cnt, src_lane), p0 = simt::shfl(pos, src_lane);
                 const uint32_t lo32 = simt::shflu((uint32_t)(reinterpret_cast<uintptr_t>(src)), src_lane), hi32 = simt::shflu((uint32_t)(reinterpret_cast<uintptr_t>(src) >> 32), src_lane);
                 const int32_t* bsrc = reinterpret_cast<const int32_t*>(((uintptr_t)hi32 << 32) | lo32);
-                int32_t* dst = out + tb + p0;
+                int32_t* dst = otile + (uint32_t)p0;
                 for (int i = lane; i < c; i += 64) if (tb + p0 + i < out_cap) dst[i] = bsrc[i];
             }
             flushed = running + tot; sbase = quad_base(flushed);
@@ -2262,8 +2296,13 @@ TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base,
     if (flushed < running) flush(running);
     }
 }
+template <int SLOTS, bool PROMO, int STAGE>
+TKZ_DEV void tkz_place_subtiles(const EncodeParams& P, const int64_t* tile_base, int32_t* out, int64_t out_cap, int64_t sub0, const PlaceLds& LD) {
+    tkz_place_subtiles_sc<SLOTS, PROMO, STAGE>(P, out, out_cap, sub0, LD, P.pbase, tile_base, P.docord_base, P.pcount, P.mcount, P.heavy_flag, P.giant_cnt);
+}
+// (the 128-slot form's LDS, 24.9 KB a workgroup, admits six workgroups a CU: its bound says so)
 template <int SLOTS, bool PROMO>
-TKZ_KERNEL_OCC(256, TKZ_PLACE_OCC) void k_place(EncodeParams P, const int64_t* tile_base, int32_t* out, int64_t out_cap) {
+TKZ_KERNEL_OCC(256, SLOTS == 128 && TKZ_PLACE_OCC > 6 ? 6 : TKZ_PLACE_OCC) void k_place(EncodeParams P, const int64_t* tile_base, int32_t* out, int64_t out_cap) {
     if (tkz_attempt_failed(P)) return;
     TKZ_SHARED uint4 s_wave[kThreads / 64][kPlaceLdsQuadsT<SLOTS, kStageBatch>];
     const int64_t sub0 = (tkz_xcd_block(simt::bid(), simt::nblocks()) * (kThreads / 64) + simt::wave()) * kPlacePer;
