@@ -60,6 +60,10 @@ namespace Microsoft.DeepDev
         [DllImport(Lib)] internal static extern unsafe int tkz_count_batch_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
                                                                                   long* outOffsets, out long totalTokens);
         [DllImport(Lib)] internal static extern void tkz_encoder_count_calls(IntPtr encoder, out long calls, out long singleLaunch);
+        // token spans: Encode, and where every token's text starts in the string, in code units (include/tkz.h, "Token spans")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_spans_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                         int* outIds, long outCap, long* outOffsets, int* tokUnits, out long needed);
+        [DllImport(Lib)] internal static extern void tkz_encoder_spans_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -363,6 +367,47 @@ namespace Microsoft.DeepDev
             var lists = EncodeBatch(texts, allowedSpecial);
             for (int t = 0; t < texts.Count; ++t) counts[t] = lists[t].Count;
             return counts;
+        }
+
+        /// <summary>Encode(text, allowedSpecial) and, per token, the index in <paramref name="text"/> (chars, i.e. UTF-16 code units) where the token's text starts --
+        /// EncodeToTokens' Offset.  Token t is text[starts[t] .. starts[t + 1]), the last one ends at text.Length.  A token that starts inside a character (byte-level
+        /// BPE splits emoji and CJK under an English vocabulary) starts AFTER that character's chars, and a token of continuation bytes only has an empty span.
+        /// ONE call of tkz_encode_batch_spans_utf16.  A registered set the device path does not hold is NotImplementedException (-7): there is no host path.</summary>
+        public (List<int> Ids, List<int> Starts) EncodeWithOffsets(string text, IReadOnlyCollection<string>? allowedSpecial = null)
+        {
+            var (ids, starts) = EncodeWithOffsetsBatch(new[] { text }, allowedSpecial);
+            return (ids[0], starts[0]);
+        }
+
+        /// <summary>EncodeWithOffsets for every text: the strings' chars go to tkz_encode_batch_spans_utf16 as they are (copied into one char[] with string.CopyTo).</summary>
+        public unsafe (List<List<int>> Ids, List<List<int>> Starts) EncodeWithOffsetsBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial = null)
+        {
+            var outIds = new List<List<int>>(texts.Count);
+            var outStarts = new List<List<int>>(texts.Count);
+            if (texts.Count == 0) return (outIds, outStarts);
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            var units = new char[Math.Max(1, unitOffsets[texts.Count])];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = Math.Max(1, 3 * unitOffsets[texts.Count]);              // a token per byte, a char is at most three bytes
+            var ids = new int[cap];
+            var starts = new int[cap];
+            var offsets = new long[texts.Count + 1];
+            int st;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (int* ps = starts) fixed (long* pt = offsets)
+                st = Tkz.tkz_encode_batch_spans_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, pi, cap, pt, ps, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            for (int t = 0; t < texts.Count; ++t)
+            {
+                int lo = checked((int)offsets[t]), n = checked((int)(offsets[t + 1] - offsets[t]));
+                var li = new List<int>(n); li.AddRange(new ArraySegment<int>(ids, lo, n));
+                var ls = new List<int>(n); ls.AddRange(new ArraySegment<int>(starts, lo, n));
+                outIds.Add(li); outStarts.Add(ls);
+            }
+            return (outIds, outStarts);
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

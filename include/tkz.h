@@ -329,6 +329,46 @@ tkz_status tkz_count_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, co
 /* informational: successful count calls, and those of them the single-launch kernel answered */
 void tkz_encoder_count_calls(const tkz_encoder* e, int64_t* calls, int64_t* single_launch);
 
+/* ---- Token spans: which part of the text is token t (offset_mapping, decode_with_offsets, EncodeToTokens' Offset) ----
+ * The ids and out_offsets (n_docs + 1 entries) are EXACTLY those of the matching encode entry for the same arguments -- tkz_encode_batch_special_* when n_allowed > 0
+ * and literals are registered, the plain entry otherwise.  For document d with tokens out_offsets[d] .. out_offsets[d + 1], token t also gets
+ *   tok_bytes[t] (int32)  the offset of the token's first byte from the start of ITS DOCUMENT, in the document's UTF-8 form.  The spans partition the document: its
+ *                         first token has 0, token t ends where t + 1 starts, the last one ends at the document's length, and the bytes in between are the
+ *                         vocabulary key of ids[t] (the literal, for an allowed special token);
+ *   tok_units[t] (int32)  the same position in UTF-16 code units, by the rule of cut_units (tkz_encode_batch_trim_device): the number of units BEGUN in
+ *                         [document start, token start) -- one per non-continuation byte and one more per byte >= 0xF0.  So
+ *                           - a token that starts inside a multi-byte character (byte-level BPE does that to emoji and CJK under an English vocabulary) starts
+ *                             AFTER that character's units: for F0 9F 98 80 split into several tokens the first token carries both units;
+ *                           - a token made of continuation bytes only has an EMPTY unit span (it starts where the next token starts);
+ *                           - (UTF-16 entries) a lone surrogate, which the transcoder replaced by EF BF BD, counts as the one unit it is.
+ * Either array may be NULL, not both (TKZ_E_ARG); each has out_cap entries, as the ids have.  A document of 2^31 bytes or more is TKZ_E_UNSUPPORTED for these
+ * entries only: the host entries see it in the offsets, the device entry learns it from the device, like its other device-side errors.
+ *   tkz_encode_batch_spans_device: device buffers.  Errors, retries, workspace growth and TKZ_E_CAPACITY (*total_tokens the required count, nothing promised in
+ *     the outputs) as tkz_encode_batch_trim_device; allowed / n_allowed and tkz_encoder_special_stats as tkz_encode_batch_special_device.  An empty batch clears
+ *     d_out_offsets on the stream.  The launch sequence is the piece-granular one of the trim entry (it waits once, inside, for the number of pieces), the ids go
+ *     straight into d_out_ids; behind it k_tokspan_mark, k_tokspan_count, two scans and k_tokspan_write.  Workspace beyond the trim entry's piece arrays: a bit per
+ *     input byte and 24 bytes per KiB.  One lane walks the ids of a piece of several tokens: a single piece of many megabytes is walked by one lane.
+ *   tkz_encode_batch_spans_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as tkz_encode_batch_trim_utf8:
+ *     no chunk pipeline, no single-launch route.
+ *   tkz_encode_batch_spans_utf16: code units in, transcoded on the device as tkz_encode_batch_trim_utf16; unit_offsets and tok_units in code units.  There is no
+ *     tok_bytes: the bytes never exist on the host.  Literals that hold U+FFFD as in the other UTF-16 special entries.
+ *   tkz_encode_spans_utf8 / _utf16: ONE text -- the batch entry with one document, at every size.  TKZ_E_ARG for a negative len or a null n_out; *n_out is the
+ *     required count on TKZ_E_CAPACITY.
+ * There is no _begin / _end form. */
+tkz_status tkz_encode_batch_spans_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                         const int32_t* allowed, int32_t n_allowed, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                         int32_t* d_tok_bytes, int32_t* d_tok_units, void* hip_stream, int64_t* total_tokens);
+tkz_status tkz_encode_batch_spans_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int32_t* tok_bytes, int32_t* tok_units, int64_t* needed);
+tkz_status tkz_encode_batch_spans_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int32_t* tok_units, int64_t* needed);
+tkz_status tkz_encode_spans_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                 int32_t* tok_bytes, int32_t* tok_units, int64_t* n_out);
+tkz_status tkz_encode_spans_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                  int32_t* tok_units, int64_t* n_out);
+/* informational: successful calls of the span entries */
+void tkz_encoder_spans_calls(const tkz_encoder* e, int64_t* calls);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -480,6 +520,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * kernel since the last reset (arrays of TKZ_K_COUNT).  Not inside any bracket (microseconds each): the fill of the workspace's zero region,
  * k_doccount2 and the scan of its counts, k_list_stats (which also finds the giant pieces and fills k_merge_coop's queue); of a trim call
  * (tkz_encode_batch_trim_device) k_trim_cut, the scan of the kept lengths and k_trim_gather, which run behind TKZ_K_DOCOFFS.
+ * Of a span call (tkz_encode_batch_spans_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the pieces AND the span stage behind it (the fill of the interior
+ * bitmap, k_tokspan_mark, k_tokspan_count, two scans, k_tokspan_write): the closing event is recorded again behind the stage.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

@@ -5,6 +5,7 @@
 //                              EncodeBatchFlat: (ids, offsets) in page-locked buffers that are kept from call to call (tkz::FlatBatch)
 //                              EncodeTrimSuffix / EncodeTrimPrefix x2   ITokenizer.cs:30-44, TikTokenizer.cs:288-579
 //                              CountTokens / CountTokensBatch (+ Utf16): Encode(...).Count from the device's count entries, no ids
+//                              EncodeWithOffsets / EncodeWithOffsetsBatch (+ Utf16): Encode, and where every token's text starts (bytes / code units)
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -481,6 +482,29 @@ public:
         for (size_t t = 0; t < texts.size(); ++t) counts[t] = static_cast<int64_t>(ids[t].size());
         return counts;
     }
+    // ---- token spans: Encode, and where every token's text starts (tkz_encode_spans_utf8 / _utf16, tkz_encode_batch_spans_utf8 / _utf16) ----
+    // std::string: offsets in BYTES of the text, whose spans are exactly the tokens' keys; std::u16string: offsets in CODE UNITS -- a token that starts inside a
+    // character starts after that character's units, one of continuation bytes only has an empty span (tkz.h).  Token t is [starts[t], starts[t + 1]), the last
+    // one ends at the text's length.  A registered set the device's special entries do not hold is a NotImplementedError here: there is no host path.
+    struct TokenSpans { std::vector<int32_t> ids; std::vector<int32_t> starts; };
+    TokenSpans EncodeWithOffsets(const std::string& text, const std::vector<std::string>& allowedSpecial = {}) const {
+        return std::move(EncodeWithOffsetsBatch(std::vector<std::string>{text}, allowedSpecial)[0]);
+    }
+    std::vector<TokenSpans> EncodeWithOffsetsBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial = {}) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return spans_batch<uint8_t>(bytes, offs, allowedSpecial, false);
+    }
+    TokenSpans EncodeWithOffsetsUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial = {}) const {
+        return std::move(EncodeWithOffsetsBatchUtf16(std::vector<std::u16string>{text}, allowedSpecial)[0]);
+    }
+    std::vector<TokenSpans> EncodeWithOffsetsBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial = {}) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return spans_batch<uint16_t>(units, offs, allowedSpecial, true);
+    }
     // (one string: tkz_encode_trim_utf16, the single-text trim entry)
     Trimmed16 EncodeTrimSuffixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         Trimmed16 out;
@@ -638,6 +662,31 @@ private:
         check(st);
         ids.resize(static_cast<size_t>(n));
         return true;
+    }
+    // ONE call of the batch span entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a TokenSpans per text
+    template <class UNIT>
+    std::vector<TokenSpans> spans_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, const std::vector<std::string>& allowedSpecial, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        std::vector<TokenSpans> out(static_cast<size_t>(n));
+        if (n == 0) return out;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = std::max<int64_t>(1, static_cast<int64_t>(items.size()) * (utf16 ? 3 : 1));      // (a token per byte; a unit is at most three bytes)
+        if (items.empty()) items.push_back(0);
+        std::vector<int32_t> ids(static_cast<size_t>(cap)), starts(static_cast<size_t>(cap));
+        std::vector<int64_t> ooff(static_cast<size_t>(n) + 1, 0);
+        int64_t needed = 0;
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_spans_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()),
+                                                     ids.data(), cap, ooff.data(), starts.data(), &needed);
+        else st = tkz_encode_batch_spans_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()),
+                                              ids.data(), cap, ooff.data(), starts.data(), nullptr, &needed);
+        check(st);
+        for (int64_t d = 0; d < n; ++d) {
+            out[static_cast<size_t>(d)].ids.assign(ids.begin() + ooff[d], ids.begin() + ooff[d + 1]);
+            out[static_cast<size_t>(d)].starts.assign(starts.begin() + ooff[d], starts.begin() + ooff[d + 1]);
+        }
+        return out;
     }
     std::vector<int32_t> allowed_index(const std::vector<std::string>& allowedSpecial) const {
         std::vector<int32_t> index;

@@ -173,6 +173,13 @@ class Library:
         L.tkz_count_utf16.argtypes = [vp, vp, i64, vp, i32, pi64]
         L.tkz_encoder_count_calls.argtypes = [vp, pi64, pi64]
         L.tkz_encoder_count_calls.restype = None
+        L.tkz_encode_batch_spans_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, vp, i64, vp, vp, vp, vp, pi64]
+        L.tkz_encode_batch_spans_utf8.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, vp, vp, pi64]
+        L.tkz_encode_batch_spans_utf16.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, vp, pi64]
+        L.tkz_encode_spans_utf8.argtypes = [vp, vp, i64, vp, i32, vp, i64, vp, vp, pi64]
+        L.tkz_encode_spans_utf16.argtypes = [vp, vp, i64, vp, i32, vp, i64, vp, pi64]
+        L.tkz_encoder_spans_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_spans_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -707,6 +714,104 @@ class Encoder:
         a, b = C.c_int64(0), C.c_int64(0)
         self.lib.L.tkz_encoder_count_calls(self._h, C.byref(a), C.byref(b))
         return a.value, b.value
+
+    # -- token spans: the ids, and where every token's text starts in its document --
+    def encode_batch_spans(self, data: np.ndarray, offsets: np.ndarray, allowed=(), want_bytes=True, want_units=True, out_cap=None):
+        """(ids int32, offsets int64[n+1], tok_bytes int32 or None, tok_units int32 or None): the ids and offsets of encode_batch / encode_batch_special and, per
+        token, the document-relative position of its first byte and the same position in UTF-16 code units: tkz_encode_batch_spans_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = len(data) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        tb = np.empty(max(1, cap), np.int32) if want_bytes else None
+        tu = np.empty(max(1, cap), np.int32) if want_units else None
+        ooff = np.empty(n + 1, np.int64)
+        needed = C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_spans_utf8(self._h, _ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None,
+                                                                  len(allowed), _ptr(ids), cap, _ptr(ooff), _ptr(tb) if want_bytes else None,
+                                                                  _ptr(tu) if want_units else None, C.byref(needed)))
+        except TkzError as ex:
+            ex.needed = needed.value                          # (E_CAPACITY: the required count)
+            raise
+        k = needed.value
+        return ids[:k], ooff, tb[:k] if want_bytes else None, tu[:k] if want_units else None
+
+    def encode_batch_spans_utf16(self, units: np.ndarray, offsets: np.ndarray, allowed=(), out_cap=None):
+        """encode_batch_spans for UTF-16 documents (uint16[total], offsets in units): (ids, offsets, tok_units) -- tkz_encode_batch_spans_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = 3 * len(units) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        tu = np.empty(max(1, cap), np.int32)
+        ooff = np.empty(n + 1, np.int64)
+        needed = C.c_int64(0)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_spans_utf16(self._h, _ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed),
+                                                                   _ptr(ids), cap, _ptr(ooff), _ptr(tu), C.byref(needed)))
+        except TkzError as ex:
+            ex.needed = needed.value
+            raise
+        return ids[:needed.value], ooff, tu[:needed.value]
+
+    def encode_batch_spans_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, d_out_ids, out_cap, d_out_offsets, d_tok_bytes=0, d_tok_units=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_spans_device.  Returns the token total; a TkzError carries it as `needed`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot = C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_spans_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                    len(allowed), d_out_ids or None, out_cap, d_out_offsets or None, d_tok_bytes or None,
+                                                                    d_tok_units or None, stream or None, C.byref(tot)))
+        except TkzError as ex:
+            ex.needed = tot.value
+            raise
+        return tot.value
+
+    def encode_spans(self, text: bytes, allowed=(), want_bytes=True, want_units=True, out_cap=None):
+        """ONE text: (ids, tok_bytes or None, tok_units or None) as lists -- tkz_encode_spans_utf8."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        cap = len(text) if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        tb = np.empty(max(1, cap), np.int32) if want_bytes else None
+        tu = np.empty(max(1, cap), np.int32) if want_units else None
+        n = C.c_int64(0)
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_spans_utf8(self._h, _ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed), _ptr(ids), cap,
+                                                            _ptr(tb) if want_bytes else None, _ptr(tu) if want_units else None, C.byref(n)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
+        k = n.value
+        return ids[:k].tolist(), tb[:k].tolist() if want_bytes else None, tu[:k].tolist() if want_units else None
+
+    def encode_spans_utf16(self, units, allowed=(), out_cap=None):
+        """The same for a .NET `string` given as its UTF-16 code units: (ids, tok_units) -- tkz_encode_spans_utf16."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n_units = len(u) - 1
+        cap = 3 * n_units if out_cap is None else out_cap
+        ids = np.empty(max(1, cap), np.int32)
+        tu = np.empty(max(1, cap), np.int32)
+        n = C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_spans_utf16(self._h, _ptr(u), n_units, _ptr(allowed) if len(allowed) else None, len(allowed), _ptr(ids), cap, _ptr(tu),
+                                                             C.byref(n)))
+        except TkzError as ex:
+            ex.needed = n.value
+            raise
+        return ids[:n.value].tolist(), tu[:n.value].tolist()
+
+    def spans_calls(self):
+        """successful calls of the span entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_spans_calls(self._h, C.byref(a))
+        return a.value
 
     def set_special_tokens(self, specials):
         """specials: {literal str: id}.  Registers SpecialTokensDecoder for Decode (TikTokenizer.cs:79) and, in this order, the literals the special

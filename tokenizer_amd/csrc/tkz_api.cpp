@@ -148,6 +148,10 @@ struct TrimBufs {   // the trim entries: the untrimmed ids, {kept token range, c
     DevBuf t_ids, t_keep, t_bsum, t_stage;
     void release() { release_each({&t_ids, &t_keep, &t_bsum, &t_stage}); }
 };
+struct SpanBufs {   // the span entries: the interior token starts, {token starts, begun units} per sub-tile and their scans (+ the two totals); the host entries' two span arrays
+    DevBuf sp_intbits, sp_cnt, sp_base, sp_stage;
+    void release() { release_each({&sp_intbits, &sp_cnt, &sp_base, &sp_stage}); }
+};
 // The UTF-16 batch entry points: code units, their document marks, per-tile / per-group lengths (two sets: the units of chunk k+1 are uploaded and measured while
 // chunk k is encoded), the UTF-8 batch they become and its byte offsets (u16_measure / u16_write)
 struct U16Stage {
@@ -204,7 +208,7 @@ struct tkz_vocab { tkz::Vocab v; };
 // call, so host threads sharing one encoder run concurrently, each on its own workspace and streams ("one encoder
 // usable from many host threads") -- the reference's instance is likewise safe to share (its only shared mutable state, the LRU
 // memo, is locked: LRUCache.cs:61,99).
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs {
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -253,7 +257,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -294,6 +298,7 @@ struct tkz_encoder {
     bool lit_fffd = false;                 // a registered literal holds U+FFFD (TkzLitTable's second 256-bit set is not empty)
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
+    std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
     std::atomic<int64_t> count_calls{0}, count_single{0};                  // tkz_encoder_count_calls: successful count calls, and those of them that took the single launch
     int64_t bytes_allocated = 0;           // tables
     std::atomic<int64_t> last_xcount{0}, last_xcount2{0};   // tkz_encoder_pretok_leftovers
@@ -337,6 +342,8 @@ struct SpecialCall { tkz::TkzLitAllowed allowed; bool fffd = false; };      // f
 struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piece; int64_t piece_cap; int64_t n_pieces; };
 // A call of one of the trim entries: the side, the maximum (uniform, or one per document on the device) and where the cut of every document goes (device, may be null)
 struct TrimCall { int32_t side; int64_t max_tokens; const int64_t* d_max; int64_t* d_cut_bytes; int64_t* d_cut_units; };
+// A call of one of the span entries: where the byte and the UTF-16 unit position of every token go (device, out_cap entries each; either may be null, not both)
+struct SpanCall { int32_t* d_tok_bytes; int32_t* d_tok_units; };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -345,7 +352,8 @@ enum class CallKind {
     OnePiecePerDoc,  // tkz_encode_pieces: no pre-tokenizer, every "document" is one piece
     BitmapOnly,      // tkz_pretokenize_utf8: the piece-start bitmap and nothing else
     Pieces,          // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
-    Trim             // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
+    Trim,            // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
+    Spans            // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -359,6 +367,7 @@ struct BatchCall {
     PiecesOut* pieces = nullptr;               // Pieces: where the piece arrays go
     const SpecialCall* special = nullptr;      // the special entries (an ordinary encode or a trim call); null: no literal is looked for
     const TrimCall* trim = nullptr;            // Trim: what to keep (pieces then points at the workspace's piece arrays)
+    const SpanCall* spans = nullptr;           // Spans: where the positions go (pieces points at the workspace's piece arrays as well)
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -367,7 +376,7 @@ struct BatchCall {
     bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || kind == CallKind::Trim ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || kind == CallKind::Trim || kind == CallKind::Spans ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -685,7 +694,7 @@ tkz_status drop_promotions(tkz_encoder* e, bool retire) {
 // workspace of one batch of `total` bytes / n_docs documents (grow-only buffers: nothing happens once they are large enough)
 tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, CallKind kind) {
     using namespace tkz;
-    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces || kind == CallKind::Trim;
+    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces || kind == CallKind::Trim || kind == CallKind::Spans;
     const int64_t nwords = total / 64 + 1;
     const int64_t ntiles = (total + kSub - 1) / kSub;
     const int64_t nblk = (ntiles + kScanBlock - 1) / kScanBlock;
@@ -998,7 +1007,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             // piece arrays too small: the launch sequence still runs to its end (without the piece arrays), so that the caller
             // learns BOTH required sizes from this one call (tkz.h: *n_pieces and *needed_ids on TKZ_E_CAPACITY)
             *pieces_over = po->n_pieces > po->piece_cap;
-            if (c.trim) {                                               // (the workspace's piece arrays: sized for the pieces there are, not for one per byte)
+            if (c.trim || c.spans) {                                    // (the workspace's piece arrays: sized for the pieces there are, not for one per byte)
                 for (DevBuf* b : {&ws->p_boffs, &ws->p_toffs}) HIP_TRY(b->ensure((size_t)(po->n_pieces + 1) * 8, &ws->bytes_allocated));
                 po->piece_boffs = ws->p_boffs.as<int64_t>(); po->piece_toffs = ws->p_toffs.as<int64_t>();
             }
@@ -1025,6 +1034,16 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                     launch_trim(L, R, ws->t_ids.as<int32_t>(), total, c.d_out, c.out_cap, c.d_out_offs, kept);
                     produced = kept;
                 }
+                if (c.spans && !*pieces_over) {                         // (the position of every token, and the document offsets from the piece arrays)
+                    HIP_TRY(hipMemsetAsync(ws->sp_intbits.p, 0, (size_t)nwords * 8, stream));
+                    int32_t* const cnt = ws->sp_cnt.as<int32_t>();
+                    int64_t* const base = ws->sp_base.as<int64_t>();
+                    const SpanParams S{d_bytes, total, d_offs, n_docs, startbits, docbits, ws->sp_intbits.as<uint64_t>(), nwords, ntiles,
+                                       po->doc_piece, po->piece_boffs, po->piece_toffs, po->n_pieces, c.d_out, c.out_cap, grand,
+                                       cnt, cnt + ntiles, base, base + ntiles, base + 2 * ntiles, ws->w_bsum.as<int64_t>(),
+                                       c.d_out_offs, c.spans->d_tok_bytes, c.spans->d_tok_units, counters};
+                    launch_tokspans(L, S, e->D);
+                }
                 launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
@@ -1049,6 +1068,7 @@ tkz_status check_counters(tkz_encoder* e, Workspace* ws, const BatchCall& call, 
     if (err & kErrOffsets) return fail(TKZ_E_ARG, "document offsets must start at 0, be non-decreasing and end at the byte count");
     if (err & kErrUtf8) return fail(TKZ_E_INVALID_UTF8, "input is not well-formed UTF-8 (or a document boundary falls inside a character)");
     if (err & kErrTooLong) return fail(TKZ_E_UNSUPPORTED, "a single piece longer than 2^30 bytes");
+    if (err & kErrSpanDoc) return fail(TKZ_E_UNSUPPORTED, "token spans: a document of 2^31 bytes or more");
     // (what is wrong from here on is the size of a buffer)
     if (!bitmap_only) ws->sized = true;
     if (!bitmap_only && nsample < 0 && total > e->latency_bytes) {      // (the next batch's form of the long pieces' kernels: side_streams)
@@ -1087,6 +1107,7 @@ tkz_status check_counters(tkz_encoder* e, Workspace* ws, const BatchCall& call, 
             return fail(TKZ_E_OUT_OF_MEMORY, "piece records: " + std::to_string(need) + " bytes could not be allocated");
     } else {
         if (err & kErrKeyNotFound) return fail(TKZ_E_KEY_NOT_FOUND, "a byte of the input is not in the vocabulary (KeyNotFoundException in the reference)");
+        if (err & kErrSpanSum) return fail(TKZ_E_DEVICE, "token spans: the key lengths of a piece's ids do not add up to the piece");
         if (!bitmap_only && e->piece_stats) {
             std::lock_guard<std::mutex> lock(e->mu);
             ++e->stat_batches; e->stat_giants += (int64_t)c.heavy_count;
@@ -2555,6 +2576,147 @@ tkz_status tkz_encode_trim_utf16(tkz_encoder* e, const uint16_t* text, int64_t l
     *n_out = needed;
     if (cut_units) *cut_units = cu;
     return st;
+}
+
+// ---- token spans: the ids and offsets of the matching encode entry, and where every token's text starts in its document (bytes, UTF-16 code units) ----
+
+namespace {
+// the span call on device buffers, on a workspace the entry holds: the piece-granular launch sequence with the piece arrays in the workspace and the ids in the
+// caller's buffer, then the token starts (enqueue_attempt)
+tkz_status spans_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, const SpanCall& sc, const SpecialCall* sp, int64_t* total_tokens) {
+    int64_t* acc = &ws->bytes_allocated;
+    PiecesOut po{nullptr, nullptr, nullptr, c.total, 0};                // (pieces <= bytes: the arrays are sized once the pieces are counted)
+    if (c.total > 0) {
+        const int64_t nwords = c.total / 64 + 1, ntiles = (c.total + tkz::kSub - 1) / tkz::kSub;
+        HIP_TRY(ws->p_docp.ensure((size_t)(c.n_docs + 1) * 8, acc));
+        HIP_TRY(ws->sp_intbits.ensure((size_t)(nwords + 8) * 8, acc));
+        HIP_TRY(ws->sp_cnt.ensure((size_t)ntiles * 2 * 4, acc));
+        HIP_TRY(ws->sp_base.ensure((size_t)(ntiles * 2 + 2) * 8, acc));
+        po.doc_piece = ws->p_docp.as<int64_t>();
+    }
+    c.kind = CallKind::Spans; c.pieces = &po; c.spans = &sc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (st == TKZ_OK) { ++e->spans_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a span host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the ids, their offsets and the two span
+// arrays, ONE span call, the results back.  A document of 2^31 bytes or more is refused from the byte offsets when the caller's were in bytes (h_offs), by the
+// device otherwise.
+tkz_status spans_staged(tkz_encoder* e, Workspace* ws, BatchCall c, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                        int32_t* tok_bytes, int32_t* tok_units, int64_t* needed) {
+    const int64_t n_docs = c.n_docs;
+    c.out_cap = std::min<int64_t>(out_cap, c.total);
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap));
+    HIP_TRY(ws->sp_stage.ensure((size_t)cap * 2 * 4, &ws->bytes_allocated));
+    int32_t* const d_tb = ws->sp_stage.as<int32_t>(), * const d_tu = d_tb + cap;
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = ws->s_outoffs[0].as<int64_t>();
+    int64_t tokens = 0;
+    const tkz_status st = spans_on_device(e, ws, c, SpanCall{tok_bytes ? d_tb : nullptr, tok_units ? d_tu : nullptr}, sp, &tokens);
+    if (needed) *needed = tokens;
+    if (st != TKZ_OK) return st;
+    TKZ_TRY(fetch(ws, out_ids, tokens, out_offsets, n_docs));
+    if (tok_bytes && tokens) HIP_TRY(hipMemcpy(tok_bytes, d_tb, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    if (tok_units && tokens) HIP_TRY(hipMemcpy(tok_units, d_tu, (size_t)tokens * 4, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+const char* const kMsgSpanArrays = "token spans: tok_bytes and tok_units are both null";
+const char* const kMsgSpanDoc = "token spans: a document of 2^31 bytes or more";
+}  // namespace
+
+tkz_status tkz_encode_batch_spans_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                         const int32_t* allowed, int32_t n_allowed, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                         int32_t* d_tok_bytes, int32_t* d_tok_units, void* hip_stream, int64_t* total_tokens) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (!d_tok_bytes && !d_tok_units) return fail(TKZ_E_ARG, kMsgSpanArrays);
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_device_call(e, scope, c));
+    Lease lease(e);
+    return spans_on_device(e, lease.ws, c, SpanCall{d_tok_bytes, d_tok_units}, sp, total_tokens);
+}
+
+tkz_status tkz_encode_batch_spans_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int32_t* tok_bytes, int32_t* tok_units, int64_t* needed) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (!tok_bytes && !tok_units) return fail(TKZ_E_ARG, kMsgSpanArrays);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    if (needed) *needed = 0;
+    for (int64_t d = 0; d < n_docs; ++d) if (doc_offsets[d + 1] - doc_offsets[d] > (int64_t)INT32_MAX) return fail(TKZ_E_UNSUPPORTED, kMsgSpanDoc);
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_trim_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return spans_staged(e, ws, staged_call(ws, n_docs, total, 0), sp, out_ids, out_cap, out_offsets, tok_bytes, tok_units, needed);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_trim_utf16 does; positions in code units only -- the bytes
+// never exist on the host.
+tkz_status tkz_encode_batch_spans_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int32_t* tok_units, int64_t* needed) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (!tok_units) return fail(TKZ_E_ARG, kMsgSpanArrays);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    if (needed) *needed = 0;
+    if (total == 0) {
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, out_offsets));
+        ++e->spans_calls;
+        if (sp) ++e->spec_batches;
+        return TKZ_OK;
+    }
+    // (a unit is at most three bytes: a document of fewer than 2^31 / 3 units cannot reach 2^31 bytes; a longer one is measured by the device)
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return spans_staged(e, ws, c, sp, out_ids, out_cap, out_offsets, nullptr, tok_units, needed);
+}
+
+// ONE text: the batch entry with one document, at every size
+tkz_status tkz_encode_spans_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                 int32_t* tok_bytes, int32_t* tok_units, int64_t* n_out) {
+    if (len < 0 || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    const tkz_status st = tkz_encode_batch_spans_utf8(e, text, offs, 1, allowed, n_allowed, out_ids, out_cap, oo, tok_bytes, tok_units, &needed);
+    *n_out = needed;
+    return st;
+}
+tkz_status tkz_encode_spans_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int32_t* out_ids, int64_t out_cap,
+                                  int32_t* tok_units, int64_t* n_out) {
+    if (len < 0 || (!text && len) || !n_out) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, needed = 0;
+    const tkz_status st = tkz_encode_batch_spans_utf16(e, text, offs, 1, allowed, n_allowed, out_ids, out_cap, oo, tok_units, &needed);
+    *n_out = needed;
+    return st;
+}
+void tkz_encoder_spans_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->spans_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

@@ -235,6 +235,21 @@ struct TrimParams {
     const int32_t* counters;
 };
 void launch_trim(const Launch& L, const TrimParams& R, const int32_t* ids, int64_t ids_cap, int32_t* out, int64_t out_cap, int64_t* out_offs, int64_t* kept_total);
+// Token spans (tkz_encode_batch_spans_device): behind the piece-granular launch sequence with the ids in the caller's buffer -- the interior token starts of the
+// pieces of several tokens (k_tokspan_mark, which also writes out_offs, n_docs + 1 entries), the token starts and begun UTF-16 units of every sub-tile, their
+// scans, and the document-relative byte and unit position of every token (k_tokspan_write).  intbits: nwords words, zeroed by the caller.  cnt_* / base_*: an
+// entry per sub-tile; sums: [2], the scans' totals; bsum: nsub / kScanBlock + 2 entries.  tok_bytes / tok_units: out_cap entries each, either may be null (without
+// tok_units the bytes are not read again).  counters: the batch's counter block -- kErrSpanDoc / kErrSpanSum are set there; with an error bit in it, or with
+// *grand > out_cap, the span arrays are left alone.
+struct SpanParams {
+    const uint8_t* bytes; int64_t total; const int64_t* offs; int64_t n_docs;
+    const uint64_t* startbits; const uint64_t* docbits; uint64_t* intbits; int64_t nwords, nsub;
+    const int64_t* doc_piece; const int64_t* piece_boffs; const int64_t* piece_toffs; int64_t n_pieces;
+    const int32_t* ids; int64_t out_cap; const int64_t* grand;
+    int32_t* cnt_tok; int32_t* cnt_unit; int64_t* base_tok; int64_t* base_unit; int64_t* sums; int64_t* bsum;
+    int64_t* out_offs; int32_t* tok_bytes; int32_t* tok_units; int32_t* counters;
+};
+void launch_tokspans(const Launch& L, const SpanParams& S, const TkzDecodeTable& D);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

@@ -3552,6 +3552,167 @@ TKZ_KERNEL(256) void k_offsets_scan(int64_t* offs, int64_t n, int64_t* total) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// Token spans (tkz_encode_batch_spans_device): where every token's text starts, behind the piece-granular launch sequence -- which leaves the ids in the
+// caller's buffer and the byte and token offset of every piece and the first piece of every document in the workspace.
+//   k_tokspan_mark   one lane per piece.  A piece of one token (nearly all, and every taken special-token literal) starts where the piece starts: that bit is in
+//                    startbits.  A piece of several tokens walks its ids through the decode table and sets a bit at every INTERIOR token start in `intbits`
+//                    (zeroed by the host); key lengths that do not add up to the piece are kErrSpanSum.  The token-start bitmap is startbits | intbits.
+//                    The same launch writes the document offsets, out_offs[d] = piece_toffs[doc_piece[d]], and refuses a document of 2^31 bytes or more.
+//   k_tokspan_count  one wavefront per sub-tile, a lane per 16 bytes: the token starts and the UTF-16 units begun (one per non-continuation byte, one more per
+//                    byte >= 0xF0: k_trim_gather's rule) in the sub-tile.  (k_scan_*: their exclusive scans.)
+//   k_tokspan_write  the same walk again: the ordinal of a token-start bit IS the token's index (tokens are ordered by byte), its document starts at the last
+//                    document mark at or before it -- in its own lane's 16 bits, in an earlier lane (a maximum scan over the lanes), or in front of the sub-tile
+//                    (the 64 bitmap words before it, else one binary search over the offsets per wavefront; for the units the recount of that sub-tile's bytes in front of the
+//                    document start).
+// An attempt whose counter block holds an error bit, or whose ids did not fit the caller's buffer, leaves the span arrays alone: nothing is promised then.
+// -------------------------------------------------------------------------------------------------
+// the token-start (or, with intbits null, document-start) bits of the 16 bytes at p0, those at or beyond `total` cleared
+TKZ_DEV uint32_t tkz_span_bits16(const uint64_t* bits, const uint64_t* intbits, int64_t total, int64_t p0) {
+    const int64_t lim = total - p0;
+    if (lim <= 0) return 0u;
+    uint64_t w = bits[p0 >> 6];
+    if (intbits) w |= intbits[p0 >> 6];
+    uint32_t m = (uint32_t)(w >> (p0 & 63)) & 0xFFFFu;
+    if (lim < 16) m &= (1u << (int)lim) - 1u;
+    return m;
+}
+// of the 16 bytes at p0 (16-byte aligned; nothing is read at or beyond `total`): bit k of *begun set <=> byte k is no continuation byte, bit k of *four <=> it is
+// >= 0xF0 -- the bytes below `end` only
+TKZ_DEV void tkz_span_units16(const uint8_t* bytes, int64_t total, int64_t p0, int64_t end, uint32_t* begun, uint32_t* four) {
+    uint32_t q[4] = {0u, 0u, 0u, 0u};
+    if (p0 + 16 <= total) { const uint4 v = *reinterpret_cast<const uint4*>(bytes + p0); q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
+    else for (int k = 0; p0 + k < total; ++k) q[k >> 2] |= (uint32_t)bytes[p0 + k] << (8 * (k & 3));
+    uint32_t b = 0, f = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t x = (q[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+        b |= ((x & 0xC0u) != 0x80u ? 1u : 0u) << k;
+        f |= (x >= 0xF0u ? 1u : 0u) << k;
+    }
+    const int64_t lim = (end < total ? end : total) - p0;
+    const uint32_t keep = lim <= 0 ? 0u : (lim >= 16 ? 0xFFFFu : (1u << (int)lim) - 1u);
+    *begun = b & keep; *four = f & keep;
+}
+TKZ_DEV int tkz_span_units_below(uint32_t begun, uint32_t four, int k) { const uint32_t low = (1u << k) - 1u; return tkz_popc32(begun & low) + tkz_popc32(four & low); }
+
+TKZ_KERNEL(256) void k_tokspan_mark(SpanParams S, TkzDecodeTable D) {
+    const int64_t stride = simt::nblocks() * simt::nthreads(), i0 = simt::bid() * simt::nthreads() + simt::tid();
+    for (int64_t d = i0; d <= S.n_docs; d += stride) {
+        S.out_offs[d] = S.piece_toffs[S.doc_piece[d]];
+        if (d < S.n_docs && S.offs[d + 1] - S.offs[d] > (int64_t)0x7FFFFFFF) simt::atomic_or((unsigned*)&S.counters[0], (unsigned)kErrSpanDoc);
+    }
+    const int64_t g = *S.grand;
+    if (S.counters[0] != 0 || g > S.out_cap) return;
+    for (int64_t i = i0; i < S.n_pieces; i += stride) {
+        const int64_t t0 = S.piece_toffs[i], t1 = S.piece_toffs[i + 1];
+        if (t1 - t0 == 1) continue;
+        const int64_t b1 = S.piece_boffs[i + 1];
+        int64_t pos = S.piece_boffs[i];
+        bool bad = t1 <= t0 || t0 < 0 || t1 > g;
+        // (four tokens a round: their ids, then their key lengths, are loads that do not wait for one another -- a token at a time was two dependent
+        //  round trips a token, and nearly every wavefront has a lane that walks)
+        for (int64_t t = t0; !bad && t < t1; t += 4) {
+            int32_t id[4];
+            uint32_t len[4];
+            bool have[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) id[k] = t + k < t1 ? S.ids[t + k] : 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { uint32_t off; len[k] = 0; have[k] = t + k < t1 && tkz_dec_find(D, id[k], &off, &len[k]); }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (t + k >= t1 || bad) continue;
+                if (!have[k]) { bad = true; continue; }
+                pos += len[k];
+                if (t + k + 1 == t1) continue;
+                if (pos >= b1) bad = true;                  // (an interior start lies inside the piece: nothing is set outside the bitmap)
+                else simt::atomic_or64((unsigned long long*)&S.intbits[pos >> 6], 1ull << (pos & 63));
+            }
+        }
+        if (bad || pos != b1) simt::atomic_or((unsigned*)&S.counters[0], (unsigned)kErrSpanSum);
+    }
+}
+
+TKZ_KERNEL(256) void k_tokspan_count(SpanParams S) {
+    const int lane = simt::lane();
+    const int64_t sub = simt::bid() * (kThreads / 64) + simt::wave();
+    if (sub >= S.nsub) return;
+    const int64_t p0 = sub * kSub + lane * 16;
+    int tot;
+    (void)tkz_wave_scan_sum(tkz_popc32(tkz_span_bits16(S.startbits, S.intbits, S.total, p0)), &tot);
+    if (lane == 0) S.cnt_tok[sub] = tot;
+    if (!S.tok_units) return;
+    uint32_t begun, four;
+    tkz_span_units16(S.bytes, S.total, p0, S.total, &begun, &four);
+    (void)tkz_wave_scan_sum(tkz_popc32(begun) + tkz_popc32(four), &tot);
+    if (lane == 0) S.cnt_unit[sub] = tot;
+}
+
+TKZ_KERNEL(256) void k_tokspan_write(SpanParams S) {
+    const int lane = simt::lane();
+    const int64_t sub = simt::bid() * (kThreads / 64) + simt::wave();
+    if (sub >= S.nsub || S.counters[0] != 0 || *S.grand > S.out_cap) return;
+    // (as many token starts as there are ids: the marks and the encode kernels agree over the whole batch)
+    if (sub == 0 && lane == 0 && S.sums[0] != *S.grand) simt::atomic_or((unsigned*)&S.counters[0], (unsigned)kErrSpanSum);
+    const int64_t sub0 = sub * kSub, p0 = sub0 + lane * 16;
+    uint32_t m = tkz_span_bits16(S.startbits, S.intbits, S.total, p0);
+    const uint32_t dm = tkz_span_bits16(S.docbits, nullptr, S.total, p0);
+    int tot;
+    int64_t o = S.base_tok[sub] + tkz_wave_scan_sum(tkz_popc32(m), &tot);
+    if (tot == 0) return;                                   // (wave-uniform)
+    const bool units = S.tok_units != nullptr;
+    uint32_t begun = 0, four = 0;
+    int upre = 0;                                           // units begun in [sub0, p0)
+    if (units) {
+        tkz_span_units16(S.bytes, S.total, p0, S.total, &begun, &four);
+        int utot;
+        upre = tkz_wave_scan_sum(tkz_popc32(begun) + tkz_popc32(four), &utot);
+    }
+    // the last document start of an EARLIER lane of this sub-tile: (byte in the sub-tile + 1) << 12 | units begun in front of it (< 2,048), ascending with the
+    // byte, so the maximum over the lanes in front is the nearest one; 0: none
+    int mine = 0;
+    if (dm) { const int k = tkz_msb32(dm); mine = ((lane * 16 + k + 1) << 12) | (upre + tkz_span_units_below(begun, four, k)); }
+    int run = mine;
+    for (int d = 1; d < 64; d <<= 1) { const int y = simt::shfl_up(run, d); if (lane >= d && y > run) run = y; }
+    int before = simt::shfl_up(run, 1);
+    if (lane == 0) before = 0;
+    // ... and the document that is open where the sub-tile begins (wave-uniform; not needed when a document starts at the sub-tile's first byte)
+    int64_t in_pos = sub0, in_units = 0;
+    if (!(simt::shfl((int)dm, 0) & 1)) {
+        // (the last document mark in front of the sub-tile: in the 64 bitmap words before it, a lane a word -- documents of up to 4 KiB --, else by binary search
+        //  over the offsets: 24 dependent loads a wavefront on ten million documents were most of this kernel)
+        const int64_t w0 = sub0 >> 6, wl = w0 - 1 - lane;
+        const uint64_t x = wl >= 0 ? S.docbits[wl] : 0ull;
+        const uint64_t found = simt::ballot(x != 0);
+        if (found) { const int src = tkz_ctz64(found); in_pos = ((w0 - 1 - src) << 6) + tkz_msb64((uint64_t)tkz_shfl64((int64_t)x, src)); }
+        else in_pos = S.offs[tkz_last_le(S.offs, 0, S.n_docs - 1, sub0)];
+        if (in_pos < 0) in_pos = 0;
+        if (in_pos > sub0) in_pos = sub0;
+        if (units) {
+            const int64_t isub = in_pos / kSub;
+            uint32_t ib, if4;
+            tkz_span_units16(S.bytes, S.total, isub * kSub + lane * 16, in_pos, &ib, &if4);
+            int itot;
+            (void)tkz_wave_scan_sum(tkz_popc32(ib) + tkz_popc32(if4), &itot);
+            in_units = S.base_unit[isub] + itot;
+        }
+    }
+    const int64_t ubase = units ? S.base_unit[sub] : 0;
+    for (; m; m &= m - 1, ++o) {
+        const int k = tkz_ctz32(m);
+        const uint32_t dd = dm & ((2u << k) - 1u);          // document starts of this lane at or before bit k
+        const int u = units ? upre + tkz_span_units_below(begun, four, k) : 0;
+        int64_t boff, uoff;
+        if (dd) { const int s = tkz_msb32(dd); boff = k - s; uoff = u - (upre + tkz_span_units_below(begun, four, s)); }
+        else if (before) { boff = lane * 16 + k - ((before >> 12) - 1); uoff = u - (before & 0xFFF); }
+        else { boff = p0 + k - in_pos; uoff = ubase + u - in_units; }
+        if (o < 0 || o >= S.out_cap) continue;
+        if (S.tok_bytes) S.tok_bytes[o] = (int32_t)boff;
+        if (units) S.tok_units[o] = (int32_t)uoff;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // k_small: the WHOLE launch sequence for a small batch in ONE kernel, one workgroup (ITokenizer.Encode of a prompt, TikTokenizer.cs:178-207;
 // the shape of BASELINE.json configs[0]).  The batch path above is ~25 launches and as many dependent kernel boundaries: ~160 us for a
 // 64-byte prompt, whatever the kernels do.  Here the phases are the same device functions (tkz_probe_subtile, tkz_merge_short_group,
@@ -4289,6 +4450,15 @@ void launch_trim(const Launch& L, const TrimParams& R, const int32_t* ids, int64
     // (a wavefront per tile of the larger of the two ranges -- the kept ids are at most the bytes --, grid-strided beyond 2,048 workgroups)
     const int64_t tiles = cdiv(R.total, kTrimTile), g = cdiv(tiles, kThreads / 64);
     TKZ_LAUNCH(k_trim_gather, g < 1 ? 1 : (g > 2048 ? 2048 : g), kThreads, L.stream, R, ids, ids_cap, (const int64_t*)out_offs, out, out_cap, kept_total);
+}
+// (the bracket: the stage extends K_DOCOFFS's -- the closing event is recorded again behind it, as launch_lit_fix does for K_PRETOK)
+void launch_tokspans(const Launch& L, const SpanParams& S, const TkzDecodeTable& D) {
+    TKZ_LAUNCH(k_tokspan_mark, grid_for(S.n_pieces > S.n_docs ? S.n_pieces : S.n_docs + 1), kThreads, L.stream, S, D);
+    const int64_t g = grid1(cdiv(S.nsub, kThreads / 64));
+    TKZ_LAUNCH(k_tokspan_count, g, kThreads, L.stream, S);
+    launch_scan2(L, S.nsub, S.bsum, S.cnt_tok, S.base_tok, S.sums, 1, S.tok_units ? S.cnt_unit : nullptr, S.base_unit, S.sums + 1, 1, -1);
+    TKZ_LAUNCH(k_tokspan_write, g, kThreads, L.stream, S);
+    hook(L, K_DOCOFFS, 1);
 }
 int64_t dec_tiles(int64_t total_ids) { return cdiv(total_ids, kDecTile); }
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum) {

@@ -297,6 +297,35 @@ class TikTokenizer:
                 self._special_on_host = True
         return [len(x) for x in self.EncodeBatch(texts, allowedSpecialOrApply)]
 
+    # ---- token spans: which part of the text is token t -------------------------------------------------
+    def EncodeWithOffsets(self, text: str, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bytes: bool = False):
+        """(ids, starts): Encode(text, allowedSpecialOrApply) and, per token, where its text starts.  starts[t] indexes the `str` as .NET / JavaScript index a
+        string -- in UTF-16 CODE UNITS, which is a Python index as long as the text stays inside the BMP --: token t is the units starts[t] .. starts[t + 1], the
+        last one ends at the text's length in units.  A token that starts inside a character (byte-level BPE splits emoji and CJK under an English vocabulary) starts
+        AFTER that character's units, and a token of continuation bytes only has an empty span.  bytes=True: offsets into text.encode("utf-8") instead, where the
+        spans are exactly the tokens' keys.  (HuggingFace's offset_mapping, tiktoken's decode_with_offsets, EncodeToTokens' Offset.)"""
+        ids, starts = self.EncodeWithOffsetsBatch([text], allowedSpecialOrApply, bytes)
+        return ids[0], starts[0]
+
+    def EncodeWithOffsetsBatch(self, texts: Sequence[str], allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bytes: bool = False):
+        """([ids of text d], [starts of text d]) from ONE call of the device's span entry (tkz_encode_batch_spans_utf8)."""
+        if not texts:
+            return [], []
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not plain and (self._special_on_host or (self._fffd_literal and any(_has_lone_surrogate(t) for t in texts))):
+            raise N.UnsupportedError(N.E_UNSUPPORTED, "EncodeWithOffsets: the device's special entries do not hold this set of literals (or a literal holds U+FFFD "
+                                                      "and a text a lone surrogate)")
+        segs = [_utf8_like_dotnet(t) for t in texts]
+        offs = np.zeros(len(segs) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+        data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+        names = set(allowed) if not plain else ()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+        ids, ooff, tb, tu = self._encoder.encode_batch_spans(data, offs, index, want_bytes=bytes, want_units=not bytes)
+        flat, pos = ids.tolist(), (tb if bytes else tu).tolist()
+        return [flat[ooff[d]:ooff[d + 1]] for d in range(len(texts))], [pos[ooff[d]:ooff[d + 1]] for d in range(len(texts))]
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
