@@ -64,6 +64,11 @@ namespace Microsoft.DeepDev
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_spans_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
                                                                                          int* outIds, long outCap, long* outOffsets, int* tokUnits, out long needed);
         [DllImport(Lib)] internal static extern void tkz_encoder_spans_calls(IntPtr encoder, out long calls);
+        // token-budget chunks: Encode, and the tokens of every text cut into chunks of at most maxTokens (include/tkz.h, "Token-budget chunks")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_chunks_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                          long maxTokens, int* outIds, long outCap, long* outOffsets, long* docChunkOffsets,
+                                                                                          long* chunkTokens, long* chunkUnits, long chunkCap, out long neededIds, out long neededChunks);
+        [DllImport(Lib)] internal static extern void tkz_encoder_chunks_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -408,6 +413,58 @@ namespace Microsoft.DeepDev
                 outIds.Add(li); outStarts.Add(ls);
             }
             return (outIds, outStarts);
+        }
+
+        /// <summary>The text cut into chunks of at most <paramref name="maxTokenCount"/> tokens, in ONE call: what a loop over EncodeTrimSuffix on the rest of the
+        /// string yields while no piece exceeds the budget -- and, where that loop would never end (the next piece alone holds more tokens), runs of maxTokenCount
+        /// tokens of that piece, the last partial run going on with the pieces that follow (include/tkz.h states the rule).  The ids concatenate to Encode's, the
+        /// texts to the input; a character cut by a chunk boundary goes to the earlier chunk.  maxTokenCount below 1 is ArgumentOutOfRangeException.  A registered set
+        /// the device path does not hold is NotImplementedException (-7): there is no host path.</summary>
+        public List<(List<int> TokenIds, string Text)> EncodeChunks(string text, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount)
+        {
+            return EncodeChunksBatch(new[] { text }, allowedSpecial, maxTokenCount)[0];
+        }
+
+        /// <summary>EncodeChunks for every text: the strings' chars go to tkz_encode_batch_chunks_utf16 as they are (copied into one char[] with string.CopyTo).</summary>
+        public unsafe List<List<(List<int> TokenIds, string Text)>> EncodeChunksBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount)
+        {
+            if (maxTokenCount < 1) throw new ArgumentOutOfRangeException(nameof(maxTokenCount));
+            var result = new List<List<(List<int> TokenIds, string Text)>>(texts.Count);
+            if (texts.Count == 0) return result;
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = Math.Max(1, 3 * total);                                   // a token per byte, a char is at most three bytes
+            long chunkCap = Math.Max(1, Math.Min(3 * total, texts.Count + 2 * (3 * total) / maxTokenCount));      // the chunks that always suffice (tkz.h)
+            var ids = new int[cap];
+            var offsets = new long[texts.Count + 1];
+            var docChunks = new long[texts.Count + 1];
+            var chunkTokens = new long[chunkCap + 1];
+            var chunkUnits = new long[chunkCap];
+            int st;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* pt = offsets) fixed (long* pd = docChunks)
+            fixed (long* pc = chunkTokens) fixed (long* pn = chunkUnits)
+                st = Tkz.tkz_encode_batch_chunks_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, maxTokenCount, pi, cap, pt, pd, pc, pn, chunkCap,
+                                                       out _, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            for (int t = 0; t < texts.Count; ++t)
+            {
+                var chunks = new List<(List<int> TokenIds, string Text)>(checked((int)(docChunks[t + 1] - docChunks[t])));
+                for (long c = docChunks[t]; c < docChunks[t + 1]; ++c)
+                {
+                    int lo = checked((int)chunkTokens[c]), n = checked((int)(chunkTokens[c + 1] - chunkTokens[c]));
+                    var li = new List<int>(n); li.AddRange(new ArraySegment<int>(ids, lo, n));
+                    int a = checked((int)chunkUnits[c]), b = c + 1 < docChunks[t + 1] ? checked((int)chunkUnits[c + 1]) : texts[t].Length;
+                    chunks.Add((li, texts[t].Substring(a, b - a)));
+                }
+                result.Add(chunks);
+            }
+            return result;
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

@@ -369,6 +369,65 @@ tkz_status tkz_encode_spans_utf16(tkz_encoder* e, const uint16_t* text, int64_t 
 /* informational: successful calls of the span entries */
 void tkz_encoder_spans_calls(const tkz_encoder* e, int64_t* calls);
 
+/* ---- Token-budget chunks: a document cut into pieces of at most max_tokens tokens, in ONE call ----
+ * What a caller gets by calling EncodeTrimSuffix(rest, allowedSpecial, max_tokens), taking the returned text off the front and calling again to the end of the
+ * document -- without a call a chunk, without encoding the remainder again, and without the loop that never ends when the next piece alone exceeds the budget.
+ * THE RULE.  The items of a document are those of the trim entries (TikTokenizer.cs:288-341): the regex pieces of its plain stretches and one item of one token per
+ * allowed literal, in order.  Chunks partition the document's tokens:
+ *   - a chunk starts at token s; the first chunk starts at the document's first token;
+ *   - it ends at the largest item boundary b with s < b <= s + max_tokens;
+ *   - if there is no such boundary, the item at s still has more than max_tokens tokens left, and the chunk ends at s + max_tokens, inside that item;
+ *   - the next chunk starts where this one ended.
+ * So: while no item exceeds the budget the chunks are exactly the results of the repeated EncodeTrimSuffix loop, ids and texts alike; an item over the budget is cut
+ * into runs of max_tokens, and its last partial run begins a chunk that goes on taking the items that follow; no chunk is empty and none exceeds max_tokens; an
+ * empty document has no chunks; max_tokens < 1 is TKZ_E_ARG.
+ * POSITIONS follow the span entries' rules.  Bytes: the byte start of a chunk that begins inside an item is the item's byte start plus the key lengths of the item's
+ * tokens in front of it.  UTF-16 units: the number of units BEGUN in [document start, chunk start) -- one per non-continuation byte and one more per byte >= 0xF0;
+ * a cut inside a character therefore leaves the whole character, and a surrogate pair, to the earlier chunk.  (UTF-16 entries) a lone surrogate, which the
+ * transcoder replaced by EF BF BD, counts as the one unit it is.
+ * OUTPUTS.  d_out_ids / d_out_offsets (n_docs + 1 entries) are EXACTLY what the matching encode entry writes for the same arguments -- tkz_encode_batch_special_*
+ * when n_allowed > 0 and literals are registered, the plain entry otherwise; the ids go straight into the caller's buffer.
+ *   doc_chunk_offsets (n_docs + 1 entries)   the chunks of document d are [doc_chunk_offsets[d], doc_chunk_offsets[d + 1]);
+ *   chunk_tokens (chunk_cap + 1 entries)     entry c is the index in out_ids of chunk c's first token, entry n_chunks the token total: chunk c is the ids
+ *                                            [chunk_tokens[c], chunk_tokens[c + 1]);
+ *   chunk_bytes, chunk_units (chunk_cap entries each, int64; either or both may be NULL)   the chunk's start relative to ITS DOCUMENT.  A chunk ends where the next
+ *                                            chunk of its document starts, or at the document's length.  The positions are 64-bit: the span entries' limit of 2^31
+ *                                            bytes a document does not apply.
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap or chunk_cap is short: *total_tokens and *n_chunks then hold the required sizes, nothing is promised in the outputs.
+ * A document of t tokens has at most 2 * t / max_tokens + 1 chunks (two consecutive chunks hold more than max_tokens tokens together), and a token is at least a
+ * byte: n_docs + 2 * total_bytes / max_tokens chunks ALWAYS suffice (and total_bytes ids).
+ *   tkz_encode_batch_chunks_device: device buffers.  Everything else -- allowed / n_allowed, TKZ_E_ARG, TKZ_E_UNSUPPORTED, tkz_encoder_special_stats, device-side
+ *     errors, retries inside the call, workspace growth -- as tkz_encode_batch_spans_device; an empty batch clears d_out_offsets and d_doc_chunk_offsets on the
+ *     stream (and sets chunk_tokens[0] = 0).  The launch sequence is the piece-granular one of the trim entry (it waits once, inside, for the number of pieces);
+ *     behind it the documents are walked twice -- count (k_chunk_walk, k_chunk_walk_long), scan, write -- and, with d_chunk_units, k_chunk_unitcount, a scan and
+ *     k_chunk_units.  Workspace beyond the trim entry's piece arrays: 24 bytes a document, and with d_chunk_units 12 bytes per 128 bytes of text.
+ *     SERIAL LIMITS.  A document of at most 1,024 items is walked by ONE lane, a galloping search a chunk.  A longer one is walked by ONE wavefront: its chunks are a
+ *     chain, each starts where the one before ended, so one document of many megabytes costs a step a chunk and a load per 64 items on that wavefront -- the walk
+ *     is not split inside a document.  The bytes of an item over the budget are found by ONE lane that walks the item's ids: an item of many megabytes is walked
+ *     by one lane, as in the span entries.
+ *   tkz_encode_batch_chunks_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as tkz_encode_batch_spans_utf8:
+ *     no chunk pipeline, no single-launch route.  *needed_ids / *needed_chunks: the counts, the required ones on TKZ_E_CAPACITY.
+ *   tkz_encode_batch_chunks_utf16: code units in, transcoded on the device as tkz_encode_batch_trim_utf16; unit_offsets and chunk_units in code units.  There is no
+ *     chunk_bytes: the bytes never exist on the host.  Literals that hold U+FFFD as in the other UTF-16 special entries.
+ *   tkz_encode_chunks_utf8 / _utf16: ONE text -- the batch entry with one document, at every size.  TKZ_E_ARG for a negative len or a null n_out / n_chunks.
+ * There is no overlap between chunks, no budget per document, no _begin / _end form and no form that returns the boundaries without the ids. */
+tkz_status tkz_encode_batch_chunks_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                          int64_t* d_doc_chunk_offsets, int64_t* d_chunk_tokens, int64_t* d_chunk_bytes, int64_t* d_chunk_units, int64_t chunk_cap,
+                                          void* hip_stream, int64_t* total_tokens, int64_t* n_chunks);
+tkz_status tkz_encode_batch_chunks_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int64_t max_tokens, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* doc_chunk_offsets, int64_t* chunk_tokens,
+                                        int64_t* chunk_bytes, int64_t* chunk_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks);
+tkz_status tkz_encode_batch_chunks_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int64_t max_tokens, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* doc_chunk_offsets, int64_t* chunk_tokens,
+                                         int64_t* chunk_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks);
+tkz_status tkz_encode_chunks_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* out_ids,
+                                  int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_bytes, int64_t* chunk_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks);
+tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* out_ids,
+                                   int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks);
+/* informational: successful calls of the chunk entries */
+void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -521,7 +580,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * k_doccount2 and the scan of its counts, k_list_stats (which also finds the giant pieces and fills k_merge_coop's queue); of a trim call
  * (tkz_encode_batch_trim_device) k_trim_cut, the scan of the kept lengths and k_trim_gather, which run behind TKZ_K_DOCOFFS.
  * Of a span call (tkz_encode_batch_spans_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the pieces AND the span stage behind it (the fill of the interior
- * bitmap, k_tokspan_mark, k_tokspan_count, two scans, k_tokspan_write): the closing event is recorded again behind the stage.
+ * bitmap, k_tokspan_mark, k_tokspan_count, two scans, k_tokspan_write): the closing event is recorded again behind the stage.  Of a chunk call
+ * (tkz_encode_batch_chunks_device) likewise: k_docoffs over the pieces and the chunk stage (the two walks, their scan, the unit counts, k_chunk_units).
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

@@ -6,6 +6,7 @@
 //                              EncodeTrimSuffix / EncodeTrimPrefix x2   ITokenizer.cs:30-44, TikTokenizer.cs:288-579
 //                              CountTokens / CountTokensBatch (+ Utf16): Encode(...).Count from the device's count entries, no ids
 //                              EncodeWithOffsets / EncodeWithOffsetsBatch (+ Utf16): Encode, and where every token's text starts (bytes / code units)
+//                              EncodeChunks / EncodeChunksBatch (+ Utf16): the text cut into chunks of at most maxTokenCount tokens, (ids, text) each
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -505,6 +506,37 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return spans_batch<uint16_t>(units, offs, allowedSpecial, true);
     }
+    // ---- token-budget chunks: the repeated-EncodeTrimSuffix loop in ONE call (tkz_encode_batch_chunks_utf8 / _utf16; tkz.h states the rule) ----
+    // A list of (ids, text) per text: chunks of at most maxTokenCount tokens that end at piece boundaries where one is in reach; a piece of more tokens than the
+    // budget is cut into runs of maxTokenCount.  The ids concatenate to Encode's and the texts to the input.  std::string: the texts are sliced at the chunks' BYTE
+    // starts, so a chunk may begin inside a character; std::u16string: at their starts in CODE UNITS -- a character cut by a chunk boundary goes to the earlier
+    // chunk.  maxTokenCount < 1 is the C ABI's TKZ_E_ARG.  A registered set the device's special entries do not hold is a NotImplementedError here: there is
+    // no host path.
+    std::vector<Trimmed> EncodeChunks(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        return std::move(EncodeChunksBatch(std::vector<std::string>{text}, allowedSpecial, maxTokenCount)[0]);
+    }
+    std::vector<Trimmed> EncodeChunks(const std::string& text, int maxTokenCount, bool applySpecialTokens = true) const {
+        return EncodeChunks(text, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount);
+    }
+    std::vector<std::vector<Trimmed>> EncodeChunksBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return chunks_batch<uint8_t, std::string>(bytes, offs, texts, allowedSpecial, maxTokenCount, false);
+    }
+    std::vector<std::vector<Trimmed>> EncodeChunksBatch(const std::vector<std::string>& texts, int maxTokenCount, bool applySpecialTokens = true) const {
+        return EncodeChunksBatch(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount);
+    }
+    using Chunk16 = std::pair<std::vector<int32_t>, std::u16string>;
+    std::vector<Chunk16> EncodeChunksUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        return std::move(EncodeChunksBatchUtf16(std::vector<std::u16string>{text}, allowedSpecial, maxTokenCount)[0]);
+    }
+    std::vector<std::vector<Chunk16>> EncodeChunksBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return chunks_batch<uint16_t, std::u16string>(units, offs, texts, allowedSpecial, maxTokenCount, true);
+    }
     // (one string: tkz_encode_trim_utf16, the single-text trim entry)
     Trimmed16 EncodeTrimSuffixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         Trimmed16 out;
@@ -685,6 +717,37 @@ private:
         for (int64_t d = 0; d < n; ++d) {
             out[static_cast<size_t>(d)].ids.assign(ids.begin() + ooff[d], ids.begin() + ooff[d + 1]);
             out[static_cast<size_t>(d)].starts.assign(starts.begin() + ooff[d], starts.begin() + ooff[d + 1]);
+        }
+        return out;
+    }
+    // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text
+    template <class UNIT, class STR>
+    std::vector<std::vector<std::pair<std::vector<int32_t>, STR>>> chunks_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, const std::vector<STR>& texts,
+                                                                              const std::vector<std::string>& allowedSpecial, int maxTokenCount, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        std::vector<std::vector<std::pair<std::vector<int32_t>, STR>>> out(static_cast<size_t>(n));
+        if (n == 0 && maxTokenCount >= 1) return out;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t total = static_cast<int64_t>(items.size()) * (utf16 ? 3 : 1), mx = maxTokenCount;      // (a token per byte; a unit is at most three bytes)
+        const int64_t cap = std::max<int64_t>(1, total);
+        const int64_t ccap = std::max<int64_t>(1, std::min<int64_t>(total, n + 2 * total / std::max<int64_t>(mx, 1)));      // (tkz.h: the chunks that always suffice)
+        if (items.empty()) items.push_back(0);
+        std::vector<int32_t> ids(static_cast<size_t>(cap));
+        std::vector<int64_t> ooff(static_cast<size_t>(n) + 1, 0), dco(static_cast<size_t>(n) + 1, 0), ct(static_cast<size_t>(ccap) + 1, 0), starts(static_cast<size_t>(ccap), 0);
+        int64_t needed = 0, chunks = 0;
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_chunks_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), mx,
+                                                      ids.data(), cap, ooff.data(), dco.data(), ct.data(), starts.data(), ccap, &needed, &chunks);
+        else st = tkz_encode_batch_chunks_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), mx,
+                                               ids.data(), cap, ooff.data(), dco.data(), ct.data(), starts.data(), nullptr, ccap, &needed, &chunks);
+        check(st);
+        for (int64_t d = 0; d < n; ++d) {
+            const STR& t = texts[static_cast<size_t>(d)];
+            for (int64_t c = dco[d]; c < dco[d + 1]; ++c) {
+                const size_t a = static_cast<size_t>(starts[c]), b = c + 1 < dco[d + 1] ? static_cast<size_t>(starts[c + 1]) : t.size();
+                out[static_cast<size_t>(d)].emplace_back(std::vector<int32_t>(ids.begin() + ct[c], ids.begin() + ct[c + 1]), t.substr(a, b - a));
+            }
         }
         return out;
     }

@@ -180,6 +180,13 @@ class Library:
         L.tkz_encode_spans_utf16.argtypes = [vp, vp, i64, vp, i32, vp, i64, vp, pi64]
         L.tkz_encoder_spans_calls.argtypes = [vp, pi64]
         L.tkz_encoder_spans_calls.restype = None
+        L.tkz_encode_batch_chunks_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, pi64, pi64]
+        L.tkz_encode_batch_chunks_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_batch_chunks_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_chunks_utf8.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_chunks_utf16.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, i64, pi64, pi64]
+        L.tkz_encoder_chunks_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_chunks_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -811,6 +818,100 @@ class Encoder:
         """successful calls of the span entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_spans_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- token-budget chunks: the ids, and every document's tokens cut into chunks of at most max_tokens (tkz.h: the rule) --
+    @staticmethod
+    def chunk_bound(n_docs, total, max_tokens):
+        """chunks that always suffice (tkz.h), and never more than a chunk a byte"""
+        return max(0, min(total, n_docs + 2 * total // max(1, max_tokens)))
+
+    def _chunks_call(self, fn, head, max_tokens, n, cap, ccap, want_bytes, want_units, batch):
+        """the shared tail of the host entries: (ids, offsets or None, doc_chunk_offsets or None, chunk_tokens, chunk_bytes or None, chunk_units or None)"""
+        ids = np.empty(max(1, cap), np.int32)
+        ct = np.empty(max(1, ccap) + 1, np.int64)
+        cb = np.empty(max(1, ccap), np.int64) if want_bytes else None
+        cu = np.empty(max(1, ccap), np.int64) if want_units else None
+        ooff, dco = (np.empty(n + 1, np.int64), np.empty(n + 1, np.int64)) if batch else (None, None)
+        ni, nc = C.c_int64(0), C.c_int64(0)
+        args = list(head) + [max_tokens, _ptr(ids), cap]
+        if batch:
+            args += [_ptr(ooff), _ptr(dco)]
+        args += [_ptr(ct)] + ([_ptr(cb) if want_bytes else None] if want_bytes is not None else []) + [_ptr(cu) if want_units else None, ccap, C.byref(ni), C.byref(nc)]
+        try:
+            self.lib.check(fn(self._h, *args))
+        except TkzError as ex:
+            ex.needed, ex.needed_chunks = ni.value, nc.value          # (E_CAPACITY: the required counts)
+            raise
+        k, c = ni.value, nc.value
+        return ids[:k], ooff, dco, ct[:c + 1], cb[:c] if want_bytes else None, cu[:c] if want_units else None
+
+    def encode_batch_chunks(self, data: np.ndarray, offsets: np.ndarray, max_tokens, allowed=(), want_bytes=True, want_units=True, out_cap=None, chunk_cap=None):
+        """(ids int32, offsets int64[n+1], doc_chunk_offsets int64[n+1], chunk_tokens int64[chunks+1], chunk_bytes int64 or None, chunk_units int64 or None): the ids
+        and offsets of encode_batch / encode_batch_special and the chunk table -- tkz_encode_batch_chunks_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = len(data) if out_cap is None else out_cap
+        ccap = self.chunk_bound(n, len(data), max_tokens) if chunk_cap is None else chunk_cap
+        head = [_ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        return self._chunks_call(self.lib.L.tkz_encode_batch_chunks_utf8, head, max_tokens, n, cap, ccap, bool(want_bytes), want_units, True)
+
+    def encode_batch_chunks_utf16(self, units: np.ndarray, offsets: np.ndarray, max_tokens, allowed=(), out_cap=None, chunk_cap=None):
+        """encode_batch_chunks for UTF-16 documents (uint16[total], offsets in units): (ids, offsets, doc_chunk_offsets, chunk_tokens, chunk_units) --
+        tkz_encode_batch_chunks_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = 3 * len(units) if out_cap is None else out_cap
+        ccap = self.chunk_bound(n, 3 * len(units), max_tokens) if chunk_cap is None else chunk_cap
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        head = [_ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_call(self.lib.L.tkz_encode_batch_chunks_utf16, head, max_tokens, n, cap, ccap, None, True, True)
+        return r[0], r[1], r[2], r[3], r[5]
+
+    def encode_batch_chunks_device(self, d_bytes, d_offsets, n_docs, total_bytes, max_tokens, allowed, d_out_ids, out_cap, d_out_offsets, d_doc_chunk_offsets,
+                                   d_chunk_tokens, d_chunk_bytes=0, d_chunk_units=0, chunk_cap=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_chunks_device.  Returns (token total, chunks); a TkzError carries them as `needed` and `needed_chunks`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, nch = C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_chunks_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                     len(allowed), max_tokens, d_out_ids or None, out_cap, d_out_offsets or None, d_doc_chunk_offsets or None,
+                                                                     d_chunk_tokens or None, d_chunk_bytes or None, d_chunk_units or None, chunk_cap, stream or None,
+                                                                     C.byref(tot), C.byref(nch)))
+        except TkzError as ex:
+            ex.needed, ex.needed_chunks = tot.value, nch.value
+            raise
+        return tot.value, nch.value
+
+    def encode_chunks(self, text: bytes, max_tokens, allowed=(), want_bytes=True, want_units=True, out_cap=None, chunk_cap=None):
+        """ONE text: (ids, chunk_tokens, chunk_bytes or None, chunk_units or None) as lists -- tkz_encode_chunks_utf8."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        cap = len(text) if out_cap is None else out_cap
+        ccap = self.chunk_bound(1, len(text), max_tokens) if chunk_cap is None else chunk_cap
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        head = [_ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_call(self.lib.L.tkz_encode_chunks_utf8, head, max_tokens, 1, cap, ccap, bool(want_bytes), want_units, False)
+        return r[0].tolist(), r[3].tolist(), r[4].tolist() if want_bytes else None, r[5].tolist() if want_units else None
+
+    def encode_chunks_utf16(self, units, max_tokens, allowed=(), out_cap=None, chunk_cap=None):
+        """The same for a .NET `string` given as its UTF-16 code units: (ids, chunk_tokens, chunk_units) -- tkz_encode_chunks_utf16."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n_units = len(u) - 1
+        cap = 3 * n_units if out_cap is None else out_cap
+        ccap = self.chunk_bound(1, 3 * n_units, max_tokens) if chunk_cap is None else chunk_cap
+        head = [_ptr(u), n_units, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_call(self.lib.L.tkz_encode_chunks_utf16, head, max_tokens, 1, cap, ccap, None, True, False)
+        return r[0].tolist(), r[3].tolist(), r[5].tolist()
+
+    def chunks_calls(self):
+        """successful calls of the chunk entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_chunks_calls(self._h, C.byref(a))
         return a.value
 
     def set_special_tokens(self, specials):

@@ -107,6 +107,8 @@ struct CounterBlock {          // mirrors the device block
     unsigned long long miss_short, miss_long;   // pieces of the batch that missed the key tables as a whole (k_list_stats: the sums of mcount)
     unsigned long long n_literals;         // the special entries: special-token literals taken (k_lit_resolve)
     int64_t kept_total;                    // the trim entries: ids kept over the whole batch (k_trim_gather)
+    int64_t n_chunks;                      // the chunk entries: chunks of the whole batch (k_chunk_walk's writing pass)
+    unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
 };
 // ... and the 64-byte block of the length scans (the UTF-16 transcoder, the two decoders): k_docmark's / k_dec_write's error bits, the scans' grand totals
 struct LenCounters { int32_t err, pad; int64_t grand /* UTF-8 bytes */, grand16 /* UTF-16 code units (tkz_decode_batch_utf16 only) */; };
@@ -208,7 +210,11 @@ struct tkz_vocab { tkz::Vocab v; };
 // call, so host threads sharing one encoder run concurrently, each on its own workspace and streams ("one encoder
 // usable from many host threads") -- the reference's instance is likewise safe to share (its only shared mutable state, the LRU
 // memo, is locked: LRUCache.cs:61,99).
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs {
+struct ChunkBufs {   // the chunk entries: chunks per document and their scan's partial sums, the listed long documents, begun units per sub-tile and their scan (+ the total); the host entries' table
+    DevBuf ck_cnt, ck_bsum, ck_list, ck_ucnt, ck_ubase, ck_stage;
+    void release() { release_each({&ck_cnt, &ck_bsum, &ck_list, &ck_ucnt, &ck_ubase, &ck_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -257,7 +263,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -298,6 +304,7 @@ struct tkz_encoder {
     bool lit_fffd = false;                 // a registered literal holds U+FFFD (TkzLitTable's second 256-bit set is not empty)
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
+    std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
     std::atomic<int64_t> count_calls{0}, count_single{0};                  // tkz_encoder_count_calls: successful count calls, and those of them that took the single launch
     int64_t bytes_allocated = 0;           // tables
@@ -344,6 +351,8 @@ struct PiecesOut { int64_t* piece_boffs; int64_t* piece_toffs; int64_t* doc_piec
 struct TrimCall { int32_t side; int64_t max_tokens; const int64_t* d_max; int64_t* d_cut_bytes; int64_t* d_cut_units; };
 // A call of one of the span entries: where the byte and the UTF-16 unit position of every token go (device, out_cap entries each; either may be null, not both)
 struct SpanCall { int32_t* d_tok_bytes; int32_t* d_tok_units; };
+// A call of one of the chunk entries: the budget, where the chunk table goes (device; bytes and units may be null) and, on the host, where the number of chunks goes
+struct ChunkCall { int64_t max_tokens; int64_t* d_doc_chunk_offs; int64_t* d_chunk_tokens; int64_t* d_chunk_bytes; int64_t* d_chunk_units; int64_t chunk_cap; int64_t* n_chunks; };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -353,7 +362,8 @@ enum class CallKind {
     BitmapOnly,      // tkz_pretokenize_utf8: the piece-start bitmap and nothing else
     Pieces,          // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
     Trim,            // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
-    Spans            // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
+    Spans,           // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
+    Chunks           // tkz_encode_batch_chunks_device: as Spans, then the chunk table
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -368,6 +378,7 @@ struct BatchCall {
     const SpecialCall* special = nullptr;      // the special entries (an ordinary encode or a trim call); null: no literal is looked for
     const TrimCall* trim = nullptr;            // Trim: what to keep (pieces then points at the workspace's piece arrays)
     const SpanCall* spans = nullptr;           // Spans: where the positions go (pieces points at the workspace's piece arrays as well)
+    const ChunkCall* chunks = nullptr;         // Chunks: the budget and where the table goes (pieces likewise)
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -375,8 +386,9 @@ struct BatchCall {
     bool pretokenizes() const { return kind != CallKind::OnePiecePerDoc; }
     bool bitmap_only() const { return kind == CallKind::BitmapOnly; }
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
+    bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || kind == CallKind::Trim || kind == CallKind::Spans ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -694,7 +706,7 @@ tkz_status drop_promotions(tkz_encoder* e, bool retire) {
 // workspace of one batch of `total` bytes / n_docs documents (grow-only buffers: nothing happens once they are large enough)
 tkz_status prepare_workspace(Workspace* ws, int64_t total, int64_t n_docs, CallKind kind) {
     using namespace tkz;
-    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces || kind == CallKind::Trim || kind == CallKind::Spans;
+    const bool bitmap_only = kind == CallKind::BitmapOnly, pieces = kind == CallKind::Pieces || kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks;
     const int64_t nwords = total / 64 + 1;
     const int64_t ntiles = (total + kSub - 1) / kSub;
     const int64_t nblk = (ntiles + kScanBlock - 1) / kScanBlock;
@@ -1007,7 +1019,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             // piece arrays too small: the launch sequence still runs to its end (without the piece arrays), so that the caller
             // learns BOTH required sizes from this one call (tkz.h: *n_pieces and *needed_ids on TKZ_E_CAPACITY)
             *pieces_over = po->n_pieces > po->piece_cap;
-            if (c.trim || c.spans) {                                    // (the workspace's piece arrays: sized for the pieces there are, not for one per byte)
+            if (c.piece_granular()) {                                   // (the workspace's piece arrays: sized for the pieces there are, not for one per byte)
                 for (DevBuf* b : {&ws->p_boffs, &ws->p_toffs}) HIP_TRY(b->ensure((size_t)(po->n_pieces + 1) * 8, &ws->bytes_allocated));
                 po->piece_boffs = ws->p_boffs.as<int64_t>(); po->piece_toffs = ws->p_toffs.as<int64_t>();
             }
@@ -1043,6 +1055,18 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                                        cnt, cnt + ntiles, base, base + ntiles, base + 2 * ntiles, ws->w_bsum.as<int64_t>(),
                                        c.d_out_offs, c.spans->d_tok_bytes, c.spans->d_tok_units, counters};
                     launch_tokspans(L, S, e->D);
+                }
+                if (c.chunks && !*pieces_over) {                        // (the chunk table, and the document offsets from the piece arrays)
+                    const ChunkCall& k = *c.chunks;
+                    int64_t* const ubase = ws->ck_ubase.as<int64_t>();
+                    const int64_t nspan = (total + kChunkUnitSpan - 1) / kChunkUnitSpan;
+                    const ChunkParams C{d_bytes, total, d_offs, n_docs, po->doc_piece, po->piece_boffs, po->piece_toffs, c.d_out, c.out_cap, grand, k.max_tokens,
+                                        ws->ck_cnt.as<int64_t>(), ws->ck_bsum.as<int64_t>(), ws->ck_list.as<int64_t>(),
+                                        reinterpret_cast<unsigned long long*>(cb + offsetof(CounterBlock, chunk_long)),
+                                        nspan, ws->ck_ucnt.as<int32_t>(), ubase, ubase + nspan + 2, ubase + nspan,
+                                        c.d_out_offs, k.d_doc_chunk_offs, k.d_chunk_tokens, k.d_chunk_bytes, k.d_chunk_units, k.chunk_cap,
+                                        reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, n_chunks)), counters};
+                    launch_chunks(L, C, e->D);
                 }
                 launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
@@ -1108,6 +1132,7 @@ tkz_status check_counters(tkz_encoder* e, Workspace* ws, const BatchCall& call, 
     } else {
         if (err & kErrKeyNotFound) return fail(TKZ_E_KEY_NOT_FOUND, "a byte of the input is not in the vocabulary (KeyNotFoundException in the reference)");
         if (err & kErrSpanSum) return fail(TKZ_E_DEVICE, "token spans: the key lengths of a piece's ids do not add up to the piece");
+        if (err & kErrChunkSum) return fail(TKZ_E_DEVICE, "chunks: the key lengths of an item's ids do not lead to a position inside the item");
         if (!bitmap_only && e->piece_stats) {
             std::lock_guard<std::mutex> lock(e->mu);
             ++e->stat_batches; e->stat_giants += (int64_t)c.heavy_count;
@@ -1204,6 +1229,10 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
             { Launch L0{stream, nullptr, ws}; launch_counts3(L0, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3); }
             if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
+            if (c.chunks) {                                       // (no chunks: both offset arrays cleared, and the token total behind the last chunk)
+                HIP_TRY(hipMemsetAsync(c.chunks->d_doc_chunk_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
+                HIP_TRY(hipMemsetAsync(c.chunks->d_chunk_tokens, 0, sizeof(int64_t), stream));
+            }
             if (c.trim && n_docs > 0) for (int64_t* cut : {c.trim->d_cut_bytes, c.trim->d_cut_units}) if (cut) HIP_TRY(hipMemsetAsync(cut, 0, (size_t)n_docs * sizeof(int64_t), stream));
             if (c.d_bitmap) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(c.d_bitmap, &one, 8, hipMemcpyHostToDevice, stream)); }
             if (phase == kCallBegin) return TKZ_OK;               // (_begin returns without waiting)
@@ -1252,8 +1281,10 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         if (c.literals()) e->spec_literals += ws->spec_taken;
         const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
         if (total_tokens) *total_tokens = produced;
+        if (c.chunks && c.chunks->n_chunks) *c.chunks->n_chunks = ws->h_counters->n_chunks;      // (both required sizes from one call)
         if (pieces_over) return fail(TKZ_E_CAPACITY, "piece arrays too small");
         if (!c.count_only && produced > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small");      // (a count call stores no ids)
+        if (c.chunks && ws->h_counters->n_chunks > c.chunks->chunk_cap) return fail(TKZ_E_CAPACITY, "chunk table capacity too small");
         return TKZ_OK;
     }
     return fail(TKZ_E_DEVICE, "unreachable");
@@ -2717,6 +2748,164 @@ tkz_status tkz_encode_spans_utf16(tkz_encoder* e, const uint16_t* text, int64_t 
 }
 void tkz_encoder_spans_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->spans_calls.load() : 0;
+}
+
+// ---- token-budget chunks: the ids and offsets of the matching encode entry, and every document's tokens cut into chunks of at most max_tokens (tkz.h: the rule) ----
+
+namespace {
+// the chunk call on device buffers, on a workspace the entry holds: the piece-granular launch sequence with the piece arrays in the workspace and the ids in the
+// caller's buffer, then the two walks and the table (enqueue_attempt)
+tkz_status chunks_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, ChunkCall cc, const SpecialCall* sp, int64_t* total_tokens, int64_t* n_chunks) {
+    int64_t* acc = &ws->bytes_allocated;
+    int64_t chunks = 0;
+    PiecesOut po{nullptr, nullptr, nullptr, c.total, 0};                // (pieces <= bytes: the arrays are sized once the pieces are counted)
+    if (c.total > 0) {
+        const int64_t nspan = (c.total + tkz::kChunkUnitSpan - 1) / tkz::kChunkUnitSpan;
+        HIP_TRY(ws->p_docp.ensure((size_t)(c.n_docs + 1) * 8, acc));
+        HIP_TRY(ws->ck_cnt.ensure((size_t)(c.n_docs + 1) * 8, acc));
+        HIP_TRY(ws->ck_bsum.ensure((size_t)(c.n_docs / tkz::kScanBlock + 2) * 8, acc));
+        HIP_TRY(ws->ck_list.ensure((size_t)std::max<int64_t>(c.n_docs, 1) * 8, acc));
+        if (cc.d_chunk_units) {
+            HIP_TRY(ws->ck_ucnt.ensure((size_t)nspan * 4, acc));
+            HIP_TRY(ws->ck_ubase.ensure((size_t)(nspan + 2 + nspan / tkz::kScanBlock + 2) * 8, acc));      // (the bases, the total, the scan's partial sums)
+        }
+        po.doc_piece = ws->p_docp.as<int64_t>();
+    }
+    if (cc.max_tokens > (int64_t(1) << 62)) cc.max_tokens = int64_t(1) << 62;      // (s + max_tokens is computed on the device)
+    cc.n_chunks = &chunks;
+    c.kind = CallKind::Chunks; c.pieces = &po; c.chunks = &cc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (n_chunks) *n_chunks = chunks;
+    if (st == TKZ_OK) { ++e->chunks_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a chunk host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the ids, their offsets and the table,
+// ONE chunk call, the results back.
+tkz_status chunks_staged(tkz_encoder* e, Workspace* ws, BatchCall c, int64_t max_tokens, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                         int64_t* doc_chunk_offsets, int64_t* chunk_tokens, int64_t* chunk_bytes, int64_t* chunk_units, int64_t chunk_cap,
+                         int64_t* needed_ids, int64_t* needed_chunks) {
+    const int64_t n_docs = c.n_docs;
+    c.out_cap = std::min<int64_t>(out_cap, c.total);
+    const int64_t ccap = std::min<int64_t>(chunk_cap, c.total), cap = std::max<int64_t>(ccap, 1);      // (chunks <= tokens <= bytes: more capacity is never used)
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap));
+    HIP_TRY(ws->ck_stage.ensure((size_t)((n_docs + 1) + (cap + 1) + 2 * cap) * 8, &ws->bytes_allocated));
+    int64_t* const d_dco = ws->ck_stage.as<int64_t>(), * const d_ct = d_dco + n_docs + 1, * const d_cb = d_ct + cap + 1, * const d_cu = d_cb + cap;
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = ws->s_outoffs[0].as<int64_t>();
+    int64_t tokens = 0, chunks = 0;
+    const tkz_status st = chunks_on_device(e, ws, c, ChunkCall{max_tokens, d_dco, d_ct, chunk_bytes ? d_cb : nullptr, chunk_units ? d_cu : nullptr, ccap, nullptr}, sp, &tokens, &chunks);
+    if (needed_ids) *needed_ids = tokens;
+    if (needed_chunks) *needed_chunks = chunks;
+    if (st != TKZ_OK) return st;
+    TKZ_TRY(fetch(ws, out_ids, tokens, out_offsets, n_docs));
+    HIP_TRY(hipMemcpy(doc_chunk_offsets, d_dco, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(chunk_tokens, d_ct, (size_t)(chunks + 1) * 8, hipMemcpyDeviceToHost));
+    if (chunk_bytes && chunks) HIP_TRY(hipMemcpy(chunk_bytes, d_cb, (size_t)chunks * 8, hipMemcpyDeviceToHost));
+    if (chunk_units && chunks) HIP_TRY(hipMemcpy(chunk_units, d_cu, (size_t)chunks * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+const char* const kMsgChunkMax = "chunks: max_tokens must be at least 1";
+const char* const kMsgChunkBufs = "chunks: null chunk table buffer or negative chunk_cap";
+}  // namespace
+
+tkz_status tkz_encode_batch_chunks_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
+                                          int64_t* d_doc_chunk_offsets, int64_t* d_chunk_tokens, int64_t* d_chunk_bytes, int64_t* d_chunk_units, int64_t chunk_cap,
+                                          void* hip_stream, int64_t* total_tokens, int64_t* n_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (max_tokens < 1) return fail(TKZ_E_ARG, kMsgChunkMax);
+    if (!d_doc_chunk_offsets || !d_chunk_tokens || chunk_cap < 0) return fail(TKZ_E_ARG, kMsgChunkBufs);
+    if (n_chunks) *n_chunks = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_device_call(e, scope, c));
+    Lease lease(e);
+    return chunks_on_device(e, lease.ws, c, ChunkCall{max_tokens, d_doc_chunk_offsets, d_chunk_tokens, d_chunk_bytes, d_chunk_units, chunk_cap, nullptr}, sp, total_tokens, n_chunks);
+}
+
+tkz_status tkz_encode_batch_chunks_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int64_t max_tokens, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* doc_chunk_offsets, int64_t* chunk_tokens,
+                                        int64_t* chunk_bytes, int64_t* chunk_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (max_tokens < 1) return fail(TKZ_E_ARG, kMsgChunkMax);
+    if (!doc_chunk_offsets || !chunk_tokens || chunk_cap < 0) return fail(TKZ_E_ARG, kMsgChunkBufs);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    if (needed_ids) *needed_ids = 0;
+    if (needed_chunks) *needed_chunks = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_spans_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return chunks_staged(e, ws, staged_call(ws, n_docs, total, 0), max_tokens, sp, out_ids, out_cap, out_offsets, doc_chunk_offsets, chunk_tokens, chunk_bytes, chunk_units,
+                         chunk_cap, needed_ids, needed_chunks);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_spans_utf16 does; positions in code units only -- the bytes
+// never exist on the host.
+tkz_status tkz_encode_batch_chunks_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int64_t max_tokens, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int64_t* doc_chunk_offsets, int64_t* chunk_tokens,
+                                         int64_t* chunk_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    if (max_tokens < 1) return fail(TKZ_E_ARG, kMsgChunkMax);
+    if (!doc_chunk_offsets || !chunk_tokens || chunk_cap < 0) return fail(TKZ_E_ARG, kMsgChunkBufs);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    if (needed_ids) *needed_ids = 0;
+    if (needed_chunks) *needed_chunks = 0;
+    if (total == 0) {
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, out_offsets));
+        std::fill_n(doc_chunk_offsets, n_docs + 1, int64_t(0));
+        chunk_tokens[0] = 0;
+        ++e->chunks_calls;
+        if (sp) ++e->spec_batches;
+        return TKZ_OK;
+    }
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return chunks_staged(e, ws, c, max_tokens, sp, out_ids, out_cap, out_offsets, doc_chunk_offsets, chunk_tokens, nullptr, chunk_units, chunk_cap, needed_ids, needed_chunks);
+}
+
+// ONE text: the batch entry with one document, at every size
+tkz_status tkz_encode_chunks_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* out_ids,
+                                  int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_bytes, int64_t* chunk_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks) {
+    if (len < 0 || !n_out || !n_chunks) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0; *n_chunks = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, dco[2] = {0, 0};
+    return tkz_encode_batch_chunks_utf8(e, text, offs, 1, allowed, n_allowed, max_tokens, out_ids, out_cap, oo, dco, chunk_tokens, chunk_bytes, chunk_units, chunk_cap, n_out, n_chunks);
+}
+tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* out_ids,
+                                   int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks) {
+    if (len < 0 || (!text && len) || !n_out || !n_chunks) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0; *n_chunks = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, dco[2] = {0, 0};
+    return tkz_encode_batch_chunks_utf16(e, text, offs, 1, allowed, n_allowed, max_tokens, out_ids, out_cap, oo, dco, chunk_tokens, chunk_units, chunk_cap, n_out, n_chunks);
+}
+void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->chunks_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

@@ -26,7 +26,8 @@
 #define TKZ_NOKEY 0xFFFFFFFFu
 
 enum : int32_t { kErrUtf8 = 1, kErrKeyNotFound = 2, kErrOffsets = 4, kErrPool = 8, kErrTooLong = 16, kErrCapacity = 32, kErrMissCap = 64,
-                 kErrSpanDoc = 128 /* the span entries: a document of 2^31 bytes or more */, kErrSpanSum = 256 /* ... the key lengths of a piece's ids are not the piece */ };
+                 kErrSpanDoc = 128 /* the span entries: a document of 2^31 bytes or more */, kErrSpanSum = 256 /* ... the key lengths of a piece's ids are not the piece */,
+                 kErrChunkSum = 512 /* the chunk entries: the key lengths of an item's ids do not lead to a position inside the item */ };
 
 
 // Per-lane scratch of tkz_bpe_lane<NMAX>: NMAX pair keys, 16-byte aligned so that the min scan is NMAX/4 16-byte LDS reads -- the

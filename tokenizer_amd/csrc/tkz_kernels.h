@@ -250,6 +250,27 @@ struct SpanParams {
     int64_t* out_offs; int32_t* tok_bytes; int32_t* tok_units; int32_t* counters;
 };
 void launch_tokspans(const Launch& L, const SpanParams& S, const TkzDecodeTable& D);
+// Token-budget chunks (tkz_encode_batch_chunks_device): behind the piece-granular launch sequence with the ids in the caller's buffer -- every document's tokens cut
+// into chunks of at most max_tokens that end at item boundaries where one is in reach (tkz.h states the rule).  The documents are walked TWICE: k_chunk_walk counts
+// the chunks of every document (doc_cnt, n_docs entries; a document of more than kChunkLongItems items goes on long_list and is counted by a wavefront,
+// k_chunk_walk_long), the counts are scanned into doc_chunk_offs (n_docs + 1 entries; the total also goes to *n_chunks), and the same two kernels walk again and
+// write chunk_tokens (chunk_cap + 1 entries), chunk_bytes and chunk_units (chunk_cap entries each, either may be null).  The counting walk also writes out_offs
+// (n_docs + 1 entries).  The unit starts: the begun units of every span of kChunkUnitSpan bytes of the batch (k_chunk_unitcount -> cnt_unit, nspan entries, scanned
+// into base_unit; ubsum: nspan / kScanBlock + 2 entries, usum: the scan's total), then k_chunk_units turns the batch byte positions the writing walk left in chunk_units into units relative to the document.
+// long_list: n_docs entries; long_count: one counter, zeroed by the caller; bsum: n_docs / kScanBlock + 2 entries.  counters: the batch's counter block --
+// kErrChunkSum is set there; with an error bit in it the counts are 0, and with one, with *grand > out_cap or with *n_chunks > chunk_cap the table is left alone.
+constexpr int64_t kChunkLongItems = 1024;
+constexpr int kChunkUnitSpan = 128;
+struct ChunkParams {
+    const uint8_t* bytes; int64_t total; const int64_t* offs; int64_t n_docs;
+    const int64_t* doc_piece; const int64_t* piece_boffs; const int64_t* piece_toffs;
+    const int32_t* ids; int64_t out_cap; const int64_t* grand; int64_t max_tokens;
+    int64_t* doc_cnt; int64_t* bsum; int64_t* long_list; unsigned long long* long_count;
+    int64_t nspan; int32_t* cnt_unit; int64_t* base_unit; int64_t* ubsum; int64_t* usum;
+    int64_t* out_offs; int64_t* doc_chunk_offs; int64_t* chunk_tokens; int64_t* chunk_bytes; int64_t* chunk_units; int64_t chunk_cap;
+    int64_t* n_chunks; int32_t* counters;
+};
+void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& D);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

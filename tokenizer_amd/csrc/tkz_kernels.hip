@@ -3552,6 +3552,208 @@ TKZ_KERNEL(256) void k_offsets_scan(int64_t* offs, int64_t n, int64_t* total) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// Token-budget chunks (tkz_encode_batch_chunks_device), behind the piece-granular launch sequence -- which leaves the ids in the caller's buffer and the byte and
+// token offset of every item (piece_boffs, piece_toffs: a taken special-token literal is ONE item of ONE token) and the first item of every document in the
+// workspace.  The rule (tkz.h): a chunk that starts at token s ends at the largest item boundary b with s < b <= s + max; with none, at s + max inside the item.
+// How many chunks there are is known only after the walk, so the documents are walked TWICE -- count, scan, write -- rather than written into slots reserved by the
+// bound 2 * count / max + 1 and compacted: the walk reads piece_toffs only, a document that fits the budget costs two loads in either pass, and the table goes
+// straight into the caller's arrays with nothing between to size, zero or move.
+//   k_chunk_walk       one lane per document, the same kernel for both passes.  A document of at most max tokens is one chunk with no search.  Otherwise the end
+//                      of a chunk is found by a galloping search forward from its start (1, 2, 4 ... items ahead, then a binary search inside the last stride):
+//                      chunks span a few hundred items at most.  A document of more than kChunkLongItems items is put on a list instead.
+//   k_chunk_walk_long  one wavefront per listed document: the lanes hold 64 consecutive piece_toffs entries (one coalesced load), a ballot of
+//                      toffs <= s + max and a population count give the chunk's end; the window moves on only when a chunk runs past it, so a load
+//                      serves every chunk that ends inside it, and the next three windows are loaded ahead.  What remains serial is one document's chain of chunks on ONE wavefront: a step a chunk, and
+//                      a load per 64 items.
+//   (k_scan_partials64, k_scan_top, k_scan_final64: the counts -> doc_chunk_offs)
+//   the writing pass   chunk_tokens[c] = s (piece_toffs are batch-wide).  The byte start at an item boundary is piece_boffs; inside an item the walking lane adds
+//                      the key lengths of the item's ids in front of s through the decode table (as k_tokspan_mark does), going on from where the chunk before
+//                      stopped.  chunk_units[c] receives the BATCH byte position for k_chunk_units.
+//   k_chunk_unitcount  the UTF-16 units begun in every span of kChunkUnitSpan = 128 bytes (tkz_span_units16 holds the rule); launch_scan: their exclusive scan.
+//                      (Per 1 KiB sub-tile, as the span entries count, a chunk's position cost half a KiB of text read on average: 11 GB for the 24 million
+//                      chunks of the headline batch at a budget of 64, and k_chunk_units was 8 - 10 ms of the call.)
+//   k_chunk_units      a wavefront per 64 chunks, a lane finds the document of its chunk; for every chunk that is not its document's first a group of 16 lanes
+//                      counts the units of the span in front of the position (8 lanes) and in front of the document's start (8 lanes): base + count, one
+//                      minus the other.
+// With an error bit in the counter block the counts are 0; with one, with ids that did not fit or with more chunks than chunk_cap the table is left alone.
+// -------------------------------------------------------------------------------------------------
+TKZ_DEV void tkz_span_units16(const uint8_t* bytes, int64_t total, int64_t p0, int64_t end, uint32_t* begun, uint32_t* four);      // (the span helpers, below)
+TKZ_DEV int tkz_chunk_popc2(uint32_t a, uint32_t b) { return tkz_popc32(a) + tkz_popc32(b); }
+// The end of the chunk that starts at token s inside item *p (toffs[*p] == *tp <= s < toffs[*p + 1]) of a document whose items end at p1, with MORE than m tokens
+// left (toffs[p1] > s + m): the last item boundary at or below s + m -- *p and *tp move there -- or, when that is *p itself, s + m inside the item.
+TKZ_DEV int64_t tkz_chunk_end(const int64_t* toffs, int64_t p1, int64_t s, int64_t m, int64_t* p, int64_t* tp) {
+    const int64_t lim = s + m;
+    int64_t lo = *p, tlo = *tp, hi = p1;
+    for (int64_t step = 1; lo + step < hi; step <<= 1) {
+        const int64_t i = lo + step, v = toffs[i];
+        if (v > lim) { hi = i; break; }
+        lo = i; tlo = v;
+    }
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2, v = toffs[mid];
+        if (v <= lim) { lo = mid; tlo = v; } else hi = mid;
+    }
+    if (lo == *p) return lim;
+    *p = lo; *tp = tlo;
+    return tlo;
+}
+struct TkzChunkItem { int64_t item, tok, pos; };           // the item a walk is inside of: its ids in front of token `tok` end at batch byte `pos`
+// chunk o of the table: it starts at token s, in item p (whose first token is tp) of the document that starts at byte a; first: the document's first chunk
+TKZ_DEV void tkz_chunk_emit(const ChunkParams& C, const TkzDecodeTable& D, int64_t o, int64_t a, bool first, int64_t s, int64_t p, int64_t tp, TkzChunkItem* W) {
+    if (o < 0 || o >= C.chunk_cap) return;
+    C.chunk_tokens[o] = s;
+    if (!C.chunk_bytes && !C.chunk_units) return;
+    int64_t pos = a;
+    if (!first && s == tp) pos = C.piece_boffs[p];
+    else if (!first) {
+        const int64_t b0 = C.piece_boffs[p], b1 = C.piece_boffs[p + 1];
+        if (W->item != p) { W->item = p; W->tok = tp; W->pos = b0; }
+        bool bad = false;
+        for (int64_t t = W->tok; t < s; ++t) {
+            uint32_t off, len = 0;
+            if (!tkz_dec_find(D, C.ids[t], &off, &len)) bad = true;
+            W->pos += len;
+        }
+        W->tok = s;
+        pos = W->pos;
+        if (bad || pos <= b0 || pos >= b1) {               // (the start lies inside the item: nothing is read outside the text)
+            simt::atomic_or((unsigned*)&C.counters[0], (unsigned)kErrChunkSum);
+            pos = b0;
+        }
+    }
+    if (C.chunk_bytes) C.chunk_bytes[o] = pos - a;
+    if (C.chunk_units) C.chunk_units[o] = first ? 0 : pos;
+}
+
+TKZ_KERNEL(256) void k_chunk_walk(ChunkParams C, TkzDecodeTable D, int write) {
+    const int64_t stride = simt::nblocks() * simt::nthreads(), i0 = simt::bid() * simt::nthreads() + simt::tid();
+    const bool bad = C.counters[0] != 0;
+    const int64_t m = C.max_tokens;
+    if (write) {
+        const int64_t nch = C.doc_chunk_offs[C.n_docs];
+        if (i0 == 0) *C.n_chunks = nch;
+        if (bad || *C.grand > C.out_cap || nch > C.chunk_cap) return;
+        if (i0 == 0) C.chunk_tokens[nch] = *C.grand;
+    }
+    for (int64_t d = i0; d <= C.n_docs; d += stride) {
+        if (bad) { if (d < C.n_docs) C.doc_cnt[d] = 0; C.out_offs[d] = 0; continue; }
+        const int64_t p0 = C.doc_piece[d];
+        int64_t tp = C.piece_toffs[p0];
+        if (!write) C.out_offs[d] = tp;
+        if (d == C.n_docs) break;
+        const int64_t p1 = C.doc_piece[d + 1], tend = C.piece_toffs[p1];
+        int64_t c = 0;
+        if (tend - tp > m && p1 - p0 > kChunkLongItems) {     // (k_chunk_walk_long's: the count as well)
+            if (!write) C.long_list[simt::atomic_add64(C.long_count, 1ull)] = d;
+            continue;
+        }
+        if (tend > tp) {
+            const int64_t base = write ? C.doc_chunk_offs[d] : 0, a = write ? C.offs[d] : 0;
+            int64_t s = tp, p = p0;
+            TkzChunkItem W{-1, 0, 0};
+            for (;;) {
+                if (write) tkz_chunk_emit(C, D, base + c, a, c == 0, s, p, tp, &W);
+                ++c;
+                if (tend - s <= m) break;
+                s = tkz_chunk_end(C.piece_toffs, p1, s, m, &p, &tp);
+            }
+        }
+        if (!write) C.doc_cnt[d] = c;
+    }
+}
+
+TKZ_KERNEL(256) void k_chunk_walk_long(ChunkParams C, TkzDecodeTable D, int write) {
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    if (C.counters[0] != 0) return;                           // (nothing was listed)
+    if (write && (*C.grand > C.out_cap || C.doc_chunk_offs[C.n_docs] > C.chunk_cap)) return;
+    const int64_t m = C.max_tokens, nlong = (int64_t)*C.long_count, none = (int64_t)0x7FFFFFFFFFFFFFFFll;
+    for (int64_t q = wave0; q < nlong; q += nwaves) {
+        const int64_t d = C.long_list[q], p0 = C.doc_piece[d], p1 = C.doc_piece[d + 1], tend = C.piece_toffs[p1];
+        const int64_t base = write ? C.doc_chunk_offs[d] : 0, a = write ? C.offs[d] : 0;
+        int64_t tp = C.piece_toffs[p0], s = tp, p = p0, c = 0;
+        // the window: v is piece_toffs[w + lane] (beyond the document: `none`); w <= p + 1 <= w + 63 wherever a chunk starts.  The three windows behind it are
+        // on their way (n1, n2, n3): a step to the next window waits for a load issued three steps ago, not for one it has just issued
+        int64_t w = p0 + 1;
+        const int64_t* const tl = C.piece_toffs + lane;
+        int64_t v = w + lane <= p1 ? tl[w] : none, n1 = w + 64 + lane <= p1 ? tl[w + 64] : none, n2 = w + 128 + lane <= p1 ? tl[w + 128] : none,
+                n3 = w + 192 + lane <= p1 ? tl[w + 192] : none;
+        TkzChunkItem W{-1, 0, 0};
+        for (;;) {
+            if (write && lane == 0) tkz_chunk_emit(C, D, base + c, a, c == 0, s, p, tp, &W);
+            ++c;
+            if (tend - s <= m) break;
+            const int64_t lim = s + m;
+            int64_t k = p, tk = tp;                           // the last boundary at or below lim
+            for (;;) {
+                const int n = tkz_popc64(simt::ballot(v <= lim));      // (ascending: the lanes at or below lim are the first n)
+                if (n > 0 && w + n - 1 > k) { k = w + n - 1; tk = tkz_shfl64(v, n - 1); }
+                if (n < 64) break;
+                w += 64; v = n1; n1 = n2; n2 = n3; n3 = w + 192 + lane <= p1 ? tl[w + 192] : none;
+            }
+            if (k > p) { s = tk; p = k; tp = tk; } else s = lim;
+        }
+        if (!write && lane == 0) C.doc_cnt[d] = c;
+    }
+}
+
+TKZ_KERNEL(256) void k_chunk_unitcount(ChunkParams C) {
+    const int lane = simt::lane();
+    const int64_t sub = simt::bid() * (kThreads / 64) + simt::wave();
+    if (sub * kSub >= C.total) return;
+    uint32_t begun, four;
+    tkz_span_units16(C.bytes, C.total, sub * kSub + lane * 16, C.total, &begun, &four);
+    int c = tkz_chunk_popc2(begun, four);
+    for (int m = 1; m < kChunkUnitSpan / 16; m <<= 1) c += simt::shfl_xor(c, m);
+    const int64_t span = sub * (kSub / kChunkUnitSpan) + lane / (kChunkUnitSpan / 16);
+    if ((lane & (kChunkUnitSpan / 16 - 1)) == 0 && span < C.nspan) C.cnt_unit[span] = c;
+}
+// The UTF-16 units begun in [0, x) of the batch (0 <= x < total), by a GROUP of 8 lanes (l8: the lane in its group; every lane of the wavefront calls, every lane
+// of a group gets its group's sum): the base of x's span of kChunkUnitSpan bytes and the span's bytes in front of x.  x == 0 reads nothing.
+TKZ_DEV int64_t tkz_chunk_units_before(const ChunkParams& C, int64_t x, int l8) {
+    int64_t span = x / kChunkUnitSpan;
+    if (span >= C.nspan) span = C.nspan - 1;
+    const int64_t p0 = span * kChunkUnitSpan + l8 * 16;
+    int c = 0;
+    if (p0 < x) {
+        uint32_t begun, four;
+        tkz_span_units16(C.bytes, C.total, p0, x, &begun, &four);
+        c = tkz_chunk_popc2(begun, four);
+    }
+    for (int m = 1; m < kChunkUnitSpan / 16; m <<= 1) c += simt::shfl_xor(c, m);
+    return x > 0 ? C.base_unit[span] + c : 0;
+}
+TKZ_KERNEL(256) void k_chunk_units(ChunkParams C) {
+    const int lane = simt::lane(), sl = lane & 15, g0 = lane & 48;
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t nch = C.doc_chunk_offs[C.n_docs];
+    if (C.counters[0] != 0 || *C.grand > C.out_cap || nch > C.chunk_cap) return;
+    for (int64_t c0 = wave0 * 64; c0 < nch; c0 += nwaves * 64) {
+        const int64_t c1 = c0 + 64 < nch ? c0 + 64 : nch, c = c0 + lane;
+        // the documents of the tile's first and last chunk (wave-uniform), then every lane's own among them
+        const int64_t d0 = tkz_last_le(C.doc_chunk_offs, 0, C.n_docs - 1, c0), d1 = tkz_last_le(C.doc_chunk_offs, d0, C.n_docs - 1, c1 - 1);
+        int64_t pos = 0, a = 0, units = 0;
+        bool work = false;
+        if (c < c1) {
+            const int64_t d = d0 == d1 ? d0 : tkz_last_le(C.doc_chunk_offs, d0, d1, c);
+            if (C.doc_chunk_offs[d] != c) { work = true; pos = C.chunk_units[c]; a = C.offs[d]; }      // (a document's first chunk starts at unit 0: written already)
+        }
+        if (work && (pos <= a || pos >= C.total)) { pos = a; simt::atomic_or((unsigned*)&C.counters[0], (unsigned)kErrChunkSum); }
+        if (!work) pos = a = 0;
+        // a group of 16 lanes takes the chunks of its own lanes one after the other, the four groups side by side (the control flow stays wave-uniform: a group
+        // with nothing to do counts in front of byte 0, which reads nothing): its lower 8 lanes count in front of the chunk's start, its upper 8 in front of the
+        // document's start, at the same time
+        for (int r = 0; r < 16; ++r) {
+            const int64_t rpos = tkz_shfl64(pos, g0 + r), ra = tkz_shfl64(a, g0 + r);
+            if (simt::ballot(rpos != 0) == 0) continue;
+            const int64_t mine = tkz_chunk_units_before(C, sl < 8 ? rpos : ra, sl & 7), other = tkz_shfl64(mine, lane ^ 8);
+            if (sl == r) units = sl < 8 ? mine - other : other - mine;
+        }
+        if (work) C.chunk_units[c] = units;
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // Token spans (tkz_encode_batch_spans_device): where every token's text starts, behind the piece-granular launch sequence -- which leaves the ids in the
 // caller's buffer and the byte and token offset of every piece and the first piece of every document in the workspace.
 //   k_tokspan_mark   one lane per piece.  A piece of one token (nearly all, and every taken special-token literal) starts where the piece starts: that bit is in
@@ -4458,6 +4660,27 @@ void launch_tokspans(const Launch& L, const SpanParams& S, const TkzDecodeTable&
     TKZ_LAUNCH(k_tokspan_count, g, kThreads, L.stream, S);
     launch_scan2(L, S.nsub, S.bsum, S.cnt_tok, S.base_tok, S.sums, 1, S.tok_units ? S.cnt_unit : nullptr, S.base_unit, S.sums + 1, 1, -1);
     TKZ_LAUNCH(k_tokspan_write, g, kThreads, L.stream, S);
+    hook(L, K_DOCOFFS, 1);
+}
+// (the bracket: K_DOCOFFS's again.  How many documents are listed and how many chunks there are is known on the device only: the wavefront kernels get a grid
+//  that the bounds allow -- a listed document has more than kChunkLongItems bytes, chunk_cap chunks at most are written -- and stride over what there is)
+void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& D) {
+    const int64_t g_docs = grid_for(C.n_docs + 1), nblk = grid1(cdiv(C.n_docs, kScanBlock));
+    int64_t g_long = cdiv(C.total / kChunkLongItems, kThreads / 64), g_units = cdiv(cdiv(C.chunk_cap, 64), kThreads / 64);
+    g_long = g_long < 1 ? 1 : (g_long > 1024 ? 1024 : g_long);
+    g_units = g_units < 1 ? 1 : (g_units > 2048 ? 2048 : g_units);
+    TKZ_LAUNCH(k_chunk_walk, g_docs, kThreads, L.stream, C, D, 0);
+    TKZ_LAUNCH(k_chunk_walk_long, g_long, kThreads, L.stream, C, D, 0);
+    TKZ_LAUNCH(k_scan_partials64, nblk, kThreads, L.stream, (const int64_t*)C.doc_cnt, C.n_docs, C.bsum);
+    TKZ_LAUNCH(k_scan_top, 1, kThreads, L.stream, C.bsum, nblk, C.doc_chunk_offs + C.n_docs);
+    TKZ_LAUNCH(k_scan_final64, nblk, kThreads, L.stream, (const int64_t*)C.doc_cnt, C.n_docs, (const int64_t*)C.bsum, C.doc_chunk_offs);
+    if (C.chunk_units) {
+        TKZ_LAUNCH(k_chunk_unitcount, grid1(cdiv(cdiv(C.total, kSub), kThreads / 64)), kThreads, L.stream, C);
+        launch_scan(L, C.cnt_unit, C.nspan, C.ubsum, C.base_unit, C.usum, -1, 1);
+    }
+    TKZ_LAUNCH(k_chunk_walk, g_docs, kThreads, L.stream, C, D, 1);
+    TKZ_LAUNCH(k_chunk_walk_long, g_long, kThreads, L.stream, C, D, 1);
+    if (C.chunk_units) TKZ_LAUNCH(k_chunk_units, g_units, kThreads, L.stream, C);
     hook(L, K_DOCOFFS, 1);
 }
 int64_t dec_tiles(int64_t total_ids) { return cdiv(total_ids, kDecTile); }

@@ -474,6 +474,77 @@ class TikTokenizer:
                 break
         return token_ids[cut_tokens:], self._utf16_prefix(text, cut_len, drop=True)
 
+    # ---- token-budget chunks: the repeated-EncodeTrimSuffix loop in one call (include/tkz.h, "Token-budget chunks") ----
+    def EncodeChunks(self, text: str, a, b=None):
+        """The text cut into chunks of at most maxTokenCount tokens: a list of (ids, text).  The two overload shapes of EncodeTrimSuffix.  While no piece exceeds the
+        budget the chunks are what `while rest: ids, part = EncodeTrimSuffix(rest, ...); rest = rest[len(part):]` yields; a piece of more tokens than the budget is
+        cut into runs of maxTokenCount tokens (that loop would never end there), its last partial run begins a chunk that goes on with the pieces that follow.  The
+        ids concatenate to Encode's, the texts -- sliced in UTF-16 code units, a character cut by a chunk boundary goes to the earlier chunk -- to the input.
+        maxTokenCount < 1 is a ValueError."""
+        return self.EncodeChunksBatch([text], a, b)[0]
+
+    def EncodeChunksBatch(self, texts: Sequence[str], a, b=None):
+        """EncodeChunks for every text, in ONE device call (tkz_encode_batch_chunks_utf8): one list of (ids, text) per text."""
+        allowed, max_tokens = self._trim_args(a, b)
+        if max_tokens < 1:
+            raise ValueError("maxTokenCount must be at least 1")
+        if not texts:
+            return []
+        plain = not allowed or self._special_re is None
+        if not plain and (self._special_on_host or (self._fffd_literal and any(_has_lone_surrogate(t) for t in texts))):
+            return [self._chunks_host(t, allowed, max_tokens) for t in texts]
+        segs = [_utf8_like_dotnet(t) for t in texts]
+        offs = np.zeros(len(segs) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+        data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+        names = set(allowed) if not plain else set()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]           # (registration order = the alternation's)
+        try:
+            ids, _, dco, ct, _, cu = self._encoder.encode_batch_chunks(data, offs, max_tokens, index, want_bytes=False)
+        except N.UnsupportedError:
+            self._special_on_host = True
+            return [self._chunks_host(t, allowed, max_tokens) for t in texts]
+        flat, ct, cu = ids.tolist(), ct.tolist(), cu.tolist()
+        out = []
+        for d, t in enumerate(texts):
+            lo, hi = int(dco[d]), int(dco[d + 1])
+            raw = t.encode("utf-16-le", "surrogatepass")
+            cuts = cu[lo:hi] + [len(raw) // 2]
+            out.append([(flat[ct[c]:ct[c + 1]], raw[2 * cuts[c - lo]:2 * cuts[c - lo + 1]].decode("utf-16-le", "surrogatepass")) for c in range(lo, hi)])
+        return out
+
+    def _units_of_ids(self, ids) -> int:
+        """the UTF-16 units begun in the keys of `ids`: one per non-continuation byte, one more per byte >= 0xF0"""
+        data, _ = self._encoder.decode_batch(np.asarray(ids, np.int32), np.asarray([0, len(ids)], np.int64))
+        data = np.asarray(data, np.uint8)
+        return int(((data & 0xC0) != 0x80).sum() + (data >= 0xF0).sum())
+
+    def _chunks_host(self, text: str, allowed, max_tokens: int):
+        """the host walk over _piece_items by the rule of tkz.h: the fallback of EncodeChunksBatch"""
+        import bisect
+        items = self._piece_items(text, allowed)
+        flat: List[int] = []
+        tcum, ucum = [0], [0]                                   # tokens and UTF-16 units in front of every item
+        for n, ids, ulen, _ in items:
+            flat.extend(ids)
+            tcum.append(tcum[-1] + n)
+            ucum.append(ucum[-1] + ulen)
+        total = tcum[-1]
+        starts = []                                            # (first token, first unit) of every chunk
+        s = p = 0                                              # the chunk starts at token s, in (or at the start of) item p
+        while s < total:
+            starts.append((s, ucum[p] + (self._units_of_ids(items[p][1][:s - tcum[p]]) if s > tcum[p] else 0)))
+            if total - s <= max_tokens:
+                break
+            k = bisect.bisect_right(tcum, s + max_tokens) - 1   # the last boundary at or below s + max
+            if tcum[k] > s:
+                s, p = tcum[k], k
+            else:
+                s += max_tokens                                # (no boundary in reach: inside item p)
+        raw = text.encode("utf-16-le", "surrogatepass")
+        ends = starts[1:] + [(total, len(raw) // 2)]
+        return [(flat[s:e], raw[2 * u:2 * v].decode("utf-16-le", "surrogatepass")) for (s, u), (e, v) in zip(starts, ends)]
+
     def Decode(self, tokens: Sequence[int]) -> str:
         """TikTokenizer.cs:586-604: ids that are neither in the vocabulary nor special tokens are dropped; the bytes are decoded as
         UTF-8 (Encoding.UTF8.GetString: malformed sequences become U+FFFD).  One id list is one kernel launch (tkz_decode_utf8)."""
