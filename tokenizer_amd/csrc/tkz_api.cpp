@@ -109,7 +109,10 @@ struct CounterBlock {          // mirrors the device block
     int64_t kept_total;                    // the trim entries: ids kept over the whole batch (k_trim_gather)
     int64_t n_chunks;                      // the chunk entries: chunks of the whole batch (k_chunk_walk's writing pass)
     unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
+    // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
+    int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
 };
+constexpr size_t kCountersRerun = offsetof(CounterBlock, has_empty);      // what a re-run clears of the counter block
 // ... and the 64-byte block of the length scans (the UTF-16 transcoder, the two decoders): k_docmark's / k_dec_write's error bits, the scans' grand totals
 struct LenCounters { int32_t err, pad; int64_t grand /* UTF-8 bytes */, grand16 /* UTF-16 code units (tkz_decode_batch_utf16 only) */; };
 const char* const kMsgByteOffsets = "document offsets must start at 0, be non-decreasing and end at the byte count";
@@ -922,8 +925,9 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
     uint64_t* docbits = ws->w_docbits.as<uint64_t>();
     uint64_t* startbits = ws->w_startbits.as<uint64_t>();
     const SpecialCall* const special = c.literals();
-    if (marks_reused) {      // (the counters and the sub-tile flags only)
-        HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, 256, stream));
+    int32_t* const has_empty = reinterpret_cast<int32_t*>(cb + offsetof(CounterBlock, has_empty));
+    if (marks_reused) {      // (the counters and the sub-tile flags only; has_empty stays what the first attempt's k_docmark made it)
+        HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, kCountersRerun, stream));
         if (!c.bitmap_only()) HIP_TRY(hipMemsetAsync(ws->w_heavyq.p, 0, (size_t)(ws->w_zero.as<char>() + ws->zero_bytes - ws->w_heavyq.as<char>()), stream));
     } else {
         if (c.ingest) launch_ingest(L, c.ingest->h_bytes, total, const_cast<uint8_t*>(d_bytes), c.ingest->h_offs, n_docs + 1, const_cast<int64_t*>(d_offs), ws->w_zero.p, (int64_t)ws->zero_bytes);
@@ -931,7 +935,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
         //  a blit kernel that queued behind its D2H blit of the chunk before -- the 16 MB call's second chunk started when the first one's download ended.)
         else if (ws->zero_bytes <= (size_t(8) << 20)) launch_ingest(L, nullptr, 0, nullptr, nullptr, 0, nullptr, ws->w_zero.p, (int64_t)ws->zero_bytes);
         else HIP_TRY(hipMemsetAsync(ws->w_zero.p, 0, ws->zero_bytes, stream));
-        launch_docmark(L, d_offs, n_docs, total, docbits, counters);
+        launch_docmark(L, d_offs, n_docs, total, docbits, counters, has_empty);
         // the special entries: the pre-tokenizer splits between SEGMENT marks (the documents cut at the literals taken), from a bitmap or -- the scanners that take
         // offsets: the sequential one, o200k's last resort -- from the segments' offsets
         const uint64_t* isobits = docbits;
@@ -1036,7 +1040,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             if (c.count_only) launch_tokcount(L, P, ws->w_tbase.as<int64_t>(), ws->w_dcount.as<int32_t>(), ntiles);
             else launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
-                if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs);
+                if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs, has_empty);
                 const int64_t* produced = grand;
                 if (c.trim) {
                     int64_t* const keep = ws->t_keep.as<int64_t>();
@@ -1071,7 +1075,7 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                 launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
-                               n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+                               has_empty, n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
         }
     }
     HIP_TRY(hipMemcpyAsync(ws->h_counters, counters, sizeof(CounterBlock), hipMemcpyDeviceToHost, stream));

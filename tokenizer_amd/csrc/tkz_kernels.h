@@ -167,7 +167,8 @@ typedef void (*KernelHook)(void* ctx, int kernel_id, int phase /*0 before, 1 aft
 // beside k_merge_short on `stream` (a large batch only: EncodeParams::tc_atomic says that the token counts of the sub-tiles are summed with atomics from zero)
 struct Launch { hipStream_t stream; KernelHook hook; void* hook_ctx; hipStream_t side = nullptr, side2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr; };
 
-void launch_docmark(const Launch& L, const int64_t* d_offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters);
+// has_empty: null, or a zeroed word that is set when an item is empty (launch_docoffs)
+void launch_docmark(const Launch& L, const int64_t* d_offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters, int32_t* has_empty = nullptr);
 // position-parallel Regex.Matches; xq / xcount: queue of row blocks left to the sequential matcher (o200k only)
 void launch_pretok_rows(const Launch& L, int pattern, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs, int64_t total,
                         const uint64_t* docbits, uint64_t* startbits, int64_t nrows, const uint8_t* bmp, int32_t* counters,
@@ -186,9 +187,10 @@ void launch_place(const Launch& L, const EncodeParams& P, const int64_t* tile_ba
 // a count call (tkz_count_*): P.doc_tok as launch_place leaves it and nothing else -- no ids.  dcount: the marks of every sub-tile (launch_doccount2)
 void launch_tokcount(const Launch& L, const EncodeParams& P, const int64_t* tile_base, const int32_t* dcount, int64_t nsub);
 // (c3a / c3b / c3c: null, or blocks that receive {c3_docs, total, *grand}: launch_counts3's job done by the same launch)
+// has_empty: the word launch_docmark set when an item of the batch is empty (zero: the ordinal of item d's mark is d, and the bitmap is not searched)
 void launch_docoffs(const Launch& L, const int64_t* d_offs, int64_t n_docs, int64_t total, const int64_t* tile_base,
                     const uint64_t* docbits, const int64_t* docord_base, const int32_t* doc_tok, const int64_t* grand, int64_t* out_offs,
-                    int64_t c3_docs = 0, int64_t* c3a = nullptr, int64_t* c3b = nullptr, int64_t* c3c = nullptr);
+                    const int32_t* has_empty, int64_t c3_docs = 0, int64_t* c3a = nullptr, int64_t* c3b = nullptr, int64_t* c3c = nullptr);
 // the counts of two bitmaps per sub-tile in one pass; the scan of one or two count arrays -- a single launch up to 8,192 sub-tiles
 void launch_doccount2(const Launch& L, const uint64_t* bits_a, const uint64_t* bits_b, int64_t nwords, int64_t total, int64_t nsub, int32_t* cnt_a, int32_t* cnt_b);
 void launch_scan2(const Launch& L, int64_t ntiles, int64_t* bsum, const int32_t* cnt_a, int64_t* base_a, int64_t* grand_a, int round_to_a,

@@ -34,14 +34,21 @@ namespace tkz {
 // -------------------------------------------------------------------------------------------------
 // k_docmark
 // -------------------------------------------------------------------------------------------------
-TKZ_KERNEL(256) void k_docmark(const int64_t* offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters) {
+// has_empty: null, or a word that is set when an item is empty (offs[d] == offs[d + 1]): k_docoffs then looks every mark's ordinal up, and takes the
+// item's index for it otherwise.  (A plain store of the same 1 by every lane that sees one: an atomic per empty document would serialise a batch of a
+// million of them on one line, as k_probe's REPORT once did.)
+TKZ_KERNEL(256) void k_docmark(const int64_t* offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters, int32_t* has_empty) {
     const int64_t stride = simt::nblocks() * simt::nthreads();
     for (int64_t d = simt::bid() * simt::nthreads() + simt::tid(); d <= n_items; d += stride) {
         const int64_t pos = offs[d];
         bool ok = pos >= 0 && pos <= total;
         if (d == 0) ok = ok && pos == 0;
         if (d == n_items) ok = ok && pos == total;
-        else ok = ok && pos <= offs[d + 1];
+        else {
+            const int64_t next = offs[d + 1];
+            ok = ok && pos <= next;
+            if (has_empty && pos == next) *has_empty = 1;
+        }
         if (!ok) { simt::atomic_or((unsigned*)&counters[0], (unsigned)kErrOffsets); continue; }
         // One plain store per bitmap word, by the first item that starts in it (the words were zeroed; 10 M atomics were a read-modify-write of nearly every
         // line of a 640 MB bitmap).  Offsets that are not monotone are reported by the item that sees it and the batch fails: what is stored then is never used.
@@ -2636,10 +2643,17 @@ TKZ_KERNEL(256) void k_scan_final(const int32_t* cnt, int64_t n, const int64_t* 
 // k_docoffs
 // -------------------------------------------------------------------------------------------------
 // (c3a / c3b / c3c: null, or blocks that receive {c3_docs, total, *grand} -- the batch's counts, k_counts3's job, by the first thread: one launch less)
+// The ordinal of item d's mark.  The marks are the DISTINCT start positions below `total`, and k_place / k_tokcount fill doc_tok by a mark's ordinal among
+// them.  When no item of the batch is empty (*has_empty == 0: k_docmark saw offs[d] < offs[d + 1] for every d < n_docs) the offsets increase strictly on
+// [0, n_docs], so the starts below `total` are exactly items 0 .. n_docs - 1, all distinct and in order: the mark of item d has ordinal d, and neither the
+// bitmap nor docord_base is read.  (Offsets that are not monotone fail the batch in k_docmark; d <= n_docs < the n_docs + 2 entries of doc_tok whatever they
+// say.)  At piece granularity the items are the piece starts as k_piece_index read them off the bitmap: distinct by construction, so the same holds; a batch
+// with an empty document takes the search there too.  With an empty item several items share a mark, and the ordinal is searched as before.
 TKZ_KERNEL(256) void k_docoffs(const int64_t* offs, int64_t n_docs, int64_t total, const int64_t* tile_base, const uint64_t* docbits,
                                const int64_t* docord_base, const int32_t* doc_tok, const int64_t* grand, int64_t* out_offs,
-                               int64_t c3_docs, int64_t* c3a, int64_t* c3b, int64_t* c3c) {
+                               int64_t c3_docs, int64_t* c3a, int64_t* c3b, int64_t* c3c, const int32_t* has_empty) {
     const int64_t stride = simt::nblocks() * simt::nthreads();
+    const bool search = *has_empty != 0;                // (one word for the whole grid: wave-uniform)
     if (simt::bid() == 0 && simt::tid() == 0) {
         const int64_t g = *grand;
         if (c3a) { c3a[0] = c3_docs; c3a[1] = total; c3a[2] = g; }
@@ -2651,6 +2665,7 @@ TKZ_KERNEL(256) void k_docoffs(const int64_t* offs, int64_t n_docs, int64_t tota
         if (pos >= total) { out_offs[d] = *grand; continue; }
         if (pos < 0) { out_offs[d] = 0; continue; }
         const int64_t sub = pos / kSub, wpos = pos >> 6;
+        if (!search) { out_offs[d] = tile_base[sub] + doc_tok[d]; continue; }
         int64_t ord = docord_base[sub];
         for (int64_t w = sub * (kSub / 64); w < wpos; ++w) ord += tkz_popc64(docbits[w]);
         ord += tkz_popc64(docbits[wpos] & tkz_lowmask((int)(pos & 63)));
@@ -4404,9 +4419,9 @@ static inline int64_t grid1(int64_t g) { return g < 1 ? 1 : g; }
 static inline int64_t xcd_grid(int64_t blocks) { return (blocks + 7) & ~(int64_t)7; }     // tkz_xcd_block: XCD x takes the x-th eighth of the blocks
 static inline int64_t grid_for(int64_t items) { const int64_t g = cdiv(items, kThreads); return g < 1 ? 1 : (g > 16384 ? 16384 : g); }
 
-void launch_docmark(const Launch& L, const int64_t* d_offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters) {
+void launch_docmark(const Launch& L, const int64_t* d_offs, int64_t n_items, int64_t total, uint64_t* bits, int32_t* counters, int32_t* has_empty) {
     hook(L, K_DOCMARK, 0);
-    TKZ_LAUNCH(k_docmark, grid_for(n_items + 1), kThreads, L.stream, d_offs, n_items, total, bits, counters);
+    TKZ_LAUNCH(k_docmark, grid_for(n_items + 1), kThreads, L.stream, d_offs, n_items, total, bits, counters, has_empty);
     hook(L, K_DOCMARK, 1);
 }
 void launch_pretok_rows(const Launch& L, int pattern, const uint8_t* d_bytes, const int64_t* d_offs, int64_t n_docs, int64_t total,
@@ -4596,9 +4611,9 @@ void launch_scan(const Launch& L, const int32_t* tile_count, int64_t ntiles, int
 }
 void launch_docoffs(const Launch& L, const int64_t* d_offs, int64_t n_docs, int64_t total, const int64_t* tile_base,
                     const uint64_t* docbits, const int64_t* docord_base, const int32_t* doc_tok, const int64_t* grand, int64_t* out_offs,
-                    int64_t c3_docs, int64_t* c3a, int64_t* c3b, int64_t* c3c) {
+                    const int32_t* has_empty, int64_t c3_docs, int64_t* c3a, int64_t* c3b, int64_t* c3c) {
     hook(L, K_DOCOFFS, 0);
-    TKZ_LAUNCH(k_docoffs, grid_for(n_docs + 1), kThreads, L.stream, d_offs, n_docs, total, tile_base, docbits, docord_base, doc_tok, grand, out_offs, c3_docs, c3a, c3b, c3c);
+    TKZ_LAUNCH(k_docoffs, grid_for(n_docs + 1), kThreads, L.stream, d_offs, n_docs, total, tile_base, docbits, docord_base, doc_tok, grand, out_offs, c3_docs, c3a, c3b, c3c, has_empty);
     hook(L, K_DOCOFFS, 1);
 }
 void launch_case_equiv_fix(const Launch& L, const uint8_t* d_bytes, int64_t total, const uint64_t* docbits, uint64_t* startbits) {
