@@ -142,6 +142,36 @@ TKZ_DEV void tkz_rows_sequential(const TkzSrc& S, const uint64_t* docbits, uint6
     if (simt::ballot(bad != 0) && lane == 0) simt::atomic_or((unsigned*)&counters[0], (unsigned)kErrUtf8);
 }
 
+// The 4 KiB of a block (rows first .. first+63: 16-byte chunk c = lane + 64 q is part c%4 of row c/4) and the first 16 bytes of the row behind it (a char of
+// the last row may end there), requested TOGETHER: four named requests and the trailing one per lane, nothing waited for in between -- one round trip to the
+// memory, where a rolled loop (request, wait, LDS write, four times) and a scalar load of the trailing row made five.  Every staged row is a full row of the
+// corpus (`inside`, the caller's), so a chunk in front of the corpus (block 0: pos < 0) and the lanes that have no trailing row to fetch read the block's
+// first bytes instead -- a line the wavefront requests anyway -- and drop them: no request sits inside a branch, and none is uniform (a uniform one goes
+// through the scalar cache and is waited for on its own).
+struct PretokStage { uint4 v0, v1, v2, v3, z; };
+TKZ_DEV uint4 tkz_load16_or_zero(const uint8_t* bytes, int64_t pos, int64_t safe, bool ok) {
+    uint4 v = tkz_load16(bytes + (ok ? pos : safe));
+    if (!ok) v.x = v.y = v.z = v.w = 0;
+    return v;
+}
+TKZ_DEV void tkz_pretok_request(const uint8_t* bytes, int64_t total, int64_t first, PretokStage& st) {
+    const int lane = simt::lane();
+    const int64_t safe = first < 0 ? 0 : first << 6;
+    const int64_t p0 = (first << 6) + 16 * (int64_t)lane, p1 = p0 + 1024, p2 = p0 + 2048, p3 = p0 + 3072;
+    const int64_t tpos = (first + 64) << 6;
+    st.v0 = tkz_load16_or_zero(bytes, p0, safe, p0 >= 0);
+    st.v1 = tkz_load16_or_zero(bytes, p1, safe, p1 >= 0);
+    st.v2 = tkz_load16_or_zero(bytes, p2, safe, p2 >= 0);
+    st.v3 = tkz_load16_or_zero(bytes, p3, safe, p3 >= 0);
+    st.z = tkz_load16_or_zero(bytes, tpos, safe, lane == 0 && tpos + 16 <= total);
+}
+TKZ_DEV void tkz_pretok_fill(uint4* s_blk, const PretokStage& st) {
+    const int lane = simt::lane();
+    uint4* const at = s_blk + ((lane >> 2) * kBlockRowStride + (lane & 3) * 16) / 16;       // chunk c = lane; chunk c + 64 is 16 rows further on
+    at[0] = st.v0; at[kBlockRowStride] = st.v1; at[2 * kBlockRowStride] = st.v2; at[3 * kBlockRowStride] = st.v3;
+    if (lane < kBlockRowStride / 16) s_blk[(64 * kBlockRowStride) / 16 + lane] = st.z;      // (lane 0: the trailing row's bytes; zeros beyond)
+}
+
 template <int PATTERN>
 TKZ_KERNEL(64) void k_pretok_rows(const uint8_t* bytes, int64_t total, const uint64_t* docbits, uint64_t* startbits,
                                   int64_t nrows, const uint8_t* bmp, int32_t* counters, int64_t* xq, unsigned long long* xcount) {
@@ -155,24 +185,15 @@ TKZ_KERNEL(64) void k_pretok_rows(const uint8_t* bytes, int64_t total, const uin
     const int64_t first = r0 - 1;                          // row of lane 0
     const bool inside = ((first + 64) << 6) <= total;       // every staged row is a full row of the corpus
     if (inside) {
-        for (int c = lane; c < 256; c += 64) {             // 16-byte chunk c of the 4 KiB block: row c/4, part c%4
-            const int64_t pos = (first << 6) + 16 * (int64_t)c;
-            uint4 v; v.x = v.y = v.z = v.w = 0;
-            if (pos >= 0) v = tkz_load16(bytes + pos);
-            s_blk[((c >> 2) * kBlockRowStride + (c & 3) * 16) / 16] = v;
-        }
-        if (lane < kBlockRowStride / 16) {                 // the row after the block: its first 16 bytes (a char of the last row may end there), zeros beyond
-            uint4 z; z.x = z.y = z.z = z.w = 0;
-            const int64_t pos = (first + 64) << 6;
-            if (lane == 0 && pos + 16 <= total) z = tkz_load16(bytes + pos);
-            s_blk[(64 * kBlockRowStride) / 16 + lane] = z;
-        }
-    }
-    simt::sync();
-    if (r0 >= nrows) return;
-    if (inside) {
+        // the block, the row behind it and this lane's word of document marks: all requested before the first wait
         const int64_t row = first + lane;
-        const uint64_t ds = (row >= 0 && row < nrows) ? docbits[row] : 0;
+        uint64_t ds = 0;
+        PretokStage st;
+        tkz_pretok_request(bytes, total, first, st);
+        if (row >= 0 && row < nrows) ds = docbits[row];
+        tkz_pretok_fill(s_blk, st);
+        simt::sync();
+        if (r0 >= nrows) return;
         uint64_t out;
         bool done;
         if constexpr (PATTERN == TKZ_PAT_O200K) {
@@ -184,7 +205,7 @@ TKZ_KERNEL(64) void k_pretok_rows(const uint8_t* bytes, int64_t total, const uin
             if (PATTERN == TKZ_PAT_O200K && lane == 0) reinterpret_cast<uint8_t*>(xq)[simt::bid()] = 0;
             return;
         }
-    }
+    } else if (r0 >= nrows) return;                        // (`inside` is the same for the whole workgroup -- one wavefront -- so every lane meets the same barriers)
     const int64_t r1 = r0 + kRowsPerWave < nrows ? r0 + kRowsPerWave : nrows;
     if constexpr (PATTERN == TKZ_PAT_O200K) {
         // no row-sequential scanner for o200k: the block's rows start as the document-start bits and the block goes to
@@ -215,21 +236,13 @@ TKZ_DEV void tkz_pretok_block(int64_t blk, uint4* s_blk, const uint16_t* s_aflag
     const bool inside = ((first + 64) << 6) <= total;       // every staged row is a full row of the corpus
     if (inside) {
         (void)simt::ballot(true);                          // (the block before this one is no longer read)
-        for (int c = lane; c < 256; c += 64) {
-            const int64_t pos = (first << 6) + 16 * (int64_t)c;
-            uint4 v; v.x = v.y = v.z = v.w = 0;
-            if (pos >= 0) v = tkz_load16(bytes + pos);
-            s_blk[((c >> 2) * kBlockRowStride + (c & 3) * 16) / 16] = v;
-        }
-        if (lane < kBlockRowStride / 16) {
-            uint4 z; z.x = z.y = z.z = z.w = 0;
-            const int64_t pos = (first + 64) << 6;
-            if (lane == 0 && pos + 16 <= total) z = tkz_load16(bytes + pos);
-            s_blk[(64 * kBlockRowStride) / 16 + lane] = z;
-        }
-        (void)simt::ballot(true);
         const int64_t row = first + lane;
-        const uint64_t ds = (row >= 0 && row < nrows) ? docbits[row] : 0;
+        uint64_t ds = 0;
+        PretokStage st;
+        tkz_pretok_request(bytes, total, first, st);       // (as in k_pretok_rows: every request before the first wait)
+        if (row >= 0 && row < nrows) ds = docbits[row];
+        tkz_pretok_fill(s_blk, st);
+        (void)simt::ballot(true);
         uint64_t out;
         if (tkz_block_eval<PATTERN>(reinterpret_cast<const uint8_t*>(s_blk), ds, bmp, &out)) {
             if (lane >= 1 && lane <= kRowsPerWave && row < nrows) startbits[row] = out;
@@ -260,26 +273,37 @@ TKZ_KERNEL_OCC(64, 3) void k_pretok_mb_blocks(const uint8_t* bytes, int64_t tota
         simt::sync();                                          // (the previous block's rows are no longer read)
         // rows first .. first+63 and the first 16 bytes of the row behind them; what lies outside the corpus reads as 0 -- the
         // sentinel bit at `total` makes whatever follows the last document a document of its own, so the padding changes nothing
-        for (int c = lane; c < 260; c += 64) {
+        // (five named requests a lane -- chunk c = lane + 64 q, the fifth by lanes 0..3 -- and the lane's word of document marks, all in front of the first
+        //  wait; the chunk the corpus ends in is rare and is put together byte by byte behind them)
+        const int64_t row = first + lane;
+        uint64_t ds = 0;
+        auto request = [&](int q) -> uint4 {                   // chunk c = lane + 64 q where the corpus holds all 16 bytes of it, zeros elsewhere
+            const int c = lane + 64 * q;
             const int64_t pos = (first << 6) + 16 * (int64_t)c;
             uint4 v; v.x = v.y = v.z = v.w = 0;
-            if (pos >= 0 && pos + 16 <= total) v = tkz_load16(bytes + pos);
-            else if (pos >= 0 && pos < total) {
+            if (c < 260 && pos >= 0 && pos + 16 <= total) v = tkz_load16(bytes + pos);
+            return v;
+        };
+        auto fill = [&](int q, uint4 v) {
+            const int c = lane + 64 * q;
+            const int64_t pos = (first << 6) + 16 * (int64_t)c;
+            if (c < 260 && pos >= 0 && pos + 16 > total && pos < total) {
                 uint32_t w[4] = {0, 0, 0, 0};
                 for (int j = 0; j < 16; ++j) if (pos + j < total) w[j >> 2] |= (uint32_t)bytes[pos + j] << (8 * (j & 3));
                 v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
             }
             if (c < 256) s_blk[((c >> 2) * kBlockRowStride + (c & 3) * 16) / 16] = v;
-            else {
-                uint4 z; z.x = z.y = z.z = z.w = 0;
-                s_blk[(64 * kBlockRowStride) / 16 + (c - 256)] = c == 256 ? v : z;
+            else if (c < 260) {
+                if (c != 256) v.x = v.y = v.z = v.w = 0;
+                s_blk[(64 * kBlockRowStride) / 16 + (c - 256)] = v;
             }
-        }
+        };
+        const uint4 v0 = request(0), v1 = request(1), v2 = request(2), v3 = request(3), v4 = request(4);
+        if (row >= 0 && row < nrows) ds = docbits[row];
+        fill(0, v0); fill(1, v1); fill(2, v2); fill(3, v3); fill(4, v4);
         if (lane == 0) { uint4 z; z.x = z.y = z.z = z.w = 0; s_blk[(64 * kBlockRowStride) / 16 + 4] = z; }
         simt::sync();
         {
-            const int64_t row = first + lane;
-            const uint64_t ds = (row >= 0 && row < nrows) ? docbits[row] : 0;
             TkzBlockCtx X; X.bytes = bytes; X.docbits = docbits; X.total = total; X.nrows = nrows; X.row0 = first;
             done = tkz_block_eval_o200k_mb(reinterpret_cast<const uint8_t*>(s_blk), ds, X, bmp, by_code_point != 0, &out);
             if (done && lane >= 1 && lane <= kRowsPerWave && row < nrows) startbits[row] = out;
