@@ -137,7 +137,10 @@ tkz_status tkz_encode_batch_utf8(tkz_encoder* e, const uint8_t* bytes, const int
 /* Same with every buffer already resident in HBM on the encoder's device (d_bytes 16-byte aligned).
  * Work is enqueued on `hip_stream` (a hipStream_t, NULL = default stream); the call returns after
  * the stream has drained and *total_tokens is final (it is also the required capacity when the call
- * returns TKZ_E_CAPACITY). */
+ * returns TKZ_E_CAPACITY).  For this and every other device entry: nothing outside d_bytes[0, total_bytes) is read
+ * as text and no padding behind it is needed, nothing is written at or behind out_cap -- a successful call
+ * leaves [*total_tokens, out_cap) as it found it -- or outside the n_docs + 1 entries of an offset array
+ * (tests/test_gpu_buffer_contract.py). */
 tkz_status tkz_encode_batch_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets,
                                    int64_t n_docs, int64_t total_bytes, int32_t* d_out_ids,
                                    int64_t out_cap, int64_t* d_out_offsets, void* hip_stream,
