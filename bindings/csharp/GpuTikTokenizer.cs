@@ -69,6 +69,11 @@ namespace Microsoft.DeepDev
                                                                                           long maxTokens, int* outIds, long outCap, long* outOffsets, long* docChunkOffsets,
                                                                                           long* chunkTokens, long* chunkUnits, long chunkCap, out long neededIds, out long neededChunks);
         [DllImport(Lib)] internal static extern void tkz_encoder_chunks_calls(IntPtr encoder, out long calls);
+        // packed rows: Encode's ids framed by bos / eos ids, in rows of the context length, with positions and segment starts (include/tkz.h, "Packed rows")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_packed_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                          int bosId, int eosId, long rowLen, int padId, int* outIds, long outCap, long* outOffsets,
+                                                                                          int* pos, long* segStarts, long segCap, out long totalTokens, out long neededIds, out long neededSegs);
+        [DllImport(Lib)] internal static extern void tkz_encoder_packed_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -465,6 +470,48 @@ namespace Microsoft.DeepDev
                 result.Add(chunks);
             }
             return result;
+        }
+
+        /// <summary>Every text's ids -- Encode's for the same arguments -- with <paramref name="bos"/> in front and <paramref name="eos"/> behind it (null: none;
+        /// any id of 0 or more is taken as it is), the stream cut into rows of <paramref name="rowLen"/> and padded with <paramref name="pad"/>, in ONE call
+        /// (tkz_encode_batch_packed_utf16; include/tkz.h states the rule).  Ids and Pos are rows x rowLen; Pos restarts at every text and every row; SegStarts
+        /// (cu_seqlens) ends with the stream's length; DocOffsets[d] is where text d starts in the stream.  A registered set the device path does not hold is
+        /// NotImplementedException (-7): there is no host path.</summary>
+        public unsafe (int[,] Ids, int[,] Pos, long[] SegStarts, long[] DocOffsets) EncodeBatchPacked(IReadOnlyList<string> texts, int rowLen,
+                                                                                                      IReadOnlyCollection<string>? allowedSpecial = null, int? bos = null,
+                                                                                                      int? eos = null, int pad = 0)
+        {
+            if (rowLen < 1) throw new ArgumentOutOfRangeException(nameof(rowLen));
+            if (bos < 0 || eos < 0) throw new ArgumentOutOfRangeException(bos < 0 ? nameof(bos) : nameof(eos));
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            int framing = (bos.HasValue ? 1 : 0) + (eos.HasValue ? 1 : 0);
+            long rowsBound = (3 * total + (long)framing * texts.Count + rowLen - 1) / rowLen;      // the sizes that always suffice (tkz.h): a token per byte, a char is at most three bytes
+            long cap = rowsBound * rowLen, segCap = texts.Count + rowsBound;
+            var ids = new int[Math.Max(1, cap)];
+            var pos = new int[Math.Max(1, cap)];
+            var seg = new long[segCap + 1];
+            var offsets = new long[texts.Count + 1];
+            int st;
+            long neededIds, neededSegs;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (int* pp = pos) fixed (long* ps = seg) fixed (long* pt = offsets)
+                st = Tkz.tkz_encode_batch_packed_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, bos ?? -1, eos ?? -1, rowLen, pad, pi, cap, pt,
+                                                       pp, ps, segCap, out _, out neededIds, out neededSegs);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            int rows = checked((int)(neededIds / rowLen));
+            var outIds = new int[rows, rowLen];
+            var outPos = new int[rows, rowLen];
+            Buffer.BlockCopy(ids, 0, outIds, 0, checked((int)(neededIds * sizeof(int))));
+            Buffer.BlockCopy(pos, 0, outPos, 0, checked((int)(neededIds * sizeof(int))));
+            var segStarts = new long[neededSegs + 1];
+            Array.Copy(seg, segStarts, neededSegs + 1);
+            return (outIds, outPos, segStarts, offsets);
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

@@ -431,6 +431,57 @@ tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t
 /* informational: successful calls of the chunk entries */
 void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls);
 
+/* ---- Packed rows: BOS / EOS framing, rows of the context length, positions and segment starts, in ONE call ----
+ * What a corpus-tokenisation job does next with the ragged result: an end-of-text id behind (or a begin id in front of) every document, the stream laid out as rows
+ * of the context length, the tail padded, and the two things a packed-sequence attention kernel needs -- a position that restarts at every document and the list of
+ * segment starts (cu_seqlens).
+ * THE RULE.  Let ids / O[0..n_docs] be EXACTLY what the matching encode entry writes for the same arguments -- tkz_encode_batch_special_* when n_allowed > 0 and
+ * literals are registered, the plain entry otherwise.
+ *   Parameters.  bos_id, eos_id: -1 means none, any value >= 0 is taken as it is (it need not be in the vocabulary), < -1 is TKZ_E_ARG.  fb = bos_id >= 0,
+ *     fe = eos_id >= 0, f = fb + fe.  row_len = L with 1 <= L <= 2^31 - 1, anything else is TKZ_E_ARG.  pad_id: any int32.
+ *   Stream.  For every document in order, empty ones included: [bos_id] if fb, then the document's ids, then [eos_id] if fe.  Document d starts at stream index
+ *     s[d] = O[d] + f * d; the stream has T = O[n_docs] + f * n_docs entries.  Documents are never reordered, dropped or truncated.
+ *   Rows.  n_rows = ceil(T / L).  out_ids[t] = stream[t] for t < T, and pad_id for T <= t < n_rows * L.  Nothing at or behind n_rows * L is touched.
+ *   Offsets.  out_offsets[d] = s[d] (n_docs + 1 entries, the last is T).
+ *   Segments.  t < T is a segment start iff t % L == 0, or t == s[d] for a document with s[d + 1] > s[d].  A document start on a row boundary is ONE segment
+ *     start.  seg_starts holds them ascending, n_segs of them, and seg_starts[n_segs] = T.  Always n_segs <= n_rows + n_docs.
+ *   Positions.  pos[t] = t - (largest segment start <= t) for t < T, and 0 for the padding.  So 0 <= pos[t] < L.
+ *   Example: documents [a1 a2 a3], [], [c1 c2], no bos, eos = E.  s = 0,4,5,8 and T = 8.
+ *     L = 4: rows a1 a2 a3 E / E c1 c2 E;        seg_starts 0,4,5,8 (n_segs 3);      pos 0,1,2,3,0,0,1,2
+ *     L = 3: rows a1 a2 a3 / E E c1 / c2 E pad;  seg_starts 0,3,4,5,6,8 (n_segs 5);  pos 0,1,2,0,0,0,0,1,0
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap < n_rows * L, or when d_seg_starts != NULL && seg_cap < n_segs.  *total_tokens (T), *n_rows and *n_segs then hold the
+ * required figures, all three from the one call; nothing is promised in the outputs.  *n_segs is reported whether or not d_seg_starts is given.  Sizes that
+ * ALWAYS suffice (a token is at least a byte): ids -- and pos -- (total_bytes + f * n_docs) rounded up to a multiple of L (UTF-16: 3 * units for the bytes);
+ * segments n_docs + ceil((total_bytes + f * n_docs) / L), and one more entry for seg_starts[n_segs].
+ *   tkz_encode_batch_packed_device: device buffers.  d_pos (out_cap entries) and d_seg_starts (seg_cap + 1 entries) may each be NULL; total_tokens, n_rows and
+ *     n_segs may not (TKZ_E_ARG).  Everything else -- allowed / n_allowed, TKZ_E_ARG, TKZ_E_UNSUPPORTED, tkz_encoder_special_stats, device-side errors, retries
+ *     inside the call, workspace growth, returning after the stream has drained -- as tkz_encode_batch_spans_device.  Nothing is read outside
+ *     d_bytes[0, total_bytes), nothing is written at or behind n_rows * L (ids, pos), seg_cap + 1 (seg_starts) or n_docs + 1 (offsets).  An empty batch
+ *     (n_docs == 0) is TKZ_OK: the offsets cleared on the stream, seg_starts[0] = 0, all three counts 0; documents that are all empty still have a stream when
+ *     f > 0 (T = f * n_docs).  The encoder's {n_docs, n_bytes, n_tokens} block (and a count block where one is given) receives T.
+ *     The launch sequence is the PLAIN document-granular one of tkz_encode_batch_device -- no piece arrays, no wait for a piece count.  With f == 0 the ids are
+ *     written straight into d_out_ids as that entry writes them and are not moved again; with f > 0 the unframed ids and offsets stay in the workspace (4 bytes per
+ *     input byte, 8 per document) and the stage gathers them into the caller's buffer.  The stage: k_pack_count (segment starts per tile of 2,048 stream
+ *     positions), the scan of the counts, k_pack_write.  Workspace of the stage: 12 bytes per tile.
+ *   tkz_encode_batch_packed_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as tkz_encode_batch_spans_utf8:
+ *     no chunk pipeline, no single-launch route.  pos (out_cap entries) and seg_starts (seg_cap + 1) may be NULL, total_tokens too; *needed_ids = n_rows * L and
+ *     *needed_segs = n_segs, the required ones on TKZ_E_CAPACITY (both pointers are required).
+ *   tkz_encode_batch_packed_utf16: code units in, transcoded on the device as tkz_encode_batch_spans_utf16; unit_offsets in code units.
+ * There is no best-fit packing (documents keep their order and are cut at row ends), no per-token document index, no per-document truncation (trim first), no
+ * _begin / _end form and no single-text form (packing one text is a reshape). */
+tkz_status tkz_encode_batch_packed_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id,
+                                          int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets, int32_t* d_pos, int64_t* d_seg_starts, int64_t seg_cap,
+                                          void* hip_stream, int64_t* total_tokens, int64_t* n_rows, int64_t* n_segs);
+tkz_status tkz_encode_batch_packed_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                        int32_t* pos, int64_t* seg_starts, int64_t seg_cap, int64_t* total_tokens, int64_t* needed_ids, int64_t* needed_segs);
+tkz_status tkz_encode_batch_packed_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                         int32_t* pos, int64_t* seg_starts, int64_t seg_cap, int64_t* total_tokens, int64_t* needed_ids, int64_t* needed_segs);
+/* informational: successful calls of the packed entries */
+void tkz_encoder_packed_calls(const tkz_encoder* e, int64_t* calls);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -585,6 +636,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * Of a span call (tkz_encode_batch_spans_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the pieces AND the span stage behind it (the fill of the interior
  * bitmap, k_tokspan_mark, k_tokspan_count, two scans, k_tokspan_write): the closing event is recorded again behind the stage.  Of a chunk call
  * (tkz_encode_batch_chunks_device) likewise: k_docoffs over the pieces and the chunk stage (the two walks, their scan, the unit counts, k_chunk_units).
+ * Of a packed call (tkz_encode_batch_packed_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the documents and the packing stage behind it
+ * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

@@ -7,6 +7,7 @@
 //                              CountTokens / CountTokensBatch (+ Utf16): Encode(...).Count from the device's count entries, no ids
 //                              EncodeWithOffsets / EncodeWithOffsetsBatch (+ Utf16): Encode, and where every token's text starts (bytes / code units)
 //                              EncodeChunks / EncodeChunksBatch (+ Utf16): the text cut into chunks of at most maxTokenCount tokens, (ids, text) each
+//                              EncodeBatchPacked (std::string, std::u16string): the ids framed by bos / eos ids in rows of the context length, pos, seg_starts
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -537,6 +538,31 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return chunks_batch<uint16_t, std::u16string>(units, offs, texts, allowedSpecial, maxTokenCount, true);
     }
+    // ---- packed rows: BOS / EOS framing, rows of the context length, positions and segment starts in ONE call (tkz_encode_batch_packed_utf8 / _utf16) ----
+    // Every text's ids -- Encode's for the same arguments -- with bos in front and eos behind it (-1: none; any id >= 0 is taken as it is), the stream cut into
+    // rows of rowLen and padded with pad.  ids and pos are n_rows * rowLen entries, row-major; pos restarts at every document and every row; seg_starts
+    // (cu_seqlens) holds the segment starts and ends with the stream's length; doc_offsets[d] is where text d starts in the stream (tkz.h states the rule).
+    // A registered set the device's special entries do not hold is a NotImplementedError here: there is no host path.
+    struct PackedRows { int64_t row_len = 0, n_rows = 0, total_tokens = 0; std::vector<int32_t> ids, pos; std::vector<int64_t> seg_starts, doc_offsets; };
+    PackedRows EncodeBatchPacked(const std::vector<std::string>& texts, int64_t rowLen, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                 int32_t pad = 0) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return packed_batch<uint8_t>(bytes, offs, rowLen, allowedSpecial, bos, eos, pad, false);
+    }
+    PackedRows EncodeBatchPacked(const std::vector<std::u16string>& texts, int64_t rowLen, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                 int32_t pad = 0) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return packed_batch<uint16_t>(units, offs, rowLen, allowedSpecial, bos, eos, pad, true);
+    }
+    // (the id of a registered special token, for bos / eos)
+    int32_t SpecialTokenId(const std::string& literal) const {
+        for (const auto& kv : specials_) if (kv.first == literal) return kv.second;
+        throw Error(TKZ_E_ARG, "not a registered special token: " + literal);
+    }
     // (one string: tkz_encode_trim_utf16, the single-text trim entry)
     Trimmed16 EncodeTrimSuffixUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount) const {
         Trimmed16 out;
@@ -718,6 +744,35 @@ private:
             out[static_cast<size_t>(d)].ids.assign(ids.begin() + ooff[d], ids.begin() + ooff[d + 1]);
             out[static_cast<size_t>(d)].starts.assign(starts.begin() + ooff[d], starts.begin() + ooff[d + 1]);
         }
+        return out;
+    }
+    // ONE call of the batch packed entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), with the capacities that always suffice (tkz.h)
+    template <class UNIT>
+    PackedRows packed_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, int64_t rowLen, const std::vector<std::string>& allowedSpecial, int32_t bos, int32_t eos,
+                            int32_t pad, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        PackedRows out;
+        out.row_len = rowLen;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t framing = (bos >= 0) + (eos >= 0), bound = static_cast<int64_t>(items.size()) * (utf16 ? 3 : 1) + framing * n;      // (a token per byte; a unit is at most three bytes)
+        const int64_t rows = rowLen >= 1 ? (bound + rowLen - 1) / rowLen : 0, cap = rows * std::max<int64_t>(rowLen, 0), scap = n + rows;
+        if (items.empty()) items.push_back(0);
+        out.ids.resize(static_cast<size_t>(std::max<int64_t>(cap, 1)));
+        out.pos.resize(out.ids.size());
+        out.seg_starts.resize(static_cast<size_t>(scap) + 1);
+        out.doc_offsets.assign(static_cast<size_t>(n) + 1, 0);
+        int64_t needed = 0, nseg = 0;
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_packed_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                                      rowLen, pad, out.ids.data(), cap, out.doc_offsets.data(), out.pos.data(), out.seg_starts.data(), scap, &out.total_tokens, &needed, &nseg);
+        else st = tkz_encode_batch_packed_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                               rowLen, pad, out.ids.data(), cap, out.doc_offsets.data(), out.pos.data(), out.seg_starts.data(), scap, &out.total_tokens, &needed, &nseg);
+        check(st);
+        out.n_rows = needed / rowLen;
+        out.ids.resize(static_cast<size_t>(needed));
+        out.pos.resize(static_cast<size_t>(needed));
+        out.seg_starts.resize(static_cast<size_t>(nseg) + 1);
         return out;
     }
     // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text

@@ -187,6 +187,11 @@ class Library:
         L.tkz_encode_chunks_utf16.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, i64, pi64, pi64]
         L.tkz_encoder_chunks_calls.argtypes = [vp, pi64]
         L.tkz_encoder_chunks_calls.restype = None
+        L.tkz_encode_batch_packed_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, vp, pi64, pi64, pi64]
+        L.tkz_encode_batch_packed_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, pi64, pi64, pi64]
+        L.tkz_encode_batch_packed_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, pi64, pi64, pi64]
+        L.tkz_encoder_packed_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_packed_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -912,6 +917,73 @@ class Encoder:
         """successful calls of the chunk entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_chunks_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- packed rows: the ids framed by bos / eos ids and laid out in rows of row_len, with pos and seg_starts (tkz.h: the rule) --
+    @staticmethod
+    def packed_bounds(n_docs, total, row_len, framing):
+        """(ids, segments) that always suffice (tkz.h): the stream bound rounded up to whole rows, and a segment a document and a row"""
+        rows = -(-(total + framing * n_docs) // row_len)
+        return rows * row_len, n_docs + rows
+
+    def _packed_host(self, fn, buf, offsets, total, allowed, row_len, bos_id, eos_id, pad_id, want_pos, want_segs, out_cap, seg_cap):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        if row_len >= 1:
+            bound, sbound = self.packed_bounds(n, total, row_len, (bos_id >= 0) + (eos_id >= 0))
+        else:
+            bound = sbound = 0                                # (refused by the library)
+        cap = bound if out_cap is None else out_cap
+        scap = sbound if seg_cap is None else seg_cap
+        ids = np.empty(max(1, cap), np.int32)
+        pos = np.empty(max(1, cap), np.int32) if want_pos else None
+        seg = np.empty(max(0, scap) + 1, np.int64) if want_segs else None
+        ooff = np.empty(n + 1, np.int64)
+        tot, ni, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(fn(self._h, buf, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed), bos_id, eos_id, row_len, pad_id, _ptr(ids), cap,
+                              _ptr(ooff), _ptr(pos) if want_pos else None, _ptr(seg) if want_segs else None, scap, C.byref(tot), C.byref(ni), C.byref(ns)))
+        except TkzError as ex:
+            ex.needed, ex.needed_ids, ex.needed_segs = tot.value, ni.value, ns.value      # (E_CAPACITY: the required figures)
+            raise
+        k, rows = ni.value, ni.value // row_len
+        return (ids[:k].reshape(rows, row_len), ooff, pos[:k].reshape(rows, row_len) if want_pos else None, seg[:ns.value + 1] if want_segs else None, tot.value)
+
+    def encode_batch_packed(self, data: np.ndarray, offsets: np.ndarray, row_len, allowed=(), bos_id=-1, eos_id=-1, pad_id=0, want_pos=True, want_segs=True,
+                            out_cap=None, seg_cap=None):
+        """(ids int32[n_rows, row_len], offsets int64[n+1], pos int32[n_rows, row_len] or None, seg_starts int64[n_segs + 1] or None, T): the ids of encode_batch /
+        encode_batch_special framed and laid out in rows -- tkz_encode_batch_packed_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self._packed_host(self.lib.L.tkz_encode_batch_packed_utf8, _ptr(data) if len(data) else None, offsets, len(data), allowed, row_len, bos_id, eos_id, pad_id,
+                                 want_pos, want_segs, out_cap, seg_cap)
+
+    def encode_batch_packed_utf16(self, units: np.ndarray, offsets: np.ndarray, row_len, allowed=(), bos_id=-1, eos_id=-1, pad_id=0, want_pos=True, want_segs=True,
+                                  out_cap=None, seg_cap=None):
+        """encode_batch_packed for UTF-16 documents (uint16[total], offsets in units) -- tkz_encode_batch_packed_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        return self._packed_host(self.lib.L.tkz_encode_batch_packed_utf16, _ptr(buf), offsets, 3 * len(units), allowed, row_len, bos_id, eos_id, pad_id,
+                                 want_pos, want_segs, out_cap, seg_cap)
+
+    def encode_batch_packed_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, bos_id, eos_id, row_len, pad_id, d_out_ids, out_cap, d_out_offsets,
+                                   d_pos=0, d_seg_starts=0, seg_cap=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_packed_device.  Returns (T, n_rows, n_segs); a TkzError carries them as `needed`, `needed_rows`, `needed_segs`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, rows, segs = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_packed_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                     len(allowed), bos_id, eos_id, row_len, pad_id, d_out_ids or None, out_cap, d_out_offsets or None,
+                                                                     d_pos or None, d_seg_starts or None, seg_cap, stream or None, C.byref(tot), C.byref(rows), C.byref(segs)))
+        except TkzError as ex:
+            ex.needed, ex.needed_rows, ex.needed_segs = tot.value, rows.value, segs.value
+            raise
+        return tot.value, rows.value, segs.value
+
+    def packed_calls(self):
+        """successful calls of the packed entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_packed_calls(self._h, C.byref(a))
         return a.value
 
     def set_special_tokens(self, specials):

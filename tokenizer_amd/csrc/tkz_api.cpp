@@ -109,6 +109,7 @@ struct CounterBlock {          // mirrors the device block
     int64_t kept_total;                    // the trim entries: ids kept over the whole batch (k_trim_gather)
     int64_t n_chunks;                      // the chunk entries: chunks of the whole batch (k_chunk_walk's writing pass)
     unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
+    int64_t pack_total, pack_rows, pack_segs;   // the packed entries: T, n_rows (k_pack_count) and n_segs (the scan of its counts) -- PackParams::totals
     // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
     int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
 };
@@ -217,7 +218,12 @@ struct ChunkBufs {   // the chunk entries: chunks per document and their scan's 
     DevBuf ck_cnt, ck_bsum, ck_list, ck_ucnt, ck_ubase, ck_stage;
     void release() { release_each({&ck_cnt, &ck_bsum, &ck_list, &ck_ucnt, &ck_ubase, &ck_stage}); }
 };
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs {
+struct PackBufs {   // the packed entries: the unframed ids and their offsets (framed calls only), segment starts per tile, their scan and its partial sums; the block of a
+    // batch without bytes ({T, n_rows, n_segs}, a zero total, a zero error word); the host entries' pos and seg_starts
+    DevBuf pk_ids, pk_offs, pk_cnt, pk_base, pk_bsum, pk_tot, pk_stage;
+    void release() { release_each({&pk_ids, &pk_offs, &pk_cnt, &pk_base, &pk_bsum, &pk_tot, &pk_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -266,7 +272,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -307,6 +313,7 @@ struct tkz_encoder {
     bool lit_fffd = false;                 // a registered literal holds U+FFFD (TkzLitTable's second 256-bit set is not empty)
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
+    std::atomic<int64_t> packed_calls{0};                                 // tkz_encoder_packed_calls: successful calls of the packed entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
     std::atomic<int64_t> count_calls{0}, count_single{0};                  // tkz_encoder_count_calls: successful count calls, and those of them that took the single launch
@@ -356,6 +363,10 @@ struct TrimCall { int32_t side; int64_t max_tokens; const int64_t* d_max; int64_
 struct SpanCall { int32_t* d_tok_bytes; int32_t* d_tok_units; };
 // A call of one of the chunk entries: the budget, where the chunk table goes (device; bytes and units may be null) and, on the host, where the number of chunks goes
 struct ChunkCall { int64_t max_tokens; int64_t* d_doc_chunk_offs; int64_t* d_chunk_tokens; int64_t* d_chunk_bytes; int64_t* d_chunk_units; int64_t chunk_cap; int64_t* n_chunks; };
+// A call of one of the packed entries: the framing ids (-1: none), the row length and the pad id, where pos and seg_starts go (device, either may be null) and, on the
+// host, where the numbers of rows and segments go
+struct PackCall { int32_t bos_id, eos_id; int64_t row_len; int32_t pad_id; int32_t* d_pos; int64_t* d_seg_starts; int64_t seg_cap; int64_t* n_rows; int64_t* n_segs;
+                  int64_t frame() const { return (bos_id >= 0) + (eos_id >= 0); } };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -366,7 +377,8 @@ enum class CallKind {
     Pieces,          // tkz_encode_batch_pieces_utf8: ids, and byte / token offsets of every piece
     Trim,            // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
     Spans,           // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
-    Chunks           // tkz_encode_batch_chunks_device: as Spans, then the chunk table
+    Chunks,          // tkz_encode_batch_chunks_device: as Spans, then the chunk table
+    Packed           // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -382,6 +394,7 @@ struct BatchCall {
     const TrimCall* trim = nullptr;            // Trim: what to keep (pieces then points at the workspace's piece arrays)
     const SpanCall* spans = nullptr;           // Spans: where the positions go (pieces points at the workspace's piece arrays as well)
     const ChunkCall* chunks = nullptr;         // Chunks: the budget and where the table goes (pieces likewise)
+    const PackCall* packed = nullptr;          // Packed: the framing, the row length and where pos and seg_starts go
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -391,7 +404,7 @@ struct BatchCall {
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || piece_granular() ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -908,6 +921,39 @@ tkz_status devprof_arm(tkz::EncodeParams*, hipStream_t) { return TKZ_OK; }
 tkz_status devprof_report() { return TKZ_OK; }
 #endif
 
+// the tiles of the longest stream a packed call of `total` bytes can produce (a token a byte at most, and the framing)
+int64_t pack_tiles(int64_t total, int64_t n_docs, const PackCall& k) { return (total + k.frame() * n_docs + tkz::kPackTile - 1) / tkz::kPackTile; }
+
+// A packed call on a batch without bytes: with framing ids its stream is not empty (T = f * n_docs), and the stage runs over offsets that are all 0.
+tkz_status pack_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t* totals3) {
+    using namespace tkz;
+    const PackCall& k = *c.packed;
+    const int64_t n_docs = c.n_docs;
+    totals3[0] = totals3[1] = totals3[2] = 0;
+    const Launch L{c.stream, nullptr, ws};
+    HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
+    if (k.frame() * n_docs == 0) {
+        launch_counts3(L, n_docs, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+        HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
+        if (k.d_seg_starts) HIP_TRY(hipMemsetAsync(k.d_seg_starts, 0, sizeof(int64_t), c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return TKZ_OK;
+    }
+    HIP_TRY(ws->pk_tot.ensure(64, &ws->bytes_allocated));
+    HIP_TRY(hipMemsetAsync(ws->pk_tot.p, 0, 64, c.stream));
+    HIP_TRY(hipMemsetAsync(ws->pk_offs.p, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
+    int64_t* const tot = ws->pk_tot.as<int64_t>();
+    const PackParams K{nullptr, 0, ws->pk_offs.as<int64_t>(), n_docs, tot + 3, k.bos_id, k.eos_id, k.pad_id, k.row_len,
+                       c.d_out, c.out_cap, c.d_out_offs, k.d_pos, k.d_seg_starts, k.seg_cap,
+                       ws->pk_cnt.as<int32_t>(), pack_tiles(0, n_docs, k), ws->pk_base.as<int64_t>(), ws->pk_bsum.as<int64_t>(), tot, reinterpret_cast<const int32_t*>(tot + 4)};
+    launch_pack(L, K);
+    launch_counts3(L, n_docs, 0, tot, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+    HIP_TRY(hipMemcpyAsync(totals3, tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    HIP_TRY(hipGetLastError());
+    return TKZ_OK;
+}
+
 // One attempt on the stream: the zero region and the text (k_ingest), the document marks and the pre-tokenizer (or, on a re-run, the counters and the
 // sub-tile flags only: it starts behind the pre-tokenizer), the counts of the marks and pieces and their scan, the piece index, then the sizing probe
 // (nsample >= 0) or the whole launch sequence, and the counter block back to the host.
@@ -1038,6 +1084,8 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             // (a trim call's untrimmed ids stay in the workspace: the caller's buffer holds the kept ones only)
             // (a count call: the token position of every mark and no ids)
             if (c.count_only) launch_tokcount(L, P, ws->w_tbase.as<int64_t>(), ws->w_dcount.as<int32_t>(), ntiles);
+            // (a packed call that frames its documents: the unframed ids stay in the workspace too -- every one of them moves)
+            else if (c.packed && c.packed->frame()) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pk_ids.as<int32_t>(), total);
             else launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs, has_empty);
@@ -1073,6 +1121,17 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                     launch_chunks(L, C, e->D);
                 }
                 launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+            } else if (c.packed) {                                      // (the unframed offsets, then the rows; the counts blocks receive T)
+                const PackCall& k = *c.packed;
+                const bool framed = k.frame() > 0;
+                int64_t* const totals = reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pack_total));
+                int64_t* const unframed = framed ? ws->pk_offs.as<int64_t>() : c.d_out_offs;
+                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, unframed, has_empty);
+                const PackParams K{framed ? ws->pk_ids.as<int32_t>() : c.d_out, framed ? total : c.out_cap, unframed, n_docs, grand, k.bos_id, k.eos_id, k.pad_id, k.row_len,
+                                   c.d_out, c.out_cap, c.d_out_offs, k.d_pos, k.d_seg_starts, k.seg_cap,
+                                   ws->pk_cnt.as<int32_t>(), pack_tiles(total, n_docs, k), ws->pk_base.as<int64_t>(), ws->pk_bsum.as<int64_t>(), totals, counters};
+                launch_pack(L, K);
+                launch_counts3(L, n_docs, total, totals, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
                                has_empty, n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
@@ -1228,6 +1287,21 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
     if (c.count_only && !c.plain_encode()) return fail(TKZ_E_ARG, "a count call is an encode call");
     if (total_tokens) *total_tokens = 0;
     if (n_docs == 0 && total != 0) return fail(TKZ_E_ARG, "bytes without documents");
+    // the outcome of a packed call: the three figures, and the capacity they are held against (tkz.h)
+    const auto packed_done = [&](const int64_t* totals3) {
+        const PackCall& k = *c.packed;
+        if (total_tokens) *total_tokens = totals3[0];
+        if (k.n_rows) *k.n_rows = totals3[1];
+        if (k.n_segs) *k.n_segs = totals3[2];
+        if (totals3[1] * k.row_len > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
+        if (k.d_seg_starts && totals3[2] > k.seg_cap) return fail(TKZ_E_CAPACITY, "segment table capacity too small");
+        return TKZ_OK;
+    };
+    if (total == 0 && c.packed) {
+        int64_t totals3[3];
+        TKZ_TRY(pack_empty(e, ws, c, totals3));
+        return packed_done(totals3);
+    }
     if (total == 0) {
         if (phase != kCallEnd) {                                  // (kCallEnd: enqueued when it began)
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
@@ -1283,6 +1357,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         settle_workspace(ws, ntiles);
         if (c.pretokenizes()) after_batch(e, ws, total);
         if (c.literals()) e->spec_literals += ws->spec_taken;
+        if (c.packed) return packed_done(&ws->h_counters->pack_total);
         const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
         if (total_tokens) *total_tokens = produced;
         if (c.chunks && c.chunks->n_chunks) *c.chunks->n_chunks = ws->h_counters->n_chunks;      // (both required sizes from one call)
@@ -2910,6 +2985,146 @@ tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t
 }
 void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->chunks_calls.load() : 0;
+}
+
+// ---- packed rows: the ids of the matching encode entry framed by bos / eos ids, laid out in rows of row_len, with pos and seg_starts (tkz.h: the rule) ----
+
+namespace {
+tkz_status check_pack_args(int32_t bos_id, int32_t eos_id, int64_t row_len, const void* seg_starts, int64_t seg_cap) {
+    if (bos_id < -1 || eos_id < -1) return fail(TKZ_E_ARG, "packed rows: bos_id and eos_id are -1 (none) or an id >= 0");
+    if (row_len < 1 || row_len > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "packed rows: row_len must be in [1, 2^31 - 1]");
+    if (seg_starts && seg_cap < 0) return fail(TKZ_E_ARG, "packed rows: negative seg_cap");
+    return TKZ_OK;
+}
+// the packed call on device buffers, on a workspace the entry holds: the plain launch sequence -- with the unframed ids and offsets in the workspace when the
+// documents are framed --, then the rows (enqueue_attempt)
+tkz_status packed_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, PackCall pc, const SpecialCall* sp, int64_t* total_tokens, int64_t* n_rows, int64_t* n_segs) {
+    int64_t* acc = &ws->bytes_allocated;
+    const int64_t ntile = pack_tiles(c.total, c.n_docs, pc);
+    if (pc.frame() > 0) {
+        if (c.total > 0) HIP_TRY(ws->pk_ids.ensure((size_t)c.total * 4, acc));
+        HIP_TRY(ws->pk_offs.ensure((size_t)(c.n_docs + 1) * 8, acc));
+    }
+    HIP_TRY(ws->pk_cnt.ensure((size_t)std::max<int64_t>(ntile, 1) * 4, acc));
+    HIP_TRY(ws->pk_base.ensure((size_t)(ntile + 1) * 8, acc));
+    HIP_TRY(ws->pk_bsum.ensure((size_t)(ntile / tkz::kScanBlock + 2) * 8, acc));
+    int64_t rows = 0, segs = 0;
+    pc.n_rows = &rows; pc.n_segs = &segs;
+    c.kind = CallKind::Packed; c.packed = &pc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (n_rows) *n_rows = rows;
+    if (n_segs) *n_segs = segs;
+    if (st == TKZ_OK) { ++e->packed_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a packed host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the rows, the offsets, pos and
+// seg_starts, ONE packed call, the results back.
+tkz_status packed_staged(tkz_encoder* e, Workspace* ws, BatchCall c, int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id, const SpecialCall* sp,
+                         int32_t* out_ids, int64_t out_cap, int64_t* out_offsets, int32_t* pos, int64_t* seg_starts, int64_t seg_cap,
+                         int64_t* total_tokens, int64_t* needed_ids, int64_t* needed_segs) {
+    const int64_t n_docs = c.n_docs;
+    const PackCall frame{bos_id, eos_id, row_len, pad_id, nullptr, nullptr, 0, nullptr, nullptr};
+    const int64_t rows_bound = (c.total + frame.frame() * n_docs + row_len - 1) / row_len;      // (tokens <= bytes: more capacity is never used)
+    c.out_cap = std::min<int64_t>(out_cap, rows_bound * row_len);
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1), scap = seg_starts ? std::min<int64_t>(seg_cap, n_docs + rows_bound) : 0;
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap));
+    HIP_TRY(ws->pk_stage.ensure((size_t)(scap + 1) * 8 + (size_t)cap * 4, &ws->bytes_allocated));
+    int64_t* const d_seg = ws->pk_stage.as<int64_t>();
+    int32_t* const d_pos = reinterpret_cast<int32_t*>(d_seg + scap + 1);
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = ws->s_outoffs[0].as<int64_t>();
+    int64_t tokens = 0, rows = 0, segs = 0;
+    const tkz_status st = packed_on_device(e, ws, c, PackCall{bos_id, eos_id, row_len, pad_id, pos ? d_pos : nullptr, seg_starts ? d_seg : nullptr, scap, nullptr, nullptr}, sp,
+                                           &tokens, &rows, &segs);
+    if (total_tokens) *total_tokens = tokens;
+    *needed_ids = rows * row_len; *needed_segs = segs;
+    if (st != TKZ_OK) return st;
+    TKZ_TRY(fetch(ws, out_ids, rows * row_len, out_offsets, n_docs));
+    if (pos && rows) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)(rows * row_len) * 4, hipMemcpyDeviceToHost));
+    if (seg_starts) HIP_TRY(hipMemcpy(seg_starts, d_seg, (size_t)(segs + 1) * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+const char* const kMsgPackCounts = "packed rows: null count pointer";
+}  // namespace
+
+tkz_status tkz_encode_batch_packed_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id,
+                                          int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets, int32_t* d_pos, int64_t* d_seg_starts, int64_t seg_cap,
+                                          void* hip_stream, int64_t* total_tokens, int64_t* n_rows, int64_t* n_segs) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pack_args(bos_id, eos_id, row_len, d_seg_starts, seg_cap));
+    if (!total_tokens || !n_rows || !n_segs) return fail(TKZ_E_ARG, kMsgPackCounts);
+    *total_tokens = 0; *n_rows = 0; *n_segs = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_device_call(e, scope, c));
+    if (out_cap > 0 && !d_out_ids) return fail(TKZ_E_ARG, "null device buffer");      // (a batch without bytes still has a stream when it is framed)
+    Lease lease(e);
+    return packed_on_device(e, lease.ws, c, PackCall{bos_id, eos_id, row_len, pad_id, d_pos, d_seg_starts, seg_cap, nullptr, nullptr}, sp, total_tokens, n_rows, n_segs);
+}
+
+tkz_status tkz_encode_batch_packed_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                        int32_t* pos, int64_t* seg_starts, int64_t seg_cap, int64_t* total_tokens, int64_t* needed_ids, int64_t* needed_segs) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pack_args(bos_id, eos_id, row_len, seg_starts, seg_cap));
+    if (!needed_ids || !needed_segs) return fail(TKZ_E_ARG, kMsgPackCounts);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    if (total_tokens) *total_tokens = 0;
+    *needed_ids = 0; *needed_segs = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_spans_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return packed_staged(e, ws, staged_call(ws, n_docs, total, 0), bos_id, eos_id, row_len, pad_id, sp, out_ids, out_cap, out_offsets, pos, seg_starts, seg_cap,
+                         total_tokens, needed_ids, needed_segs);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_spans_utf16 does.
+tkz_status tkz_encode_batch_packed_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int32_t bos_id, int32_t eos_id, int64_t row_len, int32_t pad_id, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                         int32_t* pos, int64_t* seg_starts, int64_t seg_cap, int64_t* total_tokens, int64_t* needed_ids, int64_t* needed_segs) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pack_args(bos_id, eos_id, row_len, seg_starts, seg_cap));
+    if (!needed_ids || !needed_segs) return fail(TKZ_E_ARG, kMsgPackCounts);
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    if (total_tokens) *total_tokens = 0;
+    *needed_ids = 0; *needed_segs = 0;
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    if (total == 0) {                                                   // (no units: the offsets, all 0, are byte offsets as they are -- the framing is still laid out)
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, nullptr));
+        TKZ_TRY(stage_in(ws, nullptr, 0, unit_offsets, n_docs));
+        return packed_staged(e, ws, staged_call(ws, n_docs, 0, 0), bos_id, eos_id, row_len, pad_id, sp, out_ids, out_cap, out_offsets, pos, seg_starts, seg_cap,
+                             total_tokens, needed_ids, needed_segs);
+    }
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return packed_staged(e, ws, c, bos_id, eos_id, row_len, pad_id, sp, out_ids, out_cap, out_offsets, pos, seg_starts, seg_cap, total_tokens, needed_ids, needed_segs);
+}
+void tkz_encoder_packed_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->packed_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

@@ -273,6 +273,24 @@ struct ChunkParams {
     int64_t* n_chunks; int32_t* counters;
 };
 void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& D);
+// Packed rows (tkz_encode_batch_packed_device; tkz.h states the rule): behind the PLAIN document-granular launch sequence.  ids / offs are the unframed ids and
+// their n_docs + 1 document offsets as k_place / k_docoffs left them: in the workspace when a bos or eos id frames the documents (every id moves), the caller's
+// own out / out_offs when none does (ids == out: no id is moved, offs == out_offs: they stand).  The stream is dealt out in tiles of kPackTile positions, a
+// wavefront each: k_pack_count counts the segment starts of every tile of the stream (cnt, ntile entries, ntile = the tiles of total_bytes + f * n_docs
+// positions, which the stream cannot exceed), launch_scan turns them into base (bsum: ntile / kScanBlock + 2 entries) and the total, and k_pack_write writes the
+// framed ids, pad_id over [T, n_rows * row_len), pos (out_cap entries, may be null), seg_starts (seg_cap + 1 entries, may be null) and the framed out_offs.
+// totals: {T, n_rows, n_segs}.  counters: the batch's counter block -- with an error bit in it ([0]) nothing of the caller's is touched; with
+// n_rows * row_len > out_cap, or seg_starts given and n_segs > seg_cap, the totals are all that is written.
+constexpr int kPackTile = 2048;
+constexpr int kPackGridMax = 2048;     // workgroups of the two kernels: they stride over the tiles beyond
+struct PackParams {
+    const int32_t* ids; int64_t ids_cap; const int64_t* offs; int64_t n_docs; const int64_t* grand;
+    int32_t bos_id, eos_id, pad_id; int64_t row_len;
+    int32_t* out; int64_t out_cap; int64_t* out_offs; int32_t* pos; int64_t* seg_starts; int64_t seg_cap;
+    int32_t* cnt; int64_t ntile; int64_t* base; int64_t* bsum; int64_t* totals;
+    const int32_t* counters;
+};
+void launch_pack(const Launch& L, const PackParams& K);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

@@ -3323,6 +3323,98 @@ TKZ_KERNEL(256) void k_trim_gather(TrimParams R, const int32_t* ids, int64_t ids
 }
 
 // -------------------------------------------------------------------------------------------------
+// Packed rows (tkz_encode_batch_packed_device; tkz.h states the rule), behind the plain document-granular launch sequence.  The stream is every document's
+// [bos] ids [eos]; document d starts at s[d] = O[d] + f * d (O: the unframed offsets, f: 0, 1 or 2 framing ids a document), never stored: the searches compute
+// it from O.  The work is dealt out by OUTPUT position as k_trim_gather deals it: a wavefront per tile of kPackTile stream positions, grid-strided.
+//   k_pack_count   the segment starts of every tile (a position whose pos is 0)
+//   (k_scan_partials, k_scan_top, k_scan_final: the counts -> the rank of every tile's first segment start, and n_segs)
+//   k_pack_write   the framed ids (f > 0; with f == 0 k_place wrote them where they stand), the pad tail, pos, seg_starts in ascending order, the framed offsets
+// Both are ONE body (tkz_pack_tiles<WRITE>), so the count and the write cannot disagree about the predicate.  The position inside the row costs one 64-bit
+// remainder a TILE (wave-uniform); a lane then steps it by 64 with one conditional subtraction.  With f == 0 a run of empty documents repeats an offset and the
+// search returns the last of them -- the document that holds the position; an empty document starts no segment there.
+// -------------------------------------------------------------------------------------------------
+// the last d of [lo, hi] with s[d] <= x (s[lo] <= x)
+TKZ_DEV int64_t tkz_pack_doc(const int64_t* offs, int64_t f, int64_t lo, int64_t hi, int64_t x) {
+    while (lo < hi) { const int64_t mid = lo + (hi - lo + 1) / 2; if (offs[mid] + f * mid <= x) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+template <bool WRITE> TKZ_DEV void tkz_pack_tiles(const PackParams& K) {
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t fb = K.bos_id >= 0 ? 1 : 0, fe = K.eos_id >= 0 ? 1 : 0, f = fb + fe, L = K.row_len;
+    const bool bad = K.counters[0] != 0;
+    const int64_t T = bad ? 0 : *K.grand + f * K.n_docs;
+    const int64_t n_rows = (T + L - 1) / L, full = n_rows * L;
+    if (!WRITE) {
+        if (wave0 == 0 && lane == 0) { K.totals[0] = T; K.totals[1] = n_rows; }
+    } else {
+        if (bad) return;                                       // (a failed attempt: the offsets mean nothing, the caller's buffers are left alone)
+        if (f > 0) {                                           // (a lane a document; O is the workspace's, so no reader of it is overtaken)
+            const int64_t stride = simt::nblocks() * simt::nthreads();
+            for (int64_t d = simt::bid() * simt::nthreads() + simt::tid(); d <= K.n_docs; d += stride) K.out_offs[d] = K.offs[d] + f * d;
+        }
+        const int64_t n_segs = K.totals[2];
+        if (full > K.out_cap || (K.seg_starts && n_segs > K.seg_cap)) return;
+        if (K.seg_starts && wave0 == 0 && lane == 0) K.seg_starts[n_segs] = T;
+    }
+    const int64_t ntile = WRITE ? (full + kPackTile - 1) / kPackTile : K.ntile;
+    const bool pad_only = WRITE && f == 0 && !K.pos && !K.seg_starts;      // (the ids stand where k_place wrote them: only the tail is left to write)
+    for (int64_t t = wave0; t < ntile; t += nwaves) {
+        const int64_t q0 = t * kPackTile;
+        if (pad_only && q0 + kPackTile <= T) continue;
+        const int64_t q1 = WRITE ? (q0 + kPackTile < full ? q0 + kPackTile : full) : q0 + kPackTile;
+        const int64_t qT = q1 < T ? q1 : T;                    // the stream's part of the tile: [q0, qT)
+        // the two documents at its ends (wave-uniform); a tile inside one document needs no search by the lanes
+        int64_t d0 = 0, d1 = 0, od = 0, sd = 0, se = 0;
+        if (q0 < qT) {
+            // (a framed document holds a position at least: the tile's last document is then fewer than kPackTile documents on)
+            d0 = tkz_pack_doc(K.offs, f, 0, K.n_docs - 1, q0);
+            const int64_t dmax = f > 0 && d0 + kPackTile < K.n_docs ? d0 + kPackTile - 1 : K.n_docs - 1;
+            d1 = tkz_pack_doc(K.offs, f, d0, dmax, qT - 1);
+            od = K.offs[d0]; sd = od + f * d0; se = K.offs[d0 + 1] + f * (d0 + 1);
+        }
+        // the position inside the row: q0's by one division, the lane's and every later one's by additions (m < L and step < L: one subtraction is enough)
+        const int64_t m0 = q0 % L;
+        int64_t m, step;
+        if (L >= kPackTile) { m = m0 + lane; if (m >= L) m -= L; step = 64; }
+        else { m = (int64_t)(((uint32_t)m0 + (uint32_t)lane) % (uint32_t)L); step = (int64_t)(64u % (uint32_t)L); }
+        const int64_t base = WRITE && K.seg_starts && t < K.ntile ? K.base[t] : 0;
+        int run = 0;                                           // the tile's segment starts in front of this group of 64 positions
+        int64_t dl = d0, o = od, s = sd, e = se;               // the lane's document: its positions ascend, so the search goes on from the last one's
+        for (int64_t g = q0; g < q1; g += 64) {
+            const int64_t q = g + lane;
+            bool seg = false;
+            if (q < qT) {
+                if (q >= e) { dl = tkz_pack_doc(K.offs, f, dl, d1, q); o = K.offs[dl]; s = o + f * dl; e = K.offs[dl + 1] + f * (dl + 1); }
+                const int64_t j = q - s, p = j < m ? j : m;    // behind the document's start, behind the row's: pos is the nearer of the two
+                seg = p == 0;
+                if (WRITE) {
+                    if (f > 0) {
+                        int32_t v = K.pad_id;
+                        const int64_t src = o + j - fb;
+                        if (fb && j == 0) v = K.bos_id;
+                        else if (fe && q == e - 1) v = K.eos_id;
+                        else if (src >= 0 && src < K.ids_cap) v = tkz_load_nt(K.ids + src);
+                        tkz_store_nt(K.out + q, v);
+                    }
+                    if (K.pos) tkz_store_nt(K.pos + q, (int32_t)p);
+                }
+            } else if (WRITE && q < q1) {                      // the pad tail
+                tkz_store_nt(K.out + q, K.pad_id);
+                if (K.pos) tkz_store_nt(K.pos + q, 0);
+            }
+            const uint64_t mask = simt::ballot(seg);
+            if (WRITE && K.seg_starts && seg) K.seg_starts[base + run + tkz_popc64(mask & tkz_lowmask(lane))] = q;
+            run += tkz_popc64(mask);
+            m += step; if (m >= L) m -= L;
+        }
+        if (!WRITE && lane == 0) K.cnt[t] = run;
+    }
+}
+TKZ_KERNEL(256) void k_pack_count(PackParams K) { tkz_pack_tiles<false>(K); }
+TKZ_KERNEL(256) void k_pack_write(PackParams K) { tkz_pack_tiles<true>(K); }
+
+// -------------------------------------------------------------------------------------------------
 // Decode for a batch (TikTokenizer.Decode, TikTokenizer.cs:586-604): id -> bytes through the decoder table, ids that are in
 // neither the vocabulary nor the registered special tokens contribute nothing (:591-599), documents concatenated.
 //   k_dec_len      per 1024-id tile (one wavefront, 16 ids per lane): byte length of every id -> tile sum and the exclusive
@@ -4720,6 +4812,16 @@ void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& 
     TKZ_LAUNCH(k_chunk_walk, g_docs, kThreads, L.stream, C, D, 1);
     TKZ_LAUNCH(k_chunk_walk_long, g_long, kThreads, L.stream, C, D, 1);
     if (C.chunk_units) TKZ_LAUNCH(k_chunk_units, g_units, kThreads, L.stream, C);
+    hook(L, K_DOCOFFS, 1);
+}
+// (the bracket: K_DOCOFFS's again.  How long the stream is is known on the device only: the counting grid is sized for the tiles the bound allows, the writing
+//  grid for the rows that fit the caller's buffer -- beyond kPackGridMax workgroups both stride)
+void launch_pack(const Launch& L, const PackParams& K) {
+    const int64_t waves = kThreads / 64, g_count = cdiv(K.ntile, waves), g_write = cdiv(cdiv(K.out_cap, kPackTile), waves);
+    const auto capped = [](int64_t g) { return g < 1 ? 1 : (g > kPackGridMax ? kPackGridMax : g); };
+    TKZ_LAUNCH(k_pack_count, capped(g_count), kThreads, L.stream, K);
+    launch_scan(L, K.cnt, K.ntile, K.bsum, K.base, K.totals + 2, -1, 1);
+    TKZ_LAUNCH(k_pack_write, capped(g_write > g_count ? g_write : g_count), kThreads, L.stream, K);
     hook(L, K_DOCOFFS, 1);
 }
 int64_t dec_tiles(int64_t total_ids) { return cdiv(total_ids, kDecTile); }

@@ -326,6 +326,47 @@ class TikTokenizer:
         flat, pos = ids.tolist(), (tb if bytes else tu).tolist()
         return [flat[ooff[d]:ooff[d + 1]] for d in range(len(texts))], [pos[ooff[d]:ooff[d + 1]] for d in range(len(texts))]
 
+    # ---- packed rows: framing, rows of the context length, positions and segment starts (include/tkz.h, "Packed rows") ----
+    def _frame_id(self, tok) -> int:
+        """a framing id: None (none), an int taken as it is, or the literal of a registered special token"""
+        if tok is None:
+            return -1
+        if isinstance(tok, str):
+            if tok not in self.SpecialTokensEncoder:
+                raise ValueError("not a registered special token: %r" % tok)
+            return int(self.SpecialTokensEncoder[tok])
+        if int(tok) < 0:
+            raise ValueError("a framing id is not negative")
+        return int(tok)
+
+    def EncodeBatchPacked(self, texts: Sequence[str], row_len: int, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bos=None, eos=None, pad: int = 0):
+        """(ids[n_rows, row_len], pos[n_rows, row_len], seg_starts, doc_offsets) as numpy arrays, from ONE device call (tkz_encode_batch_packed_utf8 / _utf16): every
+        text's ids -- Encode's for the same arguments -- with `bos` in front and `eos` behind it, the stream cut into rows of row_len and padded with `pad`;
+        pos restarts at every document and every row, seg_starts (cu_seqlens) ends with the stream's length, doc_offsets[d] is where text d starts in the stream.
+        bos / eos: None, an int, or the literal of a registered special token."""
+        if row_len < 1:
+            raise ValueError("row_len must be at least 1")
+        bos_id, eos_id = self._frame_id(bos), self._frame_id(eos)
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not plain and self._special_on_host:
+            raise N.UnsupportedError(N.E_UNSUPPORTED, "EncodeBatchPacked: the device's special entries do not hold this set of literals")
+        names = set(allowed) if not plain else ()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+        if not plain and self._fffd_literal and any(_has_lone_surrogate(t) for t in texts):
+            # (a literal that holds U+FFFD beside a lone surrogate: only the UTF-16 entry tells the two apart)
+            raw = [t.encode("utf-16-le", "surrogatepass") for t in texts]
+            offs = np.zeros(len(raw) + 1, np.int64)
+            np.cumsum(np.fromiter((len(r) // 2 for r in raw), np.int64, len(raw)), out=offs[1:])
+            ids, ooff, pos, seg, _ = self._encoder.encode_batch_packed_utf16(np.frombuffer(b"".join(raw), "<u2"), offs, row_len, index, bos_id, eos_id, pad)
+            return ids, pos, seg, ooff
+        segs = [_utf8_like_dotnet(t) for t in texts]
+        offs = np.zeros(len(segs) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+        data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+        ids, ooff, pos, seg, _ = self._encoder.encode_batch_packed(data, offs, row_len, index, bos_id, eos_id, pad)
+        return ids, pos, seg, ooff
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
