@@ -69,6 +69,12 @@ namespace Microsoft.DeepDev
                                                                                           long maxTokens, int* outIds, long outCap, long* outOffsets, long* docChunkOffsets,
                                                                                           long* chunkTokens, long* chunkUnits, long chunkCap, out long neededIds, out long neededChunks);
         [DllImport(Lib)] internal static extern void tkz_encoder_chunks_calls(IntPtr encoder, out long calls);
+        // overlapping token-budget chunks: a chunk size and an overlap, a start and an end a chunk (include/tkz.h, "Overlapping token-budget chunks")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_chunks_overlap_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                                  long maxTokens, long overlap, int* outIds, long outCap, long* outOffsets,
+                                                                                                  long* docChunkOffsets, long* chunkTokens, long* chunkEnds, long* chunkUnits,
+                                                                                                  long* chunkEndUnits, long chunkCap, out long neededIds, out long neededChunks);
+        [DllImport(Lib)] internal static extern void tkz_encoder_chunks_overlap_calls(IntPtr encoder, out long calls);
         // packed rows: Encode's ids framed by bos / eos ids, in rows of the context length, with positions and segment starts (include/tkz.h, "Packed rows")
         [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_packed_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
                                                                                           int bosId, int eosId, long rowLen, int padId, int* outIds, long outCap, long* outOffsets,
@@ -465,6 +471,63 @@ namespace Microsoft.DeepDev
                     int lo = checked((int)chunkTokens[c]), n = checked((int)(chunkTokens[c + 1] - chunkTokens[c]));
                     var li = new List<int>(n); li.AddRange(new ArraySegment<int>(ids, lo, n));
                     int a = checked((int)chunkUnits[c]), b = c + 1 < docChunks[t + 1] ? checked((int)chunkUnits[c + 1]) : texts[t].Length;
+                    chunks.Add((li, texts[t].Substring(a, b - a)));
+                }
+                result.Add(chunks);
+            }
+            return result;
+        }
+
+        /// <summary>EncodeChunks with an overlap, as text splitters take it: consecutive chunks share at most <paramref name="overlap"/> tokens and the text of
+        /// those tokens.  A chunk is what EncodeTrimSuffix(rest, maxTokenCount) returns; the next one starts with what EncodeTrimPrefix(chunk text, overlap) keeps --
+        /// one item further on when that is the whole chunk, behind the chunk when a chunk begun there would end where this one does (include/tkz.h states the
+        /// rule).  overlap 0 gives EncodeChunks' result.  maxTokenCount below 1 and an overlap outside [0, maxTokenCount) are ArgumentOutOfRangeException.  A
+        /// registered set the device path does not hold is NotImplementedException (-7): there is no host path.</summary>
+        public List<(List<int> TokenIds, string Text)> EncodeChunksOverlap(string text, IReadOnlyCollection<string>? allowedSpecial, int maxTokenCount, int overlap)
+        {
+            return EncodeChunksOverlapBatch(new[] { text }, allowedSpecial, maxTokenCount, overlap)[0];
+        }
+
+        /// <summary>EncodeChunksOverlap for every text, in ONE call of tkz_encode_batch_chunks_overlap_utf16: every chunk is the ids [start, end) and the chars
+        /// [start unit, end unit) of its text.</summary>
+        public unsafe List<List<(List<int> TokenIds, string Text)>> EncodeChunksOverlapBatch(IReadOnlyList<string> texts, IReadOnlyCollection<string>? allowedSpecial,
+                                                                                              int maxTokenCount, int overlap)
+        {
+            if (maxTokenCount < 1) throw new ArgumentOutOfRangeException(nameof(maxTokenCount));
+            if (overlap < 0 || overlap >= maxTokenCount) throw new ArgumentOutOfRangeException(nameof(overlap));
+            var result = new List<List<(List<int> TokenIds, string Text)>>(texts.Count);
+            if (texts.Count == 0) return result;
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = Math.Max(1, 3 * total);                                   // a token per byte, a char is at most three bytes
+            long chunkCap = Math.Max(1, Math.Min(3 * total, texts.Count + 2 * (3 * total) / (maxTokenCount - overlap)));      // the chunks that always suffice (tkz.h)
+            var ids = new int[cap];
+            var offsets = new long[texts.Count + 1];
+            var docChunks = new long[texts.Count + 1];
+            var chunkTokens = new long[chunkCap];
+            var chunkEnds = new long[chunkCap];
+            var chunkUnits = new long[chunkCap];
+            var chunkEndUnits = new long[chunkCap];
+            int st;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (long* pt = offsets) fixed (long* pd = docChunks)
+            fixed (long* pc = chunkTokens) fixed (long* pe = chunkEnds) fixed (long* pn = chunkUnits) fixed (long* pm = chunkEndUnits)
+                st = Tkz.tkz_encode_batch_chunks_overlap_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, maxTokenCount, overlap, pi, cap, pt, pd,
+                                                               pc, pe, pn, pm, chunkCap, out _, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            for (int t = 0; t < texts.Count; ++t)
+            {
+                var chunks = new List<(List<int> TokenIds, string Text)>(checked((int)(docChunks[t + 1] - docChunks[t])));
+                for (long c = docChunks[t]; c < docChunks[t + 1]; ++c)
+                {
+                    int lo = checked((int)chunkTokens[c]), n = checked((int)(chunkEnds[c] - chunkTokens[c]));
+                    var li = new List<int>(n); li.AddRange(new ArraySegment<int>(ids, lo, n));
+                    int a = checked((int)chunkUnits[c]), b = checked((int)chunkEndUnits[c]);
                     chunks.Add((li, texts[t].Substring(a, b - a)));
                 }
                 result.Add(chunks);

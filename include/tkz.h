@@ -413,7 +413,8 @@ void tkz_encoder_spans_calls(const tkz_encoder* e, int64_t* calls);
  *   tkz_encode_batch_chunks_utf16: code units in, transcoded on the device as tkz_encode_batch_trim_utf16; unit_offsets and chunk_units in code units.  There is no
  *     chunk_bytes: the bytes never exist on the host.  Literals that hold U+FFFD as in the other UTF-16 special entries.
  *   tkz_encode_chunks_utf8 / _utf16: ONE text -- the batch entry with one document, at every size.  TKZ_E_ARG for a negative len or a null n_out / n_chunks.
- * There is no overlap between chunks, no budget per document, no _begin / _end form and no form that returns the boundaries without the ids. */
+ * These entries have no overlap between chunks (the overlap entries below do).  There is no budget per document, no _begin / _end form and no form that returns
+ * the boundaries without the ids. */
 tkz_status tkz_encode_batch_chunks_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
                                           const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int32_t* d_out_ids, int64_t out_cap, int64_t* d_out_offsets,
                                           int64_t* d_doc_chunk_offsets, int64_t* d_chunk_tokens, int64_t* d_chunk_bytes, int64_t* d_chunk_units, int64_t chunk_cap,
@@ -430,6 +431,56 @@ tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t
                                    int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks);
 /* informational: successful calls of the chunk entries */
 void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls);
+
+/* ---- Overlapping token-budget chunks: the chunk entries with a second number, as every text splitter takes -- a chunk size and an overlap ----
+ * max_tokens = N >= 1 and overlap = O with 0 <= O < N; anything else is TKZ_E_ARG, in every entry.  Items, T (the document's tokens) and "item boundary" are
+ * those of the chunk rule above.
+ *   - chunk c is the ids [s_c, e_c); s_0 is the document's first token;
+ *   - e_c is the chunk rule's end for a chunk that starts at s_c: T when T - s_c <= N; else the largest item boundary b with s_c < b <= s_c + N; else s_c + N,
+ *     inside the item;
+ *   - the chunk with e_c == T is the document's last;
+ *   - otherwise let x = max(e_c - O, s_c + 1): s_{c+1} is the smallest item boundary b with x <= b <= e_c, and where there is none, s_{c+1} = x (then e_c lies
+ *     inside an oversize item, and so does the next start);
+ *   - if the chunk so begun would end at e_c again it adds nothing, so s_{c+1} = e_c instead (the item behind e_c is too large for what the overlap left of the
+ *     budget).
+ * So: O = 0 gives exactly the chunks of the entries above; 1 <= e_c - s_c <= N; s_c < s_{c+1} <= e_c < e_{c+1}; consecutive chunks share e_c - s_{c+1} <= O
+ * tokens; s_{c+1} is an item boundary unless e_c is not one; e_{c+2} - e_c > N - O.  While no item exceeds the budget the chunk is EncodeTrimSuffix(rest, N) and
+ * the text the next chunk starts with is what EncodeTrimPrefix(chunk text, O) keeps -- when that keeps the whole chunk, the chunk's first item is dropped.
+ * TABLE.  The chunks no longer partition the ids:
+ *   doc_chunk_offsets (n_docs + 1 entries)   as above;
+ *   chunk_tokens (chunk_cap entries)         s_c as an index into out_ids;
+ *   chunk_ends (chunk_cap entries, required) e_c as an index into out_ids;
+ *   chunk_bytes, chunk_units                 as above: where the chunk's text starts, relative to its document;
+ *   chunk_end_bytes, chunk_end_units (chunk_cap entries each, int64; either or both may be NULL)   where the chunk's text ends, relative to its document: the
+ *                                            position of token e_c under the same rules, or the document's length in bytes or units for its last chunk.
+ * CAPACITY as above, with N - O in the place of N: a document of t tokens has at most 2 * t / (N - O) + 1 chunks, n_docs + 2 * total_bytes / (N - O) chunks ALWAYS
+ * suffice, and never more than a chunk a token (the starts ascend strictly).
+ * out_ids, out_offsets, allowed / n_allowed, the error codes, the empty batch (d_out_offsets and d_doc_chunk_offsets cleared; the table arrays are not touched)
+ * and the host entries' staging are those of the matching chunk entry.  The launch sequence is the chunk entries' with walks of its own (k_chunkov_walk,
+ * k_chunkov_walk_long) and k_chunkov_units for both unit arrays; the unit stage runs when either is given.  The serial limits are the chunk entries'; the start
+ * search adds a binary search over the chunk's items (lane walk) or a load of 64 items per 64 items of overlap (wavefront walk) to every chunk.
+ * There is no overlap or budget per document, no _begin / _end form and no form that returns the boundaries without the ids. */
+tkz_status tkz_encode_batch_chunks_overlap_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                                  const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* d_out_ids, int64_t out_cap,
+                                                  int64_t* d_out_offsets, int64_t* d_doc_chunk_offsets, int64_t* d_chunk_tokens, int64_t* d_chunk_ends,
+                                                  int64_t* d_chunk_bytes, int64_t* d_chunk_units, int64_t* d_chunk_end_bytes, int64_t* d_chunk_end_units,
+                                                  int64_t chunk_cap, void* hip_stream, int64_t* total_tokens, int64_t* n_chunks);
+tkz_status tkz_encode_batch_chunks_overlap_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
+                                                int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                                int64_t* doc_chunk_offsets, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_bytes, int64_t* chunk_units,
+                                                int64_t* chunk_end_bytes, int64_t* chunk_end_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks);
+tkz_status tkz_encode_batch_chunks_overlap_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed,
+                                                 int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                                 int64_t* doc_chunk_offsets, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_units, int64_t* chunk_end_units,
+                                                 int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks);
+tkz_status tkz_encode_chunks_overlap_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens,
+                                          int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_bytes,
+                                          int64_t* chunk_units, int64_t* chunk_end_bytes, int64_t* chunk_end_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks);
+tkz_status tkz_encode_chunks_overlap_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens,
+                                           int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_units,
+                                           int64_t* chunk_end_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks);
+/* informational: successful calls of the overlap chunk entries */
+void tkz_encoder_chunks_overlap_calls(const tkz_encoder* e, int64_t* calls);
 
 /* ---- Packed rows: BOS / EOS framing, rows of the context length, positions and segment starts, in ONE call ----
  * What a corpus-tokenisation job does next with the ragged result: an end-of-text id behind (or a begin id in front of) every document, the stream laid out as rows

@@ -7,6 +7,7 @@
 //                              CountTokens / CountTokensBatch (+ Utf16): Encode(...).Count from the device's count entries, no ids
 //                              EncodeWithOffsets / EncodeWithOffsetsBatch (+ Utf16): Encode, and where every token's text starts (bytes / code units)
 //                              EncodeChunks / EncodeChunksBatch (+ Utf16): the text cut into chunks of at most maxTokenCount tokens, (ids, text) each
+//                              EncodeChunksOverlap / EncodeChunksOverlapBatch (+ Utf16): the same with an overlap of at most `overlap` tokens between neighbours
 //                              EncodeBatchPacked (std::string, std::u16string): the ids framed by bos / eos ids in rows of the context length, pos, seg_starts
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
@@ -538,6 +539,37 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return chunks_batch<uint16_t, std::u16string>(units, offs, texts, allowedSpecial, maxTokenCount, true);
     }
+    // ---- overlapping token-budget chunks: a chunk size and an overlap (tkz_encode_batch_chunks_overlap_utf8 / _utf16; tkz.h states the rule) ----
+    // EncodeChunks with 0 <= overlap < maxTokenCount (anything else is the C ABI's TKZ_E_ARG): consecutive chunks share at most `overlap` tokens and the text of
+    // those tokens.  A chunk is what EncodeTrimSuffix(rest, maxTokenCount) returns, the next one starts with what EncodeTrimPrefix(chunk text, overlap) keeps (one
+    // item further on when that is the whole chunk, behind the chunk when a chunk begun there would end where this one does).  The texts are slices of the input
+    // [start, end): bytes for std::string, code units for std::u16string.  overlap 0 gives EncodeChunks' result.  No host path, as EncodeChunks.
+    std::vector<Trimmed> EncodeChunksOverlap(const std::string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int overlap) const {
+        return std::move(EncodeChunksOverlapBatch(std::vector<std::string>{text}, allowedSpecial, maxTokenCount, overlap)[0]);
+    }
+    std::vector<Trimmed> EncodeChunksOverlap(const std::string& text, int maxTokenCount, int overlap, bool applySpecialTokens = true) const {
+        return EncodeChunksOverlap(text, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount, overlap);
+    }
+    std::vector<std::vector<Trimmed>> EncodeChunksOverlapBatch(const std::vector<std::string>& texts, const std::vector<std::string>& allowedSpecial, int maxTokenCount,
+                                                               int overlap) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return chunks_overlap_batch<uint8_t, std::string>(bytes, offs, texts, allowedSpecial, maxTokenCount, overlap, false);
+    }
+    std::vector<std::vector<Trimmed>> EncodeChunksOverlapBatch(const std::vector<std::string>& texts, int maxTokenCount, int overlap, bool applySpecialTokens = true) const {
+        return EncodeChunksOverlapBatch(texts, applySpecialTokens ? all_specials() : std::vector<std::string>{}, maxTokenCount, overlap);
+    }
+    std::vector<Chunk16> EncodeChunksOverlapUtf16(const std::u16string& text, const std::vector<std::string>& allowedSpecial, int maxTokenCount, int overlap) const {
+        return std::move(EncodeChunksOverlapBatchUtf16(std::vector<std::u16string>{text}, allowedSpecial, maxTokenCount, overlap)[0]);
+    }
+    std::vector<std::vector<Chunk16>> EncodeChunksOverlapBatchUtf16(const std::vector<std::u16string>& texts, const std::vector<std::string>& allowedSpecial,
+                                                                    int maxTokenCount, int overlap) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return chunks_overlap_batch<uint16_t, std::u16string>(units, offs, texts, allowedSpecial, maxTokenCount, overlap, true);
+    }
     // ---- packed rows: BOS / EOS framing, rows of the context length, positions and segment starts in ONE call (tkz_encode_batch_packed_utf8 / _utf16) ----
     // Every text's ids -- Encode's for the same arguments -- with bos in front and eos behind it (-1: none; any id >= 0 is taken as it is), the stream cut into
     // rows of rowLen and padded with pad.  ids and pos are n_rows * rowLen entries, row-major; pos restarts at every document and every row; seg_starts
@@ -802,6 +834,41 @@ private:
             for (int64_t c = dco[d]; c < dco[d + 1]; ++c) {
                 const size_t a = static_cast<size_t>(starts[c]), b = c + 1 < dco[d + 1] ? static_cast<size_t>(starts[c + 1]) : t.size();
                 out[static_cast<size_t>(d)].emplace_back(std::vector<int32_t>(ids.begin() + ct[c], ids.begin() + ct[c + 1]), t.substr(a, b - a));
+            }
+        }
+        return out;
+    }
+    // chunks_batch for the overlap entries: every chunk has a start and an end, in tokens and in bytes (std::string) or code units (std::u16string)
+    template <class UNIT, class STR>
+    std::vector<std::vector<std::pair<std::vector<int32_t>, STR>>> chunks_overlap_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, const std::vector<STR>& texts,
+                                                                                      const std::vector<std::string>& allowedSpecial, int maxTokenCount, int overlap,
+                                                                                      bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        std::vector<std::vector<std::pair<std::vector<int32_t>, STR>>> out(static_cast<size_t>(n));
+        if (n == 0 && maxTokenCount >= 1 && overlap >= 0 && overlap < maxTokenCount) return out;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t total = static_cast<int64_t>(items.size()) * (utf16 ? 3 : 1), mx = maxTokenCount, ov = overlap;
+        const int64_t cap = std::max<int64_t>(1, total);
+        const int64_t ccap = std::max<int64_t>(1, std::min<int64_t>(total, n + 2 * total / std::max<int64_t>(mx - ov, 1)));      // (tkz.h: the chunks that always suffice)
+        if (items.empty()) items.push_back(0);
+        std::vector<int32_t> ids(static_cast<size_t>(cap));
+        std::vector<int64_t> ooff(static_cast<size_t>(n) + 1, 0), dco(static_cast<size_t>(n) + 1, 0);
+        std::vector<int64_t> ct(static_cast<size_t>(ccap), 0), ce(static_cast<size_t>(ccap), 0), starts(static_cast<size_t>(ccap), 0), ends(static_cast<size_t>(ccap), 0);
+        int64_t needed = 0, chunks = 0;
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_chunks_overlap_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()),
+                                                              mx, ov, ids.data(), cap, ooff.data(), dco.data(), ct.data(), ce.data(), starts.data(), ends.data(), ccap, &needed,
+                                                              &chunks);
+        else st = tkz_encode_batch_chunks_overlap_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), mx,
+                                                       ov, ids.data(), cap, ooff.data(), dco.data(), ct.data(), ce.data(), starts.data(), nullptr, ends.data(), nullptr, ccap,
+                                                       &needed, &chunks);
+        check(st);
+        for (int64_t d = 0; d < n; ++d) {
+            const STR& t = texts[static_cast<size_t>(d)];
+            for (int64_t c = dco[d]; c < dco[d + 1]; ++c) {
+                const size_t a = static_cast<size_t>(starts[c]), b = static_cast<size_t>(ends[c]);
+                out[static_cast<size_t>(d)].emplace_back(std::vector<int32_t>(ids.begin() + ct[c], ids.begin() + ce[c]), t.substr(a, b - a));
             }
         }
         return out;

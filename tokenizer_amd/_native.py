@@ -187,6 +187,13 @@ class Library:
         L.tkz_encode_chunks_utf16.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, i64, pi64, pi64]
         L.tkz_encoder_chunks_calls.argtypes = [vp, pi64]
         L.tkz_encoder_chunks_calls.restype = None
+        L.tkz_encode_batch_chunks_overlap_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, pi64, pi64]
+        L.tkz_encode_batch_chunks_overlap_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_batch_chunks_overlap_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_chunks_overlap_utf8.argtypes = [vp, vp, i64, vp, i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encode_chunks_overlap_utf16.argtypes = [vp, vp, i64, vp, i32, i64, i64, vp, i64, vp, vp, vp, vp, i64, pi64, pi64]
+        L.tkz_encoder_chunks_overlap_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_chunks_overlap_calls.restype = None
         L.tkz_encode_batch_packed_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, vp, pi64, pi64, pi64]
         L.tkz_encode_batch_packed_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, pi64, pi64, pi64]
         L.tkz_encode_batch_packed_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, pi64, pi64, pi64]
@@ -917,6 +924,106 @@ class Encoder:
         """successful calls of the chunk entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_chunks_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- overlapping token-budget chunks: a chunk size and an overlap; every chunk has a start and an end in the table (tkz.h: the rule) --
+    @staticmethod
+    def chunk_bound_overlap(n_docs, total, max_tokens, overlap):
+        """chunks that always suffice (tkz.h: chunk_bound with max_tokens - overlap in the place of max_tokens), and never more than a chunk a byte"""
+        return max(0, min(total, n_docs + 2 * total // max(1, max_tokens - overlap)))
+
+    def _chunks_overlap_call(self, fn, head, max_tokens, overlap, n, cap, ccap, want, batch):
+        """the shared tail of the host entries.  want: (bytes, units, end_bytes, end_units), None for an array the entry does not have.  Returns (ids, offsets or
+        None, doc_chunk_offsets or None, chunk_tokens, chunk_ends, [chunk_bytes, chunk_units, chunk_end_bytes, chunk_end_units] with None where not asked for)"""
+        ids = np.empty(max(1, cap), np.int32)
+        ct, ce = np.empty(max(1, ccap), np.int64), np.empty(max(1, ccap), np.int64)
+        pos = [np.empty(max(1, ccap), np.int64) if w else None for w in want]
+        ooff, dco = (np.empty(n + 1, np.int64), np.empty(n + 1, np.int64)) if batch else (None, None)
+        ni, nc = C.c_int64(0), C.c_int64(0)
+        args = list(head) + [max_tokens, overlap, _ptr(ids), cap]
+        if batch:
+            args += [_ptr(ooff), _ptr(dco)]
+        args += [_ptr(ct), _ptr(ce)] + [_ptr(a) if a is not None else None for a, w in zip(pos, want) if w is not None] + [ccap, C.byref(ni), C.byref(nc)]
+        try:
+            self.lib.check(fn(self._h, *args))
+        except TkzError as ex:
+            ex.needed, ex.needed_chunks = ni.value, nc.value          # (E_CAPACITY: the required counts)
+            raise
+        k, c = ni.value, nc.value
+        return ids[:k], ooff, dco, ct[:c], ce[:c], [a[:c] if a is not None else None for a in pos]
+
+    def encode_batch_chunks_overlap(self, data: np.ndarray, offsets: np.ndarray, max_tokens, overlap, allowed=(), want=(True, True, True, True), out_cap=None,
+                                    chunk_cap=None):
+        """(ids int32, offsets int64[n+1], doc_chunk_offsets int64[n+1], chunk_tokens int64[chunks], chunk_ends int64[chunks], chunk_bytes, chunk_units,
+        chunk_end_bytes, chunk_end_units -- int64[chunks] or None, by `want`) -- tkz_encode_batch_chunks_overlap_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = len(data) if out_cap is None else out_cap
+        ccap = self.chunk_bound_overlap(n, len(data), max_tokens, overlap) if chunk_cap is None else chunk_cap
+        head = [_ptr(data) if len(data) else None, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_overlap_call(self.lib.L.tkz_encode_batch_chunks_overlap_utf8, head, max_tokens, overlap, n, cap, ccap, [bool(w) for w in want], True)
+        return (r[0], r[1], r[2], r[3], r[4]) + tuple(r[5])
+
+    def encode_batch_chunks_overlap_utf16(self, units: np.ndarray, offsets: np.ndarray, max_tokens, overlap, allowed=(), want=(True, True), out_cap=None, chunk_cap=None):
+        """The same for UTF-16 documents (uint16[total], offsets in units): (ids, offsets, doc_chunk_offsets, chunk_tokens, chunk_ends, chunk_units, chunk_end_units)
+        -- tkz_encode_batch_chunks_overlap_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = 3 * len(units) if out_cap is None else out_cap
+        ccap = self.chunk_bound_overlap(n, 3 * len(units), max_tokens, overlap) if chunk_cap is None else chunk_cap
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        head = [_ptr(buf), _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_overlap_call(self.lib.L.tkz_encode_batch_chunks_overlap_utf16, head, max_tokens, overlap, n, cap, ccap,
+                                      [None, bool(want[0]), None, bool(want[1])], True)
+        return r[0], r[1], r[2], r[3], r[4], r[5][1], r[5][3]
+
+    def encode_batch_chunks_overlap_device(self, d_bytes, d_offsets, n_docs, total_bytes, max_tokens, overlap, allowed, d_out_ids, out_cap, d_out_offsets,
+                                           d_doc_chunk_offsets, d_chunk_tokens, d_chunk_ends, d_chunk_bytes=0, d_chunk_units=0, d_chunk_end_bytes=0, d_chunk_end_units=0,
+                                           chunk_cap=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_chunks_overlap_device.  Returns (token total, chunks); a TkzError carries them as `needed` and `needed_chunks`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, nch = C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_chunks_overlap_device(
+                self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None, len(allowed), max_tokens, overlap,
+                d_out_ids or None, out_cap, d_out_offsets or None, d_doc_chunk_offsets or None, d_chunk_tokens or None, d_chunk_ends or None, d_chunk_bytes or None,
+                d_chunk_units or None, d_chunk_end_bytes or None, d_chunk_end_units or None, chunk_cap, stream or None, C.byref(tot), C.byref(nch)))
+        except TkzError as ex:
+            ex.needed, ex.needed_chunks = tot.value, nch.value
+            raise
+        return tot.value, nch.value
+
+    def encode_chunks_overlap(self, text: bytes, max_tokens, overlap, allowed=(), want=(True, True, True, True), out_cap=None, chunk_cap=None):
+        """ONE text: (ids, chunk_tokens, chunk_ends, chunk_bytes, chunk_units, chunk_end_bytes, chunk_end_units) as lists (None where not asked for) --
+        tkz_encode_chunks_overlap_utf8."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        cap = len(text) if out_cap is None else out_cap
+        ccap = self.chunk_bound_overlap(1, len(text), max_tokens, overlap) if chunk_cap is None else chunk_cap
+        buf = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+        head = [_ptr(buf), len(text), _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_overlap_call(self.lib.L.tkz_encode_chunks_overlap_utf8, head, max_tokens, overlap, 1, cap, ccap, [bool(w) for w in want], False)
+        return (r[0].tolist(), r[3].tolist(), r[4].tolist()) + tuple(a.tolist() if a is not None else None for a in r[5])
+
+    def encode_chunks_overlap_utf16(self, units, max_tokens, overlap, allowed=(), out_cap=None, chunk_cap=None):
+        """The same for a .NET `string` given as its UTF-16 code units: (ids, chunk_tokens, chunk_ends, chunk_units, chunk_end_units) --
+        tkz_encode_chunks_overlap_utf16."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        u = np.ascontiguousarray(np.asarray(list(units) + [0], dtype=np.uint16))
+        n_units = len(u) - 1
+        cap = 3 * n_units if out_cap is None else out_cap
+        ccap = self.chunk_bound_overlap(1, 3 * n_units, max_tokens, overlap) if chunk_cap is None else chunk_cap
+        head = [_ptr(u), n_units, _ptr(allowed) if len(allowed) else None, len(allowed)]
+        r = self._chunks_overlap_call(self.lib.L.tkz_encode_chunks_overlap_utf16, head, max_tokens, overlap, 1, cap, ccap, [None, True, None, True], False)
+        return r[0].tolist(), r[3].tolist(), r[4].tolist(), r[5][1].tolist(), r[5][3].tolist()
+
+    def chunks_overlap_calls(self):
+        """successful calls of the overlap chunk entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_chunks_overlap_calls(self._h, C.byref(a))
         return a.value
 
     # -- packed rows: the ids framed by bos / eos ids and laid out in rows of row_len, with pos and seg_starts (tkz.h: the rule) --

@@ -314,6 +314,7 @@ struct tkz_encoder {
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
     std::atomic<int64_t> packed_calls{0};                                 // tkz_encoder_packed_calls: successful calls of the packed entries
+    std::atomic<int64_t> chunks_overlap_calls{0};                          // tkz_encoder_chunks_overlap_calls: successful calls of the overlap chunk entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
     std::atomic<int64_t> count_calls{0}, count_single{0};                  // tkz_encoder_count_calls: successful count calls, and those of them that took the single launch
@@ -362,7 +363,12 @@ struct TrimCall { int32_t side; int64_t max_tokens; const int64_t* d_max; int64_
 // A call of one of the span entries: where the byte and the UTF-16 unit position of every token go (device, out_cap entries each; either may be null, not both)
 struct SpanCall { int32_t* d_tok_bytes; int32_t* d_tok_units; };
 // A call of one of the chunk entries: the budget, where the chunk table goes (device; bytes and units may be null) and, on the host, where the number of chunks goes
-struct ChunkCall { int64_t max_tokens; int64_t* d_doc_chunk_offs; int64_t* d_chunk_tokens; int64_t* d_chunk_bytes; int64_t* d_chunk_units; int64_t chunk_cap; int64_t* n_chunks; };
+// overlap >= 0: one of the overlap entries -- the walks of launch_chunks_overlap, the ends of the chunks (d_chunk_ends required, the end positions may be null)
+struct ChunkCall {
+    int64_t max_tokens; int64_t* d_doc_chunk_offs; int64_t* d_chunk_tokens; int64_t* d_chunk_bytes; int64_t* d_chunk_units; int64_t chunk_cap; int64_t* n_chunks;
+    int64_t overlap = -1; int64_t* d_chunk_ends = nullptr; int64_t* d_chunk_end_bytes = nullptr; int64_t* d_chunk_end_units = nullptr;
+    bool wants_units() const { return d_chunk_units || d_chunk_end_units; }
+};
 // A call of one of the packed entries: the framing ids (-1: none), the row length and the pad id, where pos and seg_starts go (device, either may be null) and, on the
 // host, where the numbers of rows and segments go
 struct PackCall { int32_t bos_id, eos_id; int64_t row_len; int32_t pad_id; int32_t* d_pos; int64_t* d_seg_starts; int64_t seg_cap; int64_t* n_rows; int64_t* n_segs;
@@ -1118,7 +1124,8 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                                         nspan, ws->ck_ucnt.as<int32_t>(), ubase, ubase + nspan + 2, ubase + nspan,
                                         c.d_out_offs, k.d_doc_chunk_offs, k.d_chunk_tokens, k.d_chunk_bytes, k.d_chunk_units, k.chunk_cap,
                                         reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, n_chunks)), counters};
-                    launch_chunks(L, C, e->D);
+                    if (k.overlap >= 0) launch_chunks_overlap(L, ChunkOvParams{C, k.overlap, k.d_chunk_ends, k.d_chunk_end_bytes, k.d_chunk_end_units}, e->D);
+                    else launch_chunks(L, C, e->D);
                 }
                 launch_counts3(L, n_docs, total, produced, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else if (c.packed) {                                      // (the unframed offsets, then the rows; the counts blocks receive T)
@@ -1309,7 +1316,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
             if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
             if (c.chunks) {                                       // (no chunks: both offset arrays cleared, and the token total behind the last chunk)
                 HIP_TRY(hipMemsetAsync(c.chunks->d_doc_chunk_offs, 0, (size_t)(n_docs + 1) * sizeof(int64_t), stream));
-                HIP_TRY(hipMemsetAsync(c.chunks->d_chunk_tokens, 0, sizeof(int64_t), stream));
+                if (c.chunks->overlap < 0) HIP_TRY(hipMemsetAsync(c.chunks->d_chunk_tokens, 0, sizeof(int64_t), stream));      // (the overlap entries' table has no entry behind the last chunk)
             }
             if (c.trim && n_docs > 0) for (int64_t* cut : {c.trim->d_cut_bytes, c.trim->d_cut_units}) if (cut) HIP_TRY(hipMemsetAsync(cut, 0, (size_t)n_docs * sizeof(int64_t), stream));
             if (c.d_bitmap) { const uint64_t one = 1; HIP_TRY(hipMemcpyAsync(c.d_bitmap, &one, 8, hipMemcpyHostToDevice, stream)); }
@@ -2844,7 +2851,7 @@ tkz_status chunks_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, ChunkCal
         HIP_TRY(ws->ck_cnt.ensure((size_t)(c.n_docs + 1) * 8, acc));
         HIP_TRY(ws->ck_bsum.ensure((size_t)(c.n_docs / tkz::kScanBlock + 2) * 8, acc));
         HIP_TRY(ws->ck_list.ensure((size_t)std::max<int64_t>(c.n_docs, 1) * 8, acc));
-        if (cc.d_chunk_units) {
+        if (cc.wants_units()) {
             HIP_TRY(ws->ck_ucnt.ensure((size_t)nspan * 4, acc));
             HIP_TRY(ws->ck_ubase.ensure((size_t)(nspan + 2 + nspan / tkz::kScanBlock + 2) * 8, acc));      // (the bases, the total, the scan's partial sums)
         }
@@ -2855,7 +2862,7 @@ tkz_status chunks_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, ChunkCal
     c.kind = CallKind::Chunks; c.pieces = &po; c.chunks = &cc; c.special = sp;
     const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
     if (n_chunks) *n_chunks = chunks;
-    if (st == TKZ_OK) { ++e->chunks_calls; if (sp) ++e->spec_batches; }
+    if (st == TKZ_OK) { ++(cc.overlap >= 0 ? e->chunks_overlap_calls : e->chunks_calls); if (sp) ++e->spec_batches; }
     return st;
 }
 // The second half of a chunk host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the ids, their offsets and the table,
@@ -2985,6 +2992,151 @@ tkz_status tkz_encode_chunks_utf16(tkz_encoder* e, const uint16_t* text, int64_t
 }
 void tkz_encoder_chunks_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->chunks_calls.load() : 0;
+}
+
+// ---- overlapping token-budget chunks: the chunk entries with an overlap -- every chunk has a start AND an end in the table (tkz.h: the rule) ----
+
+namespace {
+const char* const kMsgChunkOverlap = "chunks: overlap must be in [0, max_tokens)";
+const char* const kMsgChunkEnds = "chunks: null chunk table buffer (chunk_ends included) or negative chunk_cap";
+tkz_status check_overlap_args(int64_t max_tokens, int64_t overlap, const void* doc_chunk_offsets, const void* chunk_tokens, const void* chunk_ends, int64_t chunk_cap) {
+    if (max_tokens < 1) return fail(TKZ_E_ARG, kMsgChunkMax);
+    if (overlap < 0 || overlap >= max_tokens) return fail(TKZ_E_ARG, kMsgChunkOverlap);
+    if (!doc_chunk_offsets || !chunk_tokens || !chunk_ends || chunk_cap < 0) return fail(TKZ_E_ARG, kMsgChunkEnds);
+    return TKZ_OK;
+}
+// where the host entries' table goes: chunk_tokens and chunk_ends, and the four position arrays (null: not asked for)
+struct OverlapTable { int64_t* tokens; int64_t* ends; int64_t* pos[4]; };      // pos: chunk_bytes, chunk_units, chunk_end_bytes, chunk_end_units
+// chunks_staged for the overlap entries: staging for the ids, their offsets and the six table arrays, ONE chunk call, the results back
+tkz_status chunks_overlap_staged(tkz_encoder* e, Workspace* ws, BatchCall c, int64_t max_tokens, int64_t overlap, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap,
+                                 int64_t* out_offsets, int64_t* doc_chunk_offsets, const OverlapTable& t, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks) {
+    const int64_t n_docs = c.n_docs;
+    c.out_cap = std::min<int64_t>(out_cap, c.total);
+    const int64_t ccap = std::min<int64_t>(chunk_cap, c.total), cap = std::max<int64_t>(ccap, 1);      // (the starts ascend: chunks <= tokens <= bytes)
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap));
+    HIP_TRY(ws->ck_stage.ensure((size_t)((n_docs + 1) + 6 * cap) * 8, &ws->bytes_allocated));
+    int64_t* const d_dco = ws->ck_stage.as<int64_t>(), * const d_ct = d_dco + n_docs + 1, * const d_ce = d_ct + cap, * const d_pos = d_ce + cap;
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = ws->s_outoffs[0].as<int64_t>();
+    ChunkCall cc{max_tokens, d_dco, d_ct, t.pos[0] ? d_pos : nullptr, t.pos[1] ? d_pos + cap : nullptr, ccap, nullptr};
+    cc.overlap = overlap; cc.d_chunk_ends = d_ce; cc.d_chunk_end_bytes = t.pos[2] ? d_pos + 2 * cap : nullptr; cc.d_chunk_end_units = t.pos[3] ? d_pos + 3 * cap : nullptr;
+    int64_t tokens = 0, chunks = 0;
+    const tkz_status st = chunks_on_device(e, ws, c, cc, sp, &tokens, &chunks);
+    if (needed_ids) *needed_ids = tokens;
+    if (needed_chunks) *needed_chunks = chunks;
+    if (st != TKZ_OK) return st;
+    TKZ_TRY(fetch(ws, out_ids, tokens, out_offsets, n_docs));
+    HIP_TRY(hipMemcpy(doc_chunk_offsets, d_dco, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (!chunks) return TKZ_OK;
+    HIP_TRY(hipMemcpy(t.tokens, d_ct, (size_t)chunks * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.ends, d_ce, (size_t)chunks * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) if (t.pos[k]) HIP_TRY(hipMemcpy(t.pos[k], d_pos + k * cap, (size_t)chunks * 8, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_chunks_overlap_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                                  const int32_t* allowed, int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* d_out_ids, int64_t out_cap,
+                                                  int64_t* d_out_offsets, int64_t* d_doc_chunk_offsets, int64_t* d_chunk_tokens, int64_t* d_chunk_ends,
+                                                  int64_t* d_chunk_bytes, int64_t* d_chunk_units, int64_t* d_chunk_end_bytes, int64_t* d_chunk_end_units,
+                                                  int64_t chunk_cap, void* hip_stream, int64_t* total_tokens, int64_t* n_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_overlap_args(max_tokens, overlap, d_doc_chunk_offsets, d_chunk_tokens, d_chunk_ends, chunk_cap));
+    if (n_chunks) *n_chunks = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_device_call(e, scope, c));
+    Lease lease(e);
+    ChunkCall cc{max_tokens, d_doc_chunk_offsets, d_chunk_tokens, d_chunk_bytes, d_chunk_units, chunk_cap, nullptr};
+    cc.overlap = overlap; cc.d_chunk_ends = d_chunk_ends; cc.d_chunk_end_bytes = d_chunk_end_bytes; cc.d_chunk_end_units = d_chunk_end_units;
+    return chunks_on_device(e, lease.ws, c, cc, sp, total_tokens, n_chunks);
+}
+
+tkz_status tkz_encode_batch_chunks_overlap_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed,
+                                                int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                                int64_t* doc_chunk_offsets, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_bytes, int64_t* chunk_units,
+                                                int64_t* chunk_end_bytes, int64_t* chunk_end_units, int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_overlap_args(max_tokens, overlap, doc_chunk_offsets, chunk_tokens, chunk_ends, chunk_cap));
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    if (needed_ids) *needed_ids = 0;
+    if (needed_chunks) *needed_chunks = 0;
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return chunks_overlap_staged(e, ws, staged_call(ws, n_docs, total, 0), max_tokens, overlap, sp, out_ids, out_cap, out_offsets, doc_chunk_offsets,
+                                 OverlapTable{chunk_tokens, chunk_ends, {chunk_bytes, chunk_units, chunk_end_bytes, chunk_end_units}}, chunk_cap, needed_ids, needed_chunks);
+}
+
+// The same for UTF-16 documents, as tkz_encode_batch_chunks_utf16: positions in code units only
+tkz_status tkz_encode_batch_chunks_overlap_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed,
+                                                 int32_t n_allowed, int64_t max_tokens, int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* out_offsets,
+                                                 int64_t* doc_chunk_offsets, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_units, int64_t* chunk_end_units,
+                                                 int64_t chunk_cap, int64_t* needed_ids, int64_t* needed_chunks) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_overlap_args(max_tokens, overlap, doc_chunk_offsets, chunk_tokens, chunk_ends, chunk_cap));
+    TKZ_TRY(check_host_outputs(out_ids, out_cap, out_offsets, "null output buffer", false));
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    if (needed_ids) *needed_ids = 0;
+    if (needed_chunks) *needed_chunks = 0;
+    if (total == 0) {
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, out_offsets));
+        std::fill_n(doc_chunk_offsets, n_docs + 1, int64_t(0));
+        ++e->chunks_overlap_calls;
+        if (sp) ++e->spec_batches;
+        return TKZ_OK;
+    }
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return chunks_overlap_staged(e, ws, c, max_tokens, overlap, sp, out_ids, out_cap, out_offsets, doc_chunk_offsets,
+                                 OverlapTable{chunk_tokens, chunk_ends, {nullptr, chunk_units, nullptr, chunk_end_units}}, chunk_cap, needed_ids, needed_chunks);
+}
+
+// ONE text: the batch entry with one document, at every size
+tkz_status tkz_encode_chunks_overlap_utf8(tkz_encoder* e, const uint8_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens,
+                                          int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_bytes,
+                                          int64_t* chunk_units, int64_t* chunk_end_bytes, int64_t* chunk_end_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks) {
+    if (len < 0 || !n_out || !n_chunks) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0; *n_chunks = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, dco[2] = {0, 0};
+    return tkz_encode_batch_chunks_overlap_utf8(e, text, offs, 1, allowed, n_allowed, max_tokens, overlap, out_ids, out_cap, oo, dco, chunk_tokens, chunk_ends, chunk_bytes,
+                                                chunk_units, chunk_end_bytes, chunk_end_units, chunk_cap, n_out, n_chunks);
+}
+tkz_status tkz_encode_chunks_overlap_utf16(tkz_encoder* e, const uint16_t* text, int64_t len, const int32_t* allowed, int32_t n_allowed, int64_t max_tokens,
+                                           int64_t overlap, int32_t* out_ids, int64_t out_cap, int64_t* chunk_tokens, int64_t* chunk_ends, int64_t* chunk_units,
+                                           int64_t* chunk_end_units, int64_t chunk_cap, int64_t* n_out, int64_t* n_chunks) {
+    if (len < 0 || (!text && len) || !n_out || !n_chunks) return fail(TKZ_E_ARG, "bad argument");
+    *n_out = 0; *n_chunks = 0;
+    const int64_t offs[2] = {0, len};
+    int64_t oo[2] = {0, 0}, dco[2] = {0, 0};
+    return tkz_encode_batch_chunks_overlap_utf16(e, text, offs, 1, allowed, n_allowed, max_tokens, overlap, out_ids, out_cap, oo, dco, chunk_tokens, chunk_ends, chunk_units,
+                                                 chunk_end_units, chunk_cap, n_out, n_chunks);
+}
+void tkz_encoder_chunks_overlap_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->chunks_overlap_calls.load() : 0;
 }
 
 // ---- packed rows: the ids of the matching encode entry framed by bos / eos ids, laid out in rows of row_len, with pos and seg_starts (tkz.h: the rule) ----

@@ -273,6 +273,15 @@ struct ChunkParams {
     int64_t* n_chunks; int32_t* counters;
 };
 void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& D);
+// Overlapping token-budget chunks (tkz_encode_batch_chunks_overlap_device; tkz.h states the rule): launch_chunks' sequence with walks and a unit kernel of their
+// own (k_chunkov_walk, k_chunkov_walk_long, k_chunkov_units; k_chunk_unitcount and the scans are shared).  C is the existing call's block, read as there, except
+// that chunk_tokens has chunk_cap entries (no total behind the last chunk).  overlap: 0 <= overlap < C.max_tokens.  chunk_ends: chunk_cap entries, required;
+// chunk_end_bytes / chunk_end_units: chunk_cap entries each, either may be null.  The unit stage runs when C.chunk_units or chunk_end_units is given.
+struct ChunkOvParams {
+    ChunkParams C; int64_t overlap;
+    int64_t* chunk_ends; int64_t* chunk_end_bytes; int64_t* chunk_end_units;
+};
+void launch_chunks_overlap(const Launch& L, const ChunkOvParams& V, const TkzDecodeTable& D);
 // Packed rows (tkz_encode_batch_packed_device; tkz.h states the rule): behind the PLAIN document-granular launch sequence.  ids / offs are the unframed ids and
 // their n_docs + 1 document offsets as k_place / k_docoffs left them: in the workspace when a bos or eos id frames the documents (every id moves), the caller's
 // own out / out_offs when none does (ids == out: no id is moved, offs == out_offs: they stand).  The stream is dealt out in tiles of kPackTile positions, a

@@ -4046,6 +4046,223 @@ TKZ_KERNEL(256) void k_tokspan_write(SpanParams S) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// Overlapping token-budget chunks (tkz_encode_batch_chunks_overlap_device): the chunk section's launch sequence -- count walk, scan, write walk, unit stage -- with
+// walks and a unit kernel of their own, so that the kernels of the entries without overlap stay the code they are.  tkz_chunk_end, tkz_chunk_emit,
+// tkz_chunk_units_before and k_chunk_unitcount are shared.  The rule (tkz.h): chunk [s, e) ends where the existing rule ends a chunk that starts at s; the next
+// one starts at the smallest item boundary in [x, e], x = max(e - overlap, s + 1), at x itself when e lies inside an item, and at e when a chunk begun there
+// would end at e again.
+//   the next start     e inside an item means that (s, e] holds no boundary: the start is x, in the same item.  Otherwise the boundaries of (s, e] are the
+//                      entries ps + 1 .. pe of piece_toffs (ps, pe: the items of s and e), toffs[pe] == e >= x, and the start is the first of them at or above x.
+//   adds nothing       a chunk begun at a boundary n < e ends at e again exactly when the boundary behind e lies beyond n + max (e - n <= overlap < max, so e
+//                      is in reach): ONE load, toffs[pe + 1], instead of a trial tkz_chunk_end.  A start inside an item never ends at e again (its end is
+//                      n + max > e or a boundary behind e), and neither does one whose rest fits the budget (it ends at the document's end, behind e).
+//   k_chunkov_walk       one lane per document.  A document of at most max tokens stays two loads.  The start is a binary search over the chunk's own items
+//                        ps + 1 .. pe: log2 of the items of a chunk, at most log2(max), loads a chunk beside the galloping search for the end.
+//   k_chunkov_walk_long  one wavefront per listed document, the window of k_chunk_walk_long.  The window is NOT stepped back for a start behind it: the end
+//                        before (item kf) is at or below the new start + max, so the search for the next end begins there, and w <= kf + 1 <= w + 63 holds
+//                        wherever a chunk starts -- the window only moves forward.  The start is searched BACK from the end item: the lanes load the 64
+//                        entries that end at pe (they have just passed through the window: cache hits), a ballot of toffs >= x and a population count give
+//                        the first, and only an overlap of more than 64 items takes another step back.  A chunk costs one such load of 64 entries per 64
+//                        items of overlap and two wave-uniform loads (the start's own entry, the boundary behind e) more than k_chunk_walk_long's.
+//   positions            TWO cursors a walk (TkzChunkItem), one for starts and one for ends: inside an oversize item the queries come in the order s, e,
+//                        e - overlap < e, each of the two sequences ascends, and neither walks an item's ids from its beginning a second time.  An end at
+//                        the document's end is the document's length and reads nothing.
+//   k_chunkov_units      k_chunk_units' scheme, once for the starts and once for the ends.  An end may be `total` itself (the last document's last chunk):
+//                        tkz_chunk_units_before clamps that position's span to the last one and counts up to `total`, so nothing is read beyond the text.
+// Errors as the chunk section: with an error bit the counts are 0; with one, with ids that did not fit or with more chunks than chunk_cap the table is left alone.
+// -------------------------------------------------------------------------------------------------
+TKZ_DEV int64_t tkz_chunkov_x(int64_t s, int64_t e, int64_t ov) { const int64_t x = e - ov; return x > s + 1 ? x : s + 1; }
+TKZ_DEV bool tkz_chunkov_adds_nothing(const int64_t* toffs, int64_t pe, int64_t n, int64_t e, int64_t m) { return n < e && toffs[pe + 1] > n + m; }
+// the end of chunk o of the table: token e, in item p (whose first token is tp), of the document [a, aend) of the batch; last: the document's last chunk
+TKZ_DEV void tkz_chunkov_emit_end(const ChunkOvParams& V, const TkzDecodeTable& D, int64_t o, int64_t a, int64_t aend, bool last, int64_t e, int64_t p, int64_t tp,
+                                  TkzChunkItem* W) {
+    const ChunkParams& C = V.C;
+    if (o < 0 || o >= C.chunk_cap) return;
+    V.chunk_ends[o] = e;
+    if (!V.chunk_end_bytes && !V.chunk_end_units) return;
+    int64_t pos = aend;
+    if (!last && e == tp) pos = C.piece_boffs[p];
+    else if (!last) {
+        const int64_t b0 = C.piece_boffs[p], b1 = C.piece_boffs[p + 1];
+        if (W->item != p) { W->item = p; W->tok = tp; W->pos = b0; }
+        bool bad = false;
+        for (int64_t t = W->tok; t < e; ++t) {
+            uint32_t off, len = 0;
+            if (!tkz_dec_find(D, C.ids[t], &off, &len)) bad = true;
+            W->pos += len;
+        }
+        W->tok = e;
+        pos = W->pos;
+        if (bad || pos <= b0 || pos >= b1) {               // (the end lies inside the item: nothing is read outside the text)
+            simt::atomic_or((unsigned*)&C.counters[0], (unsigned)kErrChunkSum);
+            pos = b1;
+        }
+    }
+    if (V.chunk_end_bytes) V.chunk_end_bytes[o] = pos - a;
+    if (V.chunk_end_units) V.chunk_end_units[o] = pos;
+}
+
+TKZ_KERNEL(256) void k_chunkov_walk(ChunkOvParams V, TkzDecodeTable D, int write) {
+    const ChunkParams& C = V.C;
+    const int64_t stride = simt::nblocks() * simt::nthreads(), i0 = simt::bid() * simt::nthreads() + simt::tid();
+    const bool bad = C.counters[0] != 0;
+    const int64_t m = C.max_tokens, ov = V.overlap;
+    const int64_t* const toffs = C.piece_toffs;
+    if (write) {
+        const int64_t nch = C.doc_chunk_offs[C.n_docs];
+        if (i0 == 0) *C.n_chunks = nch;
+        if (bad || *C.grand > C.out_cap || nch > C.chunk_cap) return;
+    }
+    for (int64_t d = i0; d <= C.n_docs; d += stride) {
+        if (bad) { if (d < C.n_docs) C.doc_cnt[d] = 0; C.out_offs[d] = 0; continue; }
+        const int64_t p0 = C.doc_piece[d];
+        int64_t tp = toffs[p0];
+        if (!write) C.out_offs[d] = tp;
+        if (d == C.n_docs) break;
+        const int64_t p1 = C.doc_piece[d + 1], tend = toffs[p1];
+        int64_t c = 0;
+        if (tend - tp > m && p1 - p0 > kChunkLongItems) {     // (k_chunkov_walk_long's: the count as well)
+            if (!write) C.long_list[simt::atomic_add64(C.long_count, 1ull)] = d;
+            continue;
+        }
+        if (tend > tp) {
+            const int64_t base = write ? C.doc_chunk_offs[d] : 0, a = write ? C.offs[d] : 0, aend = write ? C.offs[d + 1] : 0;
+            int64_t s = tp, p = p0;
+            TkzChunkItem Ws{-1, 0, 0}, We{-1, 0, 0};
+            for (;;) {
+                const bool last = tend - s <= m;
+                int64_t pe = p, tpe = tp, e = tend;
+                if (!last) e = tkz_chunk_end(toffs, p1, s, m, &pe, &tpe);
+                if (write) {
+                    tkz_chunk_emit(C, D, base + c, a, c == 0, s, p, tp, &Ws);
+                    tkz_chunkov_emit_end(V, D, base + c, a, aend, last, e, pe, tpe, &We);
+                }
+                ++c;
+                if (last) break;
+                const int64_t x = tkz_chunkov_x(s, e, ov);
+                if (pe == p) { s = x; continue; }             // (e inside item p: so is the next start)
+                int64_t lo = p + 1, hi = pe, n = e;           // the first of toffs[p + 1 .. pe] at or above x: n == toffs[hi] >= x throughout
+                while (lo < hi) {
+                    const int64_t mid = lo + (hi - lo) / 2, v = toffs[mid];
+                    if (v >= x) { hi = mid; n = v; } else lo = mid + 1;
+                }
+                if (tkz_chunkov_adds_nothing(toffs, pe, n, e, m)) { hi = pe; n = e; }
+                s = n; p = hi; tp = n;
+            }
+        }
+        if (!write) C.doc_cnt[d] = c;
+    }
+}
+
+TKZ_KERNEL(256) void k_chunkov_walk_long(ChunkOvParams V, TkzDecodeTable D, int write) {
+    const ChunkParams& C = V.C;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    if (C.counters[0] != 0) return;                           // (nothing was listed)
+    if (write && (*C.grand > C.out_cap || C.doc_chunk_offs[C.n_docs] > C.chunk_cap)) return;
+    const int64_t m = C.max_tokens, ov = V.overlap, nlong = (int64_t)*C.long_count, none = (int64_t)0x7FFFFFFFFFFFFFFFll;
+    const int64_t* const toffs = C.piece_toffs;
+    for (int64_t q = wave0; q < nlong; q += nwaves) {
+        const int64_t d = C.long_list[q], p0 = C.doc_piece[d], p1 = C.doc_piece[d + 1], tend = toffs[p1];
+        const int64_t base = write ? C.doc_chunk_offs[d] : 0, a = write ? C.offs[d] : 0, aend = write ? C.offs[d + 1] : 0;
+        int64_t tp = toffs[p0], s = tp, p = p0, c = 0;
+        // kf: the last item known to begin at or below s + max -- the item of the end before, or the start's own.  The window as in k_chunk_walk_long, with
+        // w <= kf + 1 <= w + 63 wherever a chunk starts; it only moves forward
+        int64_t kf = p0, tkf = tp;
+        int64_t w = p0 + 1;
+        const int64_t* const tl = toffs + lane;
+        int64_t v = w + lane <= p1 ? tl[w] : none, n1 = w + 64 + lane <= p1 ? tl[w + 64] : none, n2 = w + 128 + lane <= p1 ? tl[w + 128] : none,
+                n3 = w + 192 + lane <= p1 ? tl[w + 192] : none;
+        TkzChunkItem Ws{-1, 0, 0}, We{-1, 0, 0};
+        for (;;) {
+            const bool last = tend - s <= m;
+            int64_t pe = p, tpe = tp, e = tend;
+            if (!last) {
+                const int64_t lim = s + m;
+                int64_t k = kf, tk = tkf;                     // the last boundary at or below lim
+                for (;;) {
+                    const int n = tkz_popc64(simt::ballot(v <= lim));      // (ascending: the lanes at or below lim are the first n)
+                    if (n > 0 && w + n - 1 > k) { k = w + n - 1; tk = tkz_shfl64(v, n - 1); }
+                    if (n < 64) break;
+                    w += 64; v = n1; n1 = n2; n2 = n3; n3 = w + 192 + lane <= p1 ? tl[w + 192] : none;
+                }
+                if (k > p) { e = tk; pe = k; tpe = tk; } else e = lim;
+            }
+            if (write && lane == 0) {
+                tkz_chunk_emit(C, D, base + c, a, c == 0, s, p, tp, &Ws);
+                tkz_chunkov_emit_end(V, D, base + c, a, aend, last, e, pe, tpe, &We);
+            }
+            ++c;
+            if (last) break;
+            const int64_t x = tkz_chunkov_x(s, e, ov);
+            if (pe == p) { s = x; continue; }                 // (e inside item p: so is the next start, and kf == p stays)
+            // back from the end item: the entries hi - 63 .. hi, those at or below item p count as below x; the lanes at or above x are the last `back`
+            int64_t hi = pe, pn = pe;
+            for (;;) {
+                const int64_t i = hi - 63 + lane;
+                const int64_t u = i > p ? toffs[i] : (int64_t)-1;
+                const int back = tkz_popc64(simt::ballot(u >= x));
+                pn = hi - back + 1;
+                if (back < 64 || hi - 64 <= p) break;
+                hi -= 64;
+            }
+            int64_t n = pn == pe ? e : toffs[pn];
+            if (tkz_chunkov_adds_nothing(toffs, pe, n, e, m)) { pn = pe; n = e; }
+            s = n; p = pn; tp = n; kf = pe; tkf = e;
+        }
+        if (!write && lane == 0) C.doc_cnt[d] = c;
+    }
+}
+
+// The units of 64 positions: every lane's pos and the start a of its document as batch bytes (a lane with nothing to do: both 0, which reads nothing) -> the
+// units begun in [a, pos).  k_chunk_units' scheme: a group of 16 lanes takes the positions of its own lanes one after the other, its lower 8 lanes count in front
+// of the position, its upper 8 in front of the document's start.  Every lane of the wavefront calls.
+TKZ_DEV int64_t tkz_chunkov_units64(const ChunkParams& C, int64_t pos, int64_t a, int lane) {
+    const int sl = lane & 15, g0 = lane & 48;
+    int64_t units = 0;
+    for (int r = 0; r < 16; ++r) {
+        const int64_t rpos = tkz_shfl64(pos, g0 + r), ra = tkz_shfl64(a, g0 + r);
+        if (simt::ballot(rpos != 0) == 0) continue;
+        const int64_t mine = tkz_chunk_units_before(C, sl < 8 ? rpos : ra, sl & 7), other = tkz_shfl64(mine, lane ^ 8);
+        if (sl == r) units = sl < 8 ? mine - other : other - mine;
+    }
+    return units;
+}
+TKZ_KERNEL(256) void k_chunkov_units(ChunkOvParams V) {
+    const ChunkParams& C = V.C;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t nch = C.doc_chunk_offs[C.n_docs];
+    if (C.counters[0] != 0 || *C.grand > C.out_cap || nch > C.chunk_cap) return;
+    for (int64_t c0 = wave0 * 64; c0 < nch; c0 += nwaves * 64) {
+        const int64_t c1 = c0 + 64 < nch ? c0 + 64 : nch, c = c0 + lane;
+        // the documents of the tile's first and last chunk (wave-uniform), then every lane's own among them
+        const int64_t d0 = tkz_last_le(C.doc_chunk_offs, 0, C.n_docs - 1, c0), d1 = tkz_last_le(C.doc_chunk_offs, d0, C.n_docs - 1, c1 - 1);
+        int64_t a = 0, spos = 0, epos = 0;
+        bool first = true;
+        if (c < c1) {
+            const int64_t d = d0 == d1 ? d0 : tkz_last_le(C.doc_chunk_offs, d0, d1, c);
+            first = C.doc_chunk_offs[d] == c;
+            a = C.offs[d];
+        }
+        if (C.chunk_units) {                                  // (a document's first chunk starts at unit 0: written already)
+            const bool work = c < c1 && !first;
+            if (work) spos = C.chunk_units[c];
+            if (work && (spos <= a || spos >= C.total)) { spos = a; simt::atomic_or((unsigned*)&C.counters[0], (unsigned)kErrChunkSum); }
+            const int64_t units = tkz_chunkov_units64(C, spos, work ? a : 0, lane);
+            if (work) C.chunk_units[c] = units;
+        }
+        if (V.chunk_end_units) {                              // (every chunk has an end behind its document's start; the last one's may be `total`)
+            const bool work = c < c1;
+            if (work) epos = V.chunk_end_units[c];
+            if (work && (epos <= a || epos > C.total)) { epos = a; simt::atomic_or((unsigned*)&C.counters[0], (unsigned)kErrChunkSum); }
+            const int64_t units = tkz_chunkov_units64(C, epos, work ? a : 0, lane);
+            if (work) V.chunk_end_units[c] = units;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // k_small: the WHOLE launch sequence for a small batch in ONE kernel, one workgroup (ITokenizer.Encode of a prompt, TikTokenizer.cs:178-207;
 // the shape of BASELINE.json configs[0]).  The batch path above is ~25 launches and as many dependent kernel boundaries: ~160 us for a
 // 64-byte prompt, whatever the kernels do.  Here the phases are the same device functions (tkz_probe_subtile, tkz_merge_short_group,
@@ -4812,6 +5029,28 @@ void launch_chunks(const Launch& L, const ChunkParams& C, const TkzDecodeTable& 
     TKZ_LAUNCH(k_chunk_walk, g_docs, kThreads, L.stream, C, D, 1);
     TKZ_LAUNCH(k_chunk_walk_long, g_long, kThreads, L.stream, C, D, 1);
     if (C.chunk_units) TKZ_LAUNCH(k_chunk_units, g_units, kThreads, L.stream, C);
+    hook(L, K_DOCOFFS, 1);
+}
+// (launch_chunks' sequence and grids with the overlap walks; the unit stage runs for either unit array)
+void launch_chunks_overlap(const Launch& L, const ChunkOvParams& V, const TkzDecodeTable& D) {
+    const ChunkParams& C = V.C;
+    const int64_t g_docs = grid_for(C.n_docs + 1), nblk = grid1(cdiv(C.n_docs, kScanBlock));
+    int64_t g_long = cdiv(C.total / kChunkLongItems, kThreads / 64), g_units = cdiv(cdiv(C.chunk_cap, 64), kThreads / 64);
+    g_long = g_long < 1 ? 1 : (g_long > 1024 ? 1024 : g_long);
+    g_units = g_units < 1 ? 1 : (g_units > 2048 ? 2048 : g_units);
+    const bool units = C.chunk_units || V.chunk_end_units;
+    TKZ_LAUNCH(k_chunkov_walk, g_docs, kThreads, L.stream, V, D, 0);
+    TKZ_LAUNCH(k_chunkov_walk_long, g_long, kThreads, L.stream, V, D, 0);
+    TKZ_LAUNCH(k_scan_partials64, nblk, kThreads, L.stream, (const int64_t*)C.doc_cnt, C.n_docs, C.bsum);
+    TKZ_LAUNCH(k_scan_top, 1, kThreads, L.stream, C.bsum, nblk, C.doc_chunk_offs + C.n_docs);
+    TKZ_LAUNCH(k_scan_final64, nblk, kThreads, L.stream, (const int64_t*)C.doc_cnt, C.n_docs, (const int64_t*)C.bsum, C.doc_chunk_offs);
+    if (units) {
+        TKZ_LAUNCH(k_chunk_unitcount, grid1(cdiv(cdiv(C.total, kSub), kThreads / 64)), kThreads, L.stream, C);
+        launch_scan(L, C.cnt_unit, C.nspan, C.ubsum, C.base_unit, C.usum, -1, 1);
+    }
+    TKZ_LAUNCH(k_chunkov_walk, g_docs, kThreads, L.stream, V, D, 1);
+    TKZ_LAUNCH(k_chunkov_walk_long, g_long, kThreads, L.stream, V, D, 1);
+    if (units) TKZ_LAUNCH(k_chunkov_units, g_units, kThreads, L.stream, V);
     hook(L, K_DOCOFFS, 1);
 }
 // (the bracket: K_DOCOFFS's again.  How long the stream is is known on the device only: the counting grid is sized for the tiles the bound allows, the writing

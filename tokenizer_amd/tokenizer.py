@@ -586,6 +586,85 @@ class TikTokenizer:
         ends = starts[1:] + [(total, len(raw) // 2)]
         return [(flat[s:e], raw[2 * u:2 * v].decode("utf-16-le", "surrogatepass")) for (s, u), (e, v) in zip(starts, ends)]
 
+    # ---- overlapping token-budget chunks: a chunk size and an overlap (include/tkz.h, "Overlapping token-budget chunks") ----
+    def EncodeChunksOverlap(self, text: str, a, b, c=None):
+        """EncodeChunks with an overlap: a list of (ids, text) whose consecutive entries share at most `overlap` tokens, and the text of those tokens.  The shapes
+        are (text, allowedSpecial, maxTokenCount, overlap) and (text, maxTokenCount, overlap, applySpecialTokens = True).  A chunk is what EncodeTrimSuffix(rest,
+        maxTokenCount) returns; the next one starts with what EncodeTrimPrefix(chunk text, overlap) keeps -- one item further on when that is the whole chunk, and
+        behind the chunk when a chunk begun there would end where this one does.  overlap = 0 gives EncodeChunks' result.  The texts are slices of the input in
+        UTF-16 code units.  maxTokenCount < 1, overlap < 0 and overlap >= maxTokenCount are a ValueError."""
+        return self.EncodeChunksOverlapBatch([text], a, b, c)[0]
+
+    def EncodeChunksOverlapBatch(self, texts: Sequence[str], a, b, c=None):
+        """EncodeChunksOverlap for every text, in ONE device call (tkz_encode_batch_chunks_overlap_utf8): one list of (ids, text) per text."""
+        if isinstance(a, int) and not isinstance(a, bool):
+            (allowed, max_tokens), overlap = self._trim_args(a, c), int(b)
+        else:
+            if c is None:
+                raise TypeError("overlap is required")
+            (allowed, max_tokens), overlap = self._trim_args(a, b), int(c)
+        if max_tokens < 1:
+            raise ValueError("maxTokenCount must be at least 1")
+        if not 0 <= overlap < max_tokens:
+            raise ValueError("overlap must be at least 0 and below maxTokenCount")
+        if not texts:
+            return []
+        plain = not allowed or self._special_re is None
+        if not plain and (self._special_on_host or (self._fffd_literal and any(_has_lone_surrogate(t) for t in texts))):
+            return [self._chunks_overlap_host(t, allowed, max_tokens, overlap) for t in texts]
+        segs = [_utf8_like_dotnet(t) for t in texts]
+        offs = np.zeros(len(segs) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+        data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+        names = set(allowed) if not plain else set()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]           # (registration order = the alternation's)
+        try:
+            ids, _, dco, ct, ce, _, cu, _, ceu = self._encoder.encode_batch_chunks_overlap(data, offs, max_tokens, overlap, index, want=(False, True, False, True))
+        except N.UnsupportedError:
+            self._special_on_host = True
+            return [self._chunks_overlap_host(t, allowed, max_tokens, overlap) for t in texts]
+        flat, ct, ce, cu, ceu = ids.tolist(), ct.tolist(), ce.tolist(), cu.tolist(), ceu.tolist()
+        out = []
+        for d, t in enumerate(texts):
+            raw = t.encode("utf-16-le", "surrogatepass")
+            out.append([(flat[ct[k]:ce[k]], raw[2 * cu[k]:2 * ceu[k]].decode("utf-16-le", "surrogatepass")) for k in range(int(dco[d]), int(dco[d + 1]))])
+        return out
+
+    def _chunks_overlap_host(self, text: str, allowed, max_tokens: int, overlap: int):
+        """the host walk over _piece_items by the rule of tkz.h: the fallback of EncodeChunksOverlapBatch"""
+        import bisect
+        items = self._piece_items(text, allowed)
+        flat: List[int] = []
+        tcum, ucum = [0], [0]                                   # tokens and UTF-16 units in front of every item
+        for n, ids, ulen, _ in items:
+            flat.extend(ids)
+            tcum.append(tcum[-1] + n)
+            ucum.append(ucum[-1] + ulen)
+        total = tcum[-1]
+
+        def end_of(s):                                         # the chunk rule's end for a chunk that starts at s
+            if total - s <= max_tokens:
+                return total
+            k = bisect.bisect_right(tcum, s + max_tokens) - 1
+            return tcum[k] if tcum[k] > s else s + max_tokens
+
+        def unit_of(t):                                        # the UTF-16 unit token t starts at
+            p = bisect.bisect_right(tcum, t) - 1
+            return ucum[p] + (self._units_of_ids(items[p][1][:t - tcum[p]]) if t > tcum[p] else 0) if t < total else ucum[-1]
+        out = []
+        raw = text.encode("utf-16-le", "surrogatepass")
+        s = 0
+        while s < total:
+            e = end_of(s)
+            out.append((flat[s:e], raw[2 * unit_of(s):2 * unit_of(e)].decode("utf-16-le", "surrogatepass")))
+            if e == total:
+                break
+            x = max(e - overlap, s + 1)
+            i = bisect.bisect_left(tcum, x)
+            n = tcum[i] if tcum[i] <= e else x                 # the first boundary in [x, e], else x inside the item
+            s = e if end_of(n) == e else n                     # (a chunk begun at n that ends at e again adds nothing)
+        return out
+
     def Decode(self, tokens: Sequence[int]) -> str:
         """TikTokenizer.cs:586-604: ids that are neither in the vocabulary nor special tokens are dropped; the bytes are decoded as
         UTF-8 (Encoding.UTF8.GetString: malformed sequences become U+FFFD).  One id list is one kernel launch (tkz_decode_utf8)."""
