@@ -666,9 +666,11 @@ enum { TKZ_OPT_PRETOK_SEQUENTIAL = 1,
         * full and a promoted piece stays promoted.  With this option on the encoder follows, from batch to batch, the share of pieces that miss its key
         * tables as a whole (counted by a kernel that runs anyway); when that share has left the level at which it settled after the last promotion -- by
         * more than a quarter and a percentage point, either way, 256 MB of text or more after it -- the encoder learns again: every promotion is dropped
-        * (so a piece that stopped hitting is not chosen again), the memo is emptied (while no other call is in flight), the next learning window counts
+        * (so a piece that stopped hitting is not chosen again), the memo is emptied (while no other call is in flight: a host call that is cut into chunks does so at its first chunk, before the second is
+        * begun, so the window may wait for the next call), the next learning window counts
         * hits and the hottest pieces of the text as it is now are promoted.  Also with it on: the learning rounds go on (1, 2, 4, 8 ... GB apart: a change
-        * of text that does not move the miss share is still learnt; a round only adds pieces, a list that reaches its cap starts over), and batches smaller
+        * of text that does not move the miss share is still learnt; a round only adds pieces; a list that later rounds have filled to nine tenths of its cap starts over, one that a single window filled stays
+        * until the text drifts), and batches smaller
         * than TKZ_OPT_PROMOTE_MIN_BYTES add up to a learning window instead of never learning.  0: learn in the first batch of at least that size and once more a gigabyte later, never again
         * (round 5's behaviour).  Same ids either way. */
        TKZ_OPT_ADAPT = 9 };

@@ -24,21 +24,29 @@ struct Sim {
     size_t n_promoted = 0;
     bool ws_learning = false, opened = false;
     int64_t seen = 0;                                  // the test's own count of the bytes fed
+    uint64_t gen = 0;                                  // the generation of the tables the batch in hand took its copy of (arm_learning)
     Arm arm(int64_t total, bool others = false) {
         const Arm a = p.may_learn(total, true, true, true, true, n_promoted, others);
+        gen = p.generation();
         if (a != Arm::No) { opened = p.window_armed(a == Arm::YesClearMemo); ws_learning = true; }
         return a;
     }
     After end(int64_t total, double misses, double pieces) {
-        const After w = p.batch_ended(total, misses, pieces, ws_learning, n_promoted);
+        const After w = p.batch_ended(total, misses, pieces, ws_learning, n_promoted, gen);
         ws_learning = false; seen += total;
+        return w;
+    }
+    // a batch that was enqueued when the tables were at generation `enqueued_on` (the pipelined host path: two launch sequences ahead) and ends now
+    After late(int64_t total, double misses, double pieces, uint64_t enqueued_on) {
+        const After w = p.batch_ended(total, misses, pieces, false, n_promoted, enqueued_on);
+        seen += total;
         return w;
     }
     After batch(int64_t total, double misses, double pieces) { arm(total); return end(total, misses, pieces); }
     After quiet(int64_t total) { return batch(total, 0, 0); }      // (no pieces: the miss share is not followed, only the bytes count)
     void quiet_until(int64_t at) { while (seen < at) { const bool was = ws_learning; CHECK(quiet(at - seen) == After::Nothing && !was); } }
-    void install(int64_t added) { p.promotion_installed(added, n_promoted); n_promoted += (size_t)added; }
-    void drop() { p.promotions_dropped(); n_promoted = 0; }
+    void install(int64_t added) { if (added) p.tables_replaced(); p.promotion_installed(added, n_promoted); n_promoted += (size_t)added; }      // (install_key_tables, promote_or_drop)
+    void drop() { if (n_promoted) p.tables_replaced(); p.promotions_dropped(); n_promoted = 0; }
     bool stats_are(int64_t promotions, int64_t relearns, int64_t base, int64_t ew, int64_t since_install, int64_t window) {
         int64_t s[8] = {-7, -7, -7, -7, -7, -7, -7, -7};
         p.stats(s);
@@ -157,7 +165,7 @@ static void no_window() {
     CHECK(s.end(MB, 1, 10) == After::WindowContinues);
     // a batch of another call that ends while the slot is taken decides nothing
     CHECK(s.arm(MB) == Arm::Yes && !s.opened);
-    CHECK(s.p.batch_ended(GB, 900, 1000, false, 0) == After::Nothing);
+    CHECK(s.p.batch_ended(GB, 900, 1000, false, 0, s.p.generation()) == After::Nothing);
 }
 
 // one window with the miss share `share`, installed; then `steady`-share batches of settle_bytes each
@@ -211,14 +219,122 @@ static void settle_and_drift() {
         if (e.want == After::Relearn) { s.drop(); CHECK(s.stats_are(1, 1, -1, -1, 0, 0)); }
         else CHECK(s.stats_are(1, 0, 125000, e.misses * 1000, kMinSettled, 0));
     }
-    {   // at 90 % of the cap the list starts over, on unchanged text too
-        // (ADVICE.md item 2 calls this wrong for a list that ONE window filled, as here: the follow-up changes this assertion)
-        Sim s = settled(0.25, 58983);                                    // 58983 * 10 >= 65536 * 9
-        for (int k = 1; k <= 3; ++k) CHECK(s.batch(kSettle, 125, 1000) == After::Nothing);
-        CHECK(s.batch(kSettle, 125, 1000) == After::Relearn);
-        Sim t = settled(0.25, 58982);
-        for (int k = 1; k <= 6; ++k) CHECK(t.batch(kSettle, 125, 1000) == After::Nothing);
+}
+
+// `n` settle-sized batches at a miss share of 0.125, none of which may ask for a re-learn; a round that comes due among them is installed with `round_adds` pieces.
+// Returns the rounds that came due.
+static int steady(Sim* s, int n, int64_t round_adds) {
+    int rounds = 0;
+    for (int k = 1; k <= n; ++k) {
+        const After w = s->batch(kSettle, 125, 1000);
+        CHECK(w == After::Nothing || w == After::Promote);
+        if (w == After::Promote) { s->install(round_adds); ++rounds; }
     }
+    return rounds;
+}
+
+// the list at 90 % of its cap
+static void full_list() {
+    for (const int64_t added : {int64_t(58983), int64_t(kCap)}) {      // 58983 * 10 >= 65536 * 9; and the cap itself
+        // ONE window filled it: that list is the text's hot pieces as they are now.  Stationary miss share: nothing, for 20 settle-sized batches ...
+        // (below the cap itself the second round comes a gigabyte after the first window began, inside these 20 batches; it adds a few pieces, and
+        //  that does not make it a list the rounds have filled: the window crossed the mark)
+        Sim s = settled(0.25, added);
+        CHECK(steady(&s, 20, added < (int64_t)kCap ? 10 : 0) == (added < (int64_t)kCap ? 1 : 0));
+        CHECK(s.stats_are(added < (int64_t)kCap ? 2 : 1, 0, 125000, 125000, added < (int64_t)kCap ? 3 * kSettle : 20 * kSettle, 0));      // (the round: the 17th batch)
+        // ... and a share outside the band of a quarter and a point is a drift, as for any list: 0.125 * 1.25 + 0.01 = 0.16625, 0.125 * 0.75 - 0.01 = 0.08375
+        Sim up = s, down = s, in_hi = s, in_lo = s;
+        CHECK(up.batch(kSettle, 167, 1000) == After::Relearn);
+        CHECK(down.batch(kSettle, 83, 1000) == After::Relearn);
+        CHECK(in_hi.batch(kSettle, 166, 1000) == After::Nothing && in_lo.batch(kSettle, 84, 1000) == After::Nothing);
+        up.drop();
+        CHECK(up.arm(MB) == Arm::YesClearMemo);
+    }
+    {   // LATER rounds filled it (two installs and more that added pieces since it was last empty): it starts over, on unchanged text too ...
+        Sim s = settled(0.25, 30000);
+        s.quiet_until(kRound);
+        CHECK(s.batch(kMinBytes, 250, 1000) == After::Promote);          // the second round, a gigabyte after the first window began
+        s.install(28983);                                                // (much: the round gap goes back to 1x -- the count of rounds that FILLED the list does not)
+        for (int k = 1; k <= 3; ++k) CHECK(s.batch(kSettle, 125, 1000) == After::Nothing);      // (not within adapt_min_bytes of the install)
+        CHECK(s.batch(kSettle, 125, 1000) == After::Relearn);
+        CHECK(s.arm(MB) == Arm::No);
+        s.drop();
+        CHECK(s.stats_are(2, 1, -1, -1, 0, 0));
+        // ... and the window after that start-over, which fills the list on its own, does not start over again
+        CHECK(s.arm(kMinBytes) == Arm::YesClearMemo && s.opened);
+        CHECK(s.end(kMinBytes, 250, 1000) == After::Promote);
+        s.install(58983);
+        CHECK(steady(&s, 20, 10) == 1);
+        CHECK(s.stats_are(4, 1, 125000, 125000, 3 * kSettle, 0));
+        // one short of 90 %: later rounds or not, nothing
+        Sim t = settled(0.25, 30000);
+        t.quiet_until(kRound);
+        CHECK(t.batch(kMinBytes, 250, 1000) == After::Promote);
+        t.install(28982);
+        for (int k = 1; k <= 6; ++k) CHECK(t.batch(kSettle, 125, 1000) == After::Nothing);
+        // a round that added nothing has filled nothing
+        Sim u = settled(0.25, 58983);
+        u.quiet_until(kRound);
+        CHECK(u.batch(kMinBytes, 250, 1000) == After::Promote);
+        u.install(0);
+        for (int k = 1; k <= 6; ++k) CHECK(u.batch(kSettle, 125, 1000) == After::Nothing);
+    }
+}
+
+// batches that ran on tables older than the last install (the pipelined host path enqueues two launch sequences ahead; the install lands on a thread)
+static void stale_batches() {
+    {   // the issue's case: settled at 0.25, an install, two batches still on the old tables at 0.25, then the new tables' 0.125
+        Sim s = settled(0.5, 1000);
+        CHECK(s.batch(kSettle, 250, 1000) == After::Nothing);
+        CHECK(s.stats_are(1, 0, 250000, 250000, kSettle, 0));
+        s.quiet_until(kRound);
+        CHECK(s.batch(kMinBytes, 250, 1000) == After::Promote);
+        const uint64_t before = s.p.generation();
+        s.install(50);
+        CHECK(s.p.generation() == before + 1);
+        for (int k = 1; k <= 2; ++k) {
+            CHECK(s.late(16 * MB, 250, 1000, before) == After::Nothing);
+            CHECK(s.stats_are(2, 0, -1, -1, k * 16 * MB, 0));             // their bytes count, their share enters nothing
+        }
+        CHECK(s.batch(16 * MB, 125, 1000) == After::Nothing);
+        CHECK(s.stats_are(2, 0, -1, 125000, 48 * MB, 0));
+        CHECK(s.batch(16 * MB, 125, 1000) == After::Nothing);
+        CHECK(s.stats_are(2, 0, 125000, 125000, 64 * MB, 0));             // settled at 0.125, not between the two
+        for (int k = 1; k <= 20; ++k) CHECK(s.batch(kSettle, 125, 1000) == After::Nothing);
+        CHECK(s.stats_are(2, 0, 125000, 125000, 64 * MB + 20 * kSettle, 0));
+    }
+    {   // what it was without the rule (the same feed with the stale batches handed in as current ones): a level of 0.1875 that 0.125 leaves downwards
+        Sim s = settled(0.5, 1000);
+        s.quiet_until(kRound);
+        CHECK(s.batch(kMinBytes, 250, 1000) == After::Promote);
+        s.install(50);
+        CHECK(s.batch(16 * MB, 250, 1000) == After::Nothing && s.batch(16 * MB, 250, 1000) == After::Nothing);
+        CHECK(s.batch(16 * MB, 125, 1000) == After::Nothing && s.batch(16 * MB, 125, 1000) == After::Nothing);
+        CHECK(s.stats_are(2, 0, 195312, 195312, 64 * MB, 0));            // 0.25 -> 0.21875 -> 0.1953125, and 0.1953 * 0.75 - 0.01 = 0.1365 > 0.125
+        After w = After::Nothing;
+        for (int k = 1; k <= 4 && w == After::Nothing; ++k) w = s.batch(kSettle, 125, 1000);
+        CHECK(w == After::Relearn);
+    }
+    {   // a stale batch after a DROP is stale too; one of the current generation that ends while the slot is taken decides nothing but is followed
+        Sim s = settled(0.25, 1000);
+        const uint64_t before = s.p.generation();
+        s.drop();
+        CHECK(s.p.generation() == before + 1);
+        CHECK(s.late(GB, 10, 1000, before) == After::Nothing);
+        CHECK(s.stats_are(1, 1, -1, -1, GB, 0));
+        CHECK(s.late(MB, 10, 1000, s.p.generation()) == After::Nothing);
+        CHECK(s.stats_are(1, 1, -1, 10000, GB + MB, 0));
+    }
+}
+
+// which workspaces of the pool are "another call in flight" for the call that asks (tkz_api.cpp: arm_learning hands the OR of these to may_learn)
+static void other_calls() {
+    const auto other = AdaptPolicy::other_call_in_flight;                //  (busy, the asker's own, the asker's sibling, a launch sequence in flight on it)
+    CHECK(!other(false, false, false, false) && !other(false, false, false, true));      // not leased: nobody's
+    CHECK(!other(true, true, false, false) && !other(true, true, false, true));          // the workspace the asking batch runs on
+    CHECK(other(true, false, false, false) && other(true, false, false, true));          // leased by another call, whatever runs on it
+    CHECK(!other(true, false, true, false));                                              // the asker's sibling with nothing in flight: chunk 0, before chunk 1 is begun
+    CHECK(other(true, false, true, true));                                                // ... with a chunk in flight: its kernels probe the memo
 }
 
 static void window_against_last_window() {
@@ -230,15 +346,11 @@ static void window_against_last_window() {
         CHECK(s.arm(kMinBytes / 2) == Arm::Yes && s.opened);
         CHECK(s.end(kMinBytes / 2, 0, 1000) == After::WindowContinues);
         CHECK(s.stats_are(1, 0, -1, -1, kRound - kMinBytes / 2, kMinBytes / 2));
-        // (as the code stands -- no comment states it as a rule -- the round's gap counts from the window's own start once it has opened, so a window
-        //  of a LATER round that is not complete in one batch goes on only a gap later)
-        CHECK(s.arm(kMinBytes / 2) == Arm::No);
-        s.quiet_until(2 * kRound - 1);
-        CHECK(s.arm(kMinBytes / 2) == Arm::No);
-        CHECK(s.end(1, 0, 0) == After::Nothing);
+        // an open window goes on with the next batch: the round's gap is asked of the batch that OPENS one (it was asked of every batch, counted from the
+        // window's own start: a later round's window that was not complete in one batch stalled for another gap)
         CHECK(s.arm(kMinBytes / 2) == Arm::Yes && !s.opened);
         CHECK(s.end(kMinBytes / 2, 2 * e.misses, 1000) == e.want);
-        CHECK(s.stats_are(1, 0, -1, -1, 2 * kRound - kMinBytes / 2, 0));
+        CHECK(s.stats_are(1, 0, -1, -1, kRound, 0));
         if (e.want == After::Promote) continue;
         CHECK(s.arm(MB) == Arm::No);
         s.drop();
@@ -248,14 +360,38 @@ static void window_against_last_window() {
     }
 }
 
+// a round that added nothing replaced no table: the settled level stands (a round that comes due on the batches the text changes in must not take it away)
+static void empty_round_keeps_the_level() {
+    Sim s = settled(0.25, 1000);
+    CHECK(s.batch(kSettle, 125, 1000) == After::Nothing);
+    CHECK(s.stats_are(1, 0, 125000, 125000, kSettle, 0));
+    s.quiet_until(kRound);
+    CHECK(s.batch(kMinBytes, 300, 1000) == After::Promote);              // the second round's window, on other text (0.3 <= 0.25 * 1.25 + 0.01: no drift by the windows)
+    const uint64_t gen = s.p.generation();
+    s.install(0);                                                        // ... whose pieces the memo did not take: nothing to promote
+    CHECK(s.p.generation() == gen);
+    CHECK(s.stats_are(2, 0, 125000, 125000, kRound, 0));                 // the level and the distance to the last change of the tables as they were
+    CHECK(s.batch(kSettle, 300, 1000) == After::Relearn);                // 0.125 -> 0.3 in one settle distance: left, and 256 MB are long past
+    s.drop();
+    CHECK(s.stats_are(2, 1, -1, -1, 0, 0) && s.arm(MB) == Arm::YesClearMemo);
+    // with pieces added the level is taken anew, as ever
+    Sim t = settled(0.25, 1000);
+    CHECK(t.batch(kSettle, 125, 1000) == After::Nothing);
+    t.quiet_until(kRound);
+    CHECK(t.batch(kMinBytes, 300, 1000) == After::Promote);
+    t.install(1);
+    CHECK(t.stats_are(2, 0, -1, -1, 0, 0));
+    CHECK(t.batch(kSettle, 300, 1000) == After::Nothing);
+    CHECK(t.stats_are(2, 0, 300000, 300000, kSettle, 0));
+}
+
 static void memo_clear() {
     {   // a memo three quarters full is emptied before the next window
         Sim s;
         s.p.memo_read_back(3 * 1024 - 1, 4 * 1024);
         CHECK(s.p.may_learn(MB, true, true, true, true, 0, true) == Arm::Yes);
         s.p.memo_read_back(3 * 1024, 4 * 1024);
-        // (the caller's own sibling workspace counts as another call in flight, so the pipelined host path never gets past this: the
-        //  follow-up changes what tkz_api.cpp passes, or this assertion)
+        // another call in flight: never emptied under it.  (what tkz_api.cpp hands in -- other_calls)
         CHECK(s.arm(MB, true) == Arm::No);
         CHECK(s.arm(MB, false) == Arm::YesClearMemo && s.opened);
         CHECK(s.end(MB, 1, 10) == After::WindowContinues);
@@ -264,6 +400,26 @@ static void memo_clear() {
         off.p.set_adapt(0);
         off.p.memo_read_back(4 * 1024, 4 * 1024);                        // (only with TKZ_OPT_ADAPT)
         CHECK(off.arm(kMinBytes, true) == Arm::Yes);
+    }
+    {   // a pipelined host call after a drift, chunk by chunk: chunk 0 finds its sibling idle and empties the memo, chunk 1 -- chunk 0 in flight -- finds the
+        // slot taken, chunk 2 continues the window (nothing to empty any more, whatever is in flight)
+        const auto other = AdaptPolicy::other_call_in_flight;
+        Sim s = settled(0.25, 1000);
+        CHECK(s.batch(kSettle, 125, 1000) == After::Nothing);
+        for (int k = 1; k <= 2; ++k) CHECK(s.batch(kSettle, 500, 1000) == After::Nothing);
+        CHECK(s.batch(kSettle, 500, 1000) == After::Relearn);
+        s.drop();
+        CHECK(s.arm(MB, other(true, false, true, true)) == Arm::No);                      // (a chunk in flight on the sibling: not now ...)
+        CHECK(s.end(MB, 500, 1000) == After::Nothing);
+        CHECK(s.arm(MB, other(true, false, true, false)) == Arm::YesClearMemo && s.opened);      // (... the next call's chunk 0)
+        CHECK(s.p.may_learn(MB, true, true, true, true, 0, other(true, false, true, true)) == Arm::No);      // chunk 1: the slot is taken
+        CHECK(s.end(MB, 500, 1000) == After::WindowContinues);
+        CHECK(s.arm(MB, other(true, false, true, true)) == Arm::Yes && !s.opened);        // chunk 2
+        s.p.learning_abandoned();
+        // two callers: the other call's workspaces are another call's whatever they do
+        Sim t;
+        t.p.memo_read_back(4, 4);
+        CHECK(t.arm(MB, other(true, false, false, false)) == Arm::No);
     }
     {   // could not arm (the device side failed): nothing changed, the memo is still to be emptied
         Sim s;
@@ -382,7 +538,11 @@ int main() {
     round_spacing();
     no_window();
     settle_and_drift();
+    full_list();
+    stale_batches();
+    other_calls();
     window_against_last_window();
+    empty_round_keeps_the_level();
     memo_clear();
     selection();
     if (g_failed) { fprintf(stderr, "%d check(s) failed\n", g_failed); return 1; }

@@ -410,6 +410,33 @@ def check_reserve(lib, O, vocab, ovocab, pattern=N.CL100K, seed=13):
     assert enc.workspace_bytes == w1
 
 
+ADAPT_KNOWN = ["the", "and", "with", "from", "this", "that", "have", "will"]           # (vocabulary words: whole-piece hits whatever is promoted)
+
+
+def adapt_lexicon(r, n):
+    """n pronounceable non-words: pieces that miss the vocabulary, merge to a few tokens and repeat (check_adaptation's text; tests/adapt_host_cases.py)."""
+    cons, vow = "bcdfghjklmnpqrstvwxz", "aeiou"
+    return ["".join(r.choice(cons) + r.choice(vow) for _ in range(r.randint(2, 6))) + r.choice(["", "s", "ed", "ing"]) for _ in range(n)]
+
+
+def adapt_lexicons(seed=71):
+    """check_adaptation's texts A and B: 300 words each"""
+    return adapt_lexicon(random.Random(seed + 1), 300), adapt_lexicon(random.Random(seed + 2), 300)
+
+
+def adapt_batch(lex, r, nbytes=160_000, hit_share=0.5):
+    """documents of 300 / 2,000 / 9,000 bytes until there are nbytes of them (so: nbytes + up to one document): vocabulary words and words of `lex`"""
+    docs, size = [], 0
+    while size < nbytes:
+        words = []
+        n = r.choice([300, 2000, 9000])
+        while sum(map(len, words)) < n:
+            words.append(r.choice([" ", " ", "\n", ", "]) + (r.choice(ADAPT_KNOWN) if r.random() < hit_share else r.choice(lex)))
+        docs.append("".join(words).encode("utf-8"))
+        size += len(docs[-1])
+    return docs
+
+
 def check_adaptation(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, seed=71):
     """TKZ_OPT_ADAPT: the cache follows the text.  An encoder learns text A, the text drifts to B (other words: the share of pieces that miss the key
     tables rises), the encoder drops its promotions, empties the memo, learns B -- A's pieces are promoted no longer (eviction) --, and back again.
@@ -417,23 +444,8 @@ def check_adaptation(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, seed=
     throughout.  (The thresholds are megabytes; $TKZ_ADAPT_* brings them down to the size of these batches.)"""
     monkeypatch.setenv("TKZ_ADAPT_SETTLE_BYTES", "100000")
     monkeypatch.setenv("TKZ_ADAPT_MIN_BYTES", "300000")
-    cons, vow = "bcdfghjklmnpqrstvwxz", "aeiou"
-
-    def lexicon(r, n):
-        return ["".join(r.choice(cons) + r.choice(vow) for _ in range(r.randint(2, 6))) + r.choice(["", "s", "ed", "ing"]) for _ in range(n)]
-    lex_a, lex_b = lexicon(random.Random(seed + 1), 300), lexicon(random.Random(seed + 2), 300)
-    known = ["the", "and", "with", "from", "this", "that", "have", "will"]           # (vocabulary words: whole-piece hits whatever is promoted)
-
-    def batch(lex, r, nbytes=160_000, hit_share=0.5):
-        docs, size = [], 0
-        while size < nbytes:
-            words = []
-            n = r.choice([300, 2000, 9000])
-            while sum(map(len, words)) < n:
-                words.append(r.choice([" ", " ", "\n", ", "]) + (r.choice(known) if r.random() < hit_share else r.choice(lex)))
-            docs.append("".join(words).encode("utf-8"))
-            size += len(docs[-1])
-        return docs
+    lex_a, lex_b = adapt_lexicons(seed)
+    batch = adapt_batch
     oenc = O.Encoder(ovocab, pattern)
     enc = N.Encoder(vocab, pattern)
     enc.set_option(N.OPT_PROMOTE_MIN_BYTES, 100_000)
@@ -528,15 +540,11 @@ def check_adaptation(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, seed=
     assert enc3.adapt_stats()["promotions"] == 0 and enc3.adapt_stats()["promoted_pieces"] == 0
 
 
-def check_memo_refresh(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, seed=77):
-    """The memo does not evict -- an entry is never replaced --, so text with many one-off pieces fills it and whatever the text turns into finds it closed.
-    TKZ_OPT_ADAPT (round 6): a learning round that reads the memo back three quarters full has it emptied at the start of the next learning window (the
-    reference's LRUCache evicts, LRUCache.cs:79-88).  A memo of 4,096 slots, text A with 6,000 different missed pieces, then text B with 250 that repeat: with
-    the rule B's pieces are answered by the memo (or promoted), without it (TKZ_OPT_ADAPT 0) nearly every occurrence is merged again.  Ids = the oracle's throughout."""
-    monkeypatch.setenv("TKZ_MEMO_SLOTS_LOG2", "12")
-    monkeypatch.setenv("TKZ_ADAPT_ROUND_BYTES", "300000")
-    monkeypatch.setenv("TKZ_ADAPT_SETTLE_BYTES", "100000")
-    monkeypatch.setenv("TKZ_ADAPT_MIN_BYTES", "300000")
+def memo_refresh_arm(lib, O, vocab, oenc, adapt, pattern=N.CL100K, seed=77, promotions_asserted=True):
+    """One arm of check_memo_refresh (TKZ_OPT_ADAPT `adapt`) on a fresh encoder: 6 batches of text A -- 6,000 different missed pieces: the memo of 4,096 slots
+    fills in the first --, 10 of text B -- 250 that repeat --, then one probe batch of B with nothing automatic: -> the pieces of it that were merged.
+    ($TKZ_MEMO_SLOTS_LOG2 = 12 and the $TKZ_ADAPT_* of check_memo_refresh are the caller's to set.  promotions_asserted: also the rounds text A should have seen --
+    where a call is one batch; tests/adapt_host_cases.py runs the arms through the chunk pipeline, where without TKZ_OPT_ADAPT no chunk is a window.)"""
     cons, vow = "bcdfghjklmnpqrstvwxz", "aeiou"
     r0 = random.Random(seed)
 
@@ -544,7 +552,6 @@ def check_memo_refresh(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, see
         return "".join(r.choice(cons) + r.choice(vow) for _ in range(r.randint(3, 5))) + r.choice(["", "s", "ed"])
     one_off = [word(r0) for _ in range(6000)]
     lex_b = [word(random.Random(seed + 1)) + "q" for _ in range(250)]
-    oenc = O.Encoder(ovocab, pattern)
 
     def batch(lex, r, nbytes=170_000):
         docs, size = [], 0
@@ -555,30 +562,42 @@ def check_memo_refresh(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, see
             docs.append("".join(words).encode("utf-8"))
             size += len(docs[-1])
         return docs
-    merged = {}
-    for adapt in (1, 0):
-        enc = N.Encoder(vocab, pattern)
-        assert enc.memo_slots == 4096
-        enc.set_option(N.OPT_PROMOTE_MIN_BYTES, 100_000)
-        enc.set_option(N.OPT_ADAPT, adapt)
-        rr = random.Random(seed + 5)
+    enc = N.Encoder(vocab, pattern)
+    assert enc.memo_slots == 4096
+    enc.set_option(N.OPT_PROMOTE_MIN_BYTES, 100_000)
+    enc.set_option(N.OPT_ADAPT, adapt)
+    rr = random.Random(seed + 5)
 
-        def run(docs):
-            data, offs = pack(docs)
-            ids, ooff = enc.encode_batch(data, offs)
-            e, eo = oracle_encode_docs(oenc, docs)
-            assert ids.tolist() == e and ooff.tolist() == eo
-            return enc.adapt_stats()
-        for _ in range(6):                                 # text A: the memo fills in the first batch; two rounds (the second one starts on an emptied memo and fills it again)
-            st = run(batch(one_off, rr))
+    def run(docs):
+        data, offs = pack(docs)
+        ids, ooff = enc.encode_batch(data, offs)
+        e, eo = oracle_encode_docs(oenc, docs)
+        assert ids.tolist() == e and ooff.tolist() == eo
+        return enc.adapt_stats()
+    for _ in range(6):                                 # text A: the memo fills in the first batch; two rounds (the second one starts on an emptied memo and fills it again)
+        st = run(batch(one_off, rr))
+    if promotions_asserted:
         assert st["promotions"] >= (2 if adapt else 1), st
-        for _ in range(10):                                # text B: with TKZ_OPT_ADAPT its next window empties the memo once more -- and B's pieces get in
-            st = run(batch(lex_b, rr))
-        enc.set_option(N.OPT_PROMOTE, 0)
-        enc.set_option(N.OPT_PIECE_STATS, 1)
-        enc.piece_stats(reset=True)
-        run(batch(lex_b, random.Random(seed + 9)))
-        merged[adapt] = enc.piece_stats(reset=True)["merged_short"]
+    for _ in range(10):                                # text B: with TKZ_OPT_ADAPT its next window empties the memo once more -- and B's pieces get in
+        st = run(batch(lex_b, rr))
+    enc.set_option(N.OPT_PROMOTE, 0)
+    enc.set_option(N.OPT_PIECE_STATS, 1)
+    enc.piece_stats(reset=True)
+    run(batch(lex_b, random.Random(seed + 9)))
+    return enc.piece_stats(reset=True)["merged_short"]
+
+
+def check_memo_refresh(lib, O, vocab, ovocab, monkeypatch, pattern=N.CL100K, seed=77):
+    """The memo does not evict -- an entry is never replaced --, so text with many one-off pieces fills it and whatever the text turns into finds it closed.
+    TKZ_OPT_ADAPT (round 6): a learning round that reads the memo back three quarters full has it emptied at the start of the next learning window (the
+    reference's LRUCache evicts, LRUCache.cs:79-88).  A memo of 4,096 slots, text A with 6,000 different missed pieces, then text B with 250 that repeat: with
+    the rule B's pieces are answered by the memo (or promoted), without it (TKZ_OPT_ADAPT 0) nearly every occurrence is merged again.  Ids = the oracle's throughout."""
+    monkeypatch.setenv("TKZ_MEMO_SLOTS_LOG2", "12")
+    monkeypatch.setenv("TKZ_ADAPT_ROUND_BYTES", "300000")
+    monkeypatch.setenv("TKZ_ADAPT_SETTLE_BYTES", "100000")
+    monkeypatch.setenv("TKZ_ADAPT_MIN_BYTES", "300000")
+    oenc = O.Encoder(ovocab, pattern)
+    merged = {adapt: memo_refresh_arm(lib, O, vocab, oenc, adapt, pattern, seed) for adapt in (1, 0)}
     print("merged_short with / without the rule:", merged)
     assert merged[1] * 2 < merged[0], merged
 

@@ -40,16 +40,25 @@ public:
     // batch, or -- TKZ_OPT_ADAPT -- as many smaller ones as it takes (a caller whose batches are 1 MB learns too).
     // (TKZ_OPT_ADAPT: the rounds go on -- a gigabyte after the first window began, then two, four, eight ... gigabytes after the one before: text that
     //  changed without moving the miss share, or right behind a promotion, is still learnt, a round costs one batch that counts hits and ~50 ms of a
-    //  host thread; pieces are only ever ADDED by a round -- what empties the list is a drift, or the list reaching its cap: batch_ended)
+    //  host thread; pieces are only ever ADDED by a round -- what empties the list is a drift, or later rounds filling it to its cap: batch_ended)
+    // (The gap to the next round is asked of the batch that OPENS a window.  A window that is open goes on with the next batch that may learn: asked of every
+    //  batch it counted from the window's own start, so a later round's window that was not complete in one batch -- a chunk of the host pipeline smaller than
+    //  the window -- stalled for another gap, and every round took two.)
     // Changes nothing: the caller readies the device side (counters, log, the memo emptied) and then calls window_armed, or -- that failed -- nothing at all.
     Arm may_learn(int64_t total, bool first_attempt, bool may_learn, bool memo_on, bool ranks_fit_promo_code, size_t n_promoted, bool other_calls_in_flight) const {
         const int64_t round_gap = round_bytes_ << std::min(std::max(rounds_ - 1, 0), 20);
         if (!(first_attempt && may_learn && mode_ == 1 && !learning_ && (adapt_ || rounds_ < kPromoAutoRounds) && memo_on && ranks_fit_promo_code &&
-              (adapt_ || total >= min_bytes_) && n_promoted < cap_ && (rounds_ == 0 || bytes_seen_ - bytes_at_promo_ >= round_gap))) return Arm::No;
+              (adapt_ || total >= min_bytes_) && n_promoted < cap_ && (rounds_ == 0 || learn_bytes_ > 0 || bytes_seen_ - bytes_at_promo_ >= round_gap))) return Arm::No;
         // The memo is emptied for a window that follows a drift -- it is full of the old text's pieces and takes no new ones --, and that only while
         // no OTHER call is in flight: an entry never changes once it is valid (tkz_tables.h), which is what makes a hit exact
         if (!memo_clear_pending_) return Arm::Yes;
         return other_calls_in_flight ? Arm::No : Arm::YesClearMemo;
+    }
+    // ... and what counts as another call in flight for the call that asks: a workspace of the pool that is leased (`busy`), unless it is the asking call's own
+    // -- the one the batch runs on, or the SIBLING a pipelined host call leases for its odd chunks while that has no launch sequence in flight (so at chunk
+    // 0, before chunk 1 is begun: tkz_api.cpp, HostPipeline).  With a chunk in flight on the sibling its kernels are probing the memo: never emptied then.
+    static bool other_call_in_flight(bool busy, bool askers_own, bool askers_sibling, bool sequence_in_flight) {
+        return busy && !askers_own && !(askers_sibling && !sequence_in_flight);
     }
     // ... it does: the learning slot is taken.  Returns whether the batch OPENS a window (the hit counters and the log start from zero)
     // (the gigabyte to the second round counts from the START of the first learning window: a job of 5 GB batches learns in its first two)
@@ -66,9 +75,14 @@ public:
     // A batch of `total` bytes has ended; `misses` of its `pieces` regex matches were not found in the key tables as a whole (vocabulary + promoted pieces).
     // Promote: the window is complete, install what it learnt (then promotion_installed).  Relearn: drop every promotion (then promotions_dropped).  The slot
     // stays taken through both: nothing learns meanwhile.  WindowContinues: the slot is free, the window goes on with the next batch.
-    After batch_ended(int64_t total, double misses, double pieces, bool was_learning, size_t n_promoted) {
+    // `tables_generation`: generation() as it was when the batch took its copy of the tables.  A batch that ran on tables OLDER than the last install -- the
+    // pipelined host path keeps two launch sequences enqueued ahead, and an install lands on a thread behind the batch that completed the window -- has the miss
+    // share of the tables before: its bytes count, its share does not enter the average the level settles from (it settled too high, and the first batches
+    // on the new tables then "left" it downwards: a re-learn on unchanged text).
+    After batch_ended(int64_t total, double misses, double pieces, bool was_learning, size_t n_promoted, uint64_t tables_generation) {
         bytes_seen_ += total;
         if (!was_learning) {
+            if (tables_generation != generation_) return After::Nothing;
             if (!left_settled_level(total, misses, pieces, n_promoted)) return After::Nothing;
             learning_ = true;
             return After::Relearn;
@@ -92,12 +106,17 @@ public:
     // the window's promotion is in the key tables (or failed: the tables are as they were): `added` pieces on top of `held_before`
     void promotion_installed(int64_t added, size_t held_before) {
         learning_ = false; ++rounds_; ++n_promotions_;
+        if (added > 0 && ++fills_ == 1) first_fill_ = held_before + (size_t)added;
         // A round that found much it did not know -- more than a tenth of what the list held -- is a young encoder, or text that CHANGED without the miss
         // share having had a settled level to leave (the change fell between two installs): the next round then follows a gigabyte later, not
         // 2^rounds gigabytes.  (bench.py's drift leg, synthetic -> real text: the steps beyond 2 GB ran at 0.81 of an encoder that only ever saw
         // the real text, whose second round comes after 1 GB while this one's was 4 GB away.)
         if (adapt_ && rounds_ > 1 && (size_t)added * 10 > held_before) rounds_ = 1;
         // (not start_over: the rounds and the windows go on, and window_miss_ is what the level that settles next is compared with)
+        // A round that added NOTHING replaced no table: the settled level stands, and so does the distance to the last change of the tables.  (Taking the level
+        // away let a drift go unseen: a round that comes due on the very batches the text changes in -- a memo full of the old text's pieces, nothing new in
+        // it to promote -- and the level settled again on the new text, with the old text's promotions and the old text's memo.)
+        if (added <= 0) { window_valid_ = false; return; }
         bytes_at_install_ = bytes_seen_; ew_valid_ = base_valid_ = false;
     }
     // the promotions were dropped for a relearn: the next window starts from nothing, on an empty memo
@@ -110,13 +129,17 @@ public:
     // (tools/adapt_probe.py ... 1: source text behind 3 GB of synthetic text, the change inside the first promotion's build: 95 GB/s and 2 k new pieces a round
     //  with the full memo, against a fresh encoder's 118 and 9 k.)
     void memo_read_back(uint64_t valid_slots, uint64_t slots) { if (adapt_ && valid_slots * 4 >= slots * 3) memo_clear_pending_ = true; }
+    // The key tables on the device were replaced (an install, a drop; with the encoder's mutex held, together with the replacement): batches that took their copy
+    // before ran on other tables (batch_ended)
+    uint64_t generation() const { return generation_; }
+    void tables_replaced() { ++generation_; }
 
 private:
     // the tests' handle on the three distances: their batches are kilobytes
     static int64_t env_bytes(const char* name, int64_t dflt) { const char* v = getenv(name); return v && atoll(v) > 0 ? (int64_t)atoll(v) : dflt; }
 
     void start_over() {
-        rounds_ = 0; learn_bytes_ = 0; bytes_at_promo_ = bytes_at_install_ = bytes_seen_;
+        rounds_ = 0; fills_ = 0; learn_bytes_ = 0; bytes_at_promo_ = bytes_at_install_ = bytes_seen_;
         ew_valid_ = base_valid_ = window_valid_ = last_window_valid_ = false; win_miss_ = win_pieces_ = 0;
     }
     // TKZ_OPT_ADAPT: a batch that was not a learning batch has ended.  True when the encoder should learn again: the share of pieces that missed, averaged over
@@ -143,7 +166,11 @@ private:
             return drifted;
         }
         if (since < min_settled_bytes_) return false;
-        if (n_promoted * 10 >= cap_ * 9) return true;     // the list is (nearly) full of what the rounds have added: start over from the text as it is now
+        // The list is (nearly) full of what SUCCESSIVE rounds have added: start over from the text as it is now.  Not a list that one window filled: that is
+        // the text's hot pieces as they are now -- dropping it learns the same list again, a window at the speed of an encoder without promotions and two
+        // table builds every adapt_min_bytes, for ever (may_learn opens no further round on a full list; a drift is still seen by the miss share, below).
+        // Nor one that a window brought beyond 90 % and a later round added a few pieces to.
+        if (fills_ >= 2 && first_fill_ * 10 < cap_ * 9 && n_promoted * 10 >= cap_ * 9) return true;
         return ew_miss_ > base_miss_ * 1.25 + 0.01 || ew_miss_ < base_miss_ * 0.75 - 0.01;
     }
 
@@ -157,6 +184,9 @@ private:
     int64_t min_settled_bytes_ = env_bytes("TKZ_ADAPT_MIN_BYTES", int64_t(256) << 20);
 
     int rounds_ = 0;                       // automatic promotions since the list was last empty (back to 1 after a round that added much)
+    int fills_ = 0;                        // ... those of them that added pieces (never set back), and what the list held after the first of them: a list
+    size_t first_fill_ = 0;                //     that LATER ROUNDS have filled is one of two fills and more whose first left it below 90 % of the cap
+    uint64_t generation_ = 0;              // replacements of the key tables on the device (tables_replaced)
     bool learning_ = false;                // the learning slot: a batch that counts memo hits is in flight, or what it learnt is being installed / dropped
     int64_t bytes_seen_ = 0;               // bytes the batch path has encoded
     int64_t bytes_at_promo_ = 0;           // ... when the last window opened

@@ -245,6 +245,11 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     bool place128 = false;                 // a recent batch of this workspace had more than a fifth of its sub-tiles above 64 list entries: k_place<128>
     int low_lists = 0, low_place = 0;      // consecutive batches that would have done with shorter lists / with k_place<64> (hysteresis: kLowBatches)
     bool learning = false;                 // this workspace's batch counts memo hits per slot (TkzTables::memo_hits): the encoder promotes the hottest entries when it ends
+    uint64_t tables_gen = 0;               // AdaptPolicy::generation() when this workspace's batch took its copy of the tables (arm_learning; handed to batch_ended)
+    // a pipelined host call runs on TWO leased workspaces: each names the other for the length of the call, and says whether a chunk's launch sequence is in
+    // flight on it (HostPipeline; written and read by the call's own thread only -- arm_learning asks it of the asking workspace's sibling and of no other)
+    Workspace* sibling = nullptr;
+    bool chunk_in_flight = false;
     CounterBlock* h_counters = nullptr;   // pinned
     // the single-launch path for small batches (k_small): input, output and status in ONE page-locked block the device reads and writes directly
     uint8_t* h_small = nullptr;
@@ -654,6 +659,7 @@ void install_key_tables(tkz_encoder* e, KeyTablesImage& img, bool retire) {
     e->T.mid_slots = reinterpret_cast<const TkzMidSlot*>(e->t_short.as<char>() + img.short_bytes); e->T.mid_ns = (uint32_t)img.n_mid_slots; e->T.mid_seed = img.mseed;
     e->T.promo = img.n_promo ? e->t_promo.as<uint4>() : nullptr; e->T.promo_n = (uint32_t)img.n_promo;
     e->short_slots_n = (uint32_t)img.n_short_slots; e->mid_slots_n = (uint32_t)img.n_mid_slots;
+    e->policy.tables_replaced();        // (batches that took their copy of e->T before this ran on the tables before: AdaptPolicy::batch_ended)
 }
 
 // waits for the automatic promotion in the background, if any (never with e->mu held: the promotion takes it)
@@ -845,8 +851,10 @@ tkz_status arm_learning(tkz_encoder* e, Workspace* ws, const BatchCall& c, bool 
     const hipStream_t stream = c.stream;
     {
         std::lock_guard<std::mutex> lock(e->mu);
+        // (another call: a leased workspace that is not this call's -- its own sibling counts only while a chunk is in flight on it; that mark is the owning
+        //  call's, written without the lock: read for the sibling and for no other workspace)
         bool others = false;
-        for (Workspace* w : e->pool) if (w != ws && w->busy) others = true;
+        for (Workspace* w : e->pool) if (AdaptPolicy::other_call_in_flight(w->busy, w == ws, w == ws->sibling, w == ws->sibling && w->chunk_in_flight)) others = true;
         const AdaptPolicy::Arm arm = e->policy.may_learn(total, first && !ws->learning, c.may_learn(), e->T.memo_n != 0, e->T.max_rank < (int32_t)kPromoFlag, e->promo_items.size(), others);
         if (arm != AdaptPolicy::Arm::No && e->t_memo_hits.ensure((size_t)e->memo_slots * 4, &e->bytes_allocated) == hipSuccess &&
             e->t_long_log.ensure((size_t)kLongLogCap * kLongLogDwords * 4 + 64, &e->bytes_allocated) == hipSuccess) {
@@ -858,6 +866,7 @@ tkz_status arm_learning(tkz_encoder* e, Workspace* ws, const BatchCall& c, bool 
             }
         }
         *T = e->T;
+        ws->tables_gen = e->policy.generation();
     }
     if (ws->learning) {
         T->memo_hits = e->t_memo_hits.as<uint32_t>();
@@ -1267,7 +1276,7 @@ void after_batch(tkz_encoder* e, Workspace* ws, int64_t total) {
     tkz::AdaptPolicy::After what;
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        what = e->policy.batch_ended(total, (double)(c.miss_short + c.miss_long), (double)c.npieces, ws->learning, e->promo_items.size());
+        what = e->policy.batch_ended(total, (double)(c.miss_short + c.miss_long), (double)c.npieces, ws->learning, e->promo_items.size(), ws->tables_gen);
         ws->learning = false;
     }
     const bool promote = what == tkz::AdaptPolicy::After::Promote;
@@ -1663,6 +1672,8 @@ struct HostPipeline {
     std::string first_msg;
 
     tkz_status note(tkz_status s) { if (first_err == TKZ_OK) { first_err = s; first_msg = g_err; } return s; }
+    // (the two workspaces forget each other before the second one's lease ends: the members are destroyed after this body)
+    ~HostPipeline() { for (Workspace* w : W) { w->sibling = nullptr; w->chunk_in_flight = false; } }
 
     // streams, the second workspace, staging for the largest chunk, the copy engine's signals.  Nothing is in flight yet: a failure here is returned as it is
     tkz_status reserve_staging() {
@@ -1672,6 +1683,8 @@ struct HostPipeline {
         if (nchunks > 1) {
             lease_b.reset(new Lease(e));
             W[1] = lease_b->ws;
+            // this call's own: a learning window that needs the memo emptied may open while nothing is in flight on the sibling (arm_learning) -- chunk 0
+            W[0]->sibling = W[1]; W[1]->sibling = W[0];
             if (!W[1]->st_compute) HIP_TRY(hipStreamCreate(&W[1]->st_compute));
         }
         for (int q = 0; q < (nchunks > 1 ? 2 : 1); ++q) {
@@ -1751,10 +1764,14 @@ struct HostPipeline {
         fl[q] = c.on_device(cb, co, nd, cbytes, dst_ids, over ? 0 : std::min<int64_t>(c.out_cap, cbytes), dst_offs, w->st_compute);
         if (p.ingest_in) fl[q].ingest = &ingest_src;
         if (with_repl) fl[q].d_repl = ws->u16[q].repl.as<uint64_t>();
+        // (in flight from the moment anything of it may be enqueued -- arm_learning of the OTHER workspace's next chunk asks -- until end_chunk has drained it)
+        w->chunk_in_flight = phase == kCallBegin;
         return encode_device(e, w, fl[q], phase, tokens);
     }
     tkz_status end_chunk(int64_t k, int64_t* tokens) {          // (returns when the chunk's stream has drained)
-        return encode_device(e, W[k & 1], fl[k & 1], kCallEnd, tokens);
+        const tkz_status st = encode_device(e, W[k & 1], fl[k & 1], kCallEnd, tokens);
+        W[k & 1]->chunk_in_flight = false;
+        return st;
     }
     // (an engine that refuses a copy is not asked again: that copy and the rest of the call go through the runtime)
     bool by_engine(void* dst, const void* src, size_t nb, tkz::SdmaSignal sg, bool* pending) {
@@ -1772,10 +1789,13 @@ struct HostPipeline {
     tkz_status download(int64_t k, int64_t tokens) {
         const int o = (int)(k % p.nout);
         const int64_t d0 = p.cut[(size_t)k], nd = p.cut[(size_t)k + 1] - d0;
-        bool ids_sent = tokens == 0 || c.count_only, offs_sent = false;      // (a count call: only the offsets travel back)
-        const size_t nb_ids = (size_t)tokens * 4, nb_offs = (size_t)(nd + 1) * 8;
+        // ONE writer for every entry of the caller's offsets: a chunk brings back the entry of each of its documents, nd of them, and not the one behind --
+        // that is the next chunk's first (or out_offsets[n_docs]), and run() sets it from tok_base.  (Two chunks writing it relied on the later copy landing
+        // last, which nothing orders once one goes by copy engine and the other through the runtime.)
+        bool ids_sent = tokens == 0 || c.count_only, offs_sent = nd == 0;      // (a count call: only the offsets travel back; a chunk without documents: nothing does)
+        const size_t nb_ids = (size_t)tokens * 4, nb_offs = (size_t)nd * 8;
         if (!ids_sent) ids_sent = by_engine(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, ws->sig_out[o], &sig_pending[o]);
-        offs_sent = by_engine(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
+        if (!offs_sent) offs_sent = by_engine(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, ws->sig_outoffs[o], &sigo_pending[o]);
         if (!ids_sent || !offs_sent) {
             if (!ids_sent) PIPELINE_TRY(hipMemcpyAsync(c.out_ids + tok_base[(size_t)k], ws->s_out[o].p, nb_ids, hipMemcpyDeviceToHost, ws->st_out));
             if (!offs_sent) PIPELINE_TRY(hipMemcpyAsync(c.out_offsets + d0, ws->s_outoffs[o].p, nb_offs, hipMemcpyDeviceToHost, ws->st_out));
@@ -1839,8 +1859,8 @@ struct HostPipeline {
         if (first_err != TKZ_OK) return fail(first_err, first_msg);
         if (c.needed) *c.needed = tok_base[(size_t)nchunks];
         if (over) return fail(TKZ_E_CAPACITY, "output capacity too small");
-        // the offsets came back relative to their chunk: add the chunk's token base (chunk 0 needs nothing; the shared boundary entry
-        // of two chunks was written by the later one as 0 and gets that chunk's base, which is what the earlier chunk's last entry was)
+        // the offsets came back relative to their chunk: add the chunk's token base (chunk 0 needs nothing; the first entry of a later chunk came
+        // back as 0 and gets that chunk's base -- the total of the chunks before; no chunk brought the entry behind its last document: download)
         for (int64_t k = 1; k < nchunks; ++k) {
             const int64_t tb = tok_base[(size_t)k];
             for (int64_t d = p.cut[(size_t)k]; d < p.cut[(size_t)k + 1]; ++d) c.out_offsets[d] += tb;
