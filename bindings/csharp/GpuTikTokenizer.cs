@@ -80,6 +80,12 @@ namespace Microsoft.DeepDev
                                                                                           int bosId, int eosId, long rowLen, int padId, int* outIds, long outCap, long* outOffsets,
                                                                                           int* pos, long* segStarts, long segCap, out long totalTokens, out long neededIds, out long neededSegs);
         [DllImport(Lib)] internal static extern void tkz_encoder_packed_calls(IntPtr encoder, out long calls);
+        // padded rows: Encode's ids cut to a maximum length, framed by bos / eos ids, a row a text padded to a common width, with the mask, pos and lens (include/tkz.h, "Padded rows")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_padded_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                          int bosId, int eosId, long maxLen, int cutSide, int padSide, int padId, long padMultiple,
+                                                                                          int* outIds, long outCap, byte* mask, int* pos, int* lens, long* outOffsets,
+                                                                                          out long totalTokens, out long width, out long nCut);
+        [DllImport(Lib)] internal static extern void tkz_encoder_padded_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -575,6 +581,51 @@ namespace Microsoft.DeepDev
             var segStarts = new long[neededSegs + 1];
             Array.Copy(seg, segStarts, neededSegs + 1);
             return (outIds, outPos, segStarts, offsets);
+        }
+
+        /// <summary>Every text's ids -- Encode's for the same arguments -- cut to <paramref name="maxLength"/> less the framing (<paramref name="truncateLeft"/>: the tail
+        /// is kept, else the head), with <paramref name="bos"/> in front and <paramref name="eos"/> behind what is kept (null: none; any id of 0 or more is taken as it
+        /// is), a row a text, padded with <paramref name="pad"/> (on the left with <paramref name="padLeft"/>) to the longest row rounded up to
+        /// <paramref name="padToMultipleOf"/> -- at most maxLength; 0: to maxLength itself --, in ONE call (tkz_encode_batch_padded_utf16; include/tkz.h states the rule).
+        /// Ids, Mask (1 on content) and Pos (the index inside the content) are texts x width; Lens the content lengths.  The cut is a plain cut of the id list, not
+        /// EncodeTrimSuffix's whole-item cut.  A registered set the device path does not hold is NotImplementedException (-7): there is no host path.</summary>
+        public unsafe (int[,] Ids, byte[,] Mask, int[,] Pos, int[] Lens) EncodeBatchPadded(IReadOnlyList<string> texts, int maxLength, IReadOnlyCollection<string>? allowedSpecial = null,
+                                                                                          int? bos = null, int? eos = null, int pad = 0, bool truncateLeft = false, bool padLeft = false,
+                                                                                          int padToMultipleOf = 1)
+        {
+            int framing = (bos.HasValue ? 1 : 0) + (eos.HasValue ? 1 : 0);
+            if (maxLength < Math.Max(1, framing)) throw new ArgumentOutOfRangeException(nameof(maxLength));
+            if (bos < 0 || eos < 0) throw new ArgumentOutOfRangeException(bos < 0 ? nameof(bos) : nameof(eos));
+            if (padToMultipleOf < 0) throw new ArgumentOutOfRangeException(nameof(padToMultipleOf));
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = (long)texts.Count * maxLength;                                            // the size that always suffices (tkz.h): a row of maxLength a text
+            var ids = new int[Math.Max(1, cap)];
+            var pos = new int[Math.Max(1, cap)];
+            var mask = new byte[Math.Max(1, cap)];
+            var lens = new int[Math.Max(1, texts.Count)];
+            int st;
+            long width;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (int* pp = pos) fixed (byte* pm = mask) fixed (int* pl = lens)
+                st = Tkz.tkz_encode_batch_padded_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, bos ?? -1, eos ?? -1, maxLength,
+                                                       truncateLeft ? 1 : 0, padLeft ? 1 : 0, pad, padToMultipleOf, pi, cap, pm, pp, pl, null, out _, out width, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            int w = checked((int)width);
+            var outIds = new int[texts.Count, w];
+            var outPos = new int[texts.Count, w];
+            var outMask = new byte[texts.Count, w];
+            Buffer.BlockCopy(ids, 0, outIds, 0, checked(texts.Count * w * sizeof(int)));
+            Buffer.BlockCopy(pos, 0, outPos, 0, checked(texts.Count * w * sizeof(int)));
+            Buffer.BlockCopy(mask, 0, outMask, 0, checked(texts.Count * w));
+            var outLens = new int[texts.Count];
+            Array.Copy(lens, outLens, texts.Count);
+            return (outIds, outMask, outPos, outLens);
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

@@ -533,6 +533,64 @@ tkz_status tkz_encode_batch_packed_utf16(tkz_encoder* e, const uint16_t* units, 
 /* informational: successful calls of the packed entries */
 void tkz_encoder_packed_calls(const tkz_encoder* e, int64_t* calls);
 
+/* ---- Padded rows: one row a document, cut to a maximum length, framed, padded to a common width, with the attention mask, in ONE call ----
+ * The inference half of what follows an encode call (packed rows above are the training half): tokenizer(texts, truncation=True, padding=True, max_length=L,
+ * pad_to_multiple_of=M) -- what a prefill, embedding or reranker batch and an evaluation harness need before the model can run.
+ * THE RULE.  Let ids / O[0..n_docs] be EXACTLY what the matching encode entry writes for the same arguments -- tkz_encode_batch_special_* when n_allowed > 0 and
+ * literals are registered, the plain entry otherwise.  n[d] = O[d + 1] - O[d].
+ *   Parameters.  bos_id, eos_id: as in the packed entries: -1 means none, any value >= 0 is taken as it is, < -1 is TKZ_E_ARG; fb = bos_id >= 0, fe = eos_id >= 0,
+ *     f = fb + fe.  max_len = L with max(1, f) <= L <= 2^31 - 1, anything else is TKZ_E_ARG.  cut_side: a tkz_trim_side -- TKZ_TRIM_SUFFIX cuts the end and keeps
+ *     the head, TKZ_TRIM_PREFIX cuts the front and keeps the tail.  pad_side: TKZ_PAD_RIGHT or TKZ_PAD_LEFT.  Any other side value is TKZ_E_ARG.  pad_id: any
+ *     int32.  pad_multiple = M with 0 <= M <= 2^31 - 1, anything else is TKZ_E_ARG.
+ *   Cut (token-granular).  k[d] = min(n[d], L - f) ids are kept: ids[O[d] .. O[d] + k[d]) for the suffix cut, ids[O[d + 1] - k[d] .. O[d + 1]) for the prefix
+ *     cut.  The framing is added AFTER the cut, so it always survives: len[d] = k[d] + f, and an empty document is its framing alone.  n_cut is the number of
+ *     documents with n[d] > L - f.  This is a plain cut of the id list, as truncation=True makes it; it is NOT the reference's whole-item cut
+ *     (EncodeTrimSuffix / EncodeTrimPrefix keep or drop a pre-tokenizer piece as a whole): tkz_encode_batch_trim_* remains for that.
+ *   Width.  M == 0: W = L, a fixed width.  M >= 1: W = min(L, ceil(max_d len[d] / M) * M).  W = 0 when n_docs == 0 or every len[d] is 0; nothing is written then.
+ *   Rows.  Row d is out[d * W .. (d + 1) * W).  Its content is [bos_id] kept [eos_id], len[d] entries: at columns [0, len[d]) with pad_id behind it for
+ *     TKZ_PAD_RIGHT, at columns [W - len[d], W) with pad_id in front of it for TKZ_PAD_LEFT.  mask (uint8; it views as bool): 1 on content, 0 on padding.
+ *     pos (int32): the index inside the content, 0 .. len[d] - 1, and 0 on padding.  lens[d] = len[d] (int32).  out_offsets[d] = O[d] (int64, n_docs + 1
+ *     entries): the UNCUT offsets, so n[d] - (lens[d] - f) is what was cut.
+ *   Scalars.  *total_tokens = O[n_docs], the uncut total -- which is also what the encoder's {n_docs, n_bytes, n_tokens} block receives --, *width = W, *n_cut.
+ *   Example: documents [a1 a2 a3 a4 a5], [], [c1 c2]; bos = B, no eos, L = 4, M = 1, pad P.  W = 4, lens = 4, 1, 3, n_cut = 1.
+ *     suffix cut, right pad: rows B a1 a2 a3 / B P P P / B c1 c2 P;  pos 0 1 2 3 / 0 0 0 0 / 0 1 2 0;  mask 1111 / 1000 / 1110
+ *     prefix cut, left pad:  rows B a3 a4 a5 / P P P B / P B c1 c2;  pos 0 1 2 3 / 0 0 0 0 / 0 0 1 2;  mask 1111 / 0001 / 0111
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap < n_docs * W.  *width, *total_tokens and *n_cut then hold the required figures, all from the one call; nothing is
+ * promised in the outputs.  n_docs * L entries ALWAYS suffice.
+ *   tkz_encode_batch_padded_device: device buffers.  d_mask (out_cap bytes), d_pos (out_cap entries) and d_out_offsets (n_docs + 1) may each be NULL; d_out_ids
+ *     (out_cap entries), d_lens (n_docs entries), total_tokens, width and n_cut may not (TKZ_E_ARG).  Everything else -- allowed / n_allowed, TKZ_E_UNSUPPORTED,
+ *     tkz_encoder_special_stats, device-side errors, retries of an attempt inside the call, workspace growth, returning after the stream has drained -- as
+ *     tkz_encode_batch_packed_device.  Nothing is read outside d_bytes[0, total_bytes), nothing is written at or behind n_docs * W (ids, mask, pos), n_docs (lens)
+ *     or n_docs + 1 (offsets); an attempt that is run again inside the call has written nothing into the caller's buffers.  An empty batch (n_docs == 0) is
+ *     TKZ_OK: out_offsets[0] cleared on the stream, all three scalars 0.
+ *     The launch sequence is the PLAIN document-granular one of tkz_encode_batch_device -- no piece arrays, no wait for a piece count.  The uncut ids and offsets
+ *     stay in the workspace (4 bytes per input byte, 8 per document), as a framed packed call keeps them.  The stage: k_pad_lens (a lane a document: lens, the
+ *     first kept id of every document -- 8 bytes per document of workspace --, and the longest row and the cut documents of every workgroup), then k_pad_write
+ *     (the width from those partials, the capacity check on the device, the rows by output position in tiles of 1,024).  The host does not wait between the two.
+ *   tkz_encode_batch_padded_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as
+ *     tkz_encode_batch_packed_utf8: no chunk pipeline, no single-launch route.  mask, pos and out_offsets may be NULL.  Only the rows, the mask, pos, lens and the
+ *     offsets are downloaded, NEVER the uncut ids: a batch cut to L moves n_docs * W ids over PCIe where tkz_encode_batch_utf8 moves total_tokens -- on long
+ *     documents that download is what bounds the host entries.
+ *   tkz_encode_batch_padded_utf16: code units in, transcoded on the device as tkz_encode_batch_packed_utf16; unit_offsets in code units.
+ * There is no item-granular cut in front of the rows (trim first), no maximum per document, no sorting or bucketing by length, no _begin / _end form, no chunk
+ * pipeline, no single-text form (padding one text is a slice) and no int64 or bool mask. */
+typedef enum tkz_pad_side { TKZ_PAD_RIGHT = 0, TKZ_PAD_LEFT = 1 } tkz_pad_side;
+tkz_status tkz_encode_batch_padded_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                          int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* d_out_ids, int64_t out_cap, uint8_t* d_mask,
+                                          int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets, void* hip_stream, int64_t* total_tokens, int64_t* width,
+                                          int64_t* n_cut);
+tkz_status tkz_encode_batch_padded_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                        int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens, int64_t* out_offsets,
+                                        int64_t* total_tokens, int64_t* width, int64_t* n_cut);
+tkz_status tkz_encode_batch_padded_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                         int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens, int64_t* out_offsets,
+                                         int64_t* total_tokens, int64_t* width, int64_t* n_cut);
+/* informational: successful calls of the padded entries */
+void tkz_encoder_padded_calls(const tkz_encoder* e, int64_t* calls);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -690,7 +748,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * bitmap, k_tokspan_mark, k_tokspan_count, two scans, k_tokspan_write): the closing event is recorded again behind the stage.  Of a chunk call
  * (tkz_encode_batch_chunks_device) likewise: k_docoffs over the pieces and the chunk stage (the two walks, their scan, the unit counts, k_chunk_units).
  * Of a packed call (tkz_encode_batch_packed_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the documents and the packing stage behind it
- * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.
+ * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.  Of a padded call (tkz_encode_batch_padded_device)
+ * likewise: k_docoffs over the documents, k_pad_lens and k_pad_write.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

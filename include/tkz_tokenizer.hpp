@@ -9,6 +9,7 @@
 //                              EncodeChunks / EncodeChunksBatch (+ Utf16): the text cut into chunks of at most maxTokenCount tokens, (ids, text) each
 //                              EncodeChunksOverlap / EncodeChunksOverlapBatch (+ Utf16): the same with an overlap of at most `overlap` tokens between neighbours
 //                              EncodeBatchPacked (std::string, std::u16string): the ids framed by bos / eos ids in rows of the context length, pos, seg_starts
+//                              EncodeBatchPadded (std::string, std::u16string): a row a text, cut to maxLength, framed, padded to a common width; mask, pos, lens
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -590,6 +591,27 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return packed_batch<uint16_t>(units, offs, rowLen, allowedSpecial, bos, eos, pad, true);
     }
+    // ---- padded rows: truncation, framing, padding to a common width and the attention mask in ONE call (tkz_encode_batch_padded_utf8 / _utf16) ----
+    // Every text's ids -- Encode's for the same arguments -- cut to maxLength less the framing (cutSide TKZ_TRIM_SUFFIX keeps the head, TKZ_TRIM_PREFIX the tail), with
+    // bos in front and eos behind what is kept (-1: none; any id >= 0 is taken as it is), a row a text, padded with pad on padSide to the longest row rounded up to
+    // padMultiple -- at most maxLength; padMultiple 0: to maxLength itself.  ids, mask (1 on content) and pos (the index inside the content) are n * width entries,
+    // row-major; lens the content lengths; n_cut the texts that were cut; total_tokens the uncut total (tkz.h states the rule).  The cut is a plain cut of the id
+    // list, not EncodeTrimSuffix's whole-item cut.  A registered set the device's special entries do not hold is a NotImplementedError here: there is no host path.
+    struct PaddedRows { int64_t width = 0, total_tokens = 0, n_cut = 0; std::vector<int32_t> ids, pos, lens; std::vector<uint8_t> mask; };
+    PaddedRows EncodeBatchPadded(const std::vector<std::string>& texts, int64_t maxLength, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                 int32_t pad = 0, tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return padded_batch<uint8_t>(bytes, offs, maxLength, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, false);
+    }
+    PaddedRows EncodeBatchPadded(const std::vector<std::u16string>& texts, int64_t maxLength, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                 int32_t pad = 0, tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return padded_batch<uint16_t>(units, offs, maxLength, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
+    }
     // (the id of a registered special token, for bos / eos)
     int32_t SpecialTokenId(const std::string& literal) const {
         for (const auto& kv : specials_) if (kv.first == literal) return kv.second;
@@ -805,6 +827,35 @@ private:
         out.ids.resize(static_cast<size_t>(needed));
         out.pos.resize(static_cast<size_t>(needed));
         out.seg_starts.resize(static_cast<size_t>(nseg) + 1);
+        return out;
+    }
+    // ONE call of the batch padded entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), with the capacity that always suffices (tkz.h): a row of
+    // maxLength a text
+    template <class UNIT>
+    PaddedRows padded_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, int64_t maxLength, const std::vector<std::string>& allowedSpecial, int32_t bos, int32_t eos,
+                            int32_t pad, tkz_trim_side cutSide, tkz_pad_side padSide, int64_t padMultiple, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        PaddedRows out;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = maxLength >= 1 && maxLength <= INT32_MAX ? n * maxLength : 0;      // (a maxLength out of range is refused by the library)
+        if (items.empty()) items.push_back(0);
+        out.ids.resize(static_cast<size_t>(std::max<int64_t>(cap, 1)));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(std::max<int64_t>(n, 1)));
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_padded_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                                      maxLength, cutSide, padSide, pad, padMultiple, out.ids.data(), cap, out.mask.data(), out.pos.data(), out.lens.data(), nullptr,
+                                                      &out.total_tokens, &out.width, &out.n_cut);
+        else st = tkz_encode_batch_padded_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                               maxLength, cutSide, padSide, pad, padMultiple, out.ids.data(), cap, out.mask.data(), out.pos.data(), out.lens.data(), nullptr,
+                                               &out.total_tokens, &out.width, &out.n_cut);
+        check(st);
+        out.ids.resize(static_cast<size_t>(n * out.width));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(n));
         return out;
     }
     // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text

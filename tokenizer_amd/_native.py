@@ -20,6 +20,7 @@ OPT_PIECE_STATS = 3
 OPT_PROMOTE_MIN_BYTES, OPT_PROMOTE_CAP = 5, 6
 OPT_CASE_EQUIVALENCE = 7    # cl100k's (?i:...) with .NET >= 7's case-equivalence tables ('ſ is 's)
 TRIM_SUFFIX, TRIM_PREFIX = 0, 1   # tkz_trim_side
+PAD_RIGHT, PAD_LEFT = 0, 1         # tkz_pad_side
 OPT_LATENCY_BYTES = 8       # batches of at most this many bytes merge long missed pieces a wavefront each (tkz.h)
 OPT_ADAPT = 9               # 1 (default): the encoder learns again when the text has drifted; small batches add up to a learning window (tkz.h)
 OPT_PROMOTE = 4        # 0 / 1: automatic promotion of hot memo entries into the key tables off / on; 2: promote now; 3: drop the promotions
@@ -199,6 +200,11 @@ class Library:
         L.tkz_encode_batch_packed_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, vp, i64, vp, vp, vp, i64, pi64, pi64, pi64]
         L.tkz_encoder_packed_calls.argtypes = [vp, pi64]
         L.tkz_encoder_packed_calls.restype = None
+        L.tkz_encode_batch_padded_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, vp, i64, vp, vp, vp, vp, vp, pi64, pi64, pi64]
+        L.tkz_encode_batch_padded_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, vp, i64, vp, vp, vp, vp, pi64, pi64, pi64]
+        L.tkz_encode_batch_padded_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, vp, i64, vp, vp, vp, vp, pi64, pi64, pi64]
+        L.tkz_encoder_padded_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_padded_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -1091,6 +1097,71 @@ class Encoder:
         """successful calls of the packed entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_packed_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- padded rows: a row a document, cut to max_len, framed by bos / eos ids, padded to the common width, with mask, pos and lens (tkz.h: the rule) --
+    @staticmethod
+    def padded_bounds(n_docs, max_len):
+        """the ids (and mask bytes, and pos entries) that always suffice (tkz.h): a row of max_len a document"""
+        return n_docs * max_len
+
+    def _padded_host(self, fn, buf, offsets, allowed, max_len, bos_id, eos_id, pad_id, cut_side, pad_side, pad_multiple, want_mask, want_pos, want_offs, out_cap):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        cap = (self.padded_bounds(n, max_len) if 1 <= max_len < 1 << 31 else 0) if out_cap is None else out_cap      # (a max_len out of range is refused by the library)
+        ids = np.empty(max(1, cap), np.int32)
+        mask = np.empty(max(1, cap), np.uint8) if want_mask else None
+        pos = np.empty(max(1, cap), np.int32) if want_pos else None
+        lens = np.empty(max(1, n), np.int32)
+        ooff = np.empty(n + 1, np.int64) if want_offs else None
+        tot, w, cut = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(fn(self._h, buf, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed), bos_id, eos_id, max_len, cut_side, pad_side, pad_id,
+                              pad_multiple, _ptr(ids), cap, _ptr(mask) if want_mask else None, _ptr(pos) if want_pos else None, _ptr(lens), _ptr(ooff) if want_offs else None,
+                              C.byref(tot), C.byref(w), C.byref(cut)))
+        except TkzError as ex:
+            ex.needed, ex.needed_width, ex.n_cut = tot.value, w.value, cut.value      # (E_CAPACITY: the required figures)
+            raise
+        W = w.value
+        return (ids[:n * W].reshape(n, W), mask[:n * W].reshape(n, W) if want_mask else None, pos[:n * W].reshape(n, W) if want_pos else None, lens[:n], ooff,
+                tot.value, cut.value)
+
+    def encode_batch_padded(self, data: np.ndarray, offsets: np.ndarray, max_len, allowed=(), bos_id=-1, eos_id=-1, pad_id=0, cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT,
+                            pad_multiple=1, want_mask=True, want_pos=True, want_offs=True, out_cap=None):
+        """(ids int32[n, W], mask uint8[n, W] or None, pos int32[n, W] or None, lens int32[n], offsets int64[n + 1] or None, total_tokens, n_cut): the ids of
+        encode_batch / encode_batch_special cut to max_len, framed and padded to the common width W -- tkz_encode_batch_padded_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self._padded_host(self.lib.L.tkz_encode_batch_padded_utf8, _ptr(data) if len(data) else None, offsets, allowed, max_len, bos_id, eos_id, pad_id, cut_side,
+                                 pad_side, pad_multiple, want_mask, want_pos, want_offs, out_cap)
+
+    def encode_batch_padded_utf16(self, units: np.ndarray, offsets: np.ndarray, max_len, allowed=(), bos_id=-1, eos_id=-1, pad_id=0, cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT,
+                                  pad_multiple=1, want_mask=True, want_pos=True, want_offs=True, out_cap=None):
+        """encode_batch_padded for UTF-16 documents (uint16[total], offsets in units) -- tkz_encode_batch_padded_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        return self._padded_host(self.lib.L.tkz_encode_batch_padded_utf16, _ptr(buf), offsets, allowed, max_len, bos_id, eos_id, pad_id, cut_side, pad_side, pad_multiple,
+                                 want_mask, want_pos, want_offs, out_cap)
+
+    def encode_batch_padded_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, d_out_ids, out_cap,
+                                   d_mask=0, d_pos=0, d_lens=0, d_out_offsets=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_padded_device.  Returns (total_tokens, W, n_cut); a TkzError carries them as `needed`, `needed_width`, `n_cut`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, w, cut = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_padded_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                     len(allowed), bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, d_out_ids or None, out_cap,
+                                                                     d_mask or None, d_pos or None, d_lens or None, d_out_offsets or None, stream or None,
+                                                                     C.byref(tot), C.byref(w), C.byref(cut)))
+        except TkzError as ex:
+            ex.needed, ex.needed_width, ex.n_cut = tot.value, w.value, cut.value
+            raise
+        return tot.value, w.value, cut.value
+
+    def padded_calls(self):
+        """successful calls of the padded entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_padded_calls(self._h, C.byref(a))
         return a.value
 
     def set_special_tokens(self, specials):

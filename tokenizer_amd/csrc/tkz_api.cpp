@@ -110,6 +110,7 @@ struct CounterBlock {          // mirrors the device block
     int64_t n_chunks;                      // the chunk entries: chunks of the whole batch (k_chunk_walk's writing pass)
     unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
     int64_t pack_total, pack_rows, pack_segs;   // the packed entries: T, n_rows (k_pack_count) and n_segs (the scan of its counts) -- PackParams::totals
+    int64_t pad_total, pad_width, pad_cut;      // the padded entries: the uncut total, W and n_cut (k_pad_write) -- PadParams::totals
     // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
     int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
 };
@@ -223,7 +224,12 @@ struct PackBufs {   // the packed entries: the unframed ids and their offsets (f
     DevBuf pk_ids, pk_offs, pk_cnt, pk_base, pk_bsum, pk_tot, pk_stage;
     void release() { release_each({&pk_ids, &pk_offs, &pk_cnt, &pk_base, &pk_bsum, &pk_tot, &pk_stage}); }
 };
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs {
+struct PadBufs {    // the padded entries: the uncut ids and their offsets, the first kept id of every document, the partials of k_pad_lens (kPadGridMax lengths, then
+    // as many counts); the block of a batch without bytes ({total, W, n_cut}, a zero total, a zero error word); the host entries' pos, lens and mask
+    DevBuf pd_ids, pd_offs, pd_src, pd_part, pd_tot, pd_stage;
+    void release() { release_each({&pd_ids, &pd_offs, &pd_src, &pd_part, &pd_tot, &pd_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -277,7 +283,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -319,6 +325,7 @@ struct tkz_encoder {
     std::string lit_why;
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
     std::atomic<int64_t> packed_calls{0};                                 // tkz_encoder_packed_calls: successful calls of the packed entries
+    std::atomic<int64_t> padded_calls{0};                                 // tkz_encoder_padded_calls: successful calls of the padded entries
     std::atomic<int64_t> chunks_overlap_calls{0};                          // tkz_encoder_chunks_overlap_calls: successful calls of the overlap chunk entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
@@ -378,6 +385,10 @@ struct ChunkCall {
 // host, where the numbers of rows and segments go
 struct PackCall { int32_t bos_id, eos_id; int64_t row_len; int32_t pad_id; int32_t* d_pos; int64_t* d_seg_starts; int64_t seg_cap; int64_t* n_rows; int64_t* n_segs;
                   int64_t frame() const { return (bos_id >= 0) + (eos_id >= 0); } };
+// A call of one of the padded entries: the framing ids (-1: none), the maximum length, the two sides, the pad id and the multiple, where the mask, pos and lens go
+// (device; mask and pos may be null -- and BatchCall::d_out_offs too) and, on the host, where the width and the number of cut documents go
+struct PadCall { int32_t bos_id, eos_id; int64_t max_len; int32_t cut_side, pad_side, pad_id; int64_t pad_multiple; uint8_t* d_mask; int32_t* d_pos; int32_t* d_lens;
+                 int64_t* width; int64_t* n_cut; };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -389,7 +400,8 @@ enum class CallKind {
     Trim,            // tkz_encode_batch_trim_device: Pieces with the piece arrays and the untrimmed ids kept in the workspace, then the cut and the kept ids
     Spans,           // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
     Chunks,          // tkz_encode_batch_chunks_device: as Spans, then the chunk table
-    Packed           // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
+    Packed,          // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
+    Padded           // tkz_encode_batch_padded_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a document
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -406,6 +418,7 @@ struct BatchCall {
     const SpanCall* spans = nullptr;           // Spans: where the positions go (pieces points at the workspace's piece arrays as well)
     const ChunkCall* chunks = nullptr;         // Chunks: the budget and where the table goes (pieces likewise)
     const PackCall* packed = nullptr;          // Packed: the framing, the row length and where pos and seg_starts go
+    const PadCall* padded = nullptr;           // Padded: the framing, the cut, the padding and where the mask, pos and lens go
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -415,7 +428,7 @@ struct BatchCall {
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -969,6 +982,41 @@ tkz_status pack_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t
     return TKZ_OK;
 }
 
+// the stage of a padded call over the uncut ids and offsets (the workspace's); blk: the counter block (its first word: the error bits), totals: its {total, W, n_cut}
+tkz::PadParams pad_params(Workspace* ws, const BatchCall& c, const int64_t* grand, int64_t* totals, const int32_t* blk) {
+    const PadCall& k = *c.padded;
+    int32_t* const part = ws->pd_part.as<int32_t>();
+    return tkz::PadParams{ws->pd_ids.as<int32_t>(), c.total, ws->pd_offs.as<int64_t>(), c.n_docs, grand, k.bos_id, k.eos_id, k.pad_id, k.max_len, k.cut_side, k.pad_side,
+                          k.pad_multiple, c.d_out, c.out_cap, k.d_mask, k.d_pos, k.d_lens, c.d_out_offs, ws->pd_src.as<int64_t>(), part,
+                          reinterpret_cast<int64_t*>(part + tkz::kPadGridMax), 0, totals, blk};
+}
+
+// A padded call on a batch without bytes: every document is its framing alone (all of them empty: W = 0 without framing), and the stage runs over offsets that
+// are all 0.  Without documents there is nothing but the offset to clear.
+tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t* totals3) {
+    using namespace tkz;
+    const int64_t n_docs = c.n_docs;
+    totals3[0] = totals3[1] = totals3[2] = 0;
+    const Launch L{c.stream, nullptr, ws};
+    HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
+    if (n_docs == 0) {
+        launch_counts3(L, 0, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+        if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, sizeof(int64_t), c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return TKZ_OK;
+    }
+    HIP_TRY(ws->pd_tot.ensure(64, &ws->bytes_allocated));
+    HIP_TRY(hipMemsetAsync(ws->pd_tot.p, 0, 64, c.stream));
+    HIP_TRY(hipMemsetAsync(ws->pd_offs.p, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
+    int64_t* const tot = ws->pd_tot.as<int64_t>();
+    launch_pad(L, pad_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
+    launch_counts3(L, n_docs, 0, tot, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+    HIP_TRY(hipMemcpyAsync(totals3, tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    HIP_TRY(hipGetLastError());
+    return TKZ_OK;
+}
+
 // One attempt on the stream: the zero region and the text (k_ingest), the document marks and the pre-tokenizer (or, on a re-run, the counters and the
 // sub-tile flags only: it starts behind the pre-tokenizer), the counts of the marks and pieces and their scan, the piece index, then the sizing probe
 // (nsample >= 0) or the whole launch sequence, and the counter block back to the host.
@@ -1101,6 +1149,8 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             if (c.count_only) launch_tokcount(L, P, ws->w_tbase.as<int64_t>(), ws->w_dcount.as<int32_t>(), ntiles);
             // (a packed call that frames its documents: the unframed ids stay in the workspace too -- every one of them moves)
             else if (c.packed && c.packed->frame()) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pk_ids.as<int32_t>(), total);
+            // (a padded call: the uncut ids likewise -- the rows are gathered from them)
+            else if (c.padded) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pd_ids.as<int32_t>(), total);
             else launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs, has_empty);
@@ -1148,6 +1198,10 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                                    ws->pk_cnt.as<int32_t>(), pack_tiles(total, n_docs, k), ws->pk_base.as<int64_t>(), ws->pk_bsum.as<int64_t>(), totals, counters};
                 launch_pack(L, K);
                 launch_counts3(L, n_docs, total, totals, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+            } else if (c.padded) {                                      // (the uncut offsets, then the rows; the counts blocks receive the uncut total)
+                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, ws->pd_offs.as<int64_t>(), has_empty);
+                launch_pad(L, pad_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
+                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
                                has_empty, n_docs, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
@@ -1318,6 +1372,20 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         TKZ_TRY(pack_empty(e, ws, c, totals3));
         return packed_done(totals3);
     }
+    // the outcome of a padded call likewise: the uncut total, the width and the cut documents; n_docs * W against the capacity
+    const auto padded_done = [&](const int64_t* totals3) {
+        const PadCall& k = *c.padded;
+        if (total_tokens) *total_tokens = totals3[0];
+        if (k.width) *k.width = totals3[1];
+        if (k.n_cut) *k.n_cut = totals3[2];
+        if (totals3[1] > 0 && n_docs > c.out_cap / totals3[1]) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
+        return TKZ_OK;
+    };
+    if (total == 0 && c.padded) {
+        int64_t totals3[3];
+        TKZ_TRY(pad_empty(e, ws, c, totals3));
+        return padded_done(totals3);
+    }
     if (total == 0) {
         if (phase != kCallEnd) {                                  // (kCallEnd: enqueued when it began)
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
@@ -1374,6 +1442,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         if (c.pretokenizes()) after_batch(e, ws, total);
         if (c.literals()) e->spec_literals += ws->spec_taken;
         if (c.packed) return packed_done(&ws->h_counters->pack_total);
+        if (c.padded) return padded_done(&ws->h_counters->pad_total);
         const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
         if (total_tokens) *total_tokens = produced;
         if (c.chunks && c.chunks->n_chunks) *c.chunks->n_chunks = ws->h_counters->n_chunks;      // (both required sizes from one call)
@@ -3297,6 +3366,145 @@ tkz_status tkz_encode_batch_packed_utf16(tkz_encoder* e, const uint16_t* units, 
 }
 void tkz_encoder_packed_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->packed_calls.load() : 0;
+}
+
+// ---- padded rows: the ids of the matching encode entry cut to max_len, framed by bos / eos ids, a row a document padded to the common width (tkz.h: the rule) ----
+
+namespace {
+tkz_status check_pad_args(int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int64_t pad_multiple) {
+    if (bos_id < -1 || eos_id < -1) return fail(TKZ_E_ARG, "padded rows: bos_id and eos_id are -1 (none) or an id >= 0");
+    const int64_t f = (bos_id >= 0) + (eos_id >= 0);
+    if (max_len < std::max<int64_t>(1, f) || max_len > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "padded rows: max_len must be in [max(1, framing ids), 2^31 - 1]");
+    if (cut_side != TKZ_TRIM_SUFFIX && cut_side != TKZ_TRIM_PREFIX) return fail(TKZ_E_ARG, "padded rows: cut_side must be TKZ_TRIM_SUFFIX or TKZ_TRIM_PREFIX");
+    if (pad_side != TKZ_PAD_RIGHT && pad_side != TKZ_PAD_LEFT) return fail(TKZ_E_ARG, "padded rows: pad_side must be TKZ_PAD_RIGHT or TKZ_PAD_LEFT");
+    if (pad_multiple < 0 || pad_multiple > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "padded rows: pad_multiple must be in [0, 2^31 - 1]");
+    return TKZ_OK;
+}
+const char* const kMsgPadPointers = "padded rows: null ids, lens or scalar pointer";
+// the padded call on device buffers, on a workspace the entry holds: the plain launch sequence with the uncut ids and offsets in the workspace, then the rows
+// (enqueue_attempt)
+tkz_status padded_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, const SpecialCall* sp, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    int64_t* acc = &ws->bytes_allocated;
+    if (c.n_docs < 0 || c.total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    if (c.total > 0) HIP_TRY(ws->pd_ids.ensure((size_t)c.total * 4, acc));
+    HIP_TRY(ws->pd_offs.ensure((size_t)(c.n_docs + 1) * 8, acc));
+    HIP_TRY(ws->pd_src.ensure((size_t)std::max<int64_t>(c.n_docs, 1) * 8, acc));
+    HIP_TRY(ws->pd_part.ensure((size_t)tkz::kPadGridMax * 12, acc));
+    int64_t w = 0, cut = 0;
+    pc.width = &w; pc.n_cut = &cut;
+    c.kind = CallKind::Padded; c.padded = &pc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (width) *width = w;
+    if (n_cut) *n_cut = cut;
+    if (st == TKZ_OK) { ++e->padded_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a padded host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the rows, the offsets, pos, lens and
+// the mask, ONE padded call, the results back -- n_docs * W entries of each, never the uncut ids.
+tkz_status padded_staged(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos,
+                         int32_t* lens, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    const int64_t n_docs = c.n_docs;
+    const bool fits = n_docs == 0 || out_cap / pc.max_len >= n_docs;      // (n_docs * max_len always suffices: more capacity is never used)
+    c.out_cap = fits ? n_docs * pc.max_len : out_cap;
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1), nl = std::max<int64_t>(n_docs, 1);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap, out_offsets != nullptr));
+    HIP_TRY(ws->pd_stage.ensure((size_t)(pos ? cap : 0) * 4 + (size_t)nl * 4 + (size_t)(mask ? cap : 0), &ws->bytes_allocated));
+    int32_t* const d_pos = ws->pd_stage.as<int32_t>();
+    int32_t* const d_lens = d_pos + (pos ? cap : 0);
+    uint8_t* const d_mask = reinterpret_cast<uint8_t*>(d_lens + nl);
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = out_offsets ? ws->s_outoffs[0].as<int64_t>() : nullptr;
+    pc.d_mask = mask ? d_mask : nullptr; pc.d_pos = pos ? d_pos : nullptr; pc.d_lens = d_lens;
+    const tkz_status st = padded_on_device(e, ws, c, pc, sp, total_tokens, width, n_cut);
+    if (st != TKZ_OK) return st;
+    const int64_t n = n_docs * *width;
+    TKZ_TRY(fetch(ws, out_ids, n, out_offsets, n_docs));
+    if (n_docs) HIP_TRY(hipMemcpy(lens, d_lens, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+    if (pos && n) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (mask && n) HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_padded_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                          const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                          int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* d_out_ids, int64_t out_cap, uint8_t* d_mask,
+                                          int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets, void* hip_stream, int64_t* total_tokens, int64_t* width,
+                                          int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    if (!d_out_ids || !d_lens || !total_tokens || !width || !n_cut) return fail(TKZ_E_ARG, kMsgPadPointers);
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (!d_doc_offsets || (total_bytes > 0 && !d_bytes)) return fail(TKZ_E_ARG, "null device buffer");      // (d_out_offsets may be null here)
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    Lease lease(e);
+    return padded_on_device(e, lease.ws, c, PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, d_mask, d_pos, d_lens, nullptr, nullptr}, sp,
+                            total_tokens, width, n_cut);
+}
+
+tkz_status tkz_encode_batch_padded_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                        int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens, int64_t* out_offsets,
+                                        int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    if (!out_ids || !lens || !total_tokens || !width || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgPadPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_packed_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return padded_staged(e, ws, staged_call(ws, n_docs, total, 0), PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr},
+                         sp, out_ids, out_cap, mask, pos, lens, out_offsets, total_tokens, width, n_cut);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_packed_utf16 does.
+tkz_status tkz_encode_batch_padded_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                         int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                         int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens, int64_t* out_offsets,
+                                         int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    if (!out_ids || !lens || !total_tokens || !width || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgPadPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    const PadCall pc{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    if (total == 0) {                                                   // (no units: the offsets, all 0, are byte offsets as they are -- the framing is still laid out)
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, nullptr));
+        TKZ_TRY(stage_in(ws, nullptr, 0, unit_offsets, n_docs));
+        return padded_staged(e, ws, staged_call(ws, n_docs, 0, 0), pc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, total_tokens, width, n_cut);
+    }
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return padded_staged(e, ws, c, pc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, total_tokens, width, n_cut);
+}
+void tkz_encoder_padded_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->padded_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

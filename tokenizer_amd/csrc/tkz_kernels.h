@@ -300,6 +300,24 @@ struct PackParams {
     const int32_t* counters;
 };
 void launch_pack(const Launch& L, const PackParams& K);
+// Padded rows (tkz_encode_batch_padded_device; tkz.h states the rule): behind the PLAIN document-granular launch sequence, whose uncut ids (ids, ids_cap entries)
+// and n_docs + 1 document offsets (offs) stay in the workspace.  k_pad_lens, a lane a document: the kept count and the framing into lens (the caller's, n_docs
+// entries: len[d] = k[d] + f), the source index of the first kept id into src (n_docs entries, workspace), offs copied to out_offs (may be null), and the largest
+// len and the number of cut documents of every workgroup into part_len / part_cut (kPadGridMax entries each, workspace; nparts of them are written: the grid).
+// k_pad_write: every wavefront reduces the partials to the width W and n_cut, one lane stores totals = {*grand, W, n_cut}, and when n_docs * W <= out_cap the
+// rows are written by output position in tiles of kPadTile, a wavefront each: out, mask (may be null), pos (may be null), n_docs * W entries each.  It reads
+// lens and src only -- not offs, max_len or cut_side --, so a cut of another granularity in front of it can fill the two arrays itself.
+// counters: the batch's counter block -- with an error bit in it ([0]) nothing of the caller's is touched and the totals are not written.
+constexpr int kPadTile = 1024;
+constexpr int kPadGridMax = 2048;      // workgroups of the two kernels: they stride over the documents / tiles beyond
+struct PadParams {
+    const int32_t* ids; int64_t ids_cap; const int64_t* offs; int64_t n_docs; const int64_t* grand;
+    int32_t bos_id, eos_id, pad_id; int64_t max_len; int32_t cut_side, pad_side; int64_t pad_multiple;
+    int32_t* out; int64_t out_cap; uint8_t* mask; int32_t* pos; int32_t* lens; int64_t* out_offs;
+    int64_t* src; int32_t* part_len; int64_t* part_cut; int32_t nparts; int64_t* totals;
+    const int32_t* counters;
+};
+void launch_pad(const Launch& L, PadParams K);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

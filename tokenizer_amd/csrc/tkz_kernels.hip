@@ -5089,4 +5089,124 @@ void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, in
                (const int64_t*)d_offs, d_bytes, cap_bytes);
 }
 
+// -------------------------------------------------------------------------------------------------
+// Padded rows (tkz_encode_batch_padded_device; tkz.h states the rule), behind the plain document-granular launch sequence: a row a document, cut to max_len,
+// framed, padded to the common width W on either side, with the mask and the position inside the content.  The uncut ids and offsets O stay in the workspace.
+//   k_pad_lens    a lane a document: n = O[d + 1] - O[d], k = min(n, L - f), lens[d] = k + f, src[d] = the index of the first kept id (O[d], or O[d + 1] - k
+//                 for a cut at the front), out_offs[d] = O[d].  The largest len and the number of cut documents of a workgroup go into ONE partial each: the
+//                 wavefronts' by shuffles, the four of them through 48 bytes of LDS.  Nothing is added up in memory, so the result is the same on every run.
+//   k_pad_write   every wavefront reduces the partials (nparts <= kPadGridMax, from L2) to W and n_cut, one lane stores {total, W, n_cut}, and the kernel holds
+//                 n_docs * W against out_cap itself: the host never waits for the width between the two launches.  The rows are dealt out by OUTPUT position,
+//                 a wavefront per tile of kPadTile positions, grid-strided.  Row and column of a tile's first position cost one 64-bit division a TILE
+//                 (wave-uniform); a lane steps them by 64 positions with additions and one conditional subtraction.  A row may be shorter than 64 columns (a
+//                 group of 64 positions then spans many rows: the step is 64 / W rows and 64 % W columns) or longer than a tile.  A lane loads lens and src of
+//                 its row only when its row changes.  It reads lens and src, not O: whoever fills the two arrays decides what is kept.
+// Every store of a row is tkz_store_nt, all 64 lanes, consecutive addresses.
+// -------------------------------------------------------------------------------------------------
+TKZ_DEV int tkz_pad_wave_max(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const int o = simt::shfl_xor(v, m); v = o > v ? o : v; }
+    return v;
+}
+TKZ_DEV int64_t tkz_pad_wave_sum(int64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t lo = (uint32_t)simt::shfl_xor((int)(uint32_t)v, m), hi = (uint32_t)simt::shfl_xor((int)(uint32_t)((uint64_t)v >> 32), m);
+        v += (int64_t)(((uint64_t)hi << 32) | lo);
+    }
+    return v;
+}
+TKZ_KERNEL(256) void k_pad_lens(PadParams K) {
+    TKZ_SHARED int s_len[kThreads / 64];
+    TKZ_SHARED int64_t s_cut[kThreads / 64];
+    const bool bad = K.counters[0] != 0;                       // (a failed attempt: the offsets mean nothing, the caller's buffers are left alone)
+    const int64_t f = (K.bos_id >= 0 ? 1 : 0) + (K.eos_id >= 0 ? 1 : 0), room = K.max_len - f;
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    int longest = 0;
+    int64_t ncut = 0;
+    if (!bad) for (int64_t d = simt::bid() * simt::nthreads() + simt::tid(); d < K.n_docs; d += stride) {
+        const int64_t lo = K.offs[d], hi = K.offs[d + 1], n = hi - lo, k = n < room ? n : room;
+        const int len = (int)(k + f);
+        K.lens[d] = len;
+        K.src[d] = K.cut_side ? hi - k : lo;
+        if (K.out_offs) { K.out_offs[d] = lo; if (d == K.n_docs - 1) K.out_offs[K.n_docs] = hi; }
+        longest = len > longest ? len : longest;
+        ncut += n > room ? 1 : 0;
+    }
+    longest = tkz_pad_wave_max(longest);
+    ncut = tkz_pad_wave_sum(ncut);
+    if (simt::lane() == 0) { s_len[simt::wave()] = longest; s_cut[simt::wave()] = ncut; }
+    simt::sync();
+    if (simt::tid() == 0) {
+        int64_t c = 0;
+        for (int w = 0; w < simt::nthreads() / 64; ++w) { longest = s_len[w] > longest ? s_len[w] : longest; c += s_cut[w]; }
+        K.part_len[simt::bid()] = longest;
+        K.part_cut[simt::bid()] = c;
+    }
+}
+TKZ_KERNEL(256) void k_pad_write(PadParams K) {
+    if (K.counters[0] != 0) return;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    // the width and the cut documents, from the partials
+    int longest = 0;
+    int64_t n_cut = 0;
+    for (int i = lane; i < K.nparts; i += 64) {
+        const int l = K.part_len[i];
+        longest = l > longest ? l : longest;
+        n_cut += K.part_cut[i];
+    }
+    longest = tkz_pad_wave_max(longest);
+    n_cut = tkz_pad_wave_sum(n_cut);
+    const int64_t L = K.max_len, M = K.pad_multiple;
+    int64_t W = 0;
+    if (longest > 0) { W = M == 0 ? L : (longest + M - 1) / M * M; W = W < L ? W : L; }
+    W = (int64_t)simt::uniform64((uint64_t)W);
+    if (wave0 == 0 && lane == 0) { K.totals[0] = *K.grand; K.totals[1] = W; K.totals[2] = n_cut; }
+    if (W == 0 || K.n_docs > K.out_cap / W) return;            // (nothing to write; or the rows do not fit: the totals are all that is written)
+    const int64_t N = K.n_docs * W, ntile = (N + kPadTile - 1) / kPadTile;
+    const int fb = K.bos_id >= 0 ? 1 : 0, fe = K.eos_id >= 0 ? 1 : 0;
+    // 64 positions on: rstep rows and cstep < W columns
+    const int64_t rstep = W > 64 ? 0 : (int64_t)(64u / (uint32_t)W), cstep = W > 64 ? 64 : (int64_t)(64u % (uint32_t)W);
+    for (int64_t t = wave0; t < ntile; t += nwaves) {
+        const int64_t q0 = t * kPadTile, q1 = q0 + kPadTile < N ? q0 + kPadTile : N;
+        const int64_t row0 = q0 / W, col0 = q0 - row0 * W;     // (wave-uniform: one division a tile)
+        int64_t r, c;
+        if (W >= 64) { r = row0; c = col0 + lane; if (c >= W) { c -= W; ++r; } }
+        else { const uint32_t x = (uint32_t)col0 + (uint32_t)lane; r = row0 + (int64_t)(x / (uint32_t)W); c = (int64_t)(x % (uint32_t)W); }
+        int64_t cur = -1, src = 0;
+        int len = 0;
+        for (int64_t g = q0; g < q1; g += 64) {
+            const int64_t q = g + lane;
+            if (q < q1) {
+                if (r != cur) { cur = r; len = K.lens[r]; src = K.src[r]; }
+                const int64_t j = c - (K.pad_side ? W - len : 0);     // the index inside the content
+                const bool in = j >= 0 && j < len;
+                int32_t v = K.pad_id;
+                if (in) {
+                    const int64_t s = src + j - fb;
+                    if (fb && j == 0) v = K.bos_id;
+                    else if (fe && j == len - 1) v = K.eos_id;
+                    else if (s >= 0 && s < K.ids_cap) v = tkz_load_nt(K.ids + s);
+                }
+                tkz_store_nt(K.out + q, v);
+                if (K.mask) tkz_store_nt(K.mask + q, (uint8_t)(in ? 1 : 0));
+                if (K.pos) tkz_store_nt(K.pos + q, in ? (int32_t)j : 0);
+            }
+            r += rstep; c += cstep;
+            if (c >= W) { c -= W; ++r; }
+        }
+    }
+}
+// (the bracket: K_DOCOFFS's again, as launch_pack.  The width is known on the device only: the writing grid is sized for the positions the caller's buffer
+//  holds, n_docs * max_len at most -- beyond kPadGridMax workgroups both kernels stride)
+void launch_pad(const Launch& L, PadParams K) {
+    const auto capped = [](int64_t g) { return g < 1 ? 1 : (g > kPadGridMax ? kPadGridMax : g); };
+    const int64_t most = K.n_docs > 0 && K.out_cap / K.max_len >= K.n_docs ? K.n_docs * K.max_len : K.out_cap;
+    K.nparts = (int32_t)capped(cdiv(K.n_docs, kThreads));
+    TKZ_LAUNCH(k_pad_lens, K.nparts, kThreads, L.stream, K);
+    TKZ_LAUNCH(k_pad_write, capped(cdiv(cdiv(most, kPadTile), kThreads / 64)), kThreads, L.stream, K);
+    hook(L, K_DOCOFFS, 1);
+}
+
 }  // namespace tkz

@@ -100,6 +100,12 @@ TKZ_DEV void tkz_store16_nt(void* p, uint4 v) {
     __builtin_nontemporal_store(x, reinterpret_cast<tkz_u32x4*>(p));
 }
 #endif
+// (a byte, streamed like the ids beside it: the mask of the padded rows)
+#ifdef TKZ_HOSTEMU
+inline void tkz_store_nt(uint8_t* p, uint8_t v) { *p = v; }
+#else
+TKZ_DEV void tkz_store_nt(uint8_t* p, uint8_t v) { __builtin_nontemporal_store(v, p); }
+#endif
 
 // ---- bit helpers shared by host and device code ------------------------------------------------
 TKZ_HD int tkz_popc64(uint64_t x) { return __builtin_popcountll(x); }

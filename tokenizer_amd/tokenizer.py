@@ -367,6 +367,43 @@ class TikTokenizer:
         ids, ooff, pos, seg, _ = self._encoder.encode_batch_packed(data, offs, row_len, index, bos_id, eos_id, pad)
         return ids, pos, seg, ooff
 
+    # ---- padded rows: truncation, framing, padding to a common width and the attention mask (include/tkz.h, "Padded rows") ----
+    def EncodeBatchPadded(self, texts: Sequence[str], max_length: int, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bos=None, eos=None, pad: int = 0,
+                          truncation_side: str = "right", padding_side: str = "right", pad_to_multiple_of: int = 1, fixed_width: bool = False, return_pos: bool = False):
+        """(ids[n, W], mask[n, W], lens) as numpy arrays -- and pos[n, W] with return_pos -- from ONE device call (tkz_encode_batch_padded_utf8 / _utf16): every
+        text's ids -- Encode's for the same arguments -- cut to max_length less the framing (truncation_side "right" keeps the head, "left" the tail), with `bos` in
+        front and `eos` behind what is kept, a row a text, padded with `pad` on padding_side to the longest row rounded up to pad_to_multiple_of (at most
+        max_length), or to max_length itself with fixed_width.  mask is 1 on content (uint8; .view(bool) is free), lens the content lengths.  bos / eos: None, an
+        int, or the literal of a registered special token.  The cut is a plain cut of the id list, not EncodeTrimSuffix's whole-item cut."""
+        sides = {"right": 0, "left": 1}
+        if truncation_side not in sides or padding_side not in sides:
+            raise ValueError("truncation_side and padding_side are 'right' or 'left'")
+        bos_id, eos_id = self._frame_id(bos), self._frame_id(eos)
+        if max_length < max(1, (bos_id >= 0) + (eos_id >= 0)) or max_length >= 1 << 31:
+            raise ValueError("max_length must hold the framing ids, and one id at least")
+        if pad_to_multiple_of < 1 or pad_to_multiple_of >= 1 << 31:
+            raise ValueError("pad_to_multiple_of must be at least 1")
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not plain and self._special_on_host:
+            raise N.UnsupportedError(N.E_UNSUPPORTED, "EncodeBatchPadded: the device's special entries do not hold this set of literals")
+        names = set(allowed) if not plain else ()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+        args = (max_length, index, bos_id, eos_id, pad, sides[truncation_side], sides[padding_side], 0 if fixed_width else pad_to_multiple_of, True, return_pos, False)
+        if not plain and self._fffd_literal and any(_has_lone_surrogate(t) for t in texts):
+            # (a literal that holds U+FFFD beside a lone surrogate: only the UTF-16 entry tells the two apart)
+            raw = [t.encode("utf-16-le", "surrogatepass") for t in texts]
+            offs = np.zeros(len(raw) + 1, np.int64)
+            np.cumsum(np.fromiter((len(r) // 2 for r in raw), np.int64, len(raw)), out=offs[1:])
+            ids, mask, pos, lens, _, _, _ = self._encoder.encode_batch_padded_utf16(np.frombuffer(b"".join(raw), "<u2"), offs, *args)
+        else:
+            segs = [_utf8_like_dotnet(t) for t in texts]
+            offs = np.zeros(len(segs) + 1, np.int64)
+            np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+            data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+            ids, mask, pos, lens, _, _, _ = self._encoder.encode_batch_padded(data, offs, *args)
+        return (ids, mask, lens, pos) if return_pos else (ids, mask, lens)
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
