@@ -86,6 +86,13 @@ namespace Microsoft.DeepDev
                                                                                           int* outIds, long outCap, byte* mask, int* pos, int* lens, long* outOffsets,
                                                                                           out long totalTokens, out long width, out long nCut);
         [DllImport(Lib)] internal static extern void tkz_encoder_padded_calls(IntPtr encoder, out long calls);
+        // length-bucketed padded rows: the padded rows of the texts sorted by length, every bucket of bucketRows rows at its own width (include/tkz.h, "Length-bucketed padded rows")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_bucketed_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                            int bosId, int eosId, long maxLen, int cutSide, int padSide, int padId, long padMultiple,
+                                                                                            long bucketRows, int order, int* outIds, long outCap, byte* mask, int* pos, int* lens,
+                                                                                            long* outOffsets, long* orderOut, long* rank, long* bucketOffsets, int* bucketWidths,
+                                                                                            out long totalTokens, out long totalPositions, out long nCut);
+        [DllImport(Lib)] internal static extern void tkz_encoder_bucketed_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -626,6 +633,63 @@ namespace Microsoft.DeepDev
             var outLens = new int[texts.Count];
             Array.Copy(lens, outLens, texts.Count);
             return (outIds, outMask, outPos, outLens);
+        }
+
+        /// <summary>EncodeBatchPadded's rows with the texts sorted by content length (<paramref name="descending"/>: longest first; equal lengths keep the texts' order),
+        /// cut into buckets of <paramref name="bucketRows"/> sorted rows, every bucket padded to ITS OWN longest row (rounded up to <paramref name="padToMultipleOf"/>, at
+        /// most maxLength; 0: to maxLength itself), in ONE call (tkz_encode_batch_bucketed_utf16; include/tkz.h states the rule).  Buckets[b] holds Ids and Mask of
+        /// rows x width; its row i is text Order[b * bucketRows + i]; Rank is the inverse of Order; Lens are in the texts' order.</summary>
+        public unsafe ((int[,] Ids, byte[,] Mask)[] Buckets, long[] Order, long[] Rank, int[] Lens) EncodeBatchBucketed(IReadOnlyList<string> texts, int maxLength, int bucketRows,
+                                                                                                                       IReadOnlyCollection<string>? allowedSpecial = null, int? bos = null,
+                                                                                                                       int? eos = null, int pad = 0, bool descending = false,
+                                                                                                                       bool truncateLeft = false, bool padLeft = false, int padToMultipleOf = 1)
+        {
+            int framing = (bos.HasValue ? 1 : 0) + (eos.HasValue ? 1 : 0);
+            if (maxLength < Math.Max(1, framing)) throw new ArgumentOutOfRangeException(nameof(maxLength));
+            if (bucketRows < 1) throw new ArgumentOutOfRangeException(nameof(bucketRows));
+            if (bos < 0 || eos < 0) throw new ArgumentOutOfRangeException(bos < 0 ? nameof(bos) : nameof(eos));
+            if (padToMultipleOf < 0) throw new ArgumentOutOfRangeException(nameof(padToMultipleOf));
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = (long)texts.Count * maxLength;                                            // the size that always suffices (tkz.h): a row of maxLength a text
+            int nBuckets = (texts.Count + bucketRows - 1) / bucketRows;
+            var ids = new int[Math.Max(1, cap)];
+            var mask = new byte[Math.Max(1, cap)];
+            var lens = new int[Math.Max(1, texts.Count)];
+            var order = new long[Math.Max(1, texts.Count)];
+            var rank = new long[Math.Max(1, texts.Count)];
+            var bucketOffsets = new long[nBuckets + 1];
+            var bucketWidths = new int[Math.Max(1, nBuckets)];
+            int st;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (byte* pm = mask) fixed (int* pl = lens)
+            fixed (long* pr = order) fixed (long* pk = rank) fixed (long* pb = bucketOffsets) fixed (int* pw = bucketWidths)
+                st = Tkz.tkz_encode_batch_bucketed_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, bos ?? -1, eos ?? -1, maxLength,
+                                                         truncateLeft ? 1 : 0, padLeft ? 1 : 0, pad, padToMultipleOf, bucketRows, descending ? 1 : 0, pi, cap, pm, null, pl, null,
+                                                         pr, pk, pb, pw, out _, out _, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            var buckets = new (int[,] Ids, byte[,] Mask)[nBuckets];
+            for (int b = 0; b < nBuckets; ++b)
+            {
+                int rows = Math.Min(bucketRows, texts.Count - b * bucketRows), w = bucketWidths[b];
+                var bIds = new int[rows, w];
+                var bMask = new byte[rows, w];
+                Buffer.BlockCopy(ids, checked((int)bucketOffsets[b] * sizeof(int)), bIds, 0, checked(rows * w * sizeof(int)));
+                Buffer.BlockCopy(mask, checked((int)bucketOffsets[b]), bMask, 0, checked(rows * w));
+                buckets[b] = (bIds, bMask);
+            }
+            var outLens = new int[texts.Count];
+            var outOrder = new long[texts.Count];
+            var outRank = new long[texts.Count];
+            Array.Copy(lens, outLens, texts.Count);
+            Array.Copy(order, outOrder, texts.Count);
+            Array.Copy(rank, outRank, texts.Count);
+            return (buckets, outOrder, outRank, outLens);
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

@@ -572,7 +572,8 @@ void tkz_encoder_packed_calls(const tkz_encoder* e, int64_t* calls);
  *     offsets are downloaded, NEVER the uncut ids: a batch cut to L moves n_docs * W ids over PCIe where tkz_encode_batch_utf8 moves total_tokens -- on long
  *     documents that download is what bounds the host entries.
  *   tkz_encode_batch_padded_utf16: code units in, transcoded on the device as tkz_encode_batch_packed_utf16; unit_offsets in code units.
- * There is no item-granular cut in front of the rows (trim first), no maximum per document, no sorting or bucketing by length, no _begin / _end form, no chunk
+ * There is no item-granular cut in front of the rows (trim first), no maximum per document, no sorting or bucketing by length HERE (the bucketed entries below do
+ * that), no _begin / _end form, no chunk
  * pipeline, no single-text form (padding one text is a slice) and no int64 or bool mask. */
 typedef enum tkz_pad_side { TKZ_PAD_RIGHT = 0, TKZ_PAD_LEFT = 1 } tkz_pad_side;
 tkz_status tkz_encode_batch_padded_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
@@ -590,6 +591,69 @@ tkz_status tkz_encode_batch_padded_utf16(tkz_encoder* e, const uint16_t* units, 
                                          int64_t* total_tokens, int64_t* width, int64_t* n_cut);
 /* informational: successful calls of the padded entries */
 void tkz_encoder_padded_calls(const tkz_encoder* e, int64_t* calls);
+
+/* ---- Length-bucketed padded rows: the documents sorted by token length, cut into mini-batches of B rows, every mini-batch padded to ITS OWN longest row ----
+ * What follows the padded rows above in every inference and evaluation loop (group_by_length, a length-sorted sampler, a sorted prefill queue): sort by length,
+ * cut the sorted list into buckets, pad each bucket alone, keep the permutation.  The lengths exist on the device only after the encode; this is that step there.
+ * THE RULE.  Every argument of tkz_encode_batch_padded_device keeps its meaning and its TKZ_E_ARG conditions: allowed / n_allowed, bos_id, eos_id, max_len = L,
+ * cut_side, pad_side, pad_id, pad_multiple = M.  Two more: bucket_rows = B with 1 <= B <= 2^31 - 1, and order, a tkz_bucket_order; anything else is TKZ_E_ARG.
+ *   Lengths.  n[d], k[d] = min(n[d], L - f), len[d] = k[d] + f and n_cut are EXACTLY as in the padded rule: the same cut, the framing after the cut.
+ *   Order.  order[0 .. n_docs) (int64) is the permutation of the documents by len, ascending or descending as asked; documents of equal len keep ascending
+ *     document index in BOTH directions: ascending is numpy.argsort(len, kind="stable"), descending is numpy.argsort(-len, kind="stable").  rank[d] (int64,
+ *     optional) is the inverse: rank[order[r]] = r.
+ *   Buckets.  n_buckets = ceil(n_docs / B) -- the caller computes it before the call, so there is no bucket capacity argument.  Bucket b holds the sorted rows
+ *     [b * B, min((b + 1) * B, n_docs)): R_b rows.  maxlen_b is the largest len in the bucket.  M == 0: W_b = L.  M >= 1: W_b = min(L, ceil(maxlen_b / M) * M).
+ *     W_b = 0 when maxlen_b == 0.  bucket_widths[b] = W_b (int32, n_buckets entries).  bucket_offsets[b] = the sum over b' < b of R_b' * W_b' (int64,
+ *     n_buckets + 1 entries); the last entry is P, the total number of positions.
+ *   Rows.  Sorted row r lies in bucket b = r / B as row i = r - b * B and occupies out[bucket_offsets[b] + i * W_b .. + W_b).  Its content is the padded rule's
+ *     row for document order[r] at width W_b: [bos_id] kept [eos_id] on the side pad_side says, pad_id elsewhere; mask (uint8) 1 on content; pos (int32) the
+ *     index inside the content, 0 on padding.  lens[d] (int32) and out_offsets[d] (int64, UNCUT) stay in DOCUMENT order, as in the padded entry.
+ *   Scalars.  *total_tokens = O[n_docs], the uncut total -- which is also what the encoder's {n_docs, n_bytes, n_tokens} block receives --, *total_positions = P,
+ *     *n_cut.
+ *   Example: documents [a1 a2 a3 a4 a5], [], [c1 c2], [d1 d2 d3], [e1 e2]; no bos, eos = X, L = 4, M = 1, B = 2, pad P, suffix cut, right padding.
+ *     len = 4, 1, 3, 4, 3; n_cut = 1.
+ *     ascending:  order 1, 2, 4, 0, 3; rank 3, 0, 1, 4, 2; widths 3, 4, 4; bucket offsets 0, 6, 14, 18; P = 18
+ *                 rows X P P / c1 c2 X | e1 e2 X P / a1 a2 a3 X | d1 d2 d3 X
+ *     descending: order 0, 3, 2, 4, 1; rank 0, 4, 2, 1, 3; widths 4, 3, 1; bucket offsets 0, 8, 14, 15; P = 15
+ *                 rows a1 a2 a3 X / d1 d2 d3 X | c1 c2 X / e1 e2 X | X
+ *     The padded entry writes 20 positions for the same batch.
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap < P.  *total_tokens, *total_positions and *n_cut then hold the required figures, all from the one call; nothing is
+ * promised in the outputs.  n_docs * L entries ALWAYS suffice.
+ *   tkz_encode_batch_bucketed_device: device buffers.  d_mask (out_cap bytes), d_pos (out_cap entries), d_out_offsets (n_docs + 1) and d_rank (n_docs) may each be
+ *     NULL; d_out_ids (out_cap entries), d_lens and d_order (n_docs entries), d_bucket_offsets (n_buckets + 1), d_bucket_widths (n_buckets) and the three scalars
+ *     may not (TKZ_E_ARG).  Nothing is written at or behind P (ids, mask, pos), n_docs (lens, order, rank), n_docs + 1 (offsets), n_buckets (widths) or
+ *     n_buckets + 1 (bucket offsets).  An empty batch (n_docs == 0) is TKZ_OK: bucket_offsets[0] and out_offsets[0] cleared on the stream, all three scalars 0.
+ *     Everything else -- special tokens, TKZ_E_UNSUPPORTED, device-side errors, an attempt that is run again inside the call writing nothing of the caller's,
+ *     workspace growth, returning after the stream has drained -- as tkz_encode_batch_padded_device.
+ *     The launch sequence is the padded call's up to and including k_pad_lens, unchanged.  Then, without a host wait: a stable LSD radix sort of (len, document)
+ *     -- 8 bits a pass, as many passes as the bytes L occupies (L = 512: two), k_bkt_hist, a scan and k_bkt_scatter each; 36 bytes of workspace a document --,
+ *     k_bkt_table (W_b and R_b * W_b; maxlen_b is the bucket's first or last sorted row), a 64-bit scan (the offsets and P), and k_bkt_write (the capacity check
+ *     on the device, the rows by output position in tiles of 1,024 with the width looked up per bucket).
+ *   tkz_encode_batch_bucketed_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as
+ *     tkz_encode_batch_padded_utf8.  mask, pos, out_offsets and rank may be NULL.  The rows (P positions), the mask, pos, lens, order, rank, the bucket arrays and
+ *     the offsets are downloaded, NEVER the uncut ids.
+ *   tkz_encode_batch_bucketed_utf16: code units in, transcoded on the device as tkz_encode_batch_padded_utf16; unit_offsets in code units.
+ * There is no bucketing by a TOKEN budget (rows * width <= T: a chain of dependent searches, the open problem of the one-wavefront chunk chains), no item-granular
+ * cut, no maximum per document, no _begin / _end form, no chunk pipeline for the host entries, no single-text form and no device-resident UTF-16 input. */
+typedef enum tkz_bucket_order { TKZ_BUCKET_ASCENDING = 0, TKZ_BUCKET_DESCENDING = 1 } tkz_bucket_order;
+tkz_status tkz_encode_batch_bucketed_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                            const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                            int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int64_t bucket_rows, int32_t order, int32_t* d_out_ids,
+                                            int64_t out_cap, uint8_t* d_mask, int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets, int64_t* d_order,
+                                            int64_t* d_rank, int64_t* d_bucket_offsets, int32_t* d_bucket_widths, void* hip_stream, int64_t* total_tokens,
+                                            int64_t* total_positions, int64_t* n_cut);
+tkz_status tkz_encode_batch_bucketed_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                          int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                          int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens,
+                                          int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int32_t* bucket_widths,
+                                          int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut);
+tkz_status tkz_encode_batch_bucketed_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                           int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                           int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens,
+                                           int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int32_t* bucket_widths,
+                                           int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut);
+/* informational: successful calls of the bucketed entries */
+void tkz_encoder_bucketed_calls(const tkz_encoder* e, int64_t* calls);
 
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
@@ -749,7 +813,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * (tkz_encode_batch_chunks_device) likewise: k_docoffs over the pieces and the chunk stage (the two walks, their scan, the unit counts, k_chunk_units).
  * Of a packed call (tkz_encode_batch_packed_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the documents and the packing stage behind it
  * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.  Of a padded call (tkz_encode_batch_padded_device)
- * likewise: k_docoffs over the documents, k_pad_lens and k_pad_write.
+ * likewise: k_docoffs over the documents, k_pad_lens and k_pad_write; of a bucketed call (tkz_encode_batch_bucketed_device): k_docoffs, k_pad_lens, the sort's
+ * passes, k_bkt_table, its scan and k_bkt_write.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

@@ -10,6 +10,7 @@
 //                              EncodeChunksOverlap / EncodeChunksOverlapBatch (+ Utf16): the same with an overlap of at most `overlap` tokens between neighbours
 //                              EncodeBatchPacked (std::string, std::u16string): the ids framed by bos / eos ids in rows of the context length, pos, seg_starts
 //                              EncodeBatchPadded (std::string, std::u16string): a row a text, cut to maxLength, framed, padded to a common width; mask, pos, lens
+//                              EncodeBatchBucketed (std::string, std::u16string): the same rows sorted by length, a width per bucket of bucketRows rows; order, rank
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -612,6 +613,34 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return padded_batch<uint16_t>(units, offs, maxLength, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
     }
+    // ---- length-bucketed padded rows: the padded rows of the texts sorted by length, every bucket of bucketRows rows at its own width, in ONE call
+    // (tkz_encode_batch_bucketed_utf8 / _utf16) ----
+    // EncodeBatchPadded's arguments and two more: bucketRows (1 .. 2^31 - 1) and order.  The texts are sorted by their content length -- ascending or descending,
+    // equal lengths keep the texts' order --, cut into buckets of bucketRows sorted rows, and every bucket is padded to ITS OWN longest row (rounded up to padMultiple,
+    // at most maxLength; padMultiple 0: to maxLength itself).  Bucket b is ids / mask / pos [bucket_offsets[b], bucket_offsets[b + 1]): rows(b) x bucket_widths[b],
+    // row-major; its row i is text order[b * bucketRows + i]; rank is the inverse of order; lens are in the texts' order (tkz.h states the rule).
+    struct BucketedRows {
+        int64_t total_positions = 0, total_tokens = 0, n_cut = 0, bucket_rows = 0;
+        std::vector<int32_t> ids, pos, lens, bucket_widths; std::vector<uint8_t> mask; std::vector<int64_t> order, rank, bucket_offsets;
+        int64_t buckets() const { return static_cast<int64_t>(bucket_widths.size()); }
+        int64_t rows(int64_t b) const { return std::min<int64_t>(bucket_rows, static_cast<int64_t>(order.size()) - b * bucket_rows); }
+    };
+    BucketedRows EncodeBatchBucketed(const std::vector<std::string>& texts, int64_t maxLength, int64_t bucketRows, tkz_bucket_order order = TKZ_BUCKET_ASCENDING,
+                                     const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1, int32_t pad = 0,
+                                     tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return bucketed_batch<uint8_t>(bytes, offs, maxLength, bucketRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, false);
+    }
+    BucketedRows EncodeBatchBucketed(const std::vector<std::u16string>& texts, int64_t maxLength, int64_t bucketRows, tkz_bucket_order order = TKZ_BUCKET_ASCENDING,
+                                     const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1, int32_t pad = 0,
+                                     tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return bucketed_batch<uint16_t>(units, offs, maxLength, bucketRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
+    }
     // (the id of a registered special token, for bos / eos)
     int32_t SpecialTokenId(const std::string& literal) const {
         for (const auto& kv : specials_) if (kv.first == literal) return kv.second;
@@ -856,6 +885,46 @@ private:
         out.pos.resize(out.ids.size());
         out.mask.resize(out.ids.size());
         out.lens.resize(static_cast<size_t>(n));
+        return out;
+    }
+    // ONE call of the batch bucketed entry on the concatenated texts, with the capacity that always suffices (tkz.h): a row of maxLength a text
+    template <class UNIT>
+    BucketedRows bucketed_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, int64_t maxLength, int64_t bucketRows, tkz_bucket_order order,
+                                const std::vector<std::string>& allowedSpecial, int32_t bos, int32_t eos, int32_t pad, tkz_trim_side cutSide, tkz_pad_side padSide,
+                                int64_t padMultiple, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        BucketedRows out;
+        out.bucket_rows = bucketRows;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = maxLength >= 1 && maxLength <= INT32_MAX ? n * maxLength : 0;      // (a maxLength out of range is refused by the library)
+        const int64_t nb = bucketRows >= 1 ? (n + bucketRows - 1) / bucketRows : 0;            // (... and so are bucketRows)
+        if (items.empty()) items.push_back(0);
+        out.ids.resize(static_cast<size_t>(std::max<int64_t>(cap, 1)));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(std::max<int64_t>(n, 1)));
+        out.order.resize(out.lens.size());
+        out.rank.resize(out.lens.size());
+        out.bucket_offsets.resize(static_cast<size_t>(nb) + 1);
+        out.bucket_widths.resize(static_cast<size_t>(std::max<int64_t>(nb, 1)));
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_bucketed_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos,
+                                                        eos, maxLength, cutSide, padSide, pad, padMultiple, bucketRows, order, out.ids.data(), cap, out.mask.data(), out.pos.data(),
+                                                        out.lens.data(), nullptr, out.order.data(), out.rank.data(), out.bucket_offsets.data(), out.bucket_widths.data(),
+                                                        &out.total_tokens, &out.total_positions, &out.n_cut);
+        else st = tkz_encode_batch_bucketed_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                                 maxLength, cutSide, padSide, pad, padMultiple, bucketRows, order, out.ids.data(), cap, out.mask.data(), out.pos.data(),
+                                                 out.lens.data(), nullptr, out.order.data(), out.rank.data(), out.bucket_offsets.data(), out.bucket_widths.data(),
+                                                 &out.total_tokens, &out.total_positions, &out.n_cut);
+        check(st);
+        out.ids.resize(static_cast<size_t>(out.total_positions));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(n));
+        out.order.resize(static_cast<size_t>(n));
+        out.rank.resize(static_cast<size_t>(n));
+        out.bucket_widths.resize(static_cast<size_t>(nb));
         return out;
     }
     // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text

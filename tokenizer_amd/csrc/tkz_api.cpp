@@ -110,7 +110,8 @@ struct CounterBlock {          // mirrors the device block
     int64_t n_chunks;                      // the chunk entries: chunks of the whole batch (k_chunk_walk's writing pass)
     unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
     int64_t pack_total, pack_rows, pack_segs;   // the packed entries: T, n_rows (k_pack_count) and n_segs (the scan of its counts) -- PackParams::totals
-    int64_t pad_total, pad_width, pad_cut;      // the padded entries: the uncut total, W and n_cut (k_pad_write) -- PadParams::totals
+    int64_t pad_total, pad_width, pad_cut;      // the padded entries: the uncut total, W and n_cut (k_pad_write) -- PadParams::totals; the bucketed entries: the
+                                                // uncut total, P and n_cut (k_bkt_write)
     // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
     int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
 };
@@ -229,7 +230,13 @@ struct PadBufs {    // the padded entries: the uncut ids and their offsets, the 
     DevBuf pd_ids, pd_offs, pd_src, pd_part, pd_tot, pd_stage;
     void release() { release_each({&pd_ids, &pd_offs, &pd_src, &pd_part, &pd_tot, &pd_stage}); }
 };
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs {
+struct BktBufs {    // the bucketed entries (beside PadBufs, which they use as the padded entries do): the sort's keys and documents, twice, and lens and src of the
+    // sorted rows behind them; the digit counts of every tile and their bases; the block sums of the scans; R_b * W_b and the offsets of every bucket; the host
+    // entries' order, rank, widths and offsets
+    DevBuf bk_keys, bk_idx, bk_hist, bk_base, bk_bsum, bk_cnt, bk_boffs, bk_stage;
+    void release() { release_each({&bk_keys, &bk_idx, &bk_hist, &bk_base, &bk_bsum, &bk_cnt, &bk_boffs, &bk_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs, BktBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -283,7 +290,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release(); BktBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -326,6 +333,7 @@ struct tkz_encoder {
     std::atomic<int64_t> spec_batches{0}, spec_literals{0};                // tkz_encoder_special_stats
     std::atomic<int64_t> packed_calls{0};                                 // tkz_encoder_packed_calls: successful calls of the packed entries
     std::atomic<int64_t> padded_calls{0};                                 // tkz_encoder_padded_calls: successful calls of the padded entries
+    std::atomic<int64_t> bucketed_calls{0};                               // tkz_encoder_bucketed_calls: successful calls of the bucketed entries
     std::atomic<int64_t> chunks_overlap_calls{0};                          // tkz_encoder_chunks_overlap_calls: successful calls of the overlap chunk entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
@@ -389,6 +397,10 @@ struct PackCall { int32_t bos_id, eos_id; int64_t row_len; int32_t pad_id; int32
 // (device; mask and pos may be null -- and BatchCall::d_out_offs too) and, on the host, where the width and the number of cut documents go
 struct PadCall { int32_t bos_id, eos_id; int64_t max_len; int32_t cut_side, pad_side, pad_id; int64_t pad_multiple; uint8_t* d_mask; int32_t* d_pos; int32_t* d_lens;
                  int64_t* width; int64_t* n_cut; };
+// A call of one of the bucketed entries: a PadCall (BatchCall::padded is set as well: its width receives P) and the rows a bucket, the direction, and where the
+// permutation, its inverse (may be null) and the bucket table go (device)
+struct BktCall { int64_t bucket_rows; int32_t order; int64_t* d_order; int64_t* d_rank; int64_t* d_bucket_offs; int32_t* d_bucket_widths;
+                 int64_t buckets(int64_t n_docs) const { return (n_docs + bucket_rows - 1) / bucket_rows; } };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -401,7 +413,8 @@ enum class CallKind {
     Spans,           // tkz_encode_batch_spans_device: Pieces with the piece arrays in the workspace and the ids in the caller's buffer, then the position of every token
     Chunks,          // tkz_encode_batch_chunks_device: as Spans, then the chunk table
     Packed,          // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
-    Padded           // tkz_encode_batch_padded_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a document
+    Padded,          // tkz_encode_batch_padded_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a document
+    Bucketed         // tkz_encode_batch_bucketed_device: as Padded up to the lengths, then the documents sorted by length and a width per bucket of rows
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -418,7 +431,8 @@ struct BatchCall {
     const SpanCall* spans = nullptr;           // Spans: where the positions go (pieces points at the workspace's piece arrays as well)
     const ChunkCall* chunks = nullptr;         // Chunks: the budget and where the table goes (pieces likewise)
     const PackCall* packed = nullptr;          // Packed: the framing, the row length and where pos and seg_starts go
-    const PadCall* padded = nullptr;           // Padded: the framing, the cut, the padding and where the mask, pos and lens go
+    const PadCall* padded = nullptr;           // Padded, Bucketed: the framing, the cut, the padding and where the mask, pos and lens go
+    const BktCall* bucketed = nullptr;         // Bucketed: the rows a bucket, the direction and where the permutation and the bucket table go
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -428,7 +442,7 @@ struct BatchCall {
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded || kind == CallKind::Bucketed ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -991,8 +1005,18 @@ tkz::PadParams pad_params(Workspace* ws, const BatchCall& c, const int64_t* gran
                           reinterpret_cast<int64_t*>(part + tkz::kPadGridMax), 0, totals, blk};
 }
 
+// the stage of a bucketed call: the padded stage's arguments and the workspace of the sort and the table (bucketed_on_device sizes it)
+tkz::BktParams bkt_params(Workspace* ws, const BatchCall& c, const int64_t* grand, int64_t* totals, const int32_t* blk) {
+    const BktCall& k = *c.bucketed;
+    const int64_t n = std::max<int64_t>(c.n_docs, 1), nt = tkz::bkt_sort_tiles(c.n_docs);
+    return tkz::BktParams{pad_params(ws, c, grand, totals, blk), k.bucket_rows, k.buckets(c.n_docs), k.order, 0, k.d_order, k.d_rank, k.d_bucket_offs, k.d_bucket_widths,
+                          ws->bk_keys.as<uint32_t>(), ws->bk_idx.as<int64_t>(), ws->bk_keys.as<uint32_t>() + n, ws->bk_idx.as<int64_t>() + n, ws->bk_hist.as<int32_t>(),
+                          ws->bk_base.as<int64_t>(), ws->bk_bsum.as<int64_t>(), ws->bk_base.as<int64_t>() + 256 * nt, ws->bk_cnt.as<int64_t>(), ws->bk_boffs.as<int64_t>(),
+                          reinterpret_cast<int32_t*>(ws->bk_keys.as<uint32_t>() + 2 * n), ws->bk_idx.as<int64_t>() + 2 * n};
+}
+
 // A padded call on a batch without bytes: every document is its framing alone (all of them empty: W = 0 without framing), and the stage runs over offsets that
-// are all 0.  Without documents there is nothing but the offset to clear.
+// are all 0.  Without documents there is nothing but the offset to clear.  A bucketed call likewise (its first bucket offset is cleared as well).
 tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t* totals3) {
     using namespace tkz;
     const int64_t n_docs = c.n_docs;
@@ -1002,6 +1026,7 @@ tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t*
     if (n_docs == 0) {
         launch_counts3(L, 0, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
         if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, sizeof(int64_t), c.stream));
+        if (c.bucketed) HIP_TRY(hipMemsetAsync(c.bucketed->d_bucket_offs, 0, sizeof(int64_t), c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));
         return TKZ_OK;
     }
@@ -1009,7 +1034,8 @@ tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t*
     HIP_TRY(hipMemsetAsync(ws->pd_tot.p, 0, 64, c.stream));
     HIP_TRY(hipMemsetAsync(ws->pd_offs.p, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
     int64_t* const tot = ws->pd_tot.as<int64_t>();
-    launch_pad(L, pad_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
+    if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
+    else launch_pad(L, pad_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
     launch_counts3(L, n_docs, 0, tot, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
     HIP_TRY(hipMemcpyAsync(totals3, tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
@@ -1200,7 +1226,8 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                 launch_counts3(L, n_docs, total, totals, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else if (c.padded) {                                      // (the uncut offsets, then the rows; the counts blocks receive the uncut total)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, ws->pd_offs.as<int64_t>(), has_empty);
-                launch_pad(L, pad_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
+                if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
+                else launch_pad(L, pad_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
                 launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
@@ -1378,6 +1405,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         if (total_tokens) *total_tokens = totals3[0];
         if (k.width) *k.width = totals3[1];
         if (k.n_cut) *k.n_cut = totals3[2];
+        if (c.bucketed) return totals3[1] > c.out_cap ? fail(TKZ_E_CAPACITY, "output capacity too small for the rows") : TKZ_OK;      // (totals3[1]: P, the positions)
         if (totals3[1] > 0 && n_docs > c.out_cap / totals3[1]) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
         return TKZ_OK;
     };
@@ -3505,6 +3533,172 @@ tkz_status tkz_encode_batch_padded_utf16(tkz_encoder* e, const uint16_t* units, 
 }
 void tkz_encoder_padded_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->padded_calls.load() : 0;
+}
+
+// ---- length-bucketed padded rows: the padded rows of the documents sorted by length, every bucket of bucket_rows rows at its own width (tkz.h: the rule) ----
+
+namespace {
+tkz_status check_bkt_args(int64_t bucket_rows, int32_t order) {
+    if (bucket_rows < 1 || bucket_rows > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "bucketed rows: bucket_rows must be in [1, 2^31 - 1]");
+    if (order != TKZ_BUCKET_ASCENDING && order != TKZ_BUCKET_DESCENDING) return fail(TKZ_E_ARG, "bucketed rows: order must be TKZ_BUCKET_ASCENDING or TKZ_BUCKET_DESCENDING");
+    return TKZ_OK;
+}
+const char* const kMsgBktPointers = "bucketed rows: null ids, lens, order, bucket table or scalar pointer";
+// the bucketed call on device buffers, on a workspace the entry holds: the padded call's sequence with the sort, the table and the rows behind k_pad_lens
+tkz_status bucketed_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, BktCall bc, const SpecialCall* sp, int64_t* total_tokens, int64_t* total_positions,
+                              int64_t* n_cut) {
+    int64_t* acc = &ws->bytes_allocated;
+    if (c.n_docs < 0 || c.total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    const int64_t n = std::max<int64_t>(c.n_docs, 1), nt = tkz::bkt_sort_tiles(c.n_docs), nb = bc.buckets(c.n_docs);
+    if (c.total > 0) HIP_TRY(ws->pd_ids.ensure((size_t)c.total * 4, acc));
+    HIP_TRY(ws->pd_offs.ensure((size_t)(c.n_docs + 1) * 8, acc));
+    HIP_TRY(ws->pd_src.ensure((size_t)n * 8, acc));
+    HIP_TRY(ws->pd_part.ensure((size_t)tkz::kPadGridMax * 12, acc));
+    HIP_TRY(ws->bk_keys.ensure((size_t)n * 3 * 4, acc));      // (key_a, key_b, slen)
+    HIP_TRY(ws->bk_idx.ensure((size_t)n * 3 * 8, acc));       // (idx_a, idx_b, ssrc)
+    HIP_TRY(ws->bk_hist.ensure((size_t)nt * 256 * 4, acc));
+    HIP_TRY(ws->bk_base.ensure((size_t)(nt * 256 + 1) * 8, acc));
+    HIP_TRY(ws->bk_bsum.ensure((size_t)(std::max(nt * 256, nb) / tkz::kScanBlock + 2) * 8, acc));
+    HIP_TRY(ws->bk_cnt.ensure((size_t)std::max<int64_t>(nb, 1) * 8, acc));
+    HIP_TRY(ws->bk_boffs.ensure((size_t)(nb + 1) * 8, acc));
+    int64_t p = 0, cut = 0;
+    pc.width = &p; pc.n_cut = &cut;
+    c.kind = CallKind::Bucketed; c.padded = &pc; c.bucketed = &bc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (total_positions) *total_positions = p;
+    if (n_cut) *n_cut = cut;
+    if (st == TKZ_OK) { ++e->bucketed_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a bucketed host entry, with the batch on the device as UTF-8: staging for the rows (n_docs * max_len positions at most), the offsets, pos,
+// lens, the mask, order, rank and the bucket table, ONE bucketed call, the results back -- P entries of the rows, never the uncut ids.
+tkz_status bucketed_staged(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, BktCall bc, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap, uint8_t* mask,
+                           int32_t* pos, int32_t* lens, int64_t* out_offsets, int64_t* order, int64_t* rank, int64_t* bucket_offsets, int32_t* bucket_widths,
+                           int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut) {
+    const int64_t n_docs = c.n_docs, nb = bc.buckets(n_docs);
+    const bool fits = n_docs == 0 || out_cap / pc.max_len >= n_docs;      // (n_docs * max_len always suffices: more capacity is never used)
+    c.out_cap = fits ? n_docs * pc.max_len : out_cap;
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1), nl = std::max<int64_t>(n_docs, 1);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap, out_offsets != nullptr));
+    HIP_TRY(ws->pd_stage.ensure((size_t)(pos ? cap : 0) * 4 + (size_t)nl * 4 + (size_t)(mask ? cap : 0), &ws->bytes_allocated));
+    HIP_TRY(ws->bk_stage.ensure((size_t)nl * 16 + (size_t)(nb + 1) * 8 + (size_t)(nb + 1) * 4, &ws->bytes_allocated));
+    int32_t* const d_pos = ws->pd_stage.as<int32_t>();
+    int32_t* const d_lens = d_pos + (pos ? cap : 0);
+    uint8_t* const d_mask = reinterpret_cast<uint8_t*>(d_lens + nl);
+    int64_t* const d_order = ws->bk_stage.as<int64_t>();
+    int64_t* const d_rank = d_order + nl;
+    int64_t* const d_boffs = d_rank + nl;
+    int32_t* const d_widths = reinterpret_cast<int32_t*>(d_boffs + nb + 1);
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = out_offsets ? ws->s_outoffs[0].as<int64_t>() : nullptr;
+    pc.d_mask = mask ? d_mask : nullptr; pc.d_pos = pos ? d_pos : nullptr; pc.d_lens = d_lens;
+    bc.d_order = d_order; bc.d_rank = rank ? d_rank : nullptr; bc.d_bucket_offs = d_boffs; bc.d_bucket_widths = d_widths;
+    const tkz_status st = bucketed_on_device(e, ws, c, pc, bc, sp, total_tokens, total_positions, n_cut);
+    if (st != TKZ_OK) return st;
+    const int64_t n = *total_positions;
+    TKZ_TRY(fetch(ws, out_ids, n, out_offsets, n_docs));
+    HIP_TRY(hipMemcpy(bucket_offsets, d_boffs, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost));
+    if (n_docs) {
+        HIP_TRY(hipMemcpy(lens, d_lens, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(order, d_order, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        if (rank) HIP_TRY(hipMemcpy(rank, d_rank, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bucket_widths, d_widths, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    }
+    if (pos && n) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (mask && n) HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_bucketed_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                            const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                            int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int64_t bucket_rows, int32_t order, int32_t* d_out_ids,
+                                            int64_t out_cap, uint8_t* d_mask, int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets, int64_t* d_order,
+                                            int64_t* d_rank, int64_t* d_bucket_offsets, int32_t* d_bucket_widths, void* hip_stream, int64_t* total_tokens,
+                                            int64_t* total_positions, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    if (!d_out_ids || !d_lens || !d_order || !d_bucket_offsets || !d_bucket_widths || !total_tokens || !total_positions || !n_cut) return fail(TKZ_E_ARG, kMsgBktPointers);
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (!d_doc_offsets || (total_bytes > 0 && !d_bytes)) return fail(TKZ_E_ARG, "null device buffer");      // (d_out_offsets may be null here)
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    Lease lease(e);
+    return bucketed_on_device(e, lease.ws, c, PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, d_mask, d_pos, d_lens, nullptr, nullptr},
+                              BktCall{bucket_rows, order, d_order, d_rank, d_bucket_offsets, d_bucket_widths}, sp, total_tokens, total_positions, n_cut);
+}
+
+tkz_status tkz_encode_batch_bucketed_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                          int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                          int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens,
+                                          int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int32_t* bucket_widths,
+                                          int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    if (!out_ids || !lens || !order_out || !bucket_offsets || !bucket_widths || !total_tokens || !total_positions || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgBktPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_padded_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return bucketed_staged(e, ws, staged_call(ws, n_docs, total, 0), PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr},
+                           BktCall{bucket_rows, order, nullptr, nullptr, nullptr, nullptr}, sp, out_ids, out_cap, mask, pos, lens, out_offsets, order_out, rank, bucket_offsets,
+                           bucket_widths, total_tokens, total_positions, n_cut);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_padded_utf16 does.
+tkz_status tkz_encode_batch_bucketed_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                           int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                           int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos, int32_t* lens,
+                                           int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int32_t* bucket_widths,
+                                           int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    if (!out_ids || !lens || !order_out || !bucket_offsets || !bucket_widths || !total_tokens || !total_positions || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgBktPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0;
+    const PadCall pc{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const BktCall bc{bucket_rows, order, nullptr, nullptr, nullptr, nullptr};
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    if (total == 0) {                                                   // (no units: the offsets, all 0, are byte offsets as they are -- the framing is still laid out)
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, nullptr));
+        TKZ_TRY(stage_in(ws, nullptr, 0, unit_offsets, n_docs));
+        return bucketed_staged(e, ws, staged_call(ws, n_docs, 0, 0), pc, bc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, order_out, rank, bucket_offsets, bucket_widths,
+                               total_tokens, total_positions, n_cut);
+    }
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return bucketed_staged(e, ws, c, pc, bc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, order_out, rank, bucket_offsets, bucket_widths, total_tokens, total_positions,
+                           n_cut);
+}
+void tkz_encoder_bucketed_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->bucketed_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

@@ -318,6 +318,36 @@ struct PadParams {
     const int32_t* counters;
 };
 void launch_pad(const Launch& L, PadParams K);
+// Length-bucketed padded rows (tkz_encode_batch_bucketed_device; tkz.h states the rule): the padded call's sequence up to and including k_pad_lens -- UNCHANGED:
+// pad.lens, pad.src, pad.part_cut, pad.out_offs --, then the documents sorted by len, a bucket table, and the rows with a width per bucket.
+//   The sort: a stable LSD radix sort of (key, document), key = len (ascending) or max_len - len (descending: ties keep ascending document index in both), 8 bits
+//   a pass, npass = the bytes max_len occupies (the host knows it without waiting: 512 needs two passes).  A pass is k_bkt_hist (a workgroup per tile of
+//   kBktSortTile keys: the tile's count of every digit into hist, DIGIT-MAJOR: hist[digit * ntiles + tile]), the exclusive scan of hist into hist_base
+//   (launch_scan2; scan_bsum: its block sums) and k_bkt_scatter (the same tile again: a key goes to hist_base[digit][tile] + its rank among the tile's EARLIER
+//   keys of its digit).  The first pass reads its keys from pad.lens, the last one stores the documents into `order` (the caller's) and the inverse into `rank`
+//   (the caller's, may be null); between them keys and documents ping-pong through key_a / idx_a and key_b / idx_b.
+//   The last pass also stores lens and src of every document at its SORTED row (slen, ssrc: n_docs entries each, workspace), which is what the table and the
+//   writer read.  Workspace a document: 4 + 8 bytes twice (key_a, idx_a, key_b, idx_b) and 4 + 8 (slen, ssrc).  A tile: 256 counts of 4 bytes (hist) and 256 bases of 8 (hist_base); LDS a workgroup:
+//   16 KB (a count per group of 64 keys and digit) + 2 KB (the tile's bases).
+//   k_bkt_table, a lane a bucket of bucket_rows sorted rows: maxlen_b is the len (slen) of the bucket's last (ascending) or first (descending) row, W_b from it as the
+//   padded rule makes W, widths[b] = W_b (the caller's), bkt_cnt[b] = R_b * W_b (int64, workspace).  The 64-bit scan kernels (k_scan_partials64, k_scan_top,
+//   k_scan_final64) make boffs[0 .. n_buckets] of it (workspace; the last entry is P).
+//   k_bkt_write: boffs copied to bucket_offs (the caller's), one lane stores totals = {*grand, P, n_cut} (n_cut from pad.part_cut), and when P <= out_cap the rows
+//   by output position in tiles of kBktTile, a wavefront each, grid-strided: one search over boffs a tile, then bucket, row and column carried forward.
+// counters: as PadParams -- with an error bit nothing of the caller's is touched.
+constexpr int kBktSortTile = 1024;     // keys a workgroup of k_bkt_hist / k_bkt_scatter (kBktSortTile / 64 groups of 64, four a wavefront)
+constexpr int kBktTile = 1024;         // output positions a wavefront of k_bkt_write
+struct BktParams {
+    PadParams pad;
+    int64_t bucket_rows, n_buckets; int32_t descending, npass;
+    int64_t* order; int64_t* rank; int64_t* bucket_offs; int32_t* widths;
+    uint32_t* key_a; int64_t* idx_a; uint32_t* key_b; int64_t* idx_b;
+    int32_t* hist; int64_t* hist_base; int64_t* scan_bsum; int64_t* hist_total;
+    int64_t* bkt_cnt; int64_t* boffs; int32_t* slen; int64_t* ssrc;
+};
+int bkt_passes(int64_t max_len);                               // 1 .. 4
+int64_t bkt_sort_tiles(int64_t n_docs);
+void launch_bucketed(const Launch& L, BktParams K);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

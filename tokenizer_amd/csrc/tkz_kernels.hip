@@ -5090,6 +5090,213 @@ void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, in
 }
 
 // -------------------------------------------------------------------------------------------------
+// Length-bucketed padded rows (tkz_encode_batch_bucketed_device; tkz.h states the rule), behind the padded call's sequence up to k_pad_lens, which is reused
+// unchanged (lens, src, the cut documents of every workgroup): the documents sorted by len, cut into buckets of bucket_rows sorted rows, every bucket padded to
+// ITS OWN longest row.
+//   k_bkt_hist     a pass of the stable LSD radix sort, 8 bits a pass: a workgroup per tile of kBktSortTile keys, the tile's count of every digit, digit-major.
+//   k_bkt_scatter  the same tile again behind the scan of the counts: key and document to base[digit][tile] + the key's rank among the tile's EARLIER keys of
+//                  its digit; the LAST pass stores the documents into `order`, the inverse into `rank`, and lens / src of every document at its SORTED row (slen,
+//                  ssrc: what the table and the writer read -- one dependent load less a row than through `order`).  Both kernels get that rank from tkz_bkt_rank: a wavefront owns four consecutive groups of 64 keys; inside a group the lanes
+//                  of one digit find each other with eight ballots (a lane's rank: the lanes below it in that set), the set's lowest lane stores its size into
+//                  s_cnt[group][digit]; after a barrier thread t turns column t into its exclusive prefix over the 16 groups -- the column's sum is the tile's
+//                  count of digit t --, after another a lane adds s_cnt[its group][its digit].  Nothing is added up in memory and no order depends on timing:
+//                  the sort gives the same permutation on every run.
+//   k_bkt_table    a lane a bucket: the longest len is that of the bucket's last (ascending) or first (descending) sorted row -- no reduction --, W_b, R_b * W_b.
+//   (k_scan_partials64, k_scan_top, k_scan_final64: the 64-bit scan of R_b * W_b -> the bucket offsets and P; R_b * W_b does not fit 32 bits.)
+//   k_bkt_write    the bucket offsets copied to the caller, {total, P, n_cut} stored by one lane, P held against out_cap HERE; then k_pad_write's loop with the
+//                  width looked up per bucket: a wavefront per tile of kBktTile output positions, grid-strided.  A tile finds its first bucket by ONE search
+//                  over the offsets (wave-uniform) and its row and column there by one 64-bit division; a lane then carries (bucket, row, column, positions
+//                  left in the bucket) forward by 64 positions with additions -- a 32-bit division only where it ENTERS a bucket narrower than 64 columns --
+//                  so a tile may span a hundred buckets and a row three tiles.  The next group's slen / ssrc and id are requested before this group's
+//                  stores.  Every store of a row is tkz_store_nt, all 64 lanes, consecutive addresses.
+// -------------------------------------------------------------------------------------------------
+TKZ_KERNEL(256) void k_pad_lens(PadParams K);
+constexpr int kBktGroups = kBktSortTile / 64, kBktPer = kBktSortTile / kThreads;
+// the keys of a thread: key j of the tile's group wave * kBktPer + j, lane-th of it; pass 0 makes them from lens
+TKZ_DEV void tkz_bkt_keys(const BktParams& K, const uint32_t* keys, int shift, int64_t* at, uint32_t* key, uint32_t* dig, bool* ok) {
+    const int64_t i0 = simt::bid() * kBktSortTile + simt::wave() * (kBktPer * 64) + simt::lane();
+#pragma unroll
+    for (int j = 0; j < kBktPer; ++j) {
+        const int64_t i = i0 + j * 64;
+        at[j] = i; ok[j] = i < K.pad.n_docs;
+        uint32_t k = 0;
+        if (ok[j]) k = keys ? keys[i] : (K.descending ? (uint32_t)(K.pad.max_len - K.pad.lens[i]) : (uint32_t)K.pad.lens[i]);
+        key[j] = k; dig[j] = (k >> shift) & 255u;
+    }
+}
+// rnk[j]: the number of the tile's keys IN FRONT of key j with its digit; the return value: the tile's keys with digit tid()
+TKZ_DEV int tkz_bkt_rank(int (*s_cnt)[256], const uint32_t* dig, const bool* ok, int* rnk) {
+    const int tid = simt::tid(), g0 = simt::wave() * kBktPer;
+    const uint64_t below = tkz_lowmask(simt::lane());
+    for (int g = 0; g < kBktGroups; ++g) s_cnt[g][tid] = 0;
+    simt::sync();
+#pragma unroll
+    for (int j = 0; j < kBktPer; ++j) {
+        uint64_t m = simt::ballot(ok[j]);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) { const bool bit = (dig[j] >> b) & 1u; const uint64_t has = simt::ballot(bit); m &= bit ? has : ~has; }
+        rnk[j] = tkz_popc64(m & below);
+        if (ok[j] && rnk[j] == 0) s_cnt[g0 + j][dig[j]] = tkz_popc64(m);
+    }
+    simt::sync();
+    int run = 0;
+    for (int g = 0; g < kBktGroups; ++g) { const int c = s_cnt[g][tid]; s_cnt[g][tid] = run; run += c; }
+    simt::sync();
+#pragma unroll
+    for (int j = 0; j < kBktPer; ++j) if (ok[j]) rnk[j] += s_cnt[g0 + j][dig[j]];
+    return run;
+}
+TKZ_KERNEL(256) void k_bkt_hist(BktParams K, int shift, const uint32_t* keys, int64_t ntiles) {
+    TKZ_SHARED int s_cnt[kBktGroups][256];
+    if (K.pad.counters[0] != 0) return;                        // (a failed attempt: lens means nothing)
+    int64_t at[kBktPer]; uint32_t key[kBktPer], dig[kBktPer]; bool ok[kBktPer]; int rnk[kBktPer];
+    tkz_bkt_keys(K, keys, shift, at, key, dig, ok);
+    K.hist[(int64_t)simt::tid() * ntiles + simt::bid()] = tkz_bkt_rank(s_cnt, dig, ok, rnk);
+}
+TKZ_KERNEL(256) void k_bkt_scatter(BktParams K, int shift, const uint32_t* keys, const int64_t* idx, uint32_t* keys_out, int64_t* idx_out, int64_t ntiles, int last) {
+    TKZ_SHARED int s_cnt[kBktGroups][256];
+    TKZ_SHARED int64_t s_base[256];
+    if (K.pad.counters[0] != 0) return;
+    int64_t at[kBktPer]; uint32_t key[kBktPer], dig[kBktPer]; bool ok[kBktPer]; int rnk[kBktPer];
+    tkz_bkt_keys(K, keys, shift, at, key, dig, ok);
+    s_base[simt::tid()] = K.hist_base[(int64_t)simt::tid() * ntiles + simt::bid()];
+    (void)tkz_bkt_rank(s_cnt, dig, ok, rnk);                   // (its barriers order s_base as well)
+    const int64_t n = K.pad.n_docs;
+#pragma unroll
+    for (int j = 0; j < kBktPer; ++j) {
+        if (!ok[j]) continue;
+        const int64_t to = s_base[dig[j]] + rnk[j], d = idx ? idx[at[j]] : at[j];
+        if (to < 0 || to >= n || d < 0 || d >= n) continue;      // (never, by construction: nothing is stored outside the arrays whatever the counts say)
+        if (keys_out) keys_out[to] = key[j];
+        idx_out[to] = d;
+        if (last) { K.slen[to] = K.pad.lens[d]; K.ssrc[to] = K.pad.src[d]; if (K.rank) K.rank[d] = to; }      // (the rows' lens and src in SORTED order: the writer's)
+    }
+}
+TKZ_KERNEL(256) void k_bkt_table(BktParams K) {
+    const PadParams& Q = K.pad;
+    const int64_t b = simt::bid() * simt::nthreads() + simt::tid(), n = Q.n_docs;
+    if (b >= K.n_buckets) return;
+    int64_t cnt = 0;
+    if (Q.counters[0] == 0) {
+        const int64_t r0 = b * K.bucket_rows, r1 = r0 + K.bucket_rows < n ? r0 + K.bucket_rows : n;
+        const int64_t longest = K.slen[K.descending ? r0 : r1 - 1], L = Q.max_len, M = Q.pad_multiple;
+        int64_t W = 0;
+        if (longest > 0) { W = M == 0 ? L : (longest + M - 1) / M * M; W = W < L ? W : L; }
+        K.widths[b] = (int32_t)W;
+        cnt = (r1 - r0) * W;
+    }
+    K.bkt_cnt[b] = cnt;
+}
+// a lane's place in the rows: bucket b (its first sorted row r0, its width W), row i and column c of it, and the positions from here to the bucket's end
+struct BktCursor { int64_t b, r0, left; uint32_t W, i, c, rstep, cstep; };
+TKZ_DEV void tkz_bkt_enter(const BktParams& K, BktCursor& s) {      // W, the steps of 64 positions and the bucket's positions for bucket s.b
+    const int64_t rows = s.r0 + K.bucket_rows < K.pad.n_docs ? K.bucket_rows : K.pad.n_docs - s.r0;
+    s.W = (uint32_t)K.widths[s.b];
+    s.left = rows * (int64_t)s.W;
+    s.i = 0; s.c = 0;
+    s.rstep = s.W && s.W < 64u ? 64u / s.W : 0u; s.cstep = s.W && s.W < 64u ? 64u % s.W : 64u;
+}
+TKZ_DEV void tkz_bkt_step(const BktParams& K, BktCursor& s, uint32_t delta) {      // delta <= 64 positions on; the position stays below P
+    while ((int64_t)delta >= s.left) {
+        if (s.b + 1 >= K.n_buckets) { s.left = INT64_MAX; return; }      // (never below P)
+        delta -= (uint32_t)s.left;
+        ++s.b; s.r0 += K.bucket_rows;
+        tkz_bkt_enter(K, s);
+    }
+    s.left -= delta;
+    if (s.W >= 64u) { s.c += delta; if (s.c >= s.W) { s.c -= s.W; ++s.i; } }
+    else if (delta == 64u) { s.i += s.rstep; s.c += s.cstep; if (s.c >= s.W) { s.c -= s.W; ++s.i; } }
+    else { const uint32_t x = s.c + delta; s.i += x / s.W; s.c = x % s.W; }
+}
+TKZ_KERNEL(256) void k_bkt_write(BktParams K) {
+    const PadParams& Q = K.pad;
+    if (Q.counters[0] != 0) return;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t nb = K.n_buckets, n = Q.n_docs;
+    for (int64_t b = simt::bid() * simt::nthreads() + simt::tid(); b <= nb; b += simt::nblocks() * simt::nthreads()) K.bucket_offs[b] = K.boffs[b];
+    const int64_t P = K.boffs[nb];
+    if (wave0 == 0) {                                           // the cut documents, from k_pad_lens' partials
+        int64_t n_cut = 0;
+        for (int i = lane; i < Q.nparts; i += 64) n_cut += Q.part_cut[i];
+        for (int m = 32; m >= 1; m >>= 1) n_cut += tkz_shfl64(n_cut, lane ^ m);
+        if (lane == 0) { Q.totals[0] = *Q.grand; Q.totals[1] = P; Q.totals[2] = n_cut; }
+    }
+    if (P <= 0 || P > Q.out_cap) return;                        // (nothing to write; or the rows do not fit: the totals are all that is written)
+    const int64_t ntile = (P + kBktTile - 1) / kBktTile;
+    const int fb = Q.bos_id >= 0 ? 1 : 0, fe = Q.eos_id >= 0 ? 1 : 0;
+    for (int64_t t = wave0; t < ntile; t += nwaves) {
+        const int64_t q0 = t * kBktTile, q1 = q0 + kBktTile < P ? q0 + kBktTile : P;
+        BktCursor s;
+        s.b = tkz_last_le(K.boffs, 0, nb - 1, q0);             // (wave-uniform: one search a tile; offsets that repeat -- buckets of width 0 -- give the last)
+        s.r0 = s.b * K.bucket_rows;
+        tkz_bkt_enter(K, s);
+        {   // the tile's first position: one 64-bit division a tile, then the lane's own by a step
+            const int64_t rel = q0 - K.boffs[s.b], row = s.W ? rel / (int64_t)s.W : 0;
+            s.i = (uint32_t)row; s.c = (uint32_t)(rel - row * (int64_t)s.W); s.left -= rel;
+        }
+        int64_t cur = -1, src = 0;
+        int len = 0;
+        // what a lane stores at its position: the index inside the content (or -1: padding) and the id
+        bool live = q0 + lane < q1;
+        int32_t j = -1, v = Q.pad_id;
+        for (int64_t g = q0 - 64; g < q1; g += 64) {
+            // the NEXT group's values first: its loads are in flight while this group's are stored
+            const bool live2 = g + 64 + lane < q1;
+            int32_t j2 = -1, v2 = Q.pad_id;
+            if (live2) {
+                tkz_bkt_step(K, s, g < q0 ? (uint32_t)lane : 64u);
+                const int64_t r = s.r0 + s.i;
+                if (r != cur) { cur = r; len = r < n ? K.slen[r] : 0; src = r < n ? K.ssrc[r] : 0; }
+                const int64_t jj = (int64_t)s.c - (Q.pad_side ? (int64_t)s.W - len : 0);     // the index inside the content
+                if (jj >= 0 && jj < len) {
+                    j2 = (int32_t)jj;
+                    const int64_t a = src + jj - fb;
+                    if (fb && jj == 0) v2 = Q.bos_id;
+                    else if (fe && jj == len - 1) v2 = Q.eos_id;
+                    else if (a >= 0 && a < Q.ids_cap) v2 = tkz_load_nt(Q.ids + a);
+                }
+            }
+            if (g >= q0 && live) {
+                const int64_t q = g + lane;
+                tkz_store_nt(Q.out + q, v);
+                if (Q.mask) tkz_store_nt(Q.mask + q, (uint8_t)(j >= 0 ? 1 : 0));
+                if (Q.pos) tkz_store_nt(Q.pos + q, j >= 0 ? j : 0);
+            }
+            live = live2; j = j2; v = v2;
+        }
+    }
+}
+int bkt_passes(int64_t max_len) { int bits = 1; while (bits < 32 && (max_len >> bits) != 0) ++bits; return (bits + 7) / 8; }
+int64_t bkt_sort_tiles(int64_t n_docs) { return grid1(cdiv(n_docs, kBktSortTile)); }
+// (the bracket: K_DOCOFFS's again, as launch_pad.  P is known on the device only: the writing grid is sized for the positions the caller's buffer holds,
+//  n_docs * max_len at most -- beyond kPadGridMax workgroups k_pad_lens and k_bkt_write stride; the sort and the table have a workgroup a tile / 256 buckets)
+void launch_bucketed(const Launch& L, BktParams K) {
+    const auto capped = [](int64_t g) { return g < 1 ? 1 : (g > kPadGridMax ? kPadGridMax : g); };
+    const int64_t n = K.pad.n_docs, ntiles = bkt_sort_tiles(n);
+    const int64_t most = n > 0 && K.pad.out_cap / K.pad.max_len >= n ? n * K.pad.max_len : K.pad.out_cap;
+    K.pad.nparts = (int32_t)capped(cdiv(n, kThreads));
+    K.npass = bkt_passes(K.pad.max_len);
+    TKZ_LAUNCH(k_pad_lens, K.pad.nparts, kThreads, L.stream, K.pad);
+    for (int p = 0; p < K.npass; ++p) {
+        const bool last = p + 1 == K.npass;
+        const uint32_t* keys = p == 0 ? nullptr : (p & 1 ? K.key_a : K.key_b);
+        const int64_t* idx = p == 0 ? nullptr : (p & 1 ? K.idx_a : K.idx_b);
+        TKZ_LAUNCH(k_bkt_hist, ntiles, kThreads, L.stream, K, 8 * p, keys, ntiles);
+        launch_scan2(L, 256 * ntiles, K.scan_bsum, K.hist, K.hist_base, K.hist_total, 1, nullptr, nullptr, nullptr, 1, -1);
+        TKZ_LAUNCH(k_bkt_scatter, ntiles, kThreads, L.stream, K, 8 * p, keys, idx, last ? (uint32_t*)nullptr : (p & 1 ? K.key_b : K.key_a),
+                   last ? K.order : (p & 1 ? K.idx_b : K.idx_a), ntiles, last ? 1 : 0);
+    }
+    const int64_t nblk = grid1(cdiv(K.n_buckets, kScanBlock));
+    TKZ_LAUNCH(k_bkt_table, grid1(cdiv(K.n_buckets, kThreads)), kThreads, L.stream, K);
+    TKZ_LAUNCH(k_scan_partials64, nblk, kThreads, L.stream, (const int64_t*)K.bkt_cnt, K.n_buckets, K.scan_bsum);
+    TKZ_LAUNCH(k_scan_top, 1, kThreads, L.stream, K.scan_bsum, nblk, K.boffs + K.n_buckets);
+    TKZ_LAUNCH(k_scan_final64, nblk, kThreads, L.stream, (const int64_t*)K.bkt_cnt, K.n_buckets, (const int64_t*)K.scan_bsum, K.boffs);
+    TKZ_LAUNCH(k_bkt_write, capped(cdiv(cdiv(most, kBktTile), kThreads / 64)), kThreads, L.stream, K);
+    hook(L, K_DOCOFFS, 1);
+}
+
+// -------------------------------------------------------------------------------------------------
 // Padded rows (tkz_encode_batch_padded_device; tkz.h states the rule), behind the plain document-granular launch sequence: a row a document, cut to max_len,
 // framed, padded to the common width W on either side, with the mask and the position inside the content.  The uncut ids and offsets O stay in the workspace.
 //   k_pad_lens    a lane a document: n = O[d + 1] - O[d], k = min(n, L - f), lens[d] = k + f, src[d] = the index of the first kept id (O[d], or O[d + 1] - k
