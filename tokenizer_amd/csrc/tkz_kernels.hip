@@ -658,13 +658,16 @@ TKZ_DEV ProbeLds tkz_probe_lds(uint4* wave_quads, const uint4* kmask) {
     L.spec = nullptr;
     return L;
 }
-// byte mask of a zero-padded key of 0..12 bytes (three dwords): written by threads 0..12 of the workgroup, followed by a barrier
+// byte masks of the zero-padded keys, a row per length, written by threads 0..28 of the workgroup and followed by a barrier: rows 0..12 the three dwords of
+// a SHORT key; rows 13..28 dwords 3..6 of a MID key, whose first three are always whole (the pre-pass: one LDS read in place of four computed masks)
+constexpr int kProbeMaskRows = TKZ_MID_KEY_MAX + 1;
 TKZ_DEV void tkz_probe_kmask_init(uint4* s_kmask) {
-    if (simt::tid() <= TKZ_SHORT_KEY_MAX) {
+    if (simt::tid() < kProbeMaskRows) {
         const int len = simt::tid();
-        uint32_t m[3];
-        for (int i = 0; i < 3; ++i) { const int nb = len - 4 * i; m[i] = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u)); }
-        uint4 v; v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = 0;
+        const int first = len <= TKZ_SHORT_KEY_MAX ? 0 : 3;
+        uint32_t m[4];
+        for (int i = 0; i < 4; ++i) { const int nb = len - 4 * (first + i); m[i] = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u)); }
+        uint4 v; v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = first ? m[3] : 0u;
         s_kmask[len] = v;
     }
 }
@@ -676,19 +679,28 @@ TKZ_DEV void tkz_probe_request_text(const EncodeParams& P, int64_t sub, ProbeTex
     const int64_t base = sub * kSub;
     uint4 v0, v1;
     v0.x = v0.y = v0.z = v0.w = 0; v1 = v0;
-    const int64_t p0 = base + 16 * (int64_t)lane, p1 = base + 16 * (int64_t)(lane + 64);
-    if (p0 + 16 <= P.total) v0 = tkz_load16_nt(P.bytes + p0);
-    else {
-        uint32_t w[4] = {0, 0, 0, 0};
-        for (int j = 0; j < 16; ++j) if (p0 + j < P.total) w[j >> 2] |= (uint32_t)P.bytes[p0 + j] << (8 * (j & 3));
-        v0.x = w[0]; v0.y = w[1]; v0.z = w[2]; v0.w = w[3];
-    }
-    if (lane + 64 < (kSub + kHalo) / 16) {
-        if (p1 + 16 <= P.total) v1 = tkz_load16_nt(P.bytes + p1);
+    // (a scalar base and 32-bit lane offsets; `left`: the bytes of the sub-tile and its halo that the corpus holds -- wave-uniform)
+    const uint8_t* const tb = P.bytes + base;
+    const int64_t left64 = P.total - base;
+    const int left = left64 >= kSub + kHalo ? kSub + kHalo : (left64 < 0 ? 0 : (int)left64);
+    const uint32_t o0 = 16u * (uint32_t)lane, o1 = o0 + 1024u;
+    if (left == kSub + kHalo) {                              // an interior sub-tile, nearly every one: no bound a lane
+        v0 = tkz_load16_nt(tb + o0);
+        if (lane + 64 < (kSub + kHalo) / 16) v1 = tkz_load16_nt(tb + o1);
+    } else {                                                 // the corpus ends in here
+        if ((int)o0 + 16 <= left) v0 = tkz_load16_nt(tb + o0);
         else {
             uint32_t w[4] = {0, 0, 0, 0};
-            for (int j = 0; j < 16; ++j) if (p1 + j < P.total) w[j >> 2] |= (uint32_t)P.bytes[p1 + j] << (8 * (j & 3));
-            v1.x = w[0]; v1.y = w[1]; v1.z = w[2]; v1.w = w[3];
+            for (int j = 0; j < 16; ++j) if ((int)o0 + j < left) w[j >> 2] |= (uint32_t)tb[o0 + (uint32_t)j] << (8 * (j & 3));
+            v0.x = w[0]; v0.y = w[1]; v0.z = w[2]; v0.w = w[3];
+        }
+        if (lane + 64 < (kSub + kHalo) / 16) {
+            if ((int)o1 + 16 <= left) v1 = tkz_load16_nt(tb + o1);
+            else {
+                uint32_t w[4] = {0, 0, 0, 0};
+                for (int j = 0; j < 16; ++j) if ((int)o1 + j < left) w[j >> 2] |= (uint32_t)tb[o1 + (uint32_t)j] << (8 * (j & 3));
+                v1.x = w[0]; v1.y = w[1]; v1.z = w[2]; v1.w = w[3];
+            }
         }
     }
     tx->v0 = v0; tx->v1 = v1;
@@ -749,19 +761,35 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
     const bool prof = TKZ_DEV_FLAG(P, 16);
     long long t_0 = prof ? simt::clock() : 0, t_1 = 0, t_2 = 0, t_3 = 0;
     // ---- everything the wavefront needs from memory is requested first, in ONE round trip: the sub-tile (+ halo), 16 B per lane
-    // (the halo by lanes 0..3), the bitmap words one per lane, and the 64 bitmap words after the sub-tile in which the end of
-    // its last piece is looked for -- and only then consumed ----
+    // (the halo by lanes 0..3), the bitmap words one per lane, and the bitmap word after the sub-tile in which the end of its last
+    // piece is looked for (the batch kernels: one scalar; k_small: the 64 words after it, one per lane) -- and only then consumed ----
     // (the text itself was requested even earlier: by the caller, or while the sub-tile before this one was probed -- tx)
     uint4 v0 = tx.v0, v1 = tx.v1;
     uint64_t myword = 0, mymark = 0;                      // lanes 0..15: piece-start word / mark word of the sub-tile
     uint64_t myspec = 0;                                  // (SPECIAL: the starts of the taken literals)
-    if (lane < kSub / 64) {
-        const int64_t w = sub * (kSub / 64) + lane;
-        if (w < P.nwords) { myword = P.startbits[w]; mymark = P.docbits[w]; if (SPECIAL) myspec = P.specbits[w]; }
+    // (every bitmap word at a wave-uniform base plus the lane's 32-bit index, against a 32-bit count of the words that exist: no 64-bit address or
+    //  comparison a lane)
+    const int64_t wb = sub * (kSub / 64);
+    const int64_t wleft64 = P.nwords - wb;
+    const int wleft = wleft64 >= kSub / 64 ? kSub / 64 : (wleft64 < 0 ? 0 : (int)wleft64);      // the sub-tile's words that exist: all 16, but for the last sub-tile
+    if (lane < wleft) {
+        const uint32_t wl = (uint32_t)lane;
+        myword = (P.startbits + wb)[wl]; mymark = (P.docbits + wb)[wl]; if (SPECIAL) myspec = (P.specbits + wb)[wl];
     }
     const int64_t from = base + nb, w0 = from >> 6;        // the search for the end of the last piece starts here
-    uint64_t ahead = (w0 + lane < P.nwords) ? P.startbits[w0 + lane] : 0ull;
-    const int64_t pb = P.pbase[sub];
+    const int64_t aleft64 = P.nwords - w0;
+    const int aleft = aleft64 >= 64 ? 64 : (aleft64 < 0 ? 0 : (int)aleft64);                    // of the 64 words from w0 on, those that exist
+    // The batch kernels: the first of those words is at a wave-uniform address and nearly always holds a piece start (a piece is a few bytes long), so it is
+    // read as a scalar and searched on the scalar side; the 64 lanes' words are only asked for when it holds none.  k_small wrote the bitmap in this very
+    // launch -- a scalar cache may hold what was there before --: it keeps the lanes' loads.
+    int64_t last_end = -1;
+    uint64_t ahead = 0;
+    if constexpr (REPORT) { if (lane < aleft) ahead = (P.startbits + w0)[(uint32_t)lane]; }
+    else if (aleft > 0) {
+        const uint64_t v = simt::uniform64(P.startbits[w0]) & ~tkz_lowmask((int)(from & 63));
+        if (v) last_end = (w0 << 6) + tkz_ctz64(v);
+    }
+    const int64_t pb = (int64_t)simt::uniform64((uint64_t)P.pbase[sub]);
     // ---- consume ----
     { uint4* s4 = reinterpret_cast<uint4*>(s_bytes); s4[lane] = v0; if (lane + 64 < (kSub + kHalo) / 16) s4[lane + 64] = v1; }
     if (next >= 0) tkz_probe_request_text(P, next, &tx);
@@ -772,12 +800,11 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         if (SPECIAL) { LD.spec[2 * lane] = (uint32_t)myspec; LD.spec[2 * lane + 1] = (uint32_t)(myspec >> 32); }
     }
     // end of the last piece that starts here = first piece start at or after base+nb (the sentinel at `total` bounds it)
-    int64_t last_end;
-    {
+    if (last_end < 0) {
         int64_t found = -1;
         for (int64_t c = 0; found < 0; ++c) {
             const int64_t w = w0 + c * 64 + lane;
-            uint64_t v = c == 0 ? ahead : (w < P.nwords ? P.startbits[w] : 0);
+            uint64_t v = (REPORT && c == 0) ? ahead : (w < P.nwords ? P.startbits[w] : 0);
             if (w == w0) v &= ~tkz_lowmask((int)(from & 63));
             const uint64_t any = simt::ballot(v != 0);
             if (any) {
@@ -800,6 +827,15 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         if (lane == 0) s_pstart[np] = (uint16_t)last_end_rel;         // (sentinel: the length of piece k is s_pstart[k + 1] - s_pstart[k])
     }
     (void)simt::ballot(true);                              // (LDS written by other lanes of this wavefront is read below)
+    // nrec: the sub-tile's records that the buffer holds -- all np of them, unless the attempt is one to be thrown away.  What the wavefront has to say that
+    // does not depend on the lookups is said here, so that no pointer or bound it takes is held in scalar registers across the loops: the token count zeroed
+    // for the merge kernels of both streams, which add to it (launch_encode), and a record buffer that is too small.
+    const int64_t room64 = P.prank_cap - pb;
+    const int nrec = room64 < np ? (room64 < 0 ? 0 : (int)room64) : np;
+    if (lane == 0) {
+        if (!REPORT && P.tc_atomic) P.tile_count[sub] = 0;
+        if (room64 < np) simt::atomic_or((unsigned*)&P.counters[0], (unsigned)kErrCapacity);
+    }
     if (prof) t_1 = simt::clock();
     const char* tb0 = reinterpret_cast<const char*>(T.short_slots);
     const uint32_t mid_off = (uint32_t)(reinterpret_cast<const char*>(T.mid_slots) - tb0);   // (SHORT and MID share one allocation)
@@ -831,8 +867,17 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
         const bool is_lit = SPECIAL && valid && ((LD.spec[s >> 5] >> (s & 31)) & 1u);
         const bool is_mid = valid && len <= TKZ_MID_KEY_MAX && !is_lit;
         if (is_mid) {
+            // the key's seven dwords, zero-padded: eight aligned dwords read once, seven v_alignbit, and the masks of dwords 3..6 from the row of the
+            // key's length (13..28 here: the first three dwords are whole; the eighth dword ends at byte 1051 of the staged 1088 at the latest)
+            const int w = s >> 2;
+            const uint32_t sh = (uint32_t)(s & 3) * 8u;
+            uint32_t d[8];
 #pragma unroll
-            for (int i = 0; i < 7; ++i) kk[i] = tkz_key_dword(s_bytes, s, len, i);
+            for (int i = 0; i < 8; ++i) d[i] = s_bytes[w + i];
+#pragma unroll
+            for (int i = 0; i < 7; ++i) kk[i] = simt::alignbit(d[i + 1], d[i], sh);
+            const uint4 km = s_kmask[len];
+            kk[3] &= km.x; kk[4] &= km.y; kk[5] &= km.z; kk[6] &= km.w;
             uint32_t s1, s2;
             tkz_mid_slots(T, kk, (uint32_t)len, &s1, &s2);
             oa = mid_off + 32u * s1; ob = mid_off + 32u * s2;
@@ -851,8 +896,14 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
     if (prof) t_2 = simt::clock();
     // ---- the main loop: two batches of 64 pieces per iteration, their gathers in flight together (what a sub-tile costs is its count of
     // dependent round trips to the tables) ----
+    // (the lists and the records: wave-uniform bases and a lane's 32-bit byte offset -- a list has at most kMissCapMax entries)
     uint32_t* const ml = P.mlist + sub * (int64_t)P.mcap;
     uint4* const mq = P.mquad + sub * (int64_t)P.mcap;
+    auto ml_at = [&](int i) -> uint32_t* { return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ml) + 4u * (uint32_t)i); };
+    auto mq_at = [&](int i) -> uint4* { return reinterpret_cast<uint4*>(reinterpret_cast<char*>(mq) + 16u * (uint32_t)i); };
+    int32_t* const recs = P.prank + pb;
+    const int mcap = P.mcap, lane_piece = P.lane_piece;
+    const bool has_pextra = P.pextra != nullptr;          // (wave-uniform: only when the tables hold promoted pieces)
     int ns = 0, nl = 0, midseen = 0;
     int promo_extra = 0;                                   // tokens beyond one per piece that the promoted pieces of this sub-tile stand for (P.pextra): this lane's share
     bool giant = false, coopl = false;                     // coopl: a long miss of more than kLanePiece bytes (k_merge_coop's: bit 2 of the sub-tile's flag)
@@ -886,7 +937,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
             const uint32_t slot = tkz_short_slot_first(T, kw0[u], kw1[u], kw2[u], (uint32_t)plen[u], &hs[u]);
             // the FIRST candidate bucket of every piece (idle lanes and longer pieces gather slot 0: a load inside a divergent branch
             // is waited for inside it)
-            const uint32_t oa = is_short ? 16u * slot : 0u;
+            const uint32_t oa = simt::lane_offset(is_short ? 16u * slot : 0u);
             a0[u] = tkz_load16(tb0 + oa); a1[u] = tkz_load16(tb0 + oa + 16u);
         }
         int32_t rk[U];
@@ -915,7 +966,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
             for (int u = 0; u < U; ++u) {
                 const bool want = plen[u] >= 1 && plen[u] <= TKZ_SHORT_KEY_MAX && rk[u] == TKZ_RANK_NONE;
                 if (want) {
-                    const uint32_t ob = 16u * tkz_short_slot_second(T, hs[u]);
+                    const uint32_t ob = simt::lane_offset(16u * tkz_short_slot_second(T, hs[u]));
                     a0[u] = tkz_load16(tb0 + ob); a1[u] = tkz_load16(tb0 + ob + 16u);
                 }
             }
@@ -938,7 +989,7 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
             midseen += tkz_popc64(midm);
             const bool is_giant = len > kArenaPiece;                             // (k_giant_merge looks a giant piece up itself)
             const bool miss = valid && !is_giant && rank == TKZ_RANK_NONE;
-            if (P.pextra) {                                                      // (wave-uniform: only when the tables hold promoted pieces)
+            if (has_pextra) {
                 const uint32_t ex = (valid && !is_giant && !miss && ((uint32_t)rank & kPromoFlag)) ? (((uint32_t)rank >> kPromoCntShift) & 3u) : 0u;
                 promo_extra += (int)ex;                                          // (per lane: one add a batch; summed over the wavefront once, at the end)
             }
@@ -949,20 +1000,20 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
             // (the two lists grow towards each other; an entry that would run into the other list is not written -- ns + nl > mcap is then
             //  reported below and the batch redone with longer lists)
             const uint32_t ent = (uint32_t)s | ((uint32_t)(len - 1) << kMrLenShift);
-            if (miss_s && is_ + nl < P.mcap) {
-                ml[is_] = ent;
+            if (miss_s && is_ + nl < mcap) {
+                *ml_at(is_) = ent;
                 uint4 kq; kq.x = kw0[u]; kq.y = kw1[u]; kq.z = kw2[u]; kq.w = 0;          // the piece's bytes, zero-padded, for k_merge_short
                 if (len > TKZ_SHORT_KEY_MAX) { kq.x = tkz_key_dword(s_bytes, s, len, 0); kq.y = tkz_key_dword(s_bytes, s, len, 1); kq.z = tkz_key_dword(s_bytes, s, len, 2); kq.w = tkz_key_dword(s_bytes, s, len, 3); }
-                mq[is_] = kq;
+                *mq_at(is_) = kq;
             }
-            if (miss_l && il + ns < P.mcap) ml[P.mcap - 1 - il] = ent;
+            if (miss_l && il + ns < mcap) *ml_at(mcap - 1 - il) = ent;
             uint32_t rec = ((s_mark[s >> 5] >> (s & 31)) & 1u) ? kPrMark : 0u;
             if (REPORT) giant = giant || (miss_l && len > kSmallLanePiece);      // (k_small, the only REPORT user, hands a batch with such a piece back like one with a giant piece: k_merge_coop is a kernel of the batch path)
-            else coopl = coopl || (miss_l && len > P.lane_piece);
+            else coopl = coopl || (miss_l && len > lane_piece);
             if (is_giant) { rec |= kPrMiss | kPrGiant | (uint32_t)s; giant = giant || valid; }
             else if (miss) rec |= kPrMiss | (miss_l ? (kPrLong | (uint32_t)il) : (uint32_t)is_);
             else rec |= (uint32_t)rank;
-            if (valid && pb + k < P.prank_cap) tkz_store_nt(&P.prank[pb + k], (int32_t)rec);
+            if (k < nrec) tkz_store_nt(&recs[(uint32_t)k], (int32_t)rec);
         }
         TKZ_PROBE_MARK(pf_emit);
     }
@@ -986,19 +1037,17 @@ TKZ_DEV void tkz_probe_subtile(const TkzTables& T, const EncodeParams& P, int64_
     // than kLanePiece bytes (bit 2: k_merge_coop -- k_merge_long used to flag those chunks itself: a pointer, an index and a flag alive across its merge
     // loops, 14 more spilled scalars and 4 % of that kernel on mixed text)
     const uint32_t f = (nl ? 1u : 0u) | (simt::ballot(giant) ? 2u : 0u) | (simt::ballot(coopl) ? 4u : 0u);
-    if (P.pextra) { int tot; (void)tkz_wave_scan_sum(promo_extra, &tot); promo_extra = tot; }      // (wave-uniform branch)
+    if (has_pextra) { int tot; (void)tkz_wave_scan_sum(promo_extra, &tot); promo_extra = tot; }      // (wave-uniform branch)
     if (lane == 0) {
         P.heavy_flag[sub] = (uint8_t)f;
         P.mcount[sub] = (uint32_t)ns | ((uint32_t)nl << 16);
-        if (P.pextra) P.pextra[sub] = promo_extra;
-        if (!REPORT && P.tc_atomic) P.tile_count[sub] = 0;                   // (the merge kernels of both streams add to it: launch_encode)
-        if (REPORT && ns + nl > P.mcap) { simt::atomic_or((unsigned*)&P.counters[0], (unsigned)kErrMissCap); simt::atomic_max((unsigned*)&P.counters[1], (unsigned)(ns + nl)); }
-        if (pb + np > P.prank_cap) simt::atomic_or((unsigned*)&P.counters[0], (unsigned)kErrCapacity);
+        if (has_pextra) P.pextra[sub] = promo_extra;
+        if (REPORT && ns + nl > mcap) { simt::atomic_or((unsigned*)&P.counters[0], (unsigned)kErrMissCap); simt::atomic_max((unsigned*)&P.counters[1], (unsigned)(ns + nl)); }
     }
 }
 TKZ_KERNEL_OCC(256, TKZ_PROBE_OCC) void k_probe(TkzTables T, EncodeParams P) {
     TKZ_SHARED uint4 s_wave[kThreads / 64][kProbeLdsQuads];
-    TKZ_SHARED uint4 s_kmask[TKZ_SHORT_KEY_MAX + 1];
+    TKZ_SHARED uint4 s_kmask[kProbeMaskRows];
     tkz_probe_kmask_init(s_kmask);
     simt::sync();                                         // (the only workgroup barrier: from here on every wavefront is on its own)
     const int64_t sub0 = (tkz_xcd_block(simt::bid(), simt::nblocks()) * (kThreads / 64) + simt::wave()) * kProbePer;
@@ -1017,7 +1066,7 @@ TKZ_KERNEL_OCC(256, TKZ_PROBE_OCC) void k_probe(TkzTables T, EncodeParams P) {
 // the special entries' form: the same sub-tiles, with the starts of the taken literals beside the marks
 TKZ_KERNEL_OCC(256, TKZ_PROBE_OCC) void k_probe_special(TkzTables T, EncodeParams P) {
     TKZ_SHARED uint4 s_wave[kThreads / 64][kProbeLdsQuads];
-    TKZ_SHARED uint4 s_kmask[TKZ_SHORT_KEY_MAX + 1];
+    TKZ_SHARED uint4 s_kmask[kProbeMaskRows];
     TKZ_SHARED uint32_t s_spec[kThreads / 64][kSub / 32];
     tkz_probe_kmask_init(s_kmask);
     simt::sync();
@@ -4295,11 +4344,11 @@ constexpr int kSmallLitBlock = 2048;       // bytes of text per wavefront and ro
 constexpr int kSmallLitTextQuads = (kSmallLitBlock + kLitMaxLen) / 16, kSmallLitTableQuads = kLitMetaWords / 4 + kLitBlobQuads;
 constexpr int kSmallWaves = 16;            // the workgroup is 256 threads for up to 4 sub-tiles, 1024 beyond
 constexpr int kSmallLdsQuads = kSmallWaves * kPretokBlkQuads + 16;       // 83.5 KB: the largest phase (a 4 KiB block of the pre-tokenizer per wavefront)
-static_assert(kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX + 1 && kSmallLdsQuads >= 8 * kMsLdsQuads + 32 && kSmallLdsQuads >= kLongLdsQuads &&
+static_assert(kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + kProbeMaskRows && kSmallLdsQuads >= 8 * kMsLdsQuads + 32 && kSmallLdsQuads >= kLongLdsQuads &&
               kSmallLdsQuads >= kSmallWaves * kPlaceLdsQuads && kSmallLdsQuads * 16 >= kSmallMaxBytesO200k + 64 && kSmallMaxBytes <= 8 * kGroup * kSub,
               "every phase fits the one LDS block; the o200k text too; at most 8 groups of k_merge_short");
 static_assert(kLitMetaWords % 4 == 0 && kSmallLdsQuads >= kSmallLitTableQuads + kSmallWaves * kSmallLitTextQuads &&
-              kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + TKZ_SHORT_KEY_MAX + 1 + kSmallWaves * (kSub / 128),
+              kSmallLdsQuads >= kSmallWaves * kProbeLdsQuads + kProbeMaskRows + kSmallWaves * (kSub / 128),
               "the literal phase fits the one LDS block as well, and the probe phase with the words of the literals' starts");
 template <bool SPECIAL, bool TRIM = false>
 TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
@@ -4462,7 +4511,7 @@ TKZ_KERNEL(1024) void k_small(TkzTables T, EncodeParams P, SmallArgs A) {
             ProbeText tx;
             tkz_probe_request_text(P, sub, &tx);
             ProbeLds LD = tkz_probe_lds(s_raw + wave * kProbeLdsQuads, s_kmask);
-            if constexpr (SPECIAL) LD.spec = reinterpret_cast<uint32_t*>(s_kmask + TKZ_SHORT_KEY_MAX + 1 + wave * (kSub / 128));      // (k_probe_special's s_spec: behind the mask table)
+            if constexpr (SPECIAL) LD.spec = reinterpret_cast<uint32_t*>(s_kmask + kProbeMaskRows + wave * (kSub / 128));      // (k_probe_special's s_spec: behind the mask table)
             tkz_probe_subtile<true, SPECIAL>(T, P, sub, LD, tx, -1);
             (void)simt::ballot(true);
         }

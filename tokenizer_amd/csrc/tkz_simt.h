@@ -82,6 +82,10 @@ TKZ_DEV uint32_t wave_min_u32(uint32_t v) {
 }
 // v_alignbit_b32: the low dword of ({hi, lo} >> (sh & 31)) -- an unaligned dword out of two aligned ones in ONE instruction
 TKZ_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
+// a lane's 32-bit byte offset from a wave-uniform base, kept as ONE vector register: a load or store at base + lane_offset(o) takes the base from scalar
+// registers.  (Left to itself the compiler folds the widening of an offset that comes out of a 64-bit product -- tkz_mulhi -- into that product, and then
+// forms the address with a 64-bit add a lane.)
+TKZ_DEV uint32_t lane_offset(uint32_t o) { asm("" : "+v"(o)); return o; }
 }  // namespace simt
 // Streaming accesses (touched once: the corpus, the per-piece records, the ids): non-temporal, so that they do not evict the
 // vocabulary tables every gather of the encode kernels wants to find in L2.
@@ -99,6 +103,11 @@ TKZ_DEV void tkz_store16_nt(void* p, uint4 v) {
     tkz_u32x4 x; x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
     __builtin_nontemporal_store(x, reinterpret_cast<tkz_u32x4*>(p));
 }
+#endif
+// (the CPU-emulated build's simt::lane_offset: the value itself.  It stands here, beside the product's, because the emulator's own header is part of the
+//  test suite, which a change to the kernels leaves as it is)
+#ifdef TKZ_HOSTEMU
+namespace simt { inline uint32_t lane_offset(uint32_t o) { return o; } }
 #endif
 // (a byte, streamed like the ids beside it: the mask of the padded rows)
 #ifdef TKZ_HOSTEMU
