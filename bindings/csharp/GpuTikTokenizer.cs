@@ -93,6 +93,14 @@ namespace Microsoft.DeepDev
                                                                                             long* outOffsets, long* orderOut, long* rank, long* bucketOffsets, int* bucketWidths,
                                                                                             out long totalTokens, out long totalPositions, out long nCut);
         [DllImport(Lib)] internal static extern void tkz_encoder_bucketed_calls(IntPtr encoder, out long calls);
+        // token-budget buckets: the same sorted rows cut into buckets of at most tokenBudget positions (rows x width) and bucketRows rows (include/tkz.h, "Token-budget buckets")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_budgeted_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                            int bosId, int eosId, long maxLen, int cutSide, int padSide, int padId, long padMultiple,
+                                                                                            long tokenBudget, long bucketRows, int order, int* outIds, long outCap, byte* mask, int* pos,
+                                                                                            int* lens, long* outOffsets, long* orderOut, long* rank, long* bucketOffsets,
+                                                                                            long* bucketRowsOut, int* bucketWidths, long bucketCap, out long totalTokens,
+                                                                                            out long totalPositions, out long nCut, out long nBuckets);
+        [DllImport(Lib)] internal static extern void tkz_encoder_budgeted_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -677,6 +685,67 @@ namespace Microsoft.DeepDev
             for (int b = 0; b < nBuckets; ++b)
             {
                 int rows = Math.Min(bucketRows, texts.Count - b * bucketRows), w = bucketWidths[b];
+                var bIds = new int[rows, w];
+                var bMask = new byte[rows, w];
+                Buffer.BlockCopy(ids, checked((int)bucketOffsets[b] * sizeof(int)), bIds, 0, checked(rows * w * sizeof(int)));
+                Buffer.BlockCopy(mask, checked((int)bucketOffsets[b]), bMask, 0, checked(rows * w));
+                buckets[b] = (bIds, bMask);
+            }
+            var outLens = new int[texts.Count];
+            var outOrder = new long[texts.Count];
+            var outRank = new long[texts.Count];
+            Array.Copy(lens, outLens, texts.Count);
+            Array.Copy(order, outOrder, texts.Count);
+            Array.Copy(rank, outRank, texts.Count);
+            return (buckets, outOrder, outRank, outLens);
+        }
+
+        /// <summary>EncodeBatchBucketed's sorted rows cut greedily by a TOKEN budget: a bucket takes rows while rows x width is at most <paramref name="maxTokens"/>
+        /// (the width of its longest row, rounded up to <paramref name="padToMultipleOf"/>, at most maxLength; 0: maxLength itself) and it has at most
+        /// <paramref name="maxRows"/> rows (null: no cap), in ONE call (tkz_encode_batch_budgeted_utf16; include/tkz.h states the rule).  Buckets[b] holds Ids and Mask
+        /// of rows x width; the rows of the buckets, one after the other, are the texts Order[0], Order[1], ...; Rank is the inverse of Order; Lens are in the texts'
+        /// order.  (Written out beside EncodeBatchBucketed; like it, not compiled where this repository is built.)</summary>
+        public unsafe ((int[,] Ids, byte[,] Mask)[] Buckets, long[] Order, long[] Rank, int[] Lens) EncodeBatchBudgeted(IReadOnlyList<string> texts, int maxLength, long maxTokens,
+                                                                                                                       int? maxRows = null,
+                                                                                                                       IReadOnlyCollection<string>? allowedSpecial = null, int? bos = null,
+                                                                                                                       int? eos = null, int pad = 0, bool descending = false,
+                                                                                                                       bool truncateLeft = false, bool padLeft = false, int padToMultipleOf = 1)
+        {
+            int framing = (bos.HasValue ? 1 : 0) + (eos.HasValue ? 1 : 0);
+            if (maxLength < Math.Max(1, framing)) throw new ArgumentOutOfRangeException(nameof(maxLength));
+            if (maxTokens < maxLength || maxTokens > 1L << 62) throw new ArgumentOutOfRangeException(nameof(maxTokens));
+            if (maxRows < 1) throw new ArgumentOutOfRangeException(nameof(maxRows));
+            if (bos < 0 || eos < 0) throw new ArgumentOutOfRangeException(bos < 0 ? nameof(bos) : nameof(eos));
+            if (padToMultipleOf < 0) throw new ArgumentOutOfRangeException(nameof(padToMultipleOf));
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            var unitOffsets = new long[texts.Count + 1];
+            for (int t = 0; t < texts.Count; ++t) unitOffsets[t + 1] = unitOffsets[t] + texts[t].Length;
+            long total = unitOffsets[texts.Count];
+            var units = new char[Math.Max(1, total)];
+            for (int t = 0; t < texts.Count; ++t) texts[t].CopyTo(0, units, (int)unitOffsets[t], texts[t].Length);
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = (long)texts.Count * maxLength;                                            // the sizes that always suffice (tkz.h): a row of maxLength and a bucket a text
+            var ids = new int[Math.Max(1, cap)];
+            var mask = new byte[Math.Max(1, cap)];
+            var lens = new int[Math.Max(1, texts.Count)];
+            var order = new long[Math.Max(1, texts.Count)];
+            var rank = new long[Math.Max(1, texts.Count)];
+            var bucketOffsets = new long[texts.Count + 1];
+            var bucketRows = new long[texts.Count + 1];
+            var bucketWidths = new int[Math.Max(1, texts.Count)];
+            int st;
+            long nBuckets;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (byte* pm = mask) fixed (int* pl = lens)
+            fixed (long* pr = order) fixed (long* pk = rank) fixed (long* pb = bucketOffsets) fixed (long* ps = bucketRows) fixed (int* pw = bucketWidths)
+                st = Tkz.tkz_encode_batch_budgeted_utf16(encoder, pu, po, texts.Count, allowed.Length > 0 ? pa : null, allowed.Length, bos ?? -1, eos ?? -1, maxLength,
+                                                         truncateLeft ? 1 : 0, padLeft ? 1 : 0, pad, padToMultipleOf, maxTokens, maxRows ?? int.MaxValue, descending ? 1 : 0, pi, cap,
+                                                         pm, null, pl, null, pr, pk, pb, ps, pw, texts.Count, out _, out _, out _, out nBuckets);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            var buckets = new (int[,] Ids, byte[,] Mask)[nBuckets];
+            for (int b = 0; b < nBuckets; ++b)
+            {
+                int rows = checked((int)(bucketRows[b + 1] - bucketRows[b])), w = bucketWidths[b];
                 var bIds = new int[rows, w];
                 var bMask = new byte[rows, w];
                 Buffer.BlockCopy(ids, checked((int)bucketOffsets[b] * sizeof(int)), bIds, 0, checked(rows * w * sizeof(int)));

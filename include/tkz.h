@@ -633,7 +633,7 @@ void tkz_encoder_padded_calls(const tkz_encoder* e, int64_t* calls);
  *     tkz_encode_batch_padded_utf8.  mask, pos, out_offsets and rank may be NULL.  The rows (P positions), the mask, pos, lens, order, rank, the bucket arrays and
  *     the offsets are downloaded, NEVER the uncut ids.
  *   tkz_encode_batch_bucketed_utf16: code units in, transcoded on the device as tkz_encode_batch_padded_utf16; unit_offsets in code units.
- * There is no bucketing by a TOKEN budget (rows * width <= T: a chain of dependent searches, the open problem of the one-wavefront chunk chains), no item-granular
+ * There is no bucketing by a TOKEN budget HERE (rows * width <= T: the budgeted entries below do that, with bucket_rows as a cap), no item-granular
  * cut, no maximum per document, no _begin / _end form, no chunk pipeline for the host entries, no single-text form and no device-resident UTF-16 input. */
 typedef enum tkz_bucket_order { TKZ_BUCKET_ASCENDING = 0, TKZ_BUCKET_DESCENDING = 1 } tkz_bucket_order;
 tkz_status tkz_encode_batch_bucketed_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
@@ -654,6 +654,68 @@ tkz_status tkz_encode_batch_bucketed_utf16(tkz_encoder* e, const uint16_t* units
                                            int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut);
 /* informational: successful calls of the bucketed entries */
 void tkz_encoder_bucketed_calls(const tkz_encoder* e, int64_t* calls);
+
+/* ---- Token-budget buckets: the documents sorted by token length, cut into mini-batches of at most T positions (rows * width), every one padded to ITS OWN longest row ----
+ * What training and serving loops make of a sorted batch (fairseq's max_tokens / batch_by_size, a token-budget sampler, a prefill queue with a token limit): every
+ * mini-batch costs the same memory whatever its row length, where a fixed row count lets the long buckets set the limit and the short ones waste it.
+ * THE RULE.  Every argument of tkz_encode_batch_bucketed_device keeps its meaning and its TKZ_E_ARG conditions, with these differences: bucket_rows = B becomes a
+ * CAP on the rows of a bucket, 1 <= B <= 2^31 - 1, and 2^31 - 1 means none; token_budget = T with max_len <= T <= 2^62, so a row alone always fits; bucket_cap >= 0,
+ * the entries of the caller's bucket arrays.  Anything outside these ranges is TKZ_E_ARG (and so are more than 2^31 - 1 documents).
+ *   Lengths, order, rank.  n[d], k[d], len[d], n_cut, order, rank, lens and out_offsets are EXACTLY as in the bucketed rule.
+ *   Width of a length.  w(0) = 0.  Otherwise w(l) = L when M == 0 and w(l) = min(L, ceil(l / M) * M) when M >= 1.
+ *   Buckets, greedy over the sorted rows.  Bucket 0 starts at sorted row 0.  A bucket that starts at row s ends at the largest e in (s, n_docs] with e - s <= B and
+ *     (e - s) * w(longest len in [s, e)) <= T; the longest len is that of row e - 1 ascending and of row s descending.  The next bucket starts at e; n_buckets is
+ *     the count.  Rows of width 0 cost nothing against T: only B stops them.
+ *   Bucket arrays.  bucket_rows_out[b] (int64, n_buckets + 1 entries) is the first sorted row of bucket b; the last entry is n_docs.  R_b is the difference of
+ *     two neighbours.  bucket_widths[b] = W_b (int32, n_buckets entries), the width of the bucket's longest len.  bucket_offsets[b] = the sum over b' < b of
+ *     R_b' * W_b' (int64, n_buckets + 1 entries); the last entry is P.
+ *   Rows.  Sorted row r of bucket b is row i = r - bucket_rows_out[b] and occupies out[bucket_offsets[b] + i * W_b .. + W_b).  Content, mask and pos are as in the
+ *     bucketed rule.
+ *   Scalars.  *total_tokens (uncut, and what the encoder's counts block receives), *total_positions = P, *n_cut, *n_buckets.
+ *   Example: the bucketed block's five documents, len = 4, 1, 3, 4, 3; no bos, eos = X, L = 4, M = 1, pad P, suffix cut, right padding.
+ *     T = 9, no row cap, ascending (order 1, 2, 4, 0, 3): n_buckets = 2; rows 0, 3, 5; widths 3, 4; bucket offsets 0, 9, 17
+ *                 rows X P P / c1 c2 X / e1 e2 X | a1 a2 a3 X / d1 d2 d3 X
+ *     the same descending (order 0, 3, 2, 4, 1): n_buckets = 2; rows 0, 2, 5; widths 4, 3; bucket offsets 0, 8, 17
+ *                 rows a1 a2 a3 X / d1 d2 d3 X | c1 c2 X / e1 e2 X / X P P
+ *     T = 9, B = 2, ascending: rows 0, 2, 4, 5; widths 3, 4, 4; bucket offsets 0, 6, 14, 18 -- the bucketed entry's buckets.
+ *   With T >= n_docs * L only B binds: the buckets are those of the bucketed entry with the same B, and bucket_rows_out[b] = min(b * B, n_docs).
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap < P or bucket_cap < n_buckets.  All four scalars then hold the required figures, all from the one call; nothing is
+ * promised in the outputs.  n_docs * L positions and n_docs buckets ALWAYS suffice.
+ *   tkz_encode_batch_budgeted_device: device buffers.  d_mask, d_pos, d_out_offsets and d_rank may each be NULL; d_out_ids, d_lens, d_order, d_bucket_offsets and
+ *     d_bucket_rows (bucket_cap + 1 entries each), d_bucket_widths (bucket_cap entries) and the four scalars may not (TKZ_E_ARG).  Nothing is written at or behind P
+ *     (ids, mask, pos), n_docs (lens, order, rank), n_docs + 1 (offsets), n_buckets (widths) or n_buckets + 1 (bucket offsets, bucket rows); the bucket arrays may
+ *     be larger than that.  An empty batch (n_docs == 0) is TKZ_OK: bucket_offsets[0], bucket_rows_out[0] and out_offsets[0] cleared on the stream, all four
+ *     scalars 0.  Everything else as tkz_encode_batch_bucketed_device.
+ *     The launch sequence is the bucketed call's up to and including the sort's last k_bkt_scatter, unchanged.  Then, without a host wait -- the host never learns
+ *     n_buckets before the call ends; its grids and scans are sized from n_docs, bucket_cap and out_cap --: k_tbk_mark twice around a scan (the RUNS of equal
+ *     width: at most min(n_docs, ceil(L / M) + 1), 65 at L = 512, M = 8), k_tbk_chain (ONE wavefront; inside a run every bucket has min(B, T / w) rows, so the
+ *     chain of dependent bucket ends is walked a run, not a bucket: its steps do not grow with n_buckets), a scan of the buckets a run, k_tbk_table (a lane a
+ *     bucket: its run by one search), a 64-bit scan (the offsets) and k_tbk_write (both capacity checks on the device, the bucket arrays, the rows as k_bkt_write
+ *     writes them).  Workspace beside the bucketed call's 36 bytes a document: 12 bytes a 64 documents, 56 bytes a run, 28 bytes a bucket of min(n_docs, bucket_cap).
+ *     Known limit: with M = 1 and a very large L the runs, and with them the chain's steps, can reach min(n_docs, L).
+ *   tkz_encode_batch_budgeted_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as
+ *     tkz_encode_batch_bucketed_utf8.  The rows (P positions), the optional arrays and the three bucket arrays are downloaded, NEVER the uncut ids.
+ *   tkz_encode_batch_budgeted_utf16: code units in, transcoded on the device as tkz_encode_batch_bucketed_utf16; unit_offsets in code units.
+ * There is no row-count multiple (required_batch_size_multiple), no shuffling of the buckets, no maximum per document, no budget in UNPADDED tokens, no
+ * _begin / _end form, no chunk pipeline for the host entries and no device-resident UTF-16 input. */
+tkz_status tkz_encode_batch_budgeted_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                            const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                            int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int64_t token_budget, int64_t bucket_rows, int32_t order,
+                                            int32_t* d_out_ids, int64_t out_cap, uint8_t* d_mask, int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets,
+                                            int64_t* d_order, int64_t* d_rank, int64_t* d_bucket_offsets, int64_t* d_bucket_rows, int32_t* d_bucket_widths,
+                                            int64_t bucket_cap, void* hip_stream, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets);
+tkz_status tkz_encode_batch_budgeted_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                          int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                          int64_t token_budget, int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos,
+                                          int32_t* lens, int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int64_t* bucket_rows_out,
+                                          int32_t* bucket_widths, int64_t bucket_cap, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets);
+tkz_status tkz_encode_batch_budgeted_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                           int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                           int64_t token_budget, int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos,
+                                           int32_t* lens, int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int64_t* bucket_rows_out,
+                                           int32_t* bucket_widths, int64_t bucket_cap, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets);
+/* informational: successful calls of the budgeted entries */
+void tkz_encoder_budgeted_calls(const tkz_encoder* e, int64_t* calls);
 
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
@@ -814,7 +876,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * Of a packed call (tkz_encode_batch_packed_device) the TKZ_K_DOCOFFS bracket holds k_docoffs over the documents and the packing stage behind it
  * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.  Of a padded call (tkz_encode_batch_padded_device)
  * likewise: k_docoffs over the documents, k_pad_lens and k_pad_write; of a bucketed call (tkz_encode_batch_bucketed_device): k_docoffs, k_pad_lens, the sort's
- * passes, k_bkt_table, its scan and k_bkt_write.
+ * passes, k_bkt_table, its scan and k_bkt_write; of a budgeted call (tkz_encode_batch_budgeted_device): k_docoffs, k_pad_lens, the sort's passes, k_tbk_mark
+ * twice with its scan, k_tbk_chain, the scan of the runs' buckets, k_tbk_table, its scan and k_tbk_write.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

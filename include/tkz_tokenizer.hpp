@@ -641,6 +641,34 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return bucketed_batch<uint16_t>(units, offs, maxLength, bucketRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
     }
+    // ---- token-budget buckets: the same sorted rows cut greedily into buckets of at most maxTokens positions (rows x width) and maxRows rows, in ONE call
+    // (tkz_encode_batch_budgeted_utf8 / _utf16) ----
+    // EncodeBatchBucketed's arguments with maxTokens (maxLength .. 2^62) in front of the row count, which becomes a cap (kNoRowCap: none).  Bucket b holds the sorted
+    // rows [bucket_rows[b], bucket_rows[b + 1]) -- texts order[...] -- at ids / mask / pos [bucket_offsets[b], bucket_offsets[b + 1]), rows(b) x bucket_widths[b]
+    // (tkz.h states the rule).
+    static constexpr int64_t kNoRowCap = INT32_MAX;
+    struct BudgetedRows {
+        int64_t total_positions = 0, total_tokens = 0, n_cut = 0, n_buckets = 0;
+        std::vector<int32_t> ids, pos, lens, bucket_widths; std::vector<uint8_t> mask; std::vector<int64_t> order, rank, bucket_offsets, bucket_rows;
+        int64_t buckets() const { return n_buckets; }
+        int64_t rows(int64_t b) const { return bucket_rows[static_cast<size_t>(b) + 1] - bucket_rows[static_cast<size_t>(b)]; }
+    };
+    BudgetedRows EncodeBatchBudgeted(const std::vector<std::string>& texts, int64_t maxLength, int64_t maxTokens, int64_t maxRows = kNoRowCap,
+                                     tkz_bucket_order order = TKZ_BUCKET_ASCENDING, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                     int32_t pad = 0, tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { bytes.insert(bytes.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return budgeted_batch<uint8_t>(bytes, offs, maxLength, maxTokens, maxRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, false);
+    }
+    BudgetedRows EncodeBatchBudgeted(const std::vector<std::u16string>& texts, int64_t maxLength, int64_t maxTokens, int64_t maxRows = kNoRowCap,
+                                     tkz_bucket_order order = TKZ_BUCKET_ASCENDING, const std::vector<std::string>& allowedSpecial = {}, int32_t bos = -1, int32_t eos = -1,
+                                     int32_t pad = 0, tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return budgeted_batch<uint16_t>(units, offs, maxLength, maxTokens, maxRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
+    }
     // (the id of a registered special token, for bos / eos)
     int32_t SpecialTokenId(const std::string& literal) const {
         for (const auto& kv : specials_) if (kv.first == literal) return kv.second;
@@ -925,6 +953,47 @@ private:
         out.order.resize(static_cast<size_t>(n));
         out.rank.resize(static_cast<size_t>(n));
         out.bucket_widths.resize(static_cast<size_t>(nb));
+        return out;
+    }
+    // ONE call of the batch budgeted entry on the concatenated texts, with the capacities that always suffice (tkz.h): a row of maxLength and a bucket a text
+    template <class UNIT>
+    BudgetedRows budgeted_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, int64_t maxLength, int64_t maxTokens, int64_t maxRows, tkz_bucket_order order,
+                                const std::vector<std::string>& allowedSpecial, int32_t bos, int32_t eos, int32_t pad, tkz_trim_side cutSide, tkz_pad_side padSide,
+                                int64_t padMultiple, bool utf16) const {
+        const int64_t n = static_cast<int64_t>(offs.size()) - 1;
+        BudgetedRows out;
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = maxLength >= 1 && maxLength <= INT32_MAX ? n * maxLength : 0;      // (a maxLength out of range is refused by the library)
+        if (items.empty()) items.push_back(0);
+        out.ids.resize(static_cast<size_t>(std::max<int64_t>(cap, 1)));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(std::max<int64_t>(n, 1)));
+        out.order.resize(out.lens.size());
+        out.rank.resize(out.lens.size());
+        out.bucket_offsets.resize(static_cast<size_t>(n) + 1);
+        out.bucket_rows.resize(static_cast<size_t>(n) + 1);
+        out.bucket_widths.resize(static_cast<size_t>(std::max<int64_t>(n, 1)));
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_budgeted_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos,
+                                                        eos, maxLength, cutSide, padSide, pad, padMultiple, maxTokens, maxRows, order, out.ids.data(), cap, out.mask.data(),
+                                                        out.pos.data(), out.lens.data(), nullptr, out.order.data(), out.rank.data(), out.bucket_offsets.data(),
+                                                        out.bucket_rows.data(), out.bucket_widths.data(), n, &out.total_tokens, &out.total_positions, &out.n_cut, &out.n_buckets);
+        else st = tkz_encode_batch_budgeted_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), n, index.data(), static_cast<int32_t>(index.size()), bos, eos,
+                                                 maxLength, cutSide, padSide, pad, padMultiple, maxTokens, maxRows, order, out.ids.data(), cap, out.mask.data(), out.pos.data(),
+                                                 out.lens.data(), nullptr, out.order.data(), out.rank.data(), out.bucket_offsets.data(), out.bucket_rows.data(),
+                                                 out.bucket_widths.data(), n, &out.total_tokens, &out.total_positions, &out.n_cut, &out.n_buckets);
+        check(st);
+        out.ids.resize(static_cast<size_t>(out.total_positions));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(n));
+        out.order.resize(static_cast<size_t>(n));
+        out.rank.resize(static_cast<size_t>(n));
+        out.bucket_offsets.resize(static_cast<size_t>(out.n_buckets) + 1);
+        out.bucket_rows.resize(static_cast<size_t>(out.n_buckets) + 1);
+        out.bucket_widths.resize(static_cast<size_t>(out.n_buckets));
         return out;
     }
     // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text

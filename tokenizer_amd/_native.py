@@ -22,6 +22,7 @@ OPT_CASE_EQUIVALENCE = 7    # cl100k's (?i:...) with .NET >= 7's case-equivalenc
 TRIM_SUFFIX, TRIM_PREFIX = 0, 1   # tkz_trim_side
 PAD_RIGHT, PAD_LEFT = 0, 1         # tkz_pad_side
 BUCKET_ASCENDING, BUCKET_DESCENDING = 0, 1   # tkz_bucket_order
+NO_ROW_CAP = (1 << 31) - 1                    # bucket_rows of the budgeted entries: no cap on the rows of a bucket
 OPT_LATENCY_BYTES = 8       # batches of at most this many bytes merge long missed pieces a wavefront each (tkz.h)
 OPT_ADAPT = 9               # 1 (default): the encoder learns again when the text has drifted; small batches add up to a learning window (tkz.h)
 OPT_PROMOTE = 4        # 0 / 1: automatic promotion of hot memo entries into the key tables off / on; 2: promote now; 3: drop the promotions
@@ -212,6 +213,13 @@ class Library:
         L.tkz_encode_batch_bucketed_utf16.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, pi64, pi64, pi64]
         L.tkz_encoder_bucketed_calls.argtypes = [vp, pi64]
         L.tkz_encoder_bucketed_calls.restype = None
+        L.tkz_encode_batch_budgeted_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                       vp, i64, vp, pi64, pi64, pi64, pi64]
+        L.tkz_encode_batch_budgeted_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i64, i32, i32, i32, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                                     pi64, pi64, pi64, pi64]
+        L.tkz_encode_batch_budgeted_utf16.argtypes = list(L.tkz_encode_batch_budgeted_utf8.argtypes)
+        L.tkz_encoder_budgeted_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_budgeted_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -1245,6 +1253,83 @@ class Encoder:
         """successful calls of the bucketed entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_bucketed_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- token-budget buckets: the sorted rows cut into buckets of at most token_budget positions (rows * width) and bucket_rows rows (tkz.h: the rule) --
+    def _budgeted_host(self, fn, buf, offsets, allowed, max_len, token_budget, bucket_rows, order, bos_id, eos_id, pad_id, cut_side, pad_side, pad_multiple, want_mask, want_pos,
+                       want_offs, want_rank, out_cap, bucket_cap):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        bucket_rows = NO_ROW_CAP if bucket_rows is None else bucket_rows
+        cap = (self.padded_bounds(n, max_len) if 1 <= max_len < 1 << 31 else 0) if out_cap is None else out_cap      # (a max_len out of range is refused by the library)
+        bcap = n if bucket_cap is None else bucket_cap                  # (n_docs buckets always suffice)
+        ids = np.empty(max(1, cap), np.int32)
+        mask = np.empty(max(1, cap), np.uint8) if want_mask else None
+        pos = np.empty(max(1, cap), np.int32) if want_pos else None
+        lens = np.empty(max(1, n), np.int32)
+        ooff = np.empty(n + 1, np.int64) if want_offs else None
+        perm = np.empty(max(1, n), np.int64)
+        rank = np.empty(max(1, n), np.int64) if want_rank else None
+        boffs = np.empty(max(0, bcap) + 1, np.int64)
+        brows = np.empty(max(0, bcap) + 1, np.int64)
+        widths = np.empty(max(1, bcap), np.int32)
+        tot, p, cut, nbk = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(fn(self._h, buf, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed), bos_id, eos_id, max_len, cut_side, pad_side, pad_id,
+                              pad_multiple, token_budget, bucket_rows, order, _ptr(ids), cap, _ptr(mask) if want_mask else None, _ptr(pos) if want_pos else None, _ptr(lens),
+                              _ptr(ooff) if want_offs else None, _ptr(perm), _ptr(rank) if want_rank else None, _ptr(boffs), _ptr(brows), _ptr(widths), bcap, C.byref(tot),
+                              C.byref(p), C.byref(cut), C.byref(nbk)))
+        except TkzError as ex:
+            ex.needed, ex.needed_positions, ex.n_cut, ex.needed_buckets = tot.value, p.value, cut.value, nbk.value      # (E_CAPACITY: the required figures)
+            raise
+        P, nb = p.value, nbk.value
+        return (ids[:P], mask[:P] if want_mask else None, pos[:P] if want_pos else None, lens[:n], ooff, perm[:n], rank[:n] if want_rank else None, boffs[:nb + 1],
+                brows[:nb + 1], widths[:nb], tot.value, cut.value)
+
+    def encode_batch_budgeted(self, data: np.ndarray, offsets: np.ndarray, max_len, token_budget, bucket_rows=None, order=BUCKET_ASCENDING, allowed=(), bos_id=-1, eos_id=-1,
+                              pad_id=0, cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT, pad_multiple=1, want_mask=True, want_pos=True, want_offs=True, want_rank=True, out_cap=None,
+                              bucket_cap=None):
+        """(ids int32[P], mask uint8[P] or None, pos int32[P] or None, lens int32[n], offsets int64[n + 1] or None, order int64[n], rank int64[n] or None,
+        bucket_offsets int64[n_buckets + 1], bucket_rows int64[n_buckets + 1], bucket_widths int32[n_buckets], total_tokens, n_cut): the padded rows of the documents
+        sorted by len, cut greedily into buckets of at most token_budget positions (rows * width) and bucket_rows rows (None: no cap); bucket b holds the sorted rows
+        bucket_rows[b] : bucket_rows[b + 1] at ids[bucket_offsets[b] : bucket_offsets[b + 1]] with its own width -- tkz_encode_batch_budgeted_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self._budgeted_host(self.lib.L.tkz_encode_batch_budgeted_utf8, _ptr(data) if len(data) else None, offsets, allowed, max_len, token_budget, bucket_rows, order,
+                                   bos_id, eos_id, pad_id, cut_side, pad_side, pad_multiple, want_mask, want_pos, want_offs, want_rank, out_cap, bucket_cap)
+
+    def encode_batch_budgeted_utf16(self, units: np.ndarray, offsets: np.ndarray, max_len, token_budget, bucket_rows=None, order=BUCKET_ASCENDING, allowed=(), bos_id=-1,
+                                    eos_id=-1, pad_id=0, cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT, pad_multiple=1, want_mask=True, want_pos=True, want_offs=True,
+                                    want_rank=True, out_cap=None, bucket_cap=None):
+        """encode_batch_budgeted for UTF-16 documents (uint16[total], offsets in units) -- tkz_encode_batch_budgeted_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        return self._budgeted_host(self.lib.L.tkz_encode_batch_budgeted_utf16, _ptr(buf), offsets, allowed, max_len, token_budget, bucket_rows, order, bos_id, eos_id, pad_id,
+                                   cut_side, pad_side, pad_multiple, want_mask, want_pos, want_offs, want_rank, out_cap, bucket_cap)
+
+    def encode_batch_budgeted_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, token_budget,
+                                     bucket_rows, order, d_out_ids, out_cap, d_mask=0, d_pos=0, d_lens=0, d_out_offsets=0, d_order=0, d_rank=0, d_bucket_offsets=0,
+                                     d_bucket_rows=0, d_bucket_widths=0, bucket_cap=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_budgeted_device.  Returns (total_tokens, P, n_cut, n_buckets); a TkzError carries them as `needed`,
+        `needed_positions`, `n_cut`, `needed_buckets`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, p, cut, nbk = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_budgeted_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                       len(allowed), bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, token_budget,
+                                                                       bucket_rows, order, d_out_ids or None, out_cap, d_mask or None, d_pos or None, d_lens or None,
+                                                                       d_out_offsets or None, d_order or None, d_rank or None, d_bucket_offsets or None, d_bucket_rows or None,
+                                                                       d_bucket_widths or None, bucket_cap, stream or None, C.byref(tot), C.byref(p), C.byref(cut),
+                                                                       C.byref(nbk)))
+        except TkzError as ex:
+            ex.needed, ex.needed_positions, ex.n_cut, ex.needed_buckets = tot.value, p.value, cut.value, nbk.value
+            raise
+        return tot.value, p.value, cut.value, nbk.value
+
+    def budgeted_calls(self):
+        """successful calls of the budgeted entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_budgeted_calls(self._h, C.byref(a))
         return a.value
 
     def set_special_tokens(self, specials):

@@ -112,6 +112,7 @@ struct CounterBlock {          // mirrors the device block
     int64_t pack_total, pack_rows, pack_segs;   // the packed entries: T, n_rows (k_pack_count) and n_segs (the scan of its counts) -- PackParams::totals
     int64_t pad_total, pad_width, pad_cut;      // the padded entries: the uncut total, W and n_cut (k_pad_write) -- PadParams::totals; the bucketed entries: the
                                                 // uncut total, P and n_cut (k_bkt_write)
+    int64_t pad_buckets;                        // the budgeted entries: n_buckets (k_tbk_write), behind their {uncut total, P, n_cut} in the three fields above
     // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
     int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
 };
@@ -236,7 +237,13 @@ struct BktBufs {    // the bucketed entries (beside PadBufs, which they use as t
     DevBuf bk_keys, bk_idx, bk_hist, bk_base, bk_bsum, bk_cnt, bk_boffs, bk_stage;
     void release() { release_each({&bk_keys, &bk_idx, &bk_hist, &bk_base, &bk_bsum, &bk_cnt, &bk_boffs, &bk_stage}); }
 };
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs, BktBufs {
+struct TbkBufs {    // the budgeted entries (beside PadBufs and BktBufs, which they use as the bucketed entries do): the marks of every group of 64 sorted rows and
+    // their bases; the run table (first row, width, entry row, R_w, regular buckets, the crossing bucket's end, buckets, first bucket: 56 bytes a run); the
+    // first row and the width of every bucket below min(n_docs, bucket_cap); {n_buckets, P}, the runs, a spare total; the host entries' bucket rows
+    DevBuf tb_marks, tb_runs, tb_rows, tb_fig, tb_stage;
+    void release() { release_each({&tb_marks, &tb_runs, &tb_rows, &tb_fig, &tb_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs, BktBufs, TbkBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -290,7 +297,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release(); BktBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release(); BktBufs::release(); TbkBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -334,6 +341,7 @@ struct tkz_encoder {
     std::atomic<int64_t> packed_calls{0};                                 // tkz_encoder_packed_calls: successful calls of the packed entries
     std::atomic<int64_t> padded_calls{0};                                 // tkz_encoder_padded_calls: successful calls of the padded entries
     std::atomic<int64_t> bucketed_calls{0};                               // tkz_encoder_bucketed_calls: successful calls of the bucketed entries
+    std::atomic<int64_t> budgeted_calls{0};                               // tkz_encoder_budgeted_calls: successful calls of the budgeted entries
     std::atomic<int64_t> chunks_overlap_calls{0};                          // tkz_encoder_chunks_overlap_calls: successful calls of the overlap chunk entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
@@ -401,6 +409,10 @@ struct PadCall { int32_t bos_id, eos_id; int64_t max_len; int32_t cut_side, pad_
 // permutation, its inverse (may be null) and the bucket table go (device)
 struct BktCall { int64_t bucket_rows; int32_t order; int64_t* d_order; int64_t* d_rank; int64_t* d_bucket_offs; int32_t* d_bucket_widths;
                  int64_t buckets(int64_t n_docs) const { return (n_docs + bucket_rows - 1) / bucket_rows; } };
+// A call of one of the budgeted entries: a BktCall (BatchCall::bucketed is set as well: bucket_rows is the cap B) and the token budget, the entries of the
+// caller's bucket arrays, where the buckets' first rows go (device) and, on the host, where n_buckets goes
+struct TbkCall { int64_t token_budget, bucket_cap; int64_t* d_bucket_rows; int64_t* n_buckets;
+                 int64_t table_cap(int64_t n_docs) const { return std::min(n_docs, bucket_cap); } };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -414,7 +426,8 @@ enum class CallKind {
     Chunks,          // tkz_encode_batch_chunks_device: as Spans, then the chunk table
     Packed,          // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
     Padded,          // tkz_encode_batch_padded_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a document
-    Bucketed         // tkz_encode_batch_bucketed_device: as Padded up to the lengths, then the documents sorted by length and a width per bucket of rows
+    Bucketed,        // tkz_encode_batch_bucketed_device: as Padded up to the lengths, then the documents sorted by length and a width per bucket of rows
+    Budgeted         // tkz_encode_batch_budgeted_device: as Bucketed up to the sort, then buckets of at most a token budget of positions
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -432,7 +445,8 @@ struct BatchCall {
     const ChunkCall* chunks = nullptr;         // Chunks: the budget and where the table goes (pieces likewise)
     const PackCall* packed = nullptr;          // Packed: the framing, the row length and where pos and seg_starts go
     const PadCall* padded = nullptr;           // Padded, Bucketed: the framing, the cut, the padding and where the mask, pos and lens go
-    const BktCall* bucketed = nullptr;         // Bucketed: the rows a bucket, the direction and where the permutation and the bucket table go
+    const BktCall* bucketed = nullptr;         // Bucketed, Budgeted: the rows a bucket, the direction and where the permutation and the bucket table go
+    const TbkCall* budgeted = nullptr;         // Budgeted: the token budget, the bucket capacity and where the buckets' first rows go
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -442,7 +456,7 @@ struct BatchCall {
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded || kind == CallKind::Bucketed ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded || kind == CallKind::Bucketed || kind == CallKind::Budgeted ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -1015,8 +1029,22 @@ tkz::BktParams bkt_params(Workspace* ws, const BatchCall& c, const int64_t* gran
                           reinterpret_cast<int32_t*>(ws->bk_keys.as<uint32_t>() + 2 * n), ws->bk_idx.as<int64_t>() + 2 * n};
 }
 
+// the stage of a budgeted call: the bucketed stage's arguments (the sort's workspace; its table arrays hold min(n_docs, bucket_cap) buckets) and the workspace of the
+// runs and the table (budgeted_on_device sizes it).  n_buckets_out: where the device stores n_buckets
+tkz::TbkParams tbk_params(Workspace* ws, const BatchCall& c, const int64_t* grand, int64_t* totals, const int32_t* blk, int64_t* n_buckets_out) {
+    const TbkCall& k = *c.budgeted;
+    const int64_t tc = k.table_cap(c.n_docs), rc = tkz::tbk_run_cap(c.n_docs, c.padded->max_len, c.padded->pad_multiple), ng = tkz::tbk_mark_groups(c.n_docs);
+    int64_t* const runs = ws->tb_runs.as<int64_t>();           // (five int64 arrays, then the two int32 ones)
+    int64_t* const fig = ws->tb_fig.as<int64_t>();
+    return tkz::TbkParams{bkt_params(ws, c, grand, totals, blk), k.token_budget, k.bucket_cap, tc, rc, k.d_bucket_rows, n_buckets_out,
+                          reinterpret_cast<int32_t*>(ws->tb_marks.as<int64_t>() + ng), ws->tb_marks.as<int64_t>(), fig + 3,
+                          runs, reinterpret_cast<int32_t*>(runs + 6 * rc), runs + rc, runs + 2 * rc, runs + 3 * rc, runs + 4 * rc, reinterpret_cast<int32_t*>(runs + 6 * rc) + rc,
+                          runs + 5 * rc, fig, ws->tb_rows.as<int64_t>(), reinterpret_cast<int32_t*>(ws->tb_rows.as<int64_t>() + tc + 1)};
+}
+
 // A padded call on a batch without bytes: every document is its framing alone (all of them empty: W = 0 without framing), and the stage runs over offsets that
-// are all 0.  Without documents there is nothing but the offset to clear.  A bucketed call likewise (its first bucket offset is cleared as well).
+// are all 0.  Without documents there is nothing but the offset to clear.  A bucketed call likewise (its first bucket offset is cleared as well), and a budgeted
+// one (its first bucket row too; n_buckets is the fourth figure: totals3 has four entries then).
 tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t* totals3) {
     using namespace tkz;
     const int64_t n_docs = c.n_docs;
@@ -1027,6 +1055,7 @@ tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t*
         launch_counts3(L, 0, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
         if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, sizeof(int64_t), c.stream));
         if (c.bucketed) HIP_TRY(hipMemsetAsync(c.bucketed->d_bucket_offs, 0, sizeof(int64_t), c.stream));
+        if (c.budgeted) { HIP_TRY(hipMemsetAsync(c.budgeted->d_bucket_rows, 0, sizeof(int64_t), c.stream)); totals3[3] = 0; }
         HIP_TRY(hipStreamSynchronize(c.stream));
         return TKZ_OK;
     }
@@ -1034,10 +1063,12 @@ tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t*
     HIP_TRY(hipMemsetAsync(ws->pd_tot.p, 0, 64, c.stream));
     HIP_TRY(hipMemsetAsync(ws->pd_offs.p, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
     int64_t* const tot = ws->pd_tot.as<int64_t>();
-    if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
+    if (c.budgeted) launch_budgeted(L, tbk_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4), tot + 5));
+    else if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
     else launch_pad(L, pad_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
     launch_counts3(L, n_docs, 0, tot, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
     HIP_TRY(hipMemcpyAsync(totals3, tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+    if (c.budgeted) HIP_TRY(hipMemcpyAsync(totals3 + 3, tot + 5, sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     HIP_TRY(hipGetLastError());
     return TKZ_OK;
@@ -1226,7 +1257,9 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                 launch_counts3(L, n_docs, total, totals, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else if (c.padded) {                                      // (the uncut offsets, then the rows; the counts blocks receive the uncut total)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, ws->pd_offs.as<int64_t>(), has_empty);
-                if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
+                if (c.budgeted) launch_budgeted(L, tbk_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters,
+                                                              reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_buckets))));
+                else if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
                 else launch_pad(L, pad_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
                 launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
@@ -1405,12 +1438,17 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         if (total_tokens) *total_tokens = totals3[0];
         if (k.width) *k.width = totals3[1];
         if (k.n_cut) *k.n_cut = totals3[2];
+        if (c.budgeted) {                                         // (pad_buckets lies behind the three: n_buckets; both capacities, all four figures)
+            if (c.budgeted->n_buckets) *c.budgeted->n_buckets = totals3[3];
+            if (totals3[1] > c.out_cap) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
+            return totals3[3] > c.budgeted->bucket_cap ? fail(TKZ_E_CAPACITY, "bucket table capacity too small") : TKZ_OK;
+        }
         if (c.bucketed) return totals3[1] > c.out_cap ? fail(TKZ_E_CAPACITY, "output capacity too small for the rows") : TKZ_OK;      // (totals3[1]: P, the positions)
         if (totals3[1] > 0 && n_docs > c.out_cap / totals3[1]) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
         return TKZ_OK;
     };
     if (total == 0 && c.padded) {
-        int64_t totals3[3];
+        int64_t totals3[4];
         TKZ_TRY(pad_empty(e, ws, c, totals3));
         return padded_done(totals3);
     }
@@ -3699,6 +3737,190 @@ tkz_status tkz_encode_batch_bucketed_utf16(tkz_encoder* e, const uint16_t* units
 }
 void tkz_encoder_bucketed_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->bucketed_calls.load() : 0;
+}
+
+// ---- token-budget buckets: the padded rows of the documents sorted by length, cut into buckets of at most token_budget positions and bucket_rows rows (tkz.h: the rule) ----
+
+namespace {
+tkz_status check_tbk_args(int64_t max_len, int64_t token_budget, int64_t bucket_cap, int64_t n_docs) {
+    if (token_budget < max_len || token_budget > ((int64_t)1 << 62)) return fail(TKZ_E_ARG, "budgeted rows: token_budget must be in [max_len, 2^62]");
+    if (bucket_cap < 0) return fail(TKZ_E_ARG, "budgeted rows: negative bucket_cap");
+    if (n_docs > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "budgeted rows: more than 2^31 - 1 documents");      // (the buckets of a run are counted in 32 bits)
+    return TKZ_OK;
+}
+const char* const kMsgTbkPointers = "budgeted rows: null ids, lens, order, bucket table or scalar pointer";
+// the budgeted call on device buffers, on a workspace the entry holds: the bucketed call's sequence up to the sort, then the runs, the chain, the table and the rows
+tkz_status budgeted_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, BktCall bc, TbkCall tc, const SpecialCall* sp, int64_t* total_tokens,
+                              int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets) {
+    int64_t* acc = &ws->bytes_allocated;
+    if (c.n_docs < 0 || c.total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    const int64_t n = std::max<int64_t>(c.n_docs, 1), nt = tkz::bkt_sort_tiles(c.n_docs), nb = tc.table_cap(c.n_docs);
+    const int64_t rc = tkz::tbk_run_cap(c.n_docs, pc.max_len, pc.pad_multiple), ng = tkz::tbk_mark_groups(c.n_docs);
+    if (c.total > 0) HIP_TRY(ws->pd_ids.ensure((size_t)c.total * 4, acc));
+    HIP_TRY(ws->pd_offs.ensure((size_t)(c.n_docs + 1) * 8, acc));
+    HIP_TRY(ws->pd_src.ensure((size_t)n * 8, acc));
+    HIP_TRY(ws->pd_part.ensure((size_t)tkz::kPadGridMax * 12, acc));
+    HIP_TRY(ws->bk_keys.ensure((size_t)n * 3 * 4, acc));      // (key_a, key_b, slen)
+    HIP_TRY(ws->bk_idx.ensure((size_t)n * 3 * 8, acc));       // (idx_a, idx_b, ssrc)
+    HIP_TRY(ws->bk_hist.ensure((size_t)nt * 256 * 4, acc));
+    HIP_TRY(ws->bk_base.ensure((size_t)(nt * 256 + 1) * 8, acc));
+    HIP_TRY(ws->bk_bsum.ensure((size_t)(std::max(std::max(nt * 256, nb), std::max(rc, ng)) / tkz::kScanBlock + 2) * 8, acc));
+    HIP_TRY(ws->bk_cnt.ensure((size_t)std::max<int64_t>(nb, 1) * 8, acc));
+    HIP_TRY(ws->bk_boffs.ensure((size_t)(nb + 1) * 8, acc));
+    HIP_TRY(ws->tb_marks.ensure((size_t)ng * 12, acc));
+    HIP_TRY(ws->tb_runs.ensure((size_t)rc * 56, acc));
+    HIP_TRY(ws->tb_rows.ensure((size_t)(nb + 1) * 8 + (size_t)std::max<int64_t>(nb, 1) * 4, acc));
+    HIP_TRY(ws->tb_fig.ensure(32, acc));
+    int64_t p = 0, cut = 0, buckets = 0;
+    pc.width = &p; pc.n_cut = &cut; tc.n_buckets = &buckets;
+    c.kind = CallKind::Budgeted; c.padded = &pc; c.bucketed = &bc; c.budgeted = &tc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (total_positions) *total_positions = p;
+    if (n_cut) *n_cut = cut;
+    if (n_buckets) *n_buckets = buckets;
+    if (st == TKZ_OK) { ++e->budgeted_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a budgeted host entry, with the batch on the device as UTF-8: staging as bucketed_staged, and for the three bucket arrays at
+// min(n_docs, bucket_cap) buckets; ONE budgeted call, the results back -- P entries of the rows, n_buckets of the bucket arrays, never the uncut ids.
+tkz_status budgeted_staged(tkz_encoder* e, Workspace* ws, BatchCall c, PadCall pc, BktCall bc, TbkCall tc, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap,
+                           uint8_t* mask, int32_t* pos, int32_t* lens, int64_t* out_offsets, int64_t* order, int64_t* rank, int64_t* bucket_offsets, int64_t* bucket_rows_out,
+                           int32_t* bucket_widths, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets) {
+    const int64_t n_docs = c.n_docs, nb = tc.table_cap(n_docs);
+    const bool fits = n_docs == 0 || out_cap / pc.max_len >= n_docs;      // (n_docs * max_len always suffices: more capacity is never used)
+    c.out_cap = fits ? n_docs * pc.max_len : out_cap;
+    tc.bucket_cap = nb;                                                  // (n_docs buckets always suffice likewise)
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1), nl = std::max<int64_t>(n_docs, 1);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap, out_offsets != nullptr));
+    HIP_TRY(ws->pd_stage.ensure((size_t)(pos ? cap : 0) * 4 + (size_t)nl * 4 + (size_t)(mask ? cap : 0), &ws->bytes_allocated));
+    HIP_TRY(ws->tb_stage.ensure((size_t)nl * 16 + (size_t)(nb + 1) * 20, &ws->bytes_allocated));
+    int32_t* const d_pos = ws->pd_stage.as<int32_t>();
+    int32_t* const d_lens = d_pos + (pos ? cap : 0);
+    uint8_t* const d_mask = reinterpret_cast<uint8_t*>(d_lens + nl);
+    int64_t* const d_order = ws->tb_stage.as<int64_t>();
+    int64_t* const d_rank = d_order + nl;
+    int64_t* const d_boffs = d_rank + nl;
+    int64_t* const d_brows = d_boffs + nb + 1;
+    int32_t* const d_widths = reinterpret_cast<int32_t*>(d_brows + nb + 1);
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = out_offsets ? ws->s_outoffs[0].as<int64_t>() : nullptr;
+    pc.d_mask = mask ? d_mask : nullptr; pc.d_pos = pos ? d_pos : nullptr; pc.d_lens = d_lens;
+    bc.d_order = d_order; bc.d_rank = rank ? d_rank : nullptr; bc.d_bucket_offs = d_boffs; bc.d_bucket_widths = d_widths; tc.d_bucket_rows = d_brows;
+    const tkz_status st = budgeted_on_device(e, ws, c, pc, bc, tc, sp, total_tokens, total_positions, n_cut, n_buckets);
+    if (st != TKZ_OK) return st;
+    const int64_t n = *total_positions, k = *n_buckets;
+    TKZ_TRY(fetch(ws, out_ids, n, out_offsets, n_docs));
+    HIP_TRY(hipMemcpy(bucket_offsets, d_boffs, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bucket_rows_out, d_brows, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost));
+    if (n_docs) {
+        HIP_TRY(hipMemcpy(lens, d_lens, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(order, d_order, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        if (rank) HIP_TRY(hipMemcpy(rank, d_rank, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bucket_widths, d_widths, (size_t)k * 4, hipMemcpyDeviceToHost));
+    }
+    if (pos && n) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (mask && n) HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_budgeted_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                            const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side,
+                                            int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int64_t token_budget, int64_t bucket_rows, int32_t order,
+                                            int32_t* d_out_ids, int64_t out_cap, uint8_t* d_mask, int32_t* d_pos, int32_t* d_lens, int64_t* d_out_offsets,
+                                            int64_t* d_order, int64_t* d_rank, int64_t* d_bucket_offsets, int64_t* d_bucket_rows, int32_t* d_bucket_widths,
+                                            int64_t bucket_cap, void* hip_stream, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    TKZ_TRY(check_tbk_args(max_len, token_budget, bucket_cap, n_docs));
+    if (!d_out_ids || !d_lens || !d_order || !d_bucket_offsets || !d_bucket_rows || !d_bucket_widths || !total_tokens || !total_positions || !n_cut || !n_buckets)
+        return fail(TKZ_E_ARG, kMsgTbkPointers);
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0; *n_buckets = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (!d_doc_offsets || (total_bytes > 0 && !d_bytes)) return fail(TKZ_E_ARG, "null device buffer");      // (d_out_offsets may be null here)
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    Lease lease(e);
+    return budgeted_on_device(e, lease.ws, c, PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, d_mask, d_pos, d_lens, nullptr, nullptr},
+                              BktCall{bucket_rows, order, d_order, d_rank, d_bucket_offsets, d_bucket_widths}, TbkCall{token_budget, bucket_cap, d_bucket_rows, nullptr}, sp,
+                              total_tokens, total_positions, n_cut, n_buckets);
+}
+
+tkz_status tkz_encode_batch_budgeted_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                          int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                          int64_t token_budget, int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos,
+                                          int32_t* lens, int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int64_t* bucket_rows_out,
+                                          int32_t* bucket_widths, int64_t bucket_cap, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    TKZ_TRY(check_tbk_args(max_len, token_budget, bucket_cap, n_docs));
+    if (!out_ids || !lens || !order_out || !bucket_offsets || !bucket_rows_out || !bucket_widths || !total_tokens || !total_positions || !n_cut || !n_buckets || out_cap < 0)
+        return fail(TKZ_E_ARG, kMsgTbkPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0; *n_buckets = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_bucketed_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return budgeted_staged(e, ws, staged_call(ws, n_docs, total, 0), PadCall{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr},
+                           BktCall{bucket_rows, order, nullptr, nullptr, nullptr, nullptr}, TbkCall{token_budget, bucket_cap, nullptr, nullptr}, sp, out_ids, out_cap, mask, pos,
+                           lens, out_offsets, order_out, rank, bucket_offsets, bucket_rows_out, bucket_widths, total_tokens, total_positions, n_cut, n_buckets);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_bucketed_utf16 does.
+tkz_status tkz_encode_batch_budgeted_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                           int32_t bos_id, int32_t eos_id, int64_t max_len, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple,
+                                           int64_t token_budget, int64_t bucket_rows, int32_t order, int32_t* out_ids, int64_t out_cap, uint8_t* mask, int32_t* pos,
+                                           int32_t* lens, int64_t* out_offsets, int64_t* order_out, int64_t* rank, int64_t* bucket_offsets, int64_t* bucket_rows_out,
+                                           int32_t* bucket_widths, int64_t bucket_cap, int64_t* total_tokens, int64_t* total_positions, int64_t* n_cut, int64_t* n_buckets) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pad_args(bos_id, eos_id, max_len, cut_side, pad_side, pad_multiple));
+    TKZ_TRY(check_bkt_args(bucket_rows, order));
+    TKZ_TRY(check_tbk_args(max_len, token_budget, bucket_cap, n_docs));
+    if (!out_ids || !lens || !order_out || !bucket_offsets || !bucket_rows_out || !bucket_widths || !total_tokens || !total_positions || !n_cut || !n_buckets || out_cap < 0)
+        return fail(TKZ_E_ARG, kMsgTbkPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    *total_tokens = 0; *total_positions = 0; *n_cut = 0; *n_buckets = 0;
+    const PadCall pc{bos_id, eos_id, max_len, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const BktCall bc{bucket_rows, order, nullptr, nullptr, nullptr, nullptr};
+    const TbkCall tc{token_budget, bucket_cap, nullptr, nullptr};
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    if (total == 0) {                                                   // (no units: the offsets, all 0, are byte offsets as they are -- the framing is still laid out)
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, nullptr));
+        TKZ_TRY(stage_in(ws, nullptr, 0, unit_offsets, n_docs));
+        return budgeted_staged(e, ws, staged_call(ws, n_docs, 0, 0), pc, bc, tc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, order_out, rank, bucket_offsets,
+                               bucket_rows_out, bucket_widths, total_tokens, total_positions, n_cut, n_buckets);
+    }
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return budgeted_staged(e, ws, c, pc, bc, tc, sp, out_ids, out_cap, mask, pos, lens, out_offsets, order_out, rank, bucket_offsets, bucket_rows_out, bucket_widths,
+                           total_tokens, total_positions, n_cut, n_buckets);
+}
+void tkz_encoder_budgeted_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->budgeted_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

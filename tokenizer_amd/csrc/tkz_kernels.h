@@ -348,6 +348,37 @@ struct BktParams {
 int bkt_passes(int64_t max_len);                               // 1 .. 4
 int64_t bkt_sort_tiles(int64_t n_docs);
 void launch_bucketed(const Launch& L, BktParams K);
+// Token-budget buckets (tkz_encode_batch_budgeted_device; tkz.h states the rule): the bucketed call's sequence up to and including the sort's last k_bkt_scatter --
+// UNCHANGED: order, rank, slen, ssrc --, then the sorted rows cut greedily into buckets of at most bucket_rows rows and rows * width <= token_budget positions.
+// The host never learns n_buckets before the call ends: every grid and scan below is sized from n_docs, bucket_cap and out_cap.
+//   Runs.  A run is a maximal stretch of sorted rows of one width w(slen).  k_tbk_mark, a lane a sorted row, a workgroup per tile of kTbkMarkTile rows: pass 0
+//   stores the marks (w differs from the row before) of every group of 64 rows into mark_cnt and clears run_nbk; launch_scan2 makes mark_base and *n_runs of
+//   them; pass 1 stores (first row, width) of run mark_base[group] + the marks below the lane into run_first / run_w.  run_cap = tbk_run_cap(): the runs a
+//   batch can have, min(n_docs, ceil(L / M) + 1), 2 when M == 0.
+//   k_tbk_chain, ONE wavefront: the only sequential stage walks the RUNS, not the buckets.  Inside a run every bucket has R_w = min(B, T / w) rows (B when
+//   w == 0), so it stores a run that buckets start in the entry row (run_entry), R_w (run_r), the buckets that start in the run and end with R_w rows
+//   (run_nreg) and, ascending, the end of the bucket that crosses the run's end (run_cross, 0: none); run_nbk: the buckets that start in the run.  The 64 lanes
+//   look at the next kTbkLook runs together: ascending for the last run the crossing bucket reaches, descending for the run the next entry lies in.  It also
+//   adds up fig = {n_buckets, P}.  Its steps are bounded by the runs, whatever n_buckets is.
+//   launch_scan2 makes run_bbase (the first bucket of every run) of run_nbk.  k_tbk_table, a lane a bucket below tbl_cap = min(n_docs, bucket_cap): its run by
+//   one search over run_bbase, then brow[b] (first sorted row), bw[b] (W_b) and bkt.bkt_cnt[b] = R_b * W_b; the 64-bit scan makes bkt.boffs of them.
+//   k_tbk_write: one lane stores pad.totals = {*grand, P, n_cut} and *n_buckets_out; with n_buckets <= bucket_cap the three bucket arrays are copied to the
+//   caller's (bkt.bucket_offs, bucket_rows_out, bkt.widths); with P <= out_cap as well the rows are written as k_bkt_write writes them, a bucket's first row and
+//   row count read from brow.
+// Workspace beside the sort's: 4 bytes a group of 64 rows twice (mark_cnt, mark_base: 12), 56 bytes a run, 28 bytes a bucket below tbl_cap, 16 bytes of figures.
+constexpr int kTbkMarkTile = 256;      // sorted rows a workgroup of k_tbk_mark (a count per group of 64)
+constexpr int kTbkLook = 64;           // runs the chain looks at together: a lane each
+struct TbkParams {
+    BktParams bkt;
+    int64_t token_budget, bucket_cap, tbl_cap, run_cap;
+    int64_t* bucket_rows_out; int64_t* n_buckets_out;
+    int32_t* mark_cnt; int64_t* mark_base; int64_t* n_runs;
+    int64_t* run_first; int32_t* run_w; int64_t* run_entry; int64_t* run_r; int64_t* run_nreg; int64_t* run_cross; int32_t* run_nbk; int64_t* run_bbase;
+    int64_t* fig; int64_t* brow; int32_t* bw;
+};
+int64_t tbk_run_cap(int64_t n_docs, int64_t max_len, int64_t pad_multiple);
+int64_t tbk_mark_groups(int64_t n_docs);
+void launch_budgeted(const Launch& L, TbkParams K);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

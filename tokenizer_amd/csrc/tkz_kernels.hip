@@ -5139,6 +5139,243 @@ void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, in
 }
 
 // -------------------------------------------------------------------------------------------------
+// Token-budget buckets (tkz_encode_batch_budgeted_device; tkz.h states the rule), behind the bucketed call's sequence up to the sort's last k_bkt_scatter, which
+// is reused unchanged (order, rank, and slen / ssrc in sorted order): the sorted rows cut greedily into buckets of at most bucket_rows rows and at most
+// token_budget positions (rows * width), every bucket padded to ITS OWN longest row.  Where a bucket ends depends on where the one before it ended; the chain
+// that follows from that is walked over the RUNS of equal width -- 65 at L = 512, M = 8 -- and never over the buckets.
+//   k_tbk_mark   a lane a sorted row: a row whose width differs from the row before it starts a run.  Pass 0 counts the marks of every group of 64 rows (one
+//                ballot) and clears the runs' bucket counts; behind the scan of the counts pass 1 stores (first row, width) of every run at its ordinal.
+//   k_tbk_chain  ONE wavefront, the only sequential stage.  It carries the entry row -- the first row no bucket holds yet -- from run to run.  Inside a run all
+//                buckets have R_w = min(B, T / w) rows (B for w == 0), so their starts are an arithmetic progression and the run needs four numbers, not a
+//                step a bucket.  Ascending, the bucket that crosses the run's end takes its width from its LAST row: it reaches into run m while
+//                first[m] - start < R_w(m), which only gets harder with m -- the 64 lanes test 64 following runs with one ballot, so a bucket that swallows
+//                whole runs costs a step, not one a run.  Descending, a bucket takes its width from its FIRST row and simply runs on over the run's end: the
+//                next entry is the first start at or behind the end, and the lanes find the run it lies in (first[m] <= entry) the same way.  Runs jumped
+//                over keep the zero pass 0 gave them.  The wavefront also adds up n_buckets and P.
+//   k_tbk_table  behind the scan of the buckets a run: a lane a bucket finds its run by ONE search, then its first row, R_b, W_b and R_b * W_b.
+//   (k_scan_partials64, k_scan_top, k_scan_final64: the 64-bit scan of R_b * W_b -> the bucket offsets.)
+//   k_tbk_write  {total, P, n_cut} and n_buckets stored by one lane, both capacities held against them HERE, the bucket arrays copied to the caller; then
+//                k_bkt_write's loop with a bucket's first row and row count read from the table: one search a tile, no division a position, the next
+//                group's loads requested before this group's stores, every store tkz_store_nt.
+// Nothing is added up in memory and nothing depends on timing: the same input gives the same bytes on every run.
+// Known limit: with M = 1 and a very large L there are as many runs as distinct lengths, min(n_docs, L) at most, and the chain has that many steps.
+// -------------------------------------------------------------------------------------------------
+TKZ_KERNEL(256) void k_pad_lens(PadParams K);
+TKZ_KERNEL(256) void k_bkt_hist(BktParams K, int shift, const uint32_t* keys, int64_t ntiles);
+TKZ_KERNEL(256) void k_bkt_scatter(BktParams K, int shift, const uint32_t* keys, const int64_t* idx, uint32_t* keys_out, int64_t* idx_out, int64_t ntiles, int last);
+static_assert(kTbkMarkTile == kThreads && kTbkLook == 64, "a lane a row, a lane a run");
+// w(len): the width of a row of that length (tkz.h)
+TKZ_DEV int64_t tkz_tbk_width(const PadParams& Q, int64_t len) {
+    if (len <= 0) return 0;
+    if (Q.pad_multiple == 0) return Q.max_len;
+    const int64_t w = (len + Q.pad_multiple - 1) / Q.pad_multiple * Q.pad_multiple;
+    return w < Q.max_len ? w : Q.max_len;
+}
+// R_w: the rows of a bucket all of whose rows have width w
+TKZ_DEV int64_t tkz_tbk_rows(const TbkParams& K, int64_t w) {
+    const int64_t B = K.bkt.bucket_rows, r = w > 0 ? K.token_budget / w : B;
+    return r < B ? r : B;
+}
+TKZ_KERNEL(256) void k_tbk_mark(TbkParams K, int pass) {
+    const PadParams& Q = K.bkt.pad;
+    if (Q.counters[0] != 0) return;                            // (a failed attempt: slen means nothing)
+    const int64_t r = simt::bid() * kTbkMarkTile + simt::tid(), n = Q.n_docs;
+    int64_t w = 0;
+    bool mark = false;
+    if (r < n) { w = tkz_tbk_width(Q, K.bkt.slen[r]); mark = r == 0 || tkz_tbk_width(Q, K.bkt.slen[r - 1]) != w; }
+    const uint64_t m = simt::ballot(mark);
+    if (pass == 0) {
+        if (simt::lane() == 0 && r < n) K.mark_cnt[r >> 6] = tkz_popc64(m);
+        if (r < K.run_cap) K.run_nbk[r] = 0;                   // (run_cap <= n_docs: the grid covers it)
+    } else if (mark) {
+        const int64_t j = K.mark_base[r >> 6] + tkz_popc64(m & tkz_lowmask(simt::lane()));
+        if (j >= 0 && j < K.run_cap) { K.run_first[j] = r; K.run_w[j] = (int32_t)w; }      // (always, by construction)
+    }
+}
+// the runs from k on that pass a test which only gets harder with the run: 64 at a time, a ballot each; the return value is the first run that fails (or n_runs)
+template <class Test> TKZ_DEV int64_t tkz_tbk_ahead(const TbkParams& K, int64_t k, int64_t nruns, Test passes) {
+    for (;;) {
+        const int64_t m = k + simt::lane();
+        const bool ok = m < nruns && passes(K.run_first[m], (int64_t)K.run_w[m]);
+        const int c = tkz_popc64(simt::ballot(ok));
+        k += c;
+        if (c < kTbkLook) return k;
+    }
+}
+TKZ_KERNEL(256) void k_tbk_chain(TbkParams K) {
+    const PadParams& Q = K.bkt.pad;
+    if (Q.counters[0] != 0) return;
+    const int64_t n = Q.n_docs;
+    int64_t nruns = *K.n_runs;
+    nruns = nruns < K.run_cap ? nruns : K.run_cap;
+    int64_t s = 0, j = 0, nbk = 0, P = 0;                      // the entry row, its run, the buckets and the positions so far: the same in all 64 lanes
+    while (s < n && j < nruns) {
+        const int64_t end = j + 1 < nruns ? K.run_first[j + 1] : n, w = K.run_w[j], R = tkz_tbk_rows(K, w);
+        int64_t nreg, cross = 0, nb, s2, j2;
+        if (K.bkt.descending) {                                 // every bucket that STARTS in the run has the run's width and R rows (the batch's last: what is left)
+            nreg = nb = (end - s + R - 1) / R;
+            s2 = s + nb * R;
+            P += ((s2 < n ? s2 : n) - s) * w;
+            j2 = s2 < n ? tkz_tbk_ahead(K, j + 1, nruns, [&](int64_t first, int64_t) { return first <= s2; }) - 1 : nruns;
+        } else {                                                // the buckets that END in the run, then the one that crosses its end
+            nreg = nb = (end - s) / R;
+            s2 = s + nreg * R; j2 = j + 1;
+            P += nreg * R * w;
+            if (s2 < end) {
+                const int64_t k = tkz_tbk_ahead(K, j + 1, nruns, [&](int64_t first, int64_t wm) { return first - s2 < tkz_tbk_rows(K, wm); }) - 1;      // (the last run it reaches)
+                const int64_t kend = k + 1 < nruns ? K.run_first[k + 1] : n, wk = K.run_w[k], most = s2 + tkz_tbk_rows(K, wk);
+                cross = most < kend ? most : kend;
+                P += (cross - s2) * wk;
+                ++nb;
+                j2 = cross < kend ? k : k + 1;
+                s2 = cross;
+            }
+        }
+        if (simt::lane() == 0) { K.run_entry[j] = s; K.run_r[j] = R; K.run_nreg[j] = nreg; K.run_cross[j] = cross; K.run_nbk[j] = (int32_t)nb; }
+        nbk += nb; s = s2; j = j2;
+    }
+    if (simt::lane() == 0) { K.fig[0] = nbk; K.fig[1] = P; }
+}
+TKZ_KERNEL(256) void k_tbk_table(TbkParams K) {
+    const PadParams& Q = K.bkt.pad;
+    const int64_t b = simt::bid() * simt::nthreads() + simt::tid(), n = Q.n_docs;
+    if (b >= K.tbl_cap || Q.counters[0] != 0) return;
+    const int64_t nbk = K.fig[0];
+    int64_t cnt = 0;
+    if (b < nbk && nbk <= K.bucket_cap) {
+        int64_t nruns = *K.n_runs;
+        nruns = nruns < K.run_cap ? nruns : K.run_cap;
+        const int64_t j = tkz_last_le(K.run_bbase, 0, nruns - 1, b);      // (runs without buckets repeat their neighbour's base: the last of them has the bucket)
+        const int64_t i = b - K.run_bbase[j], R = K.run_r[j], r0 = K.run_entry[j] + i * R;
+        int64_t r1 = r0 + R < n ? r0 + R : n, W = K.run_w[j];
+        if (i >= K.run_nreg[j]) { r1 = K.run_cross[j]; W = r1 > r0 && r1 <= n ? tkz_tbk_width(Q, K.bkt.slen[r1 - 1]) : 0; }      // (the crossing bucket: its LAST row's width)
+        K.brow[b] = r0; K.bw[b] = (int32_t)W;
+        if (b == nbk - 1) K.brow[nbk] = n;
+        cnt = (r1 - r0) * W;
+    }
+    K.bkt.bkt_cnt[b] = cnt;
+}
+// a lane's place in the rows: bucket b (its first sorted row r0, its width W), row i and column c of it, and the positions from here to the bucket's end
+struct TbkCursor { int64_t b, r0, left; uint32_t W, i, c, rstep, cstep; };
+TKZ_DEV void tkz_tbk_enter(const TbkParams& K, TbkCursor& s) {      // the first row, W, the steps of 64 positions and the bucket's positions for bucket s.b
+    s.r0 = K.brow[s.b];
+    s.W = (uint32_t)K.bw[s.b];
+    s.left = (K.brow[s.b + 1] - s.r0) * (int64_t)s.W;
+    s.i = 0; s.c = 0;
+    s.rstep = s.W && s.W < 64u ? 64u / s.W : 0u; s.cstep = s.W && s.W < 64u ? 64u % s.W : 64u;
+}
+TKZ_DEV void tkz_tbk_step(const TbkParams& K, TbkCursor& s, uint32_t delta, int64_t nbk) {      // delta <= 64 positions on; the position stays below P
+    while ((int64_t)delta >= s.left) {
+        if (s.b + 1 >= nbk) { s.left = INT64_MAX; return; }      // (never below P)
+        delta -= (uint32_t)s.left;
+        ++s.b;
+        tkz_tbk_enter(K, s);
+    }
+    s.left -= delta;
+    if (s.W >= 64u) { s.c += delta; if (s.c >= s.W) { s.c -= s.W; ++s.i; } }
+    else if (delta == 64u) { s.i += s.rstep; s.c += s.cstep; if (s.c >= s.W) { s.c -= s.W; ++s.i; } }
+    else { const uint32_t x = s.c + delta; s.i += x / s.W; s.c = x % s.W; }
+}
+TKZ_KERNEL(256) void k_tbk_write(TbkParams K) {
+    const PadParams& Q = K.bkt.pad;
+    if (Q.counters[0] != 0) return;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    const int64_t nbk = K.fig[0], P = K.fig[1], n = Q.n_docs;
+    if (wave0 == 0) {                                           // the cut documents, from k_pad_lens' partials
+        int64_t n_cut = 0;
+        for (int i = lane; i < Q.nparts; i += 64) n_cut += Q.part_cut[i];
+        for (int m = 32; m >= 1; m >>= 1) n_cut += tkz_shfl64(n_cut, lane ^ m);
+        if (lane == 0) { Q.totals[0] = *Q.grand; Q.totals[1] = P; Q.totals[2] = n_cut; *K.n_buckets_out = nbk; }
+    }
+    if (nbk > K.bucket_cap) return;                             // (the bucket arrays do not fit: the figures are all that is written)
+    for (int64_t b = simt::bid() * simt::nthreads() + simt::tid(); b <= nbk; b += simt::nblocks() * simt::nthreads()) {
+        K.bkt.bucket_offs[b] = K.bkt.boffs[b]; K.bucket_rows_out[b] = K.brow[b];
+        if (b < nbk) K.bkt.widths[b] = K.bw[b];
+    }
+    if (P <= 0 || P > Q.out_cap) return;                        // (nothing to write; or the rows do not fit)
+    const int64_t ntile = (P + kBktTile - 1) / kBktTile;
+    const int fb = Q.bos_id >= 0 ? 1 : 0, fe = Q.eos_id >= 0 ? 1 : 0;
+    for (int64_t t = wave0; t < ntile; t += nwaves) {
+        const int64_t q0 = t * kBktTile, q1 = q0 + kBktTile < P ? q0 + kBktTile : P;
+        TbkCursor s;
+        s.b = tkz_last_le(K.bkt.boffs, 0, nbk - 1, q0);         // (wave-uniform: one search a tile; offsets that repeat -- buckets of width 0 -- give the last)
+        tkz_tbk_enter(K, s);
+        {   // the tile's first position: one 64-bit division a tile, then the lane's own by a step
+            const int64_t rel = q0 - K.bkt.boffs[s.b], row = s.W ? rel / (int64_t)s.W : 0;
+            s.i = (uint32_t)row; s.c = (uint32_t)(rel - row * (int64_t)s.W); s.left -= rel;
+        }
+        int64_t cur = -1, src = 0;
+        int len = 0;
+        // what a lane stores at its position: the index inside the content (or -1: padding) and the id
+        bool live = q0 + lane < q1;
+        int32_t j = -1, v = Q.pad_id;
+        for (int64_t g = q0 - 64; g < q1; g += 64) {
+            // the NEXT group's values first: its loads are in flight while this group's are stored
+            const bool live2 = g + 64 + lane < q1;
+            int32_t j2 = -1, v2 = Q.pad_id;
+            if (live2) {
+                tkz_tbk_step(K, s, g < q0 ? (uint32_t)lane : 64u, nbk);
+                const int64_t r = s.r0 + s.i;
+                if (r != cur) { cur = r; len = r < n ? K.bkt.slen[r] : 0; src = r < n ? K.bkt.ssrc[r] : 0; }
+                const int64_t jj = (int64_t)s.c - (Q.pad_side ? (int64_t)s.W - len : 0);     // the index inside the content
+                if (jj >= 0 && jj < len) {
+                    j2 = (int32_t)jj;
+                    const int64_t a = src + jj - fb;
+                    if (fb && jj == 0) v2 = Q.bos_id;
+                    else if (fe && jj == len - 1) v2 = Q.eos_id;
+                    else if (a >= 0 && a < Q.ids_cap) v2 = tkz_load_nt(Q.ids + a);
+                }
+            }
+            if (g >= q0 && live) {
+                const int64_t q = g + lane;
+                tkz_store_nt(Q.out + q, v);
+                if (Q.mask) tkz_store_nt(Q.mask + q, (uint8_t)(j >= 0 ? 1 : 0));
+                if (Q.pos) tkz_store_nt(Q.pos + q, j >= 0 ? j : 0);
+            }
+            live = live2; j = j2; v = v2;
+        }
+    }
+}
+int64_t tbk_run_cap(int64_t n_docs, int64_t max_len, int64_t pad_multiple) {
+    const int64_t widths = pad_multiple == 0 ? 2 : cdiv(max_len, pad_multiple) + 1;      // (0, the multiples of M below L, L)
+    return n_docs < widths ? (n_docs < 1 ? 1 : n_docs) : widths;
+}
+int64_t tbk_mark_groups(int64_t n_docs) { return grid1(cdiv(n_docs, 64)); }
+// (the bracket: K_DOCOFFS's again, as launch_bucketed.  n_buckets and P are known on the device only: the table's grid and scan are sized for min(n_docs,
+//  bucket_cap) buckets, the writing grid for the positions the caller's buffer holds, the run scan for the runs a batch of this L and M can have)
+void launch_budgeted(const Launch& L, TbkParams K) {
+    const auto capped = [](int64_t g) { return g < 1 ? 1 : (g > kPadGridMax ? kPadGridMax : g); };
+    BktParams& S = K.bkt;
+    const int64_t n = S.pad.n_docs, ntiles = bkt_sort_tiles(n);
+    const int64_t most = n > 0 && S.pad.out_cap / S.pad.max_len >= n ? n * S.pad.max_len : S.pad.out_cap;
+    S.pad.nparts = (int32_t)capped(cdiv(n, kThreads));
+    S.npass = bkt_passes(S.pad.max_len);
+    TKZ_LAUNCH(k_pad_lens, S.pad.nparts, kThreads, L.stream, S.pad);
+    for (int p = 0; p < S.npass; ++p) {                         // (launch_bucketed's sort, as it is)
+        const bool last = p + 1 == S.npass;
+        const uint32_t* keys = p == 0 ? nullptr : (p & 1 ? S.key_a : S.key_b);
+        const int64_t* idx = p == 0 ? nullptr : (p & 1 ? S.idx_a : S.idx_b);
+        TKZ_LAUNCH(k_bkt_hist, ntiles, kThreads, L.stream, S, 8 * p, keys, ntiles);
+        launch_scan2(L, 256 * ntiles, S.scan_bsum, S.hist, S.hist_base, S.hist_total, 1, nullptr, nullptr, nullptr, 1, -1);
+        TKZ_LAUNCH(k_bkt_scatter, ntiles, kThreads, L.stream, S, 8 * p, keys, idx, last ? (uint32_t*)nullptr : (p & 1 ? S.key_b : S.key_a),
+                   last ? S.order : (p & 1 ? S.idx_b : S.idx_a), ntiles, last ? 1 : 0);
+    }
+    const int64_t gmark = grid1(cdiv(n, kTbkMarkTile)), nblk = grid1(cdiv(K.tbl_cap, kScanBlock));
+    TKZ_LAUNCH(k_tbk_mark, gmark, kThreads, L.stream, K, 0);
+    launch_scan2(L, tbk_mark_groups(n), S.scan_bsum, K.mark_cnt, K.mark_base, K.n_runs, 1, nullptr, nullptr, nullptr, 1, -1);
+    TKZ_LAUNCH(k_tbk_mark, gmark, kThreads, L.stream, K, 1);
+    TKZ_LAUNCH(k_tbk_chain, 1, 64, L.stream, K);
+    launch_scan2(L, K.run_cap, S.scan_bsum, K.run_nbk, K.run_bbase, K.fig + 2, 1, nullptr, nullptr, nullptr, 1, -1);
+    TKZ_LAUNCH(k_tbk_table, grid1(cdiv(K.tbl_cap, kThreads)), kThreads, L.stream, K);
+    TKZ_LAUNCH(k_scan_partials64, nblk, kThreads, L.stream, (const int64_t*)S.bkt_cnt, K.tbl_cap, S.scan_bsum);
+    TKZ_LAUNCH(k_scan_top, 1, kThreads, L.stream, S.scan_bsum, nblk, S.boffs + K.tbl_cap);
+    TKZ_LAUNCH(k_scan_final64, nblk, kThreads, L.stream, (const int64_t*)S.bkt_cnt, K.tbl_cap, (const int64_t*)S.scan_bsum, S.boffs);
+    TKZ_LAUNCH(k_tbk_write, capped(cdiv(cdiv(most, kBktTile), kThreads / 64)), kThreads, L.stream, K);
+    hook(L, K_DOCOFFS, 1);
+}
+
+// -------------------------------------------------------------------------------------------------
 // Length-bucketed padded rows (tkz_encode_batch_bucketed_device; tkz.h states the rule), behind the padded call's sequence up to k_pad_lens, which is reused
 // unchanged (lens, src, the cut documents of every workgroup): the documents sorted by len, cut into buckets of bucket_rows sorted rows, every bucket padded to
 // ITS OWN longest row.

@@ -452,6 +452,56 @@ class TikTokenizer:
             buckets.append(views)
         return buckets, order, rank, lens
 
+    # ---- token-budget buckets: sorted by length, mini-batches of at most max_tokens positions (include/tkz.h, "Token-budget buckets") ----
+    def EncodeBatchBudgeted(self, texts: Sequence[str], max_length: int, max_tokens: int, max_rows: Union[int, None] = None,
+                            allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bos=None, eos=None, pad: int = 0, descending: bool = False,
+                            truncation_side: str = "right", padding_side: str = "right", pad_to_multiple_of: int = 1, fixed_width: bool = False, return_pos: bool = False):
+        """(buckets, order, rank, lens) from ONE device call (tkz_encode_batch_budgeted_utf8 / _utf16): what EncodeBatchBucketed makes of the texts, with the sorted
+        list cut greedily by a TOKEN budget: a mini-batch takes rows while rows * width <= max_tokens (the width of its longest row, rounded as pad_to_multiple_of
+        says) and rows <= max_rows (None: no cap).  buckets is a list of (ids[R_b, W_b], mask[R_b, W_b]) -- and pos[R_b, W_b] with return_pos --, views of one buffer
+        each; the rows of the buckets, one after the other, are the texts order[0], order[1], ...; rank is the inverse of order, lens the content lengths in the
+        texts' order."""
+        sides = {"right": 0, "left": 1}
+        if truncation_side not in sides or padding_side not in sides:
+            raise ValueError("truncation_side and padding_side are 'right' or 'left'")
+        bos_id, eos_id = self._frame_id(bos), self._frame_id(eos)
+        if max_length < max(1, (bos_id >= 0) + (eos_id >= 0)) or max_length >= 1 << 31:
+            raise ValueError("max_length must hold the framing ids, and one id at least")
+        if pad_to_multiple_of < 1 or pad_to_multiple_of >= 1 << 31:
+            raise ValueError("pad_to_multiple_of must be at least 1")
+        if max_tokens < max_length or max_tokens > 1 << 62:
+            raise ValueError("max_tokens must hold one row of max_length")
+        if max_rows is not None and (max_rows < 1 or max_rows >= 1 << 31):
+            raise ValueError("max_rows must be at least 1")
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not plain and self._special_on_host:
+            raise N.UnsupportedError(N.E_UNSUPPORTED, "EncodeBatchBudgeted: the device's special entries do not hold this set of literals")
+        names = set(allowed) if not plain else ()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+        args = (max_length, max_tokens, max_rows, N.BUCKET_DESCENDING if descending else N.BUCKET_ASCENDING, index, bos_id, eos_id, pad, sides[truncation_side],
+                sides[padding_side], 0 if fixed_width else pad_to_multiple_of, True, return_pos, False, True)
+        if not plain and self._fffd_literal and any(_has_lone_surrogate(t) for t in texts):
+            # (a literal that holds U+FFFD beside a lone surrogate: only the UTF-16 entry tells the two apart)
+            raw = [t.encode("utf-16-le", "surrogatepass") for t in texts]
+            offs = np.zeros(len(raw) + 1, np.int64)
+            np.cumsum(np.fromiter((len(r) // 2 for r in raw), np.int64, len(raw)), out=offs[1:])
+            r = self._encoder.encode_batch_budgeted_utf16(np.frombuffer(b"".join(raw), "<u2"), offs, *args)
+        else:
+            segs = [_utf8_like_dotnet(t) for t in texts]
+            offs = np.zeros(len(segs) + 1, np.int64)
+            np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+            data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+            r = self._encoder.encode_batch_budgeted(data, offs, *args)
+        ids, mask, pos, lens, _, order, rank, boffs, brows, widths = r[:10]
+        buckets = []
+        for b, W in enumerate(widths.tolist()):
+            rows = int(brows[b + 1] - brows[b])
+            cut = slice(int(boffs[b]), int(boffs[b + 1]))
+            views = (ids[cut].reshape(rows, W), mask[cut].reshape(rows, W)) + ((pos[cut].reshape(rows, W),) if return_pos else ())
+            buckets.append(views)
+        return buckets, order, rank, lens
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
