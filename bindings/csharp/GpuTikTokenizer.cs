@@ -101,6 +101,12 @@ namespace Microsoft.DeepDev
                                                                                             long* bucketRowsOut, int* bucketWidths, long bucketCap, out long totalTokens,
                                                                                             out long totalPositions, out long nCut, out long nBuckets);
         [DllImport(Lib)] internal static extern void tkz_encoder_budgeted_calls(IntPtr encoder, out long calls);
+        // pair rows: two texts a row -- [bos] A sep B [eos] --, cut to a maximum length by a strategy, padded to a common width, with the mask, the type ids, pos, lens and the kept counts (include/tkz.h, "Pair rows")
+        [DllImport(Lib)] internal static extern unsafe int tkz_encode_batch_pairs_utf16(IntPtr encoder, char* units, long* unitOffsets, long nDocs, int* allowed, int nAllowed,
+                                                                                         int bosId, int sepId, int sepCount, int eosId, long maxLen, int strategy, int cutSide, int padSide,
+                                                                                         int padId, long padMultiple, int* outIds, long outCap, byte* mask, byte* typeIds, int* pos, int* lens,
+                                                                                         int* kept, long* outOffsets, out long totalTokens, out long width, out long nCut);
+        [DllImport(Lib)] internal static extern void tkz_encoder_pairs_calls(IntPtr encoder, out long calls);
         // multi-GPU: the count exchange and the shard arithmetic (include/tkz.h, "multi-GPU"), token shard files
         [DllImport(Lib)] internal static extern int tkz_comm_unique_id(byte[] id128);
         [DllImport(Lib)] internal static extern int tkz_comm_create(byte[] id128, int rank, int world, int device, out IntPtr comm);
@@ -759,6 +765,75 @@ namespace Microsoft.DeepDev
             Array.Copy(order, outOrder, texts.Count);
             Array.Copy(rank, outRank, texts.Count);
             return (buckets, outOrder, outRank, outLens);
+        }
+
+        /// <summary>How a pair of texts is cut to the maximum length (tkz_pair_truncation, include/tkz.h): an id at a time from the longer text -- from the second on
+        /// a tie --, the first text only (the second once nothing of the first is left), or the second text only.</summary>
+        public enum PairTruncation { LongestFirst = 0, OnlyFirst = 1, OnlySecond = 2 }
+
+        /// <summary>Row i holds <paramref name="first"/>[i] and <paramref name="second"/>[i] as a cross-encoder takes them: <paramref name="bos"/>, the first text's ids,
+        /// <paramref name="sepCount"/> (0..2) times <paramref name="sep"/>, the second text's ids, <paramref name="eos"/> (null: none; any id of 0 or more is taken as it
+        /// is) -- Encode's ids for the same arguments, the two lists cut to <paramref name="maxLength"/> less the framing TOGETHER by <paramref name="truncation"/>
+        /// (<paramref name="truncateLeft"/>: the tails are kept, else the heads), padded with <paramref name="pad"/> (on the left with <paramref name="padLeft"/>) to the
+        /// longest row rounded up to <paramref name="padToMultipleOf"/> -- at most maxLength; 0: to maxLength itself --, in ONE call (tkz_encode_batch_pairs_utf16;
+        /// include/tkz.h states the rule).  Ids, Mask (1 on content) and TypeIds (1 on the second text's ids and the eos) are pairs x width; Lens the content lengths;
+        /// Kept the ids kept of either text.  A registered set the device path does not hold is NotImplementedException (-7): there is no host path.</summary>
+        public unsafe (int[,] Ids, byte[,] Mask, byte[,] TypeIds, int[] Lens, int[,] Kept) EncodeBatchPairs(IReadOnlyList<string> first, IReadOnlyList<string> second, int maxLength,
+                                                                                                             IReadOnlyCollection<string>? allowedSpecial = null, int? bos = null,
+                                                                                                             int? sep = null, int sepCount = 1, int? eos = null, int pad = 0,
+                                                                                                             PairTruncation truncation = PairTruncation.LongestFirst,
+                                                                                                             bool truncateLeft = false, bool padLeft = false, int padToMultipleOf = 1)
+        {
+            if (first.Count != second.Count) throw new ArgumentException("first and second must hold as many texts as each other", nameof(second));
+            if (sepCount < 0 || sepCount > 2) throw new ArgumentOutOfRangeException(nameof(sepCount));
+            if (!sep.HasValue) sepCount = 0;
+            int framing = (bos.HasValue ? 1 : 0) + sepCount + (eos.HasValue ? 1 : 0);
+            if (maxLength < Math.Max(1, framing)) throw new ArgumentOutOfRangeException(nameof(maxLength));
+            if (bos < 0 || sep < 0 || eos < 0) throw new ArgumentOutOfRangeException(bos < 0 ? nameof(bos) : sep < 0 ? nameof(sep) : nameof(eos));
+            if (padToMultipleOf < 0) throw new ArgumentOutOfRangeException(nameof(padToMultipleOf));
+            bool plain = allowedSpecial is null || allowedSpecial.Count == 0 || specialTokensEncoder.Count == 0;
+            int pairs = first.Count, docs = 2 * pairs;
+            var unitOffsets = new long[docs + 1];                                                 // documents 2p and 2p + 1: the two texts of pair p
+            for (int p = 0; p < pairs; ++p)
+            {
+                unitOffsets[2 * p + 1] = unitOffsets[2 * p] + first[p].Length;
+                unitOffsets[2 * p + 2] = unitOffsets[2 * p + 1] + second[p].Length;
+            }
+            long total = unitOffsets[docs];
+            var units = new char[Math.Max(1, total)];
+            for (int p = 0; p < pairs; ++p)
+            {
+                first[p].CopyTo(0, units, (int)unitOffsets[2 * p], first[p].Length);
+                second[p].CopyTo(0, units, (int)unitOffsets[2 * p + 1], second[p].Length);
+            }
+            int[] allowed = plain ? Array.Empty<int>() : AllowedIndex(allowedSpecial!);
+            long cap = (long)pairs * maxLength;                                                   // the size that always suffices (tkz.h): a row of maxLength a pair
+            var ids = new int[Math.Max(1, cap)];
+            var mask = new byte[Math.Max(1, cap)];
+            var types = new byte[Math.Max(1, cap)];
+            var lens = new int[Math.Max(1, pairs)];
+            var kept = new int[Math.Max(1, docs)];
+            int st;
+            long width;
+            fixed (char* pu = units) fixed (long* po = unitOffsets) fixed (int* pa = allowed) fixed (int* pi = ids) fixed (byte* pm = mask) fixed (byte* pt = types) fixed (int* pl = lens)
+            fixed (int* pk = kept)
+                st = Tkz.tkz_encode_batch_pairs_utf16(encoder, pu, po, docs, allowed.Length > 0 ? pa : null, allowed.Length, bos ?? -1, sep ?? -1, sepCount, eos ?? -1, maxLength,
+                                                      (int)truncation, truncateLeft ? 1 : 0, padLeft ? 1 : 0, pad, padToMultipleOf, pi, cap, pm, pt, null, pl, pk, null,
+                                                      out _, out width, out _);
+            GC.KeepAlive(this);
+            Tkz.Check(st);
+            int w = checked((int)width);
+            var outIds = new int[pairs, w];
+            var outMask = new byte[pairs, w];
+            var outTypes = new byte[pairs, w];
+            Buffer.BlockCopy(ids, 0, outIds, 0, checked(pairs * w * sizeof(int)));
+            Buffer.BlockCopy(mask, 0, outMask, 0, checked(pairs * w));
+            Buffer.BlockCopy(types, 0, outTypes, 0, checked(pairs * w));
+            var outLens = new int[pairs];
+            Array.Copy(lens, outLens, pairs);
+            var outKept = new int[pairs, 2];
+            Buffer.BlockCopy(kept, 0, outKept, 0, checked(docs * sizeof(int)));
+            return (outIds, outMask, outTypes, outLens, outKept);
         }
 
         // the allowed literals as indices into the registered set (registration order = the alternation's)

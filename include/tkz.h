@@ -717,6 +717,77 @@ tkz_status tkz_encode_batch_budgeted_utf16(tkz_encoder* e, const uint16_t* units
 /* informational: successful calls of the budgeted entries */
 void tkz_encoder_budgeted_calls(const tkz_encoder* e, int64_t* calls);
 
+/* ---- Pair rows: one row a PAIR of texts -- [bos] A sep B [eos] --, cut to a maximum length by a strategy, padded to a common width, with mask and type ids, in ONE call ----
+ * What a cross-encoder reranker, an NLI or QA evaluation and a prompt / completion fine-tuning set feed the model: tokenizer(text_a, text_b, truncation=...,
+ * max_length=L, padding=True) -- the ids, token_type_ids and the attention mask.  How much of either text survives depends on BOTH lengths, which exist only on
+ * the device after the encode.
+ * THE RULE.  The batch holds n_docs = 2 * n_pairs documents in the usual layout (one buffer, n_docs + 1 offsets): document 2p is the first text A of pair p,
+ * document 2p + 1 its second text B.  An odd n_docs is TKZ_E_ARG.  Let ids / O[0..n_docs] be EXACTLY what the matching encode entry writes for these documents --
+ * tkz_encode_batch_special_* when n_allowed > 0 and literals are registered, the plain entry otherwise; `allowed` applies to both texts.
+ * a[p] = O[2p + 1] - O[2p], b[p] = O[2p + 2] - O[2p + 1].
+ *   Parameters.  bos_id, eos_id: as in the padded entries: -1 means none, any value >= 0 is taken as it is, < -1 is TKZ_E_ARG; fb = bos_id >= 0, fe = eos_id >= 0.
+ *     sep_count = s in {0, 1, 2}, anything else is TKZ_E_ARG; sep_id >= 0 when s > 0 (-1 or less is TKZ_E_ARG then); it is not read when s == 0.  The framing
+ *     count is f = fb + s + fe.  max_len = L with max(1, f) <= L <= 2^31 - 1, anything else is TKZ_E_ARG.  strategy: a tkz_pair_truncation, anything else is
+ *     TKZ_E_ARG.  cut_side, pad_side, pad_id and pad_multiple = M: exactly as in the padded entries; ONE cut_side serves both texts.
+ *   Cut (token-granular, a plain cut of the id lists).  R = L - f, h = R / 2 rounded down, H = R - h.  The kept counts ka, kb:
+ *     TKZ_PAIR_LONGEST_FIRST: while ka + kb > R, remove one id from the longer text, from the SECOND on a tie.  In closed form, which is what the kernel
+ *       computes: ka = min(a, max(H, R - b)), kb = min(b, max(h, R - a)).  So a shorter text that fits its half is kept whole, and when both are cut A gets the
+ *       odd id.
+ *     TKZ_PAIR_ONLY_FIRST: kb = min(b, R), ka = min(a, R - kb): A gives way first, and B is cut only once nothing of A is left.  This is total where
+ *       tokenizer(...) gives up (a second text longer than the room is an error there): the row never exceeds L.
+ *     TKZ_PAIR_ONLY_SECOND: ka = min(a, R), kb = min(b, R - ka).
+ *     TKZ_TRIM_SUFFIX keeps the heads of both texts, TKZ_TRIM_PREFIX their tails.  The framing is added AFTER the cut, so it always survives:
+ *     len[p] = ka + kb + f.  n_cut is the number of pairs with a + b > R.
+ *   Width.  As the padded rule, with max_p len[p] in place of the longest document: M == 0: W = L; M >= 1: W = min(L, ceil(max_p len[p] / M) * M).  W = 0 when
+ *     n_pairs == 0 or every len[p] is 0; nothing is written then.
+ *   Rows.  Row p is out[p * W .. (p + 1) * W).  Its content is [bos_id] A-kept sep_id x s B-kept [eos_id], len[p] entries, at columns [0, len[p]) with pad_id
+ *     behind it for TKZ_PAD_RIGHT, at columns [W - len[p], W) with pad_id in front of it for TKZ_PAD_LEFT.  mask (uint8): 1 on content, 0 on padding.
+ *     type_ids (uint8): 1 on the kept ids of B and on the eos, 0 everywhere else -- bos, A, every separator and the padding are 0: BERT's token_type_ids, and the
+ *     loss mask of a prompt / completion pair.  pos (int32): the index inside the content, 0 on padding.  lens[p] = len[p] (int32, n_pairs entries).
+ *     kept[2p] = ka, kept[2p + 1] = kb (int32, n_docs entries).  out_offsets[d] = O[d] (int64, n_docs + 1 entries): the UNCUT offsets.
+ *   Scalars.  *total_tokens = O[n_docs], the uncut total -- which is also what the encoder's {n_docs, n_bytes, n_tokens} block receives --, *width = W, *n_cut.
+ *   Example: pairs ([a1 a2 a3 a4 a5], [b1 b2 b3]) and ([], [d1]); bos C, one separator S, eos E; L = 8, M = 1, pad P, right padding.  f = 3, R = 5, W = 8,
+ *     lens = 8, 4, n_cut = 1.
+ *     LONGEST_FIRST, suffix cut: rows C a1 a2 a3 S b1 b2 E / C S d1 E P P P P;  kept 3 2 0 1;  types 00000111 / 00110000
+ *     LONGEST_FIRST, prefix cut: row 0 C a3 a4 a5 S b2 b3 E
+ *     ONLY_FIRST, suffix cut:    row 0 C a1 a2 S b1 b2 b3 E
+ *     ONLY_SECOND, suffix cut:   row 0 C a1 a2 a3 a4 a5 S E;  types of row 0 00000001
+ * CAPACITY.  TKZ_E_CAPACITY when out_cap < n_pairs * W.  *width, *total_tokens and *n_cut then hold the required figures, all from the one call; nothing is
+ * promised in the outputs.  n_pairs * L entries ALWAYS suffice.
+ *   tkz_encode_batch_pairs_device: device buffers.  d_mask, d_type_ids (out_cap bytes each), d_pos (out_cap entries), d_kept (n_docs) and d_out_offsets
+ *     (n_docs + 1) may each be NULL; d_out_ids (out_cap entries), d_lens (n_pairs entries), total_tokens, width and n_cut may not (TKZ_E_ARG).  Everything else --
+ *     allowed / n_allowed, TKZ_E_UNSUPPORTED, tkz_encoder_special_stats, device-side errors, retries of an attempt inside the call (which leave the caller's
+ *     buffers untouched), workspace growth, returning after the stream has drained, the empty batch (TKZ_OK, out_offsets[0] cleared, all three scalars 0), failed
+ *     calls not being counted -- as tkz_encode_batch_padded_device.  Nothing is written at or behind n_pairs * W (ids, mask, types, pos), n_pairs (lens), n_docs
+ *     (kept) or n_docs + 1 (offsets).
+ *     The launch sequence is the PLAIN document-granular one; the uncut ids and offsets stay in the workspace (4 bytes per input byte, 8 per document).  The
+ *     stage: k_pair_lens (a lane a pair: the two kept counts, lens, the first kept id of either text -- one record of 24 bytes a pair of workspace --, and the longest row and the
+ *     cut pairs of every workgroup), then k_pair_write (the width from those partials, the capacity check on the device, the rows by output position in tiles of
+ *     1,024).  The host does not wait between the two.
+ *   tkz_encode_batch_pairs_utf8: host buffers.  The WHOLE batch is staged, ONE call of the device entry, the results downloaded, as
+ *     tkz_encode_batch_padded_utf8.  mask, type_ids, pos, kept and out_offsets may be NULL.  Only the rows, the mask, the types, pos, lens, kept and the offsets
+ *     are downloaded, NEVER the uncut ids.
+ *   tkz_encode_batch_pairs_utf16: code units in, transcoded on the device as tkz_encode_batch_padded_utf16 (a lone surrogate is U+FFFD); unit_offsets in units.
+ * NOT in these entries: an item-granular cut, a maximum per pair, stride or overflowing windows for long second texts, more than two segments a row or templates,
+ * bucketing or budgeting of pair rows, _begin / _end halves, a chunk pipeline for the host entries, device-resident UTF-16 input, a single-pair launch, and exact
+ * agreement with any other library's tie-breaking: the rule above is the contract. */
+typedef enum tkz_pair_truncation { TKZ_PAIR_LONGEST_FIRST = 0, TKZ_PAIR_ONLY_FIRST = 1, TKZ_PAIR_ONLY_SECOND = 2 } tkz_pair_truncation;
+tkz_status tkz_encode_batch_pairs_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                         const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len,
+                                         int32_t strategy, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* d_out_ids, int64_t out_cap,
+                                         uint8_t* d_mask, uint8_t* d_type_ids, int32_t* d_pos, int32_t* d_lens, int32_t* d_kept, int64_t* d_out_offsets, void* hip_stream,
+                                         int64_t* total_tokens, int64_t* width, int64_t* n_cut);
+tkz_status tkz_encode_batch_pairs_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len, int32_t strategy, int32_t cut_side,
+                                       int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* out_ids, int64_t out_cap, uint8_t* mask, uint8_t* type_ids,
+                                       int32_t* pos, int32_t* lens, int32_t* kept, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut);
+tkz_status tkz_encode_batch_pairs_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len, int32_t strategy, int32_t cut_side,
+                                        int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* out_ids, int64_t out_cap, uint8_t* mask, uint8_t* type_ids,
+                                        int32_t* pos, int32_t* lens, int32_t* kept, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut);
+/* informational: successful calls of the pair entries */
+void tkz_encoder_pairs_calls(const tkz_encoder* e, int64_t* calls);
+
 /* ---- Decode (TikTokenizer.cs:586-604) for a batch ---------------------------------------------
  * Document d of the result is the concatenation of the byte strings of ids[id_offsets[d] .. id_offsets[d+1]): a vocabulary id
  * yields its key, a registered special token its UTF-8 literal, any other id nothing (the reference drops unknown ids silently,
@@ -877,7 +948,8 @@ enum { TKZ_K_DOCMARK = 0, TKZ_K_PRETOK = 1, TKZ_K_PROBE = 2 /* k_probe alone */,
  * (k_pack_count, the scan of its counts, k_pack_write), closed again behind the stage in the same way.  Of a padded call (tkz_encode_batch_padded_device)
  * likewise: k_docoffs over the documents, k_pad_lens and k_pad_write; of a bucketed call (tkz_encode_batch_bucketed_device): k_docoffs, k_pad_lens, the sort's
  * passes, k_bkt_table, its scan and k_bkt_write; of a budgeted call (tkz_encode_batch_budgeted_device): k_docoffs, k_pad_lens, the sort's passes, k_tbk_mark
- * twice with its scan, k_tbk_chain, the scan of the runs' buckets, k_tbk_table, its scan and k_tbk_write.
+ * twice with its scan, k_tbk_chain, the scan of the runs' buckets, k_tbk_table, its scan and k_tbk_write; of a pair call (tkz_encode_batch_pairs_device):
+ * k_docoffs over the documents, k_pair_lens and k_pair_write.
  * A batch that runs the long pieces' kernels beside k_merge_short (tkz_encoder_side_by_side_batches) has k_merge_long_q and k_merge_coop INSIDE the
  * TKZ_K_MERGE_SHORT bracket -- the three side by side, from the fork to the join -- and only what runs in front of them (the giant pieces, the class
  * queue's counting, scan and scatter) in TKZ_K_MERGE_LONG.  A batch of at most TKZ_OPT_LATENCY_BYTES likewise: its TKZ_K_MERGE_SHORT bracket is k_merge_latency

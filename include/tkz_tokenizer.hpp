@@ -11,6 +11,7 @@
 //                              EncodeBatchPacked (std::string, std::u16string): the ids framed by bos / eos ids in rows of the context length, pos, seg_starts
 //                              EncodeBatchPadded (std::string, std::u16string): a row a text, cut to maxLength, framed, padded to a common width; mask, pos, lens
 //                              EncodeBatchBucketed (std::string, std::u16string): the same rows sorted by length, a width per bucket of bucketRows rows; order, rank
+//                              EncodeBatchPairs (std::string, std::u16string): two texts a row, [bos] A sep B [eos], cut by a strategy, padded; mask, type ids, kept
 //                              Decode / DecodeBatch (bytes), DecodeUtf16 / DecodeBatchUtf16 (the string's code units)   TikTokenizer.cs:586-604
 //   tkz::TokenizerBuilder      CreateTokenizer(stream, specials, pattern)   TokenizerBuilder.cs:210-213
 //
@@ -669,6 +670,35 @@ public:
         for (const auto& t : texts) { units.insert(units.end(), t.begin(), t.end()); offs.push_back(static_cast<int64_t>(units.size())); }
         return budgeted_batch<uint16_t>(units, offs, maxLength, maxTokens, maxRows, order, allowedSpecial, bos, eos, pad, cutSide, padSide, padMultiple, true);
     }
+    // ---- pair rows: two texts a row -- [bos] first sep x sepCount second [eos] --, cut to maxLength by a strategy, padded to a common width, in ONE call
+    // (tkz_encode_batch_pairs_utf8 / _utf16) ----
+    // Row i holds first[i] and second[i]: their ids -- Encode's for the same arguments -- cut to maxLength less the framing by `truncation` (TKZ_PAIR_LONGEST_FIRST: an
+    // id at a time from the longer text, from the second on a tie; TKZ_PAIR_ONLY_FIRST; TKZ_PAIR_ONLY_SECOND), cutSide TKZ_TRIM_SUFFIX keeping the heads and
+    // TKZ_TRIM_PREFIX the tails, padded with pad on padSide to the longest row rounded up to padMultiple -- at most maxLength; padMultiple 0: to maxLength itself.  ids,
+    // mask (1 on content), type_ids (1 on the second text's ids and the eos) and pos are n * width entries, row-major; lens the content lengths; kept the ids kept of
+    // either text (2 a row); n_cut the pairs that were cut; total_tokens the uncut total (tkz.h states the rule).  bos, sep, eos: -1 for none (sepCount is 0 then).
+    // first and second of different sizes are an Error (TKZ_E_ARG).  A registered set the device's special entries do not hold is a NotImplementedError.
+    struct PairRows { int64_t width = 0, total_tokens = 0, n_cut = 0; std::vector<int32_t> ids, pos, lens, kept; std::vector<uint8_t> mask, type_ids; };
+    PairRows EncodeBatchPairs(const std::vector<std::string>& first, const std::vector<std::string>& second, int64_t maxLength, const std::vector<std::string>& allowedSpecial = {},
+                              int32_t bos = -1, int32_t sep = -1, int32_t sepCount = 1, int32_t eos = -1, int32_t pad = 0, tkz_pair_truncation truncation = TKZ_PAIR_LONGEST_FIRST,
+                              tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        if (first.size() != second.size()) throw Error(TKZ_E_ARG, "EncodeBatchPairs: first and second must hold as many texts as each other");
+        std::vector<uint8_t> bytes;
+        std::vector<int64_t> offs{0};
+        for (size_t i = 0; i < first.size(); ++i)
+            for (const std::string* t : {&first[i], &second[i]}) { bytes.insert(bytes.end(), t->begin(), t->end()); offs.push_back(static_cast<int64_t>(bytes.size())); }
+        return pairs_batch<uint8_t>(bytes, offs, maxLength, allowedSpecial, bos, sep, sepCount, eos, pad, truncation, cutSide, padSide, padMultiple, false);
+    }
+    PairRows EncodeBatchPairs(const std::vector<std::u16string>& first, const std::vector<std::u16string>& second, int64_t maxLength, const std::vector<std::string>& allowedSpecial = {},
+                              int32_t bos = -1, int32_t sep = -1, int32_t sepCount = 1, int32_t eos = -1, int32_t pad = 0, tkz_pair_truncation truncation = TKZ_PAIR_LONGEST_FIRST,
+                              tkz_trim_side cutSide = TKZ_TRIM_SUFFIX, tkz_pad_side padSide = TKZ_PAD_RIGHT, int64_t padMultiple = 1) const {
+        if (first.size() != second.size()) throw Error(TKZ_E_ARG, "EncodeBatchPairs: first and second must hold as many texts as each other");
+        std::vector<uint16_t> units;
+        std::vector<int64_t> offs{0};
+        for (size_t i = 0; i < first.size(); ++i)
+            for (const std::u16string* t : {&first[i], &second[i]}) { units.insert(units.end(), t->begin(), t->end()); offs.push_back(static_cast<int64_t>(units.size())); }
+        return pairs_batch<uint16_t>(units, offs, maxLength, allowedSpecial, bos, sep, sepCount, eos, pad, truncation, cutSide, padSide, padMultiple, true);
+    }
     // (the id of a registered special token, for bos / eos)
     int32_t SpecialTokenId(const std::string& literal) const {
         for (const auto& kv : specials_) if (kv.first == literal) return kv.second;
@@ -994,6 +1024,40 @@ private:
         out.bucket_offsets.resize(static_cast<size_t>(out.n_buckets) + 1);
         out.bucket_rows.resize(static_cast<size_t>(out.n_buckets) + 1);
         out.bucket_widths.resize(static_cast<size_t>(out.n_buckets));
+        return out;
+    }
+    // ONE call of the batch pair entry on the interleaved texts (documents 2p and 2p + 1: the two texts of row p), with the capacity that always suffices (tkz.h): a row
+    // of maxLength a pair
+    template <class UNIT>
+    PairRows pairs_batch(std::vector<UNIT>& items, const std::vector<int64_t>& offs, int64_t maxLength, const std::vector<std::string>& allowedSpecial, int32_t bos, int32_t sep,
+                         int32_t sepCount, int32_t eos, int32_t pad, tkz_pair_truncation truncation, tkz_trim_side cutSide, tkz_pad_side padSide, int64_t padMultiple, bool utf16) const {
+        const int64_t nd = static_cast<int64_t>(offs.size()) - 1, n = nd / 2;
+        PairRows out;
+        if (sep == -1) sepCount = 0;                                                           // (no separator id: no separator)
+        const bool plain = allowedSpecial.empty() || specials_.empty();
+        const std::vector<int32_t> index = plain ? std::vector<int32_t>{} : allowed_index(allowedSpecial);
+        const int64_t cap = maxLength >= 1 && maxLength <= INT32_MAX ? n * maxLength : 0;      // (a maxLength out of range is refused by the library)
+        if (items.empty()) items.push_back(0);
+        out.ids.resize(static_cast<size_t>(std::max<int64_t>(cap, 1)));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.type_ids.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(std::max<int64_t>(n, 1)));
+        out.kept.resize(static_cast<size_t>(std::max<int64_t>(nd, 1)));
+        tkz_status st;
+        if (utf16) st = tkz_encode_batch_pairs_utf16(enc_, reinterpret_cast<const uint16_t*>(items.data()), offs.data(), nd, index.data(), static_cast<int32_t>(index.size()), bos, sep,
+                                                     sepCount, eos, maxLength, truncation, cutSide, padSide, pad, padMultiple, out.ids.data(), cap, out.mask.data(),
+                                                     out.type_ids.data(), out.pos.data(), out.lens.data(), out.kept.data(), nullptr, &out.total_tokens, &out.width, &out.n_cut);
+        else st = tkz_encode_batch_pairs_utf8(enc_, reinterpret_cast<const uint8_t*>(items.data()), offs.data(), nd, index.data(), static_cast<int32_t>(index.size()), bos, sep,
+                                              sepCount, eos, maxLength, truncation, cutSide, padSide, pad, padMultiple, out.ids.data(), cap, out.mask.data(), out.type_ids.data(),
+                                              out.pos.data(), out.lens.data(), out.kept.data(), nullptr, &out.total_tokens, &out.width, &out.n_cut);
+        check(st);
+        out.ids.resize(static_cast<size_t>(n * out.width));
+        out.pos.resize(out.ids.size());
+        out.mask.resize(out.ids.size());
+        out.type_ids.resize(out.ids.size());
+        out.lens.resize(static_cast<size_t>(n));
+        out.kept.resize(static_cast<size_t>(nd));
         return out;
     }
     // ONE call of the batch chunk entry on the concatenated texts (UNIT: uint8_t bytes, uint16_t code units), cut into a list of (ids, text) per text

@@ -22,6 +22,7 @@ OPT_CASE_EQUIVALENCE = 7    # cl100k's (?i:...) with .NET >= 7's case-equivalenc
 TRIM_SUFFIX, TRIM_PREFIX = 0, 1   # tkz_trim_side
 PAD_RIGHT, PAD_LEFT = 0, 1         # tkz_pad_side
 BUCKET_ASCENDING, BUCKET_DESCENDING = 0, 1   # tkz_bucket_order
+TRUNC_LONGEST_FIRST, TRUNC_ONLY_FIRST, TRUNC_ONLY_SECOND = 0, 1, 2   # tkz_pair_truncation
 NO_ROW_CAP = (1 << 31) - 1                    # bucket_rows of the budgeted entries: no cap on the rows of a bucket
 OPT_LATENCY_BYTES = 8       # batches of at most this many bytes merge long missed pieces a wavefront each (tkz.h)
 OPT_ADAPT = 9               # 1 (default): the encoder learns again when the text has drifted; small batches add up to a learning window (tkz.h)
@@ -220,6 +221,12 @@ class Library:
         L.tkz_encode_batch_budgeted_utf16.argtypes = list(L.tkz_encode_batch_budgeted_utf8.argtypes)
         L.tkz_encoder_budgeted_calls.argtypes = [vp, pi64]
         L.tkz_encoder_budgeted_calls.restype = None
+        L.tkz_encode_batch_pairs_device.argtypes = [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                    pi64, pi64, pi64]
+        L.tkz_encode_batch_pairs_utf8.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, pi64, pi64, pi64]
+        L.tkz_encode_batch_pairs_utf16.argtypes = list(L.tkz_encode_batch_pairs_utf8.argtypes)
+        L.tkz_encoder_pairs_calls.argtypes = [vp, pi64]
+        L.tkz_encoder_pairs_calls.restype = None
         L.tkz_shard_write.argtypes = [C.c_char_p, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_write_device.argtypes = [C.c_char_p, i32, vp, i64, vp, i64, i64, i64]
         L.tkz_shard_read_header.argtypes = [C.c_char_p, pi64, pi64, pi64, pi64]
@@ -1330,6 +1337,79 @@ class Encoder:
         """successful calls of the budgeted entries"""
         a = C.c_int64(0)
         self.lib.L.tkz_encoder_budgeted_calls(self._h, C.byref(a))
+        return a.value
+
+    # -- pair rows: documents 2p and 2p + 1 as the two texts of row p, cut to max_len by a strategy, [bos] A sep x s B [eos], padded to the common width (tkz.h: the rule) --
+    @staticmethod
+    def pairs_bounds(n_pairs, max_len):
+        """the ids (and mask and type bytes, and pos entries) that always suffice (tkz.h): a row of max_len a pair"""
+        return n_pairs * max_len
+
+    def _pairs_host(self, fn, buf, offsets, allowed, max_len, bos_id, sep_id, sep_count, eos_id, pad_id, strategy, cut_side, pad_side, pad_multiple, want_mask, want_types,
+                    want_pos, want_kept, want_offs, out_cap):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        n = len(offsets) - 1
+        npairs = n // 2
+        cap = (self.pairs_bounds(npairs, max_len) if 1 <= max_len < 1 << 31 else 0) if out_cap is None else out_cap      # (a max_len out of range is refused by the library)
+        ids = np.empty(max(1, cap), np.int32)
+        mask = np.empty(max(1, cap), np.uint8) if want_mask else None
+        types = np.empty(max(1, cap), np.uint8) if want_types else None
+        pos = np.empty(max(1, cap), np.int32) if want_pos else None
+        lens = np.empty(max(1, npairs), np.int32)
+        kept = np.empty(max(1, n), np.int32) if want_kept else None
+        ooff = np.empty(n + 1, np.int64) if want_offs else None
+        tot, w, cut = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(fn(self._h, buf, _ptr(offsets), n, _ptr(allowed) if len(allowed) else None, len(allowed), bos_id, sep_id, sep_count, eos_id, max_len, strategy,
+                              cut_side, pad_side, pad_id, pad_multiple, _ptr(ids), cap, _ptr(mask) if want_mask else None, _ptr(types) if want_types else None,
+                              _ptr(pos) if want_pos else None, _ptr(lens), _ptr(kept) if want_kept else None, _ptr(ooff) if want_offs else None,
+                              C.byref(tot), C.byref(w), C.byref(cut)))
+        except TkzError as ex:
+            ex.needed, ex.needed_width, ex.n_cut = tot.value, w.value, cut.value      # (E_CAPACITY: the required figures)
+            raise
+        W = w.value
+        rows = lambda a: a[:npairs * W].reshape(npairs, W)
+        return (rows(ids), rows(mask) if want_mask else None, rows(types) if want_types else None, rows(pos) if want_pos else None, lens[:npairs],
+                kept[:2 * npairs].reshape(npairs, 2) if want_kept else None, ooff, tot.value, cut.value)
+
+    def encode_batch_pairs(self, data: np.ndarray, offsets: np.ndarray, max_len, allowed=(), bos_id=-1, sep_id=-1, sep_count=0, eos_id=-1, pad_id=0, strategy=TRUNC_LONGEST_FIRST,
+                           cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT, pad_multiple=1, want_mask=True, want_types=True, want_pos=True, want_kept=True, want_offs=True, out_cap=None):
+        """(ids int32[n_pairs, W], mask uint8[n_pairs, W] or None, type_ids uint8[n_pairs, W] or None, pos int32[n_pairs, W] or None, lens int32[n_pairs],
+        kept int32[n_pairs, 2] or None, offsets int64[n_docs + 1] or None, total_tokens, n_cut): documents 2p and 2p + 1 are the two texts of pair p; the ids of
+        encode_batch / encode_batch_special cut to max_len by the strategy, framed, joined and padded to the common width W -- tkz_encode_batch_pairs_utf8."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self._pairs_host(self.lib.L.tkz_encode_batch_pairs_utf8, _ptr(data) if len(data) else None, offsets, allowed, max_len, bos_id, sep_id, sep_count, eos_id, pad_id,
+                                strategy, cut_side, pad_side, pad_multiple, want_mask, want_types, want_pos, want_kept, want_offs, out_cap)
+
+    def encode_batch_pairs_utf16(self, units: np.ndarray, offsets: np.ndarray, max_len, allowed=(), bos_id=-1, sep_id=-1, sep_count=0, eos_id=-1, pad_id=0,
+                                 strategy=TRUNC_LONGEST_FIRST, cut_side=TRIM_SUFFIX, pad_side=PAD_RIGHT, pad_multiple=1, want_mask=True, want_types=True, want_pos=True,
+                                 want_kept=True, want_offs=True, out_cap=None):
+        """encode_batch_pairs for UTF-16 documents (uint16[total], offsets in units) -- tkz_encode_batch_pairs_utf16."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        buf = units if len(units) else np.zeros(1, np.uint16)
+        return self._pairs_host(self.lib.L.tkz_encode_batch_pairs_utf16, _ptr(buf), offsets, allowed, max_len, bos_id, sep_id, sep_count, eos_id, pad_id, strategy, cut_side,
+                                pad_side, pad_multiple, want_mask, want_types, want_pos, want_kept, want_offs, out_cap)
+
+    def encode_batch_pairs_device(self, d_bytes, d_offsets, n_docs, total_bytes, allowed, bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_id,
+                                  pad_multiple, d_out_ids, out_cap, d_mask=0, d_type_ids=0, d_pos=0, d_lens=0, d_kept=0, d_out_offsets=0, stream=0):
+        """Device buffers in and out: tkz_encode_batch_pairs_device.  Returns (total_tokens, W, n_cut); a TkzError carries them as `needed`, `needed_width`, `n_cut`."""
+        allowed = np.ascontiguousarray(allowed, dtype=np.int32)
+        tot, w, cut = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self.lib.check(self.lib.L.tkz_encode_batch_pairs_device(self._h, d_bytes or None, d_offsets or None, n_docs, total_bytes, _ptr(allowed) if len(allowed) else None,
+                                                                    len(allowed), bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_id, pad_multiple,
+                                                                    d_out_ids or None, out_cap, d_mask or None, d_type_ids or None, d_pos or None, d_lens or None,
+                                                                    d_kept or None, d_out_offsets or None, stream or None, C.byref(tot), C.byref(w), C.byref(cut)))
+        except TkzError as ex:
+            ex.needed, ex.needed_width, ex.n_cut = tot.value, w.value, cut.value
+            raise
+        return tot.value, w.value, cut.value
+
+    def pairs_calls(self):
+        """successful calls of the pair entries"""
+        a = C.c_int64(0)
+        self.lib.L.tkz_encoder_pairs_calls(self._h, C.byref(a))
         return a.value
 
     def set_special_tokens(self, specials):

@@ -111,7 +111,7 @@ struct CounterBlock {          // mirrors the device block
     unsigned long long chunk_long;         // ... documents on the wavefront walk's list (k_chunk_walk -> k_chunk_walk_long)
     int64_t pack_total, pack_rows, pack_segs;   // the packed entries: T, n_rows (k_pack_count) and n_segs (the scan of its counts) -- PackParams::totals
     int64_t pad_total, pad_width, pad_cut;      // the padded entries: the uncut total, W and n_cut (k_pad_write) -- PadParams::totals; the bucketed entries: the
-                                                // uncut total, P and n_cut (k_bkt_write)
+                                                // uncut total, P and n_cut (k_bkt_write); the pair entries: the uncut total, W and n_cut (k_pair_write)
     int64_t pad_buckets;                        // the budgeted entries: n_buckets (k_tbk_write), behind their {uncut total, P, n_cut} in the three fields above
     // The LAST field: the fill of a re-run ends in front of it (enqueue_attempt), since k_docmark, which sets it, does not run again then.
     int32_t has_empty, pad_;               // k_docmark -> k_docoffs: a document of the batch is empty (k_docoffs searches the marks' ordinals)
@@ -243,7 +243,13 @@ struct TbkBufs {    // the budgeted entries (beside PadBufs and BktBufs, which t
     DevBuf tb_marks, tb_runs, tb_rows, tb_fig, tb_stage;
     void release() { release_each({&tb_marks, &tb_runs, &tb_rows, &tb_fig, &tb_stage}); }
 };
-struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs, BktBufs, TbkBufs {
+struct PairBufs {   // the pair entries: the uncut ids and their offsets, the record of every pair (the first kept id of either text, srcA and srcB, then the row's
+    // len and the kept count ka of the first text in one word: 24 bytes a pair), the partials of k_pair_lens (kPairGridMax lengths, then as many counts); the block of a batch without bytes
+    // ({total, W, n_cut}, a zero total, a zero error word); the host entries' pos, lens, kept, mask and types
+    DevBuf pr_ids, pr_offs, pr_src, pr_part, pr_tot, pr_stage;
+    void release() { release_each({&pr_ids, &pr_offs, &pr_src, &pr_part, &pr_tot, &pr_stage}); }
+};
+struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, DecodeSmallBufs, PieceBufs, TrimBufs, SpanBufs, ChunkBufs, PackBufs, PadBufs, BktBufs, TbkBufs, PairBufs {
     // kernel workspace
     DevBuf w_gq, w_gcnt, w_xq, w_startbits, w_tmp, w_dense, w_tcount, w_prank, w_pcount, w_pbase, w_tbase, w_bsum, w_doctok, w_dcount, w_dbase, w_pool;
     // what every batch starts from as zeros -- the counter block, the document-start bitmap, the per-sub-tile flags -- lives in ONE buffer, zeroed by ONE
@@ -297,7 +303,7 @@ struct Workspace : SpecialBufs, HostStageBufs, DecodeBufs, DecodeUtf16Bufs, Deco
     int64_t launches[tkz::K_COUNT] = {};
     void release_all() {
         release_core();
-        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release(); BktBufs::release(); TbkBufs::release();
+        SpecialBufs::release(); HostStageBufs::release(); DecodeBufs::release(); DecodeUtf16Bufs::release(); DecodeSmallBufs::release(); PieceBufs::release(); TrimBufs::release(); SpanBufs::release(); ChunkBufs::release(); PackBufs::release(); PadBufs::release(); BktBufs::release(); TbkBufs::release(); PairBufs::release();
         for (U16Stage& U : u16) U.release();
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_small) (void)hipHostFree(h_small);
@@ -342,6 +348,7 @@ struct tkz_encoder {
     std::atomic<int64_t> padded_calls{0};                                 // tkz_encoder_padded_calls: successful calls of the padded entries
     std::atomic<int64_t> bucketed_calls{0};                               // tkz_encoder_bucketed_calls: successful calls of the bucketed entries
     std::atomic<int64_t> budgeted_calls{0};                               // tkz_encoder_budgeted_calls: successful calls of the budgeted entries
+    std::atomic<int64_t> pairs_calls{0};                                  // tkz_encoder_pairs_calls: successful calls of the pair entries
     std::atomic<int64_t> chunks_overlap_calls{0};                          // tkz_encoder_chunks_overlap_calls: successful calls of the overlap chunk entries
     std::atomic<int64_t> chunks_calls{0};                                  // tkz_encoder_chunks_calls: successful calls of the chunk entries
     std::atomic<int64_t> spans_calls{0};                                   // tkz_encoder_spans_calls: successful calls of the span entries
@@ -413,6 +420,11 @@ struct BktCall { int64_t bucket_rows; int32_t order; int64_t* d_order; int64_t* 
 // caller's bucket arrays, where the buckets' first rows go (device) and, on the host, where n_buckets goes
 struct TbkCall { int64_t token_budget, bucket_cap; int64_t* d_bucket_rows; int64_t* n_buckets;
                  int64_t table_cap(int64_t n_docs) const { return std::min(n_docs, bucket_cap); } };
+// A call of one of the pair entries: the framing ids (-1: none), the separator and how many of it, the maximum length, the strategy, the two sides, the pad id and
+// the multiple, where the mask, types, pos, lens and kept go (device; all but lens may be null -- and BatchCall::d_out_offs too) and, on the host, where the width
+// and the number of cut pairs go
+struct PairCall { int32_t bos_id, sep_id, sep_count, eos_id; int64_t max_len; int32_t strategy, cut_side, pad_side, pad_id; int64_t pad_multiple;
+                  uint8_t* d_mask; uint8_t* d_types; int32_t* d_pos; int32_t* d_lens; int32_t* d_kept; int64_t* width; int64_t* n_cut; };
 // the caller's page-locked text and offsets as the device sees them: encode_device fetches them itself (k_ingest) into d_bytes / d_offs
 struct IngestSrc { const uint8_t* h_bytes; const int64_t* h_offs; };
 
@@ -427,7 +439,8 @@ enum class CallKind {
     Packed,          // tkz_encode_batch_packed_device: Encode's own sequence (no piece arrays), then the framed stream laid out in rows, pos and seg_starts
     Padded,          // tkz_encode_batch_padded_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a document
     Bucketed,        // tkz_encode_batch_bucketed_device: as Padded up to the lengths, then the documents sorted by length and a width per bucket of rows
-    Budgeted         // tkz_encode_batch_budgeted_device: as Bucketed up to the sort, then buckets of at most a token budget of positions
+    Budgeted,        // tkz_encode_batch_budgeted_device: as Bucketed up to the sort, then buckets of at most a token budget of positions
+    Pairs            // tkz_encode_batch_pairs_device: Encode's own sequence with the ids in the workspace, then a cut, framed and padded row a PAIR of documents
 };
 
 // One batch as the device path sees it (encode_device and its stages).  tkz_pending and the chunk pipeline keep the descriptor they began a batch with and hand
@@ -447,6 +460,7 @@ struct BatchCall {
     const PadCall* padded = nullptr;           // Padded, Bucketed: the framing, the cut, the padding and where the mask, pos and lens go
     const BktCall* bucketed = nullptr;         // Bucketed, Budgeted: the rows a bucket, the direction and where the permutation and the bucket table go
     const TbkCall* budgeted = nullptr;         // Budgeted: the token budget, the bucket capacity and where the buckets' first rows go
+    const PairCall* pairs = nullptr;           // Pairs: the framing, the separators, the strategy, the padding and where the mask, types, pos, lens and kept go
     int64_t* d_counts3 = nullptr;              // the caller's block for this batch's {n_docs, n_bytes, n_tokens} (may be null)
     const IngestSrc* ingest = nullptr;         // the text is fetched from the caller's page-locked memory by the first attempt
     const uint64_t* d_repl = nullptr;          // the special entries on text transcoded from UTF-16: the replaced-byte bitmap (launch_lit_scan), or null
@@ -456,7 +470,7 @@ struct BatchCall {
     bool plain_encode() const { return kind == CallKind::Encode; }                        // the sizing sample and the special literals are for these
     bool piece_granular() const { return kind == CallKind::Trim || kind == CallKind::Spans || kind == CallKind::Chunks; }      // (Pieces with the piece arrays in the workspace)
     bool may_learn() const { return pretokenizes() && !bitmap_only(); }                   // pre-tokenized text that reaches the key tables
-    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded || kind == CallKind::Bucketed || kind == CallKind::Budgeted ? special : nullptr; }
+    const SpecialCall* literals() const { return plain_encode() || piece_granular() || kind == CallKind::Packed || kind == CallKind::Padded || kind == CallKind::Bucketed || kind == CallKind::Budgeted || kind == CallKind::Pairs ? special : nullptr; }
 };
 
 // tkz_encode_trim_utf8 / _utf16 (ONE text, cut to a maximum): the side, the maximum and where the cut's lengths go (host memory; either may be null)
@@ -1074,6 +1088,42 @@ tkz_status pad_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t*
     return TKZ_OK;
 }
 
+// the stage of a pair call over the uncut ids and offsets (the workspace's); blk and totals as pad_params
+tkz::PairParams pair_params(Workspace* ws, const BatchCall& c, const int64_t* grand, int64_t* totals, const int32_t* blk) {
+    const PairCall& k = *c.pairs;
+    const int64_t np = c.n_docs / 2;
+    int32_t* const part = ws->pr_part.as<int32_t>();
+    return tkz::PairParams{ws->pr_ids.as<int32_t>(), c.total, ws->pr_offs.as<int64_t>(), np, grand, k.bos_id, k.sep_id, k.sep_count, k.eos_id, k.pad_id, k.max_len,
+                           k.strategy, k.cut_side, k.pad_side, k.pad_multiple, c.d_out, c.out_cap, k.d_mask, k.d_types, k.d_pos, k.d_lens, k.d_kept, c.d_out_offs,
+                           ws->pr_src.as<int64_t>(), part, reinterpret_cast<int64_t*>(part + tkz::kPairGridMax), 0, totals, blk};
+}
+
+// A pair call on a batch without bytes, as pad_empty: every row is its framing alone (W = 0 without framing), and the stage runs over offsets that are all 0.
+// Without documents there is nothing but the offset to clear.
+tkz_status pair_empty(tkz_encoder* e, Workspace* ws, const BatchCall& c, int64_t* totals3) {
+    using namespace tkz;
+    const int64_t n_docs = c.n_docs;
+    totals3[0] = totals3[1] = totals3[2] = 0;
+    const Launch L{c.stream, nullptr, ws};
+    HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
+    if (n_docs == 0) {
+        launch_counts3(L, 0, 0, nullptr, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+        if (c.d_out_offs) HIP_TRY(hipMemsetAsync(c.d_out_offs, 0, sizeof(int64_t), c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return TKZ_OK;
+    }
+    HIP_TRY(ws->pr_tot.ensure(64, &ws->bytes_allocated));
+    HIP_TRY(hipMemsetAsync(ws->pr_tot.p, 0, 64, c.stream));
+    HIP_TRY(hipMemsetAsync(ws->pr_offs.p, 0, (size_t)(n_docs + 1) * sizeof(int64_t), c.stream));
+    int64_t* const tot = ws->pr_tot.as<int64_t>();
+    launch_pairs(L, pair_params(ws, c, tot + 3, tot, reinterpret_cast<const int32_t*>(tot + 4)));
+    launch_counts3(L, n_docs, 0, tot, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+    HIP_TRY(hipMemcpyAsync(totals3, tot, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    HIP_TRY(hipGetLastError());
+    return TKZ_OK;
+}
+
 // One attempt on the stream: the zero region and the text (k_ingest), the document marks and the pre-tokenizer (or, on a re-run, the counters and the
 // sub-tile flags only: it starts behind the pre-tokenizer), the counts of the marks and pieces and their scan, the piece index, then the sizing probe
 // (nsample >= 0) or the whole launch sequence, and the counter block back to the host.
@@ -1208,6 +1258,8 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
             else if (c.packed && c.packed->frame()) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pk_ids.as<int32_t>(), total);
             // (a padded call: the uncut ids likewise -- the rows are gathered from them)
             else if (c.padded) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pd_ids.as<int32_t>(), total);
+            // (a pair call: the same -- the rows are gathered from the two texts' ids)
+            else if (c.pairs) launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, ws->pr_ids.as<int32_t>(), total);
             else launch_place(L, P, ws->w_tbase.as<int64_t>(), ntiles, c.trim ? ws->t_ids.as<int32_t>() : c.d_out, c.trim ? total : c.out_cap);
             if (po) {
                 if (!*pieces_over) launch_docoffs(L, po->piece_boffs, po->n_pieces, total, ws->w_tbase.as<int64_t>(), markbits, P.docord_base, P.doc_tok, grand, po->piece_toffs, has_empty);
@@ -1261,6 +1313,10 @@ tkz_status enqueue_attempt(tkz_encoder* e, Workspace* ws, const tkz::Launch& L, 
                                                               reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_buckets))));
                 else if (c.bucketed) launch_bucketed(L, bkt_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
                 else launch_pad(L, pad_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
+                launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
+            } else if (c.pairs) {                                       // (the uncut offsets, then the rows of the pairs; the counts blocks receive the uncut total)
+                launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, ws->pr_offs.as<int64_t>(), has_empty);
+                launch_pairs(L, pair_params(ws, c, grand, reinterpret_cast<int64_t*>(cb + offsetof(CounterBlock, pad_total)), counters));
                 launch_counts3(L, n_docs, total, grand, e->t_counts3.as<int64_t>(), ws->w_counts3.as<int64_t>(), c.d_counts3);
             } else      // (the batch's {n_docs, n_bytes, n_tokens} blocks by the same launch)
                 launch_docoffs(L, d_offs, n_docs, total, ws->w_tbase.as<int64_t>(), docbits, P.docord_base, P.doc_tok, grand, c.d_out_offs,
@@ -1452,6 +1508,20 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         TKZ_TRY(pad_empty(e, ws, c, totals3));
         return padded_done(totals3);
     }
+    // the outcome of a pair call: the uncut total, the width and the cut pairs; n_pairs * W against the capacity
+    const auto pairs_done = [&](const int64_t* totals3) {
+        const PairCall& k = *c.pairs;
+        if (total_tokens) *total_tokens = totals3[0];
+        if (k.width) *k.width = totals3[1];
+        if (k.n_cut) *k.n_cut = totals3[2];
+        if (totals3[1] > 0 && n_docs / 2 > c.out_cap / totals3[1]) return fail(TKZ_E_CAPACITY, "output capacity too small for the rows");
+        return TKZ_OK;
+    };
+    if (total == 0 && c.pairs) {
+        int64_t totals3[3];
+        TKZ_TRY(pair_empty(e, ws, c, totals3));
+        return pairs_done(totals3);
+    }
     if (total == 0) {
         if (phase != kCallEnd) {                                  // (kCallEnd: enqueued when it began)
             HIP_TRY(ws->w_counts3.ensure(32, &ws->bytes_allocated));
@@ -1509,6 +1579,7 @@ tkz_status encode_device(tkz_encoder* e, Workspace* ws, const BatchCall& c, int 
         if (c.literals()) e->spec_literals += ws->spec_taken;
         if (c.packed) return packed_done(&ws->h_counters->pack_total);
         if (c.padded) return padded_done(&ws->h_counters->pad_total);
+        if (c.pairs) return pairs_done(&ws->h_counters->pad_total);
         const int64_t produced = c.trim ? ws->h_counters->kept_total : ws->h_counters->grand;      // (a trim call's capacity counts the kept ids)
         if (total_tokens) *total_tokens = produced;
         if (c.chunks && c.chunks->n_chunks) *c.chunks->n_chunks = ws->h_counters->n_chunks;      // (both required sizes from one call)
@@ -3921,6 +3992,158 @@ tkz_status tkz_encode_batch_budgeted_utf16(tkz_encoder* e, const uint16_t* units
 }
 void tkz_encoder_budgeted_calls(const tkz_encoder* e, int64_t* calls) {
     if (calls) *calls = e ? e->budgeted_calls.load() : 0;
+}
+
+// ---- pair rows: documents 2p and 2p + 1 as the two texts of row p -- cut to max_len by a strategy, [bos] A sep x s B [eos], padded to the common width (tkz.h: the rule) ----
+
+namespace {
+tkz_status check_pair_args(int64_t n_docs, int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len, int32_t strategy, int32_t cut_side,
+                           int32_t pad_side, int64_t pad_multiple) {
+    if (n_docs >= 0 && (n_docs & 1)) return fail(TKZ_E_ARG, "pair rows: n_docs must be even -- documents 2p and 2p + 1 are the two texts of pair p");
+    if (bos_id < -1 || eos_id < -1) return fail(TKZ_E_ARG, "pair rows: bos_id and eos_id are -1 (none) or an id >= 0");
+    if (sep_count < 0 || sep_count > 2) return fail(TKZ_E_ARG, "pair rows: sep_count must be 0, 1 or 2");
+    if (sep_count > 0 && sep_id < 0) return fail(TKZ_E_ARG, "pair rows: sep_id must be an id >= 0 when sep_count > 0");
+    const int64_t f = (bos_id >= 0) + (eos_id >= 0) + sep_count;
+    if (max_len < std::max<int64_t>(1, f) || max_len > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "pair rows: max_len must be in [max(1, framing ids), 2^31 - 1]");
+    if (strategy != TKZ_PAIR_LONGEST_FIRST && strategy != TKZ_PAIR_ONLY_FIRST && strategy != TKZ_PAIR_ONLY_SECOND)
+        return fail(TKZ_E_ARG, "pair rows: strategy must be TKZ_PAIR_LONGEST_FIRST, TKZ_PAIR_ONLY_FIRST or TKZ_PAIR_ONLY_SECOND");
+    if (cut_side != TKZ_TRIM_SUFFIX && cut_side != TKZ_TRIM_PREFIX) return fail(TKZ_E_ARG, "pair rows: cut_side must be TKZ_TRIM_SUFFIX or TKZ_TRIM_PREFIX");
+    if (pad_side != TKZ_PAD_RIGHT && pad_side != TKZ_PAD_LEFT) return fail(TKZ_E_ARG, "pair rows: pad_side must be TKZ_PAD_RIGHT or TKZ_PAD_LEFT");
+    if (pad_multiple < 0 || pad_multiple > (int64_t)INT32_MAX) return fail(TKZ_E_ARG, "pair rows: pad_multiple must be in [0, 2^31 - 1]");
+    return TKZ_OK;
+}
+const char* const kMsgPairPointers = "pair rows: null ids, lens or scalar pointer";
+// the pair call on device buffers, on a workspace the entry holds: the plain launch sequence with the uncut ids and offsets in the workspace, then the rows
+// (enqueue_attempt)
+tkz_status pairs_on_device(tkz_encoder* e, Workspace* ws, BatchCall c, PairCall pc, const SpecialCall* sp, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    int64_t* acc = &ws->bytes_allocated;
+    if (c.n_docs < 0 || c.total < 0 || c.out_cap < 0) return fail(TKZ_E_ARG, "negative size");
+    const int64_t np = std::max<int64_t>(c.n_docs / 2, 1);
+    if (c.total > 0) HIP_TRY(ws->pr_ids.ensure((size_t)c.total * 4, acc));
+    HIP_TRY(ws->pr_offs.ensure((size_t)(c.n_docs + 1) * 8, acc));
+    HIP_TRY(ws->pr_src.ensure((size_t)np * 24, acc));
+    HIP_TRY(ws->pr_part.ensure((size_t)tkz::kPairGridMax * 12, acc));
+    int64_t w = 0, cut = 0;
+    pc.width = &w; pc.n_cut = &cut;
+    c.kind = CallKind::Pairs; c.pairs = &pc; c.special = sp;
+    const tkz_status st = encode_device(e, ws, c, kCallWhole, total_tokens);
+    if (width) *width = w;
+    if (n_cut) *n_cut = cut;
+    if (st == TKZ_OK) { ++e->pairs_calls; if (sp) ++e->spec_batches; }
+    return st;
+}
+// The second half of a pair host entry, with the batch on the device as UTF-8 (c: its bytes and byte offsets): staging for the rows, the offsets, pos, lens, kept,
+// the mask and the types, ONE pair call, the results back -- n_pairs * W entries of each, never the uncut ids.
+tkz_status pairs_staged(tkz_encoder* e, Workspace* ws, BatchCall c, PairCall pc, const SpecialCall* sp, int32_t* out_ids, int64_t out_cap, uint8_t* mask, uint8_t* type_ids,
+                        int32_t* pos, int32_t* lens, int32_t* kept, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    const int64_t n_docs = c.n_docs, n_pairs = n_docs / 2;
+    const bool fits = n_pairs == 0 || out_cap / pc.max_len >= n_pairs;      // (n_pairs * max_len always suffices: more capacity is never used)
+    c.out_cap = fits ? n_pairs * pc.max_len : out_cap;
+    const int64_t cap = std::max<int64_t>(c.out_cap, 1), nl = std::max<int64_t>(n_pairs, 1);
+    TKZ_TRY(stage_out(ws, n_docs, c.out_cap, out_offsets != nullptr));
+    HIP_TRY(ws->pr_stage.ensure((size_t)(pos ? cap : 0) * 4 + (size_t)nl * 4 + (size_t)(kept ? 2 * nl : 0) * 4 + (size_t)(mask ? cap : 0) + (size_t)(type_ids ? cap : 0),
+                                &ws->bytes_allocated));
+    int32_t* const d_pos = ws->pr_stage.as<int32_t>();
+    int32_t* const d_lens = d_pos + (pos ? cap : 0);
+    int32_t* const d_kept = d_lens + nl;
+    uint8_t* const d_mask = reinterpret_cast<uint8_t*>(d_kept + (kept ? 2 * nl : 0));
+    uint8_t* const d_types = d_mask + (mask ? cap : 0);
+    c.d_out = ws->s_out[0].as<int32_t>(); c.d_out_offs = out_offsets ? ws->s_outoffs[0].as<int64_t>() : nullptr;
+    pc.d_mask = mask ? d_mask : nullptr; pc.d_types = type_ids ? d_types : nullptr; pc.d_pos = pos ? d_pos : nullptr; pc.d_lens = d_lens; pc.d_kept = kept ? d_kept : nullptr;
+    const tkz_status st = pairs_on_device(e, ws, c, pc, sp, total_tokens, width, n_cut);
+    if (st != TKZ_OK) return st;
+    const int64_t n = n_pairs * *width;
+    TKZ_TRY(fetch(ws, out_ids, n, out_offsets, n_docs));
+    if (n_pairs) HIP_TRY(hipMemcpy(lens, d_lens, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
+    if (kept && n_docs) HIP_TRY(hipMemcpy(kept, d_kept, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+    if (pos && n) HIP_TRY(hipMemcpy(pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (mask && n) HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    if (type_ids && n) HIP_TRY(hipMemcpy(type_ids, d_types, (size_t)n, hipMemcpyDeviceToHost));
+    return TKZ_OK;
+}
+}  // namespace
+
+tkz_status tkz_encode_batch_pairs_device(tkz_encoder* e, const uint8_t* d_bytes, const int64_t* d_doc_offsets, int64_t n_docs, int64_t total_bytes,
+                                         const int32_t* allowed, int32_t n_allowed, int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len,
+                                         int32_t strategy, int32_t cut_side, int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* d_out_ids, int64_t out_cap,
+                                         uint8_t* d_mask, uint8_t* d_type_ids, int32_t* d_pos, int32_t* d_lens, int32_t* d_kept, int64_t* d_out_offsets, void* hip_stream,
+                                         int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pair_args(n_docs, bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_multiple));
+    if (!d_out_ids || !d_lens || !total_tokens || !width || !n_cut) return fail(TKZ_E_ARG, kMsgPairPointers);
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    BatchCall c{d_bytes, d_doc_offsets, n_docs, total_bytes, d_out_ids, out_cap, d_out_offsets, static_cast<hipStream_t>(hip_stream)};
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    if (!d_doc_offsets || (total_bytes > 0 && !d_bytes)) return fail(TKZ_E_ARG, "null device buffer");      // (d_out_offsets may be null here)
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return fail(TKZ_E_ARG, "d_bytes must be 16-byte aligned");
+    Lease lease(e);
+    return pairs_on_device(e, lease.ws, c, PairCall{bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_id, pad_multiple, d_mask, d_type_ids, d_pos,
+                                                    d_lens, d_kept, nullptr, nullptr}, sp, total_tokens, width, n_cut);
+}
+
+tkz_status tkz_encode_batch_pairs_utf8(tkz_encoder* e, const uint8_t* bytes, const int64_t* doc_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                       int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len, int32_t strategy, int32_t cut_side,
+                                       int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* out_ids, int64_t out_cap, uint8_t* mask, uint8_t* type_ids,
+                                       int32_t* pos, int32_t* lens, int32_t* kept, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pair_args(n_docs, bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_multiple));
+    if (!out_ids || !lens || !total_tokens || !width || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgPairPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(doc_offsets, n_docs, bytes != nullptr, kSizedDocs, &total));
+    if (total == 0) TKZ_TRY(check_empty_docs(doc_offsets, n_docs, kSizedDocs, nullptr));      // (... and the device call runs all the same)
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    // the whole batch is staged and the result copied from ONE call of the device entry, as tkz_encode_batch_padded_utf8 does
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    TKZ_TRY(stage_in(ws, bytes, total, doc_offsets, n_docs));
+    return pairs_staged(e, ws, staged_call(ws, n_docs, total, 0),
+                        PairCall{bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr}, sp, out_ids, out_cap, mask, type_ids, pos, lens, kept, out_offsets, total_tokens, width, n_cut);
+}
+
+// The same for UTF-16 documents: code units staged and transcoded on the device as tkz_encode_batch_padded_utf16 does.
+tkz_status tkz_encode_batch_pairs_utf16(tkz_encoder* e, const uint16_t* units, const int64_t* unit_offsets, int64_t n_docs, const int32_t* allowed, int32_t n_allowed,
+                                        int32_t bos_id, int32_t sep_id, int32_t sep_count, int32_t eos_id, int64_t max_len, int32_t strategy, int32_t cut_side,
+                                        int32_t pad_side, int32_t pad_id, int64_t pad_multiple, int32_t* out_ids, int64_t out_cap, uint8_t* mask, uint8_t* type_ids,
+                                        int32_t* pos, int32_t* lens, int32_t* kept, int64_t* out_offsets, int64_t* total_tokens, int64_t* width, int64_t* n_cut) {
+    SpecialCall sc; const SpecialCall* sp;
+    TKZ_TRY(special_call(e, allowed, n_allowed, &sc, &sp));
+    TKZ_TRY(check_pair_args(n_docs, bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_multiple));
+    if (!out_ids || !lens || !total_tokens || !width || !n_cut || out_cap < 0) return fail(TKZ_E_ARG, kMsgPairPointers);
+    DeviceScope scope;
+    TKZ_TRY(check_encoder(e, scope));
+    int64_t total = 0;
+    TKZ_TRY(check_host_docs(unit_offsets, n_docs, units != nullptr, kUnitDocs, &total));
+    *total_tokens = 0; *width = 0; *n_cut = 0;
+    const PairCall pc{bos_id, sep_id, sep_count, eos_id, max_len, strategy, cut_side, pad_side, pad_id, pad_multiple, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Lease lease(e);
+    Workspace* ws = lease.ws;
+    if (total == 0) {                                                   // (no units: the offsets, all 0, are byte offsets as they are -- the framing is still laid out)
+        TKZ_TRY(check_empty_docs(unit_offsets, n_docs, kUnitDocs, nullptr));
+        TKZ_TRY(stage_in(ws, nullptr, 0, unit_offsets, n_docs));
+        return pairs_staged(e, ws, staged_call(ws, n_docs, 0, 0), pc, sp, out_ids, out_cap, mask, type_ids, pos, lens, kept, out_offsets, total_tokens, width, n_cut);
+    }
+    U16Stage& U = ws->u16[0];
+    const bool with_repl = sp && sp->fffd;
+    HIP_TRY(U.ensure(total, n_docs, &ws->bytes_allocated, with_repl));
+    HIP_TRY(hipMemcpy(U.units.p, units, (size_t)total * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(U.offs.p, unit_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+    const tkz::Launch L{nullptr, nullptr, ws};
+    HIP_TRY(u16_measure(U, L, total, n_docs));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int64_t nbytes = 0;                                                 // the batch as UTF-8
+    TKZ_TRY(u16_write(U, L, total, n_docs, with_repl, &ws->bytes_allocated, &nbytes));
+    BatchCall c{U.bytes.as<uint8_t>(), U.boffs.as<int64_t>(), n_docs, nbytes, nullptr, 0, nullptr, nullptr};
+    if (with_repl) c.d_repl = U.repl.as<uint64_t>();
+    return pairs_staged(e, ws, c, pc, sp, out_ids, out_cap, mask, type_ids, pos, lens, kept, out_offsets, total_tokens, width, n_cut);
+}
+void tkz_encoder_pairs_calls(const tkz_encoder* e, int64_t* calls) {
+    if (calls) *calls = e ? e->pairs_calls.load() : 0;
 }
 
 // ---- Decode (TikTokenizer.cs:586-604) ----------------------------------------------------------------

@@ -379,6 +379,25 @@ struct TbkParams {
 int64_t tbk_run_cap(int64_t n_docs, int64_t max_len, int64_t pad_multiple);
 int64_t tbk_mark_groups(int64_t n_docs);
 void launch_budgeted(const Launch& L, TbkParams K);
+// Pair rows (tkz_encode_batch_pairs_device; tkz.h states the rule): behind the PLAIN document-granular launch sequence, whose uncut ids (ids, ids_cap entries) and
+// n_docs + 1 = 2 * n_pairs + 1 document offsets (offs) stay in the workspace.  k_pair_lens, a lane a pair: the kept counts ka, kb of the two texts by the closed
+// forms of the strategy, lens (the caller's, n_pairs entries: ka + kb + f), the row's record into rows (workspace, 3 int64 a pair: the source index of the first kept
+// id of A, of B, and len | ka << 32), {ka, kb} into kept (the caller's, n_docs entries, may be null), offs copied to out_offs (may be null), and the largest len and
+// the number of cut pairs of every workgroup into part_len / part_cut (kPairGridMax entries each, workspace; nparts of them are written: the grid).
+// k_pair_write: every wavefront reduces the partials to the width W and n_cut, one lane stores totals = {*grand, W, n_cut}, and when n_pairs * W <= out_cap the
+// rows are written by output position in tiles of kPairTile, a wavefront each: out, mask, type_ids, pos (the last three may be null), n_pairs * W entries each.
+// It reads rows only -- not lens, offs, strategy or cut_side.
+// counters: the batch's counter block -- with an error bit in it ([0]) nothing of the caller's is touched and the totals are not written.
+constexpr int kPairTile = 1024;
+constexpr int kPairGridMax = 2048;     // workgroups of the two kernels: they stride over the pairs / tiles beyond
+struct PairParams {
+    const int32_t* ids; int64_t ids_cap; const int64_t* offs; int64_t n_pairs; const int64_t* grand;
+    int32_t bos_id, sep_id, sep_count, eos_id, pad_id; int64_t max_len; int32_t strategy, cut_side, pad_side; int64_t pad_multiple;
+    int32_t* out; int64_t out_cap; uint8_t* mask; uint8_t* type_ids; int32_t* pos; int32_t* lens; int32_t* kept; int64_t* out_offs;
+    int64_t* rows; int32_t* part_len; int64_t* part_cut; int32_t nparts; int64_t* totals;
+    const int32_t* counters;
+};
+void launch_pairs(const Launch& L, PairParams K);
 // batch Decode
 int64_t dec_tiles(int64_t total_ids);
 void launch_dec_len(const Launch& L, const TkzDecodeTable& D, const int32_t* ids, int64_t total, int64_t ntiles, int32_t* grp_prefix, int32_t* tile_sum);

@@ -5139,6 +5139,137 @@ void launch_corpus(hipStream_t s, int kind, uint64_t seed, int64_t first_doc, in
 }
 
 // -------------------------------------------------------------------------------------------------
+// Pair rows (tkz_encode_batch_pairs_device; tkz.h states the rule), behind the plain document-granular launch sequence: documents 2p and 2p + 1 are the two
+// texts A and B of pair p, and row p is [bos] A-kept sep x s B-kept [eos], cut to max_len as a whole, padded to the common width W on either side, with the mask,
+// the type of every position and the position inside the content.  The uncut ids and offsets O stay in the workspace.
+//   k_pair_lens   a lane a pair: a = O[2p + 1] - O[2p], b = O[2p + 2] - O[2p + 1], R = L - f, h = R / 2, H = R - h.  The kept counts in closed form --
+//                 LONGEST_FIRST ka = min(a, max(H, R - b)), kb = min(b, max(h, R - a)); ONLY_FIRST kb = min(b, R), ka = min(a, R - kb); ONLY_SECOND ka = min(a, R),
+//                 kb = min(b, R - ka) --, lens[p] = ka + kb + f, the row's RECORD of 24 bytes in the workspace -- srcA, srcB = the index of the first kept id of
+//                 either text (the head, or the tail for a cut at the front), and {len, ka} in one word --, and the caller's kept and out_offs.  The largest len and the number of cut pairs of a workgroup go into ONE partial each,
+//                 as k_pad_lens makes its own: the wavefronts' by shuffles, the four of them through 48 bytes of LDS.  Nothing is added up in memory, so the
+//                 result is the same bytes on every run.
+//   k_pair_write  k_pad_write's frame: every wavefront reduces the partials to W and n_cut, one lane stores {total, W, n_cut}, n_pairs * W is held against
+//                 out_cap here, and the rows are dealt out by OUTPUT position, a wavefront per tile of kPairTile positions, grid-strided: one 64-bit division
+//                 a TILE, additions and one conditional subtraction per group of 64 positions.  A lane loads its row's record (srcA, srcB, len, ka: 24 bytes side by
+//                 side, which measured a third faster than four loads from three arrays) only when its row changes.  The index j inside the content selects the source: bos, A (srcA + j - fb), a separator, B (srcB + j - fb - ka - s), or eos;
+//                 the type is j >= fb + ka + s.  It reads the records, not O or how the cut was made: whoever fills them decides what is kept.
+// Every store of a row is tkz_store_nt, all 64 lanes, consecutive addresses; the ids are read with tkz_load_nt, below ids_cap.
+// -------------------------------------------------------------------------------------------------
+TKZ_DEV int tkz_pad_wave_max(int v);
+TKZ_DEV int64_t tkz_pad_wave_sum(int64_t v);
+TKZ_KERNEL(256) void k_pair_lens(PairParams K) {
+    TKZ_SHARED int s_len[kThreads / 64];
+    TKZ_SHARED int64_t s_cut[kThreads / 64];
+    const bool bad = K.counters[0] != 0;                       // (a failed attempt: the offsets mean nothing, the caller's buffers are left alone)
+    const int64_t f = (K.bos_id >= 0 ? 1 : 0) + (K.eos_id >= 0 ? 1 : 0) + K.sep_count, R = K.max_len - f, h = R / 2, H = R - h;
+    const int64_t stride = simt::nblocks() * simt::nthreads();
+    int longest = 0;
+    int64_t ncut = 0;
+    if (!bad) for (int64_t p = simt::bid() * simt::nthreads() + simt::tid(); p < K.n_pairs; p += stride) {
+        const int64_t o0 = K.offs[2 * p], o1 = K.offs[2 * p + 1], o2 = K.offs[2 * p + 2], a = o1 - o0, b = o2 - o1;
+        int64_t ka, kb;
+        if (K.strategy == 1) { kb = b < R ? b : R; ka = a < R - kb ? a : R - kb; }                       // ONLY_FIRST: A gives way first
+        else if (K.strategy == 2) { ka = a < R ? a : R; kb = b < R - ka ? b : R - ka; }                  // ONLY_SECOND
+        else {                                                                                           // LONGEST_FIRST: the shorter text keeps its half at least
+            const int64_t ra = R - b > H ? R - b : H, rb = R - a > h ? R - a : h;
+            ka = a < ra ? a : ra; kb = b < rb ? b : rb;
+        }
+        const int len = (int)(ka + kb + f);
+        K.lens[p] = len;
+        K.rows[3 * p] = K.cut_side ? o1 - ka : o0;                 // the row's record: the first kept id of A, of B, and {len, ka} in one word
+        K.rows[3 * p + 1] = K.cut_side ? o2 - kb : o1;
+        K.rows[3 * p + 2] = (int64_t)((uint64_t)(uint32_t)len | ((uint64_t)(uint32_t)ka << 32));
+        if (K.kept) { K.kept[2 * p] = (int32_t)ka; K.kept[2 * p + 1] = (int32_t)kb; }
+        if (K.out_offs) { K.out_offs[2 * p] = o0; K.out_offs[2 * p + 1] = o1; if (p == K.n_pairs - 1) K.out_offs[2 * p + 2] = o2; }
+        longest = len > longest ? len : longest;
+        ncut += a + b > R ? 1 : 0;
+    }
+    longest = tkz_pad_wave_max(longest);
+    ncut = tkz_pad_wave_sum(ncut);
+    if (simt::lane() == 0) { s_len[simt::wave()] = longest; s_cut[simt::wave()] = ncut; }
+    simt::sync();
+    if (simt::tid() == 0) {
+        int64_t c = 0;
+        for (int w = 0; w < simt::nthreads() / 64; ++w) { longest = s_len[w] > longest ? s_len[w] : longest; c += s_cut[w]; }
+        K.part_len[simt::bid()] = longest;
+        K.part_cut[simt::bid()] = c;
+    }
+}
+TKZ_KERNEL(256) void k_pair_write(PairParams K) {
+    if (K.counters[0] != 0) return;
+    const int lane = simt::lane();
+    const int64_t nwaves = simt::nblocks() * (kThreads / 64), wave0 = simt::bid() * (kThreads / 64) + simt::wave();
+    // the width and the cut pairs, from the partials
+    int longest = 0;
+    int64_t n_cut = 0;
+    for (int i = lane; i < K.nparts; i += 64) {
+        const int l = K.part_len[i];
+        longest = l > longest ? l : longest;
+        n_cut += K.part_cut[i];
+    }
+    longest = tkz_pad_wave_max(longest);
+    n_cut = tkz_pad_wave_sum(n_cut);
+    const int64_t L = K.max_len, M = K.pad_multiple;
+    int64_t W = 0;
+    if (longest > 0) { W = M == 0 ? L : (longest + M - 1) / M * M; W = W < L ? W : L; }
+    W = (int64_t)simt::uniform64((uint64_t)W);
+    if (wave0 == 0 && lane == 0) { K.totals[0] = *K.grand; K.totals[1] = W; K.totals[2] = n_cut; }
+    if (W == 0 || K.n_pairs > K.out_cap / W) return;           // (nothing to write; or the rows do not fit: the totals are all that is written)
+    const int64_t N = K.n_pairs * W, ntile = (N + kPairTile - 1) / kPairTile;
+    const int fb = K.bos_id >= 0 ? 1 : 0, fe = K.eos_id >= 0 ? 1 : 0, ns = K.sep_count;
+    // 64 positions on: rstep rows and cstep < W columns
+    const int64_t rstep = W > 64 ? 0 : (int64_t)(64u / (uint32_t)W), cstep = W > 64 ? 64 : (int64_t)(64u % (uint32_t)W);
+    for (int64_t t = wave0; t < ntile; t += nwaves) {
+        const int64_t q0 = t * kPairTile, q1 = q0 + kPairTile < N ? q0 + kPairTile : N;
+        const int64_t row0 = q0 / W, col0 = q0 - row0 * W;     // (wave-uniform: one division a tile)
+        int64_t r, c;
+        if (W >= 64) { r = row0; c = col0 + lane; if (c >= W) { c -= W; ++r; } }
+        else { const uint32_t x = (uint32_t)col0 + (uint32_t)lane; r = row0 + (int64_t)(x / (uint32_t)W); c = (int64_t)(x % (uint32_t)W); }
+        int64_t cur = -1, srcA = 0, srcB = 0;
+        int len = 0, ka = 0;
+        for (int64_t g = q0; g < q1; g += 64) {
+            const int64_t q = g + lane;
+            if (q < q1) {
+                if (r != cur) {                                // (one record of 24 bytes: three loads from one stretch of memory)
+                    cur = r; srcA = K.rows[3 * r]; srcB = K.rows[3 * r + 1];
+                    const uint64_t lk = (uint64_t)K.rows[3 * r + 2];
+                    len = (int)(uint32_t)lk; ka = (int)(uint32_t)(lk >> 32);
+                }
+                const int64_t j = c - (K.pad_side ? W - len : 0);     // the index inside the content
+                const bool in = j >= 0 && j < len;
+                const int64_t seam = (int64_t)fb + ka, second = seam + ns;      // the first separator, the first id of B
+                int32_t v = K.pad_id;
+                if (in) {
+                    if (fb && j == 0) v = K.bos_id;
+                    else if (fe && j == len - 1) v = K.eos_id;
+                    else if (j >= seam && j < second) v = K.sep_id;
+                    else {
+                        const int64_t s = j < seam ? srcA + j - fb : srcB + j - second;
+                        if (s >= 0 && s < K.ids_cap) v = tkz_load_nt(K.ids + s);
+                    }
+                }
+                tkz_store_nt(K.out + q, v);
+                if (K.mask) tkz_store_nt(K.mask + q, (uint8_t)(in ? 1 : 0));
+                if (K.type_ids) tkz_store_nt(K.type_ids + q, (uint8_t)(in && j >= second ? 1 : 0));
+                if (K.pos) tkz_store_nt(K.pos + q, in ? (int32_t)j : 0);
+            }
+            r += rstep; c += cstep;
+            if (c >= W) { c -= W; ++r; }
+        }
+    }
+}
+// (the bracket: K_DOCOFFS's again, as launch_pad.  The width is known on the device only: the writing grid is sized for the positions the caller's buffer holds,
+//  n_pairs * max_len at most -- beyond kPairGridMax workgroups both kernels stride)
+void launch_pairs(const Launch& L, PairParams K) {
+    const auto capped = [](int64_t g) { return g < 1 ? 1 : (g > kPairGridMax ? kPairGridMax : g); };
+    const int64_t most = K.n_pairs > 0 && K.out_cap / K.max_len >= K.n_pairs ? K.n_pairs * K.max_len : K.out_cap;
+    K.nparts = (int32_t)capped(cdiv(K.n_pairs, kThreads));
+    TKZ_LAUNCH(k_pair_lens, K.nparts, kThreads, L.stream, K);
+    TKZ_LAUNCH(k_pair_write, capped(cdiv(cdiv(most, kPairTile), kThreads / 64)), kThreads, L.stream, K);
+    hook(L, K_DOCOFFS, 1);
+}
+
+// -------------------------------------------------------------------------------------------------
 // Token-budget buckets (tkz_encode_batch_budgeted_device; tkz.h states the rule), behind the bucketed call's sequence up to the sort's last k_bkt_scatter, which
 // is reused unchanged (order, rank, and slen / ssrc in sorted order): the sorted rows cut greedily into buckets of at most bucket_rows rows and at most
 // token_budget positions (rows * width), every bucket padded to ITS OWN longest row.  Where a bucket ends depends on where the one before it ended; the chain

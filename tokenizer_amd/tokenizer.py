@@ -502,6 +502,57 @@ class TikTokenizer:
             buckets.append(views)
         return buckets, order, rank, lens
 
+    # ---- pair rows: two texts a row, truncation by a strategy, framing, separators, type ids and padding (include/tkz.h, "Pair rows") ----
+    def EncodeBatchPairs(self, first: Sequence[str], second: Sequence[str], max_length: int, allowedSpecialOrApply: Union[bool, Sequence[str], None] = True, bos=None, sep=None,
+                         sep_count: int = 1, eos=None, pad: int = 0, truncation: str = "longest_first", truncation_side: str = "right", padding_side: str = "right",
+                         pad_to_multiple_of: int = 1, fixed_width: bool = False, return_pos: bool = False):
+        """(ids[n, W], mask[n, W], type_ids[n, W], lens, kept[n, 2]) as numpy arrays -- and pos[n, W] with return_pos -- from ONE device call
+        (tkz_encode_batch_pairs_utf8 / _utf16): row i is `bos` first[i] `sep` x sep_count second[i] `eos`, the two texts' ids -- Encode's for the same arguments --
+        cut to max_length less the framing by `truncation` ("longest_first": an id at a time from the longer text, from the second on a tie; "only_first";
+        "only_second"), truncation_side "right" keeping the heads and "left" the tails, padded with `pad` on padding_side to the longest row rounded up to
+        pad_to_multiple_of (at most max_length), or to max_length itself with fixed_width.  mask is 1 on content, type_ids 1 on the second text's ids and the eos
+        (uint8 both), lens the content lengths, kept[i] the ids kept of either text.  bos / sep / eos: None, an int, or the literal of a registered special token;
+        sep None means no separator.  The cut is a plain cut of the id lists."""
+        sides = {"right": 0, "left": 1}
+        strategies = {"longest_first": N.TRUNC_LONGEST_FIRST, "only_first": N.TRUNC_ONLY_FIRST, "only_second": N.TRUNC_ONLY_SECOND}
+        if len(first) != len(second):
+            raise ValueError("first and second must hold as many texts as each other")
+        if truncation_side not in sides or padding_side not in sides:
+            raise ValueError("truncation_side and padding_side are 'right' or 'left'")
+        if truncation not in strategies:
+            raise ValueError("truncation is 'longest_first', 'only_first' or 'only_second'")
+        bos_id, sep_id, eos_id = self._frame_id(bos), self._frame_id(sep), self._frame_id(eos)
+        if sep_count not in (0, 1, 2):
+            raise ValueError("sep_count is 0, 1 or 2")
+        if sep_id < 0:
+            sep_count = 0
+        if max_length < max(1, (bos_id >= 0) + sep_count + (eos_id >= 0)) or max_length >= 1 << 31:
+            raise ValueError("max_length must hold the framing ids, and one id at least")
+        if pad_to_multiple_of < 1 or pad_to_multiple_of >= 1 << 31:
+            raise ValueError("pad_to_multiple_of must be at least 1")
+        allowed = self._resolve_allowed(allowedSpecialOrApply)
+        plain = not allowed or self._special_re is None
+        if not plain and self._special_on_host:
+            raise N.UnsupportedError(N.E_UNSUPPORTED, "EncodeBatchPairs: the device's special entries do not hold this set of literals")
+        names = set(allowed) if not plain else ()
+        index = [i for i, k in enumerate(self.SpecialTokensEncoder) if k in names]
+        texts = [t for pair in zip(first, second) for t in pair]          # documents 2p and 2p + 1: the two texts of pair p
+        args = (max_length, index, bos_id, sep_id, sep_count, eos_id, pad, strategies[truncation], sides[truncation_side], sides[padding_side],
+                0 if fixed_width else pad_to_multiple_of, True, True, return_pos, True, False)
+        if not plain and self._fffd_literal and any(_has_lone_surrogate(t) for t in texts):
+            # (a literal that holds U+FFFD beside a lone surrogate: only the UTF-16 entry tells the two apart)
+            raw = [t.encode("utf-16-le", "surrogatepass") for t in texts]
+            offs = np.zeros(len(raw) + 1, np.int64)
+            np.cumsum(np.fromiter((len(r) // 2 for r in raw), np.int64, len(raw)), out=offs[1:])
+            ids, mask, types, pos, lens, kept = self._encoder.encode_batch_pairs_utf16(np.frombuffer(b"".join(raw), "<u2"), offs, *args)[:6]
+        else:
+            segs = [_utf8_like_dotnet(t) for t in texts]
+            offs = np.zeros(len(segs) + 1, np.int64)
+            np.cumsum(np.fromiter(map(len, segs), np.int64, len(segs)), out=offs[1:])
+            data = np.frombuffer(b"".join(segs), np.uint8) if offs[-1] else np.zeros(0, np.uint8)
+            ids, mask, types, pos, lens, kept = self._encoder.encode_batch_pairs(data, offs, *args)[:6]
+        return (ids, mask, types, lens, kept, pos) if return_pos else (ids, mask, types, lens, kept)
+
     # ---- trim variants (TikTokenizer.cs:288-579) --------------------------------------------------
     def _piece_items(self, text: str, allowed):
         """The walk both trim variants share: the text as a list of (n_tokens, ids, utf16_length) items in order --
